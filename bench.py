@@ -5,8 +5,8 @@ One "step" = one pass of the whole hot path over one batch of 32 synthetic 10-se
 with hipGraph replay -> VAE decode -> re-encode.  Since round 4 the headline (``value``) is measured with the inputs RESIDENT in
 HBM when the timed region starts and the codes left in HBM, as the round's measurement contract asks; the same loop with the
 boundary a host caller sees - H2D of the audio (20 MB from pinned host memory) in front and D2H of the FLAME codes (3.4 MB into
-pinned host memory) behind every step, SURVEY.md section 8(d), the headline of rounds 2-3 - is timed right after it and reported
-as ``host_io`` (``--host-io`` makes it the headline again; then ``resident`` is the side figure).  Weight load and graph capture
+pinned host memory) behind every step, SURVEY.md section 8(d), the headline of rounds 2-3 - is timed right after it by ``--full``
+and reported as ``host_io`` (``--host-io`` makes it the headline again; then ``resident`` is the side figure).  Weight load and graph capture
 are outside (warmup).
 
 ``python bench.py --gpus N`` is ONE command for any N: for N > 1 the parent - before it touches the GPU - starts
@@ -16,9 +16,16 @@ WORLD_SIZE in the environment mean "I am a rank").  Every rank takes its own 32 
 ``artalk_amd.dist.run_sharded``) and the step ends with the RCCL all-gather that collects the FLAME codes of all ranks.
 ``--force-collective`` runs that same init + all-gather code at N = 1.
 
-Prints ONE JSON line (rank 0).  Besides the contract keys it carries ``roofline`` (the dominant kernel, timed with HIP events
-around every eager launch of it inside the timed region) and ``cpu_baseline`` (the CPU oracle, a restatement pinned bit-exact
-to the reference, timed on the host cores for a bounded sample).
+Prints ONE JSON line (rank 0).  Besides the contract keys it carries ``stages_ms`` and ``roofline`` (the dominant kernel, timed with
+HIP events around every eager launch of it inside the timed region).  A plain run does nothing else: set-up, warm-up, the timed
+steps, the line.  ``--full`` adds everything that needs work of its own after the timed steps: ``budget_ms`` (an extra kernel-timer
+pass), ``parity`` (the benchmarked batch against the reference goldens; a failure exits 3), the ``synchronous`` and ``host_io`` /
+``resident`` loops, ``f32_mode``, ``heavy_profile``, the latency figures and ``cpu_baseline`` (the CPU oracle, a restatement pinned
+bit-exact to the reference, timed on the host cores for a bounded sample).
+
+``--dump-outputs DIR`` writes the FLAME codes of the last timed step - what the caller of the timed path receives, all ranks' clips
+after the all-gather - as ``DIR/flame_codes.npy`` (float32, clips x frames x 106; 3.4 MB at the defaults).  Weights and clips are
+generated from fixed seeds, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -104,7 +111,7 @@ def parse_args(argv=None):
     ap.add_argument("--resident", action="store_true", help="(the default since round 4; kept so that older command lines still parse)")
     ap.add_argument("--host-io", action="store_true", help="headline step = H2D of the audio from pinned host memory + the path + D2H of the codes "
                     "(what rounds 2-3 reported as `value`); default: inputs resident in HBM when the timed region starts, the PCIe-inclusive "
-                    "rate is reported beside it as `host_io`")
+                    "rate is reported beside it as `host_io` (--full)")
     ap.add_argument("--force-collective", action="store_true", help="N = 1: still create the RCCL process group and run the all-gather")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--io-probe", default="", choices=["", "h2d", "d2h"], help="(diagnosis) keep only the upload or only the download of the step's PCIe copies")
@@ -113,7 +120,14 @@ def parse_args(argv=None):
     ap.add_argument("--no-heavy-profile", action="store_true", help="skip the (untimed) outlier-weights robustness figure")
     ap.add_argument("--cpu-clips", type=int, default=12)
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of the self-launched N > 1 run (0 = pick a free one)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure and check everything beside the headline "
+                    "(kernel-time budget, parity against the reference goldens, other loops / placements / precision, heavy weights, "
+                    "latencies, CPU baseline); --no-cpu-baseline, --no-alt-mode and --no-heavy-profile trim it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the FLAME codes of the last timed step to DIR/flame_codes.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(args):
@@ -226,10 +240,10 @@ def main():
             ev.record()
             state["last_host"] = slot
         state["k"] += 1
-        return ticket, local, ev
+        return ticket, local, ev, outs
 
     def finish(p):
-        ticket, _, ev = p
+        ticket, _, ev, _ = p
         if state["pipelined"] and model.status_of(ticket) != 0:
             raise RuntimeError("range guard tripped during the benchmark: the f16x3 results of that batch are invalid")
         if ev is not None:
@@ -252,7 +266,7 @@ def main():
             h0 = time.perf_counter()
             cur = submit()
             h1 = time.perf_counter()
-            outs = cur[1]
+            outs, state["job_outs"] = cur[1], cur[3]
             if prev is not None:
                 finish(prev)
             if not state["pipelined"]:
@@ -282,6 +296,12 @@ def main():
     log(f"timed region done: {dt:.3f} s for {args.steps} steps")
     prof = model.get_profile()       # numbers of the last timed step
     model.set_profiling(0)
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path received in its last step: every clip's FLAME codes (all ranks' after the all-gather)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        codes = torch.stack(list(state["job_outs"])).float().cpu().numpy()
+        np.save(os.path.join(args.dump_outputs, "flame_codes.npy"), codes)
+        log(f"wrote {args.dump_outputs}/flame_codes.npy {codes.shape} {codes.dtype}")
 
     # Kernel-time budget per stage without a profiler: one more, untimed pass at profiling level 3 - graphs off, the
     # same clip groups one after the other, every launch with its own start / stop events (hipExtLaunchKernelGGL: the dispatch's begin /
@@ -289,7 +309,7 @@ def main():
     # difference is the time a stage's stream sat idle between kernels (single-stream stages), or - for the body, whose two clip groups
     # replay concurrently - how much of the kernel time overlapped.
     budget = None
-    if world == 1 and not args.no_alt_mode:
+    if args.full and world == 1 and not args.no_alt_mode:
         model.set_profiling(3)
         model.inference_batch(dev_audio)
         torch.cuda.synchronize()
@@ -316,7 +336,7 @@ def main():
         value = total_frames / dt
         # parity of the benchmarked batch against the reference's own outputs: every clip of rank 0 that has a golden
         parity = None
-        if args.config == "full" and args.seconds == 10.0 and os.path.exists(GOLDEN_SET):
+        if args.full and args.config == "full" and args.seconds == 10.0 and os.path.exists(GOLDEN_SET):
             g = np.load(GOLDEN_SET)
             f0, errs = 0, {}
             res = host_outs[state["last_host"]].numpy() if not state["resident"] else torch.stack(list(outs)).cpu().numpy()
@@ -409,7 +429,7 @@ def main():
             "load_s": round(t_load, 1),
         }
 
-    extras = world == 1 and not args.no_alt_mode
+    extras = args.full and world == 1 and not args.no_alt_mode
     if extras and not args.synchronous:
         # the same steps, one batch at a time: the host waits for every batch's health flags and download before it enqueues the next
         state["pipelined"] = False
@@ -525,7 +545,7 @@ def main():
         result["stream_chunk_ms"] = dict(stream_ms, workload="artalk_stream_chunk: one 4-s block (100 frames) per stream, host chunk in -> host codes out, "
                                          "median of synchronous calls; 4000 ms of audio per call")
 
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if rank == 0 and args.full and not args.no_cpu_baseline and world == 1:
         sys.path.insert(0, os.path.join(REPO, "oracle"))
         from artalk_oracle import ARTalkOracle
         cores = host_cores()

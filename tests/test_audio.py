@@ -12,8 +12,6 @@ from artalk_amd.audio import read_wav, sinc_resample_kernel
 from audio_oracle import get_sinc_resample_kernel, load_mono_16k, resample
 from conftest import GOLDEN
 
-DEMO_WAV = "/root/reference/demo/eng1.wav"
-
 
 def _write_wav(path, data_i16, sr):
     with wave.open(str(path), "wb") as w:
@@ -55,14 +53,28 @@ def test_resampler_properties():
     assert torch.equal(resample(low, 16000, 16000), low)
 
 
-@pytest.mark.skipif(not os.path.exists(DEMO_WAV), reason="reference demo wav only exists in the build container")
-def test_demo_fixture_is_reproducible():
-    """tests/golden/demo_16k_s16.npz is exactly read_wav -> resampler restatement -> int16 of the reference's demo/eng1.wav."""
-    wav, sr = read_wav(DEMO_WAV)
-    a = load_mono_16k(wav, sr).numpy()
-    q = np.clip(np.round(a * 32768.0), -32768, 32767).astype(np.int16)
+def test_demo_fixture_is_reproducible(tmp_path):
+    """tests/golden/demo_16k_s16.npz is exactly read_wav -> resampler restatement -> int16 of the reference's demo/eng1.wav.  Three
+    stretches of that wav's 48 kHz stereo PCM are committed (tests/golden/demo_eng1_48k_segments.npz, with the source file's sha256):
+    its first frames, its loudest stretch and its last frames.  Each is written back into a wav, decoded and resampled; output
+    sample j only reads input frames 3j-19 .. 3j+21, so away from a cut inside the file every sample must equal the fixture's."""
+    src = np.load(os.path.join(GOLDEN, "demo_eng1_48k_segments.npz"))
+    n, sr_in = int(src["n_frames"]), int(src["sr"])
     fx = np.load(os.path.join(GOLDEN, "demo_16k_s16.npz"))["eng1"]
-    assert q.shape == fx.shape == (217088,) and np.array_equal(q, fx)
+    assert sr_in == 48000 and fx.shape == (217088,) and n == 3 * fx.shape[0]
+    assert int(src["start"][0]) == 0 and int(src["start"][-1]) + src["pcm"].shape[1] == n     # both ends of the file are covered
+    margin = 16
+    for i, (start, pcm) in enumerate(zip(src["start"], src["pcm"])):
+        start = int(start)
+        _write_wav(tmp_path / f"eng1_{i}.wav", pcm, sr_in)
+        wav, sr = read_wav(str(tmp_path / f"eng1_{i}.wav"))
+        a = load_mono_16k(wav, sr).numpy()
+        q = np.clip(np.round(a * 32768.0), -32768, 32767).astype(np.int16)
+        assert start % 3 == 0 and q.shape == (pcm.shape[0] // 3,)
+        lo = 0 if start == 0 else margin
+        hi = q.shape[0] if start + pcm.shape[0] == n else q.shape[0] - margin
+        j0 = start // 3
+        assert np.array_equal(q[lo:hi], fx[j0 + lo:j0 + hi]), f"stretch at frame {start} differs from the 16 kHz fixture"
 
 
 def test_config1_plumbing_on_cpu_oracle():

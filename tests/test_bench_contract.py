@@ -57,3 +57,8 @@ def test_bench_defaults_are_one_gpu_and_minutes():
     spec.loader.exec_module(mod)                          # defines parse_args / main; runs nothing
     a = mod.parse_args([])
     assert a.gpus == 1 and 1 <= a.steps <= 50 and a.warmup >= 1
+    assert a.full is False and a.dump_outputs is None       # a plain run measures the headline only and writes nothing
+    a = mod.parse_args(["--steps", "7", "--full", "--dump-outputs", "d"])
+    assert a.steps == 7 and a.full is True and a.dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        mod.parse_args(["--steps", "0"])
