@@ -90,7 +90,7 @@ struct StyleLayer { float *in_w, *in_b, *out_w, *out_b, *l1_w, *l1_b, *l2_w, *l2
 // Site exponents of the P8 operand format (common.h): every producer of a P8 operand writes it with scale 2^e and every consumer removes
 // the same scale, e = kActExp (16) by default.  artalk_calibrate lowers the exponent of a site whose activations need the range
 // (a real XLS-R-class checkpoint: FFN hidden channels of 1e4 and more) - per SITE, so that one outlier channel in a few layers
-// does not cost the whole model its fast mode.  Indexed like the audit's site names.
+// does not cost the whole model its fast mode.  Named by the site table (build_site_table).
 struct SiteExps {
     int conv[8]; int fp_ln, posconv_in;
     struct W2V { int ln1, qkv, attn, ln2, ffn; } w2v[64];
@@ -147,6 +147,12 @@ struct artalk_model {
     std::vector<int*> audit_exp;                   // the site's exponent (SiteExps member) per audit slot: what artalk_calibrate adjusts
     SiteExps ex;                                   // site exponents of the P8 format (all kActExp until a calibration lowers some)
     int scales_changed = 0;                        // sites whose exponent differs from kActExp
+    // every P8 producer site the configuration can run, built from the config alone at artalk_create (build_site_table): the one
+    // place the site names are defined (the audit looks its names up here by exponent pointer) and the order of artalk_*_site_scales
+    struct Site { std::string name; int* ex; };
+    std::vector<Site> sites;
+    std::map<const int*, int> site_of;             // exponent pointer -> index into sites
+    bool stream_scales_ended = false;              // a scale change ended the streaming session (artalk_stream_chunk says so)
     // The INITIAL history of a clip (app/models.py:86-89: encode + quantise an all-zero motion) is a function of the weights only - the
     // same bits, decoder features and history tokens for every clip of every call.  It is computed once per precision mode (for ONE
     // clip, through the same run_reencode as every later history) and broadcast to the batch afterwards; only the style token in
@@ -454,14 +460,14 @@ void stage_mark(artalk_model* m, hipStream_t s, int bucket) {
 constexpr int kAuditSlots = 1024;
 // audit hook: records max |x| of a just-produced P8 buffer (or of the fp32 buffer that holds the same activation in f32 mode, or that a
 // register-staged GEMM will split).  ex = the site's exponent (a SiteExps member of this model): what the buffer was written with, and
-// what artalk_calibrate adjusts from the recorded maximum.  Works in both precision modes: the calibration pass runs in exact-f32
-// mode, where nothing can overflow on the way to a later site.
-void audit(artalk_model* m, const char* site, int idx0, const char* sub, const float* buf, int rows, int cols, long ld, bool is_p8, hipStream_t s,
-           int* ex, int junk_period = 0, int junk_from = 0) {
+// what artalk_calibrate adjusts from the recorded maximum; the site's name is the one the site table gives that member.  Works in both
+// precision modes: the calibration pass runs in exact-f32 mode, where nothing can overflow on the way to a later site.
+void audit(artalk_model* m, const float* buf, int rows, int cols, long ld, bool is_p8, hipStream_t s, int* ex, int junk_period = 0,
+           int junk_from = 0) {
     if (!m->audit || !m->audit_vals) return;
-    std::string name = site;
-    if (idx0 >= 0) name += std::to_string(idx0);
-    if (sub) name += sub;
+    auto st = m->site_of.find(ex);
+    if (st == m->site_of.end()) { m->err = "internal: audited exponent is not in the site table"; m->sticky_error = true; return; }
+    const std::string& name = m->sites[st->second].name;
     auto it = m->audit_index.find(name);
     int idx;
     if (it == m->audit_index.end()) {
@@ -623,7 +629,7 @@ void run_wav2vec(artalk_model* m, const float* audio, int c0, int n, float* out_
     SiteExps& ex = m->ex;
     launch_conv0(w.xnorm, kSamplesPerChunk, m->conv0_w, m->conv_b[0], m->conv_lnw[0], m->conv_lnb[0], w.convA, n, m->conv_T[0],
                  m->conv_S[0], s, p8, w.status, ex.conv[0]);
-    audit(m, "w2v.conv", 0, ".ln_gelu", w.convA, n * m->conv_S[0], CD, CD, p8, s, &ex.conv[0], m->conv_S[0], m->conv_T[0]);
+    audit(m, w.convA, n * m->conv_S[0], CD, CD, p8, s, &ex.conv[0], m->conv_S[0], m->conv_T[0]);
     float* src = w.convA; float* dst = w.convB;
     for (int i = 1; i < c.w2v_n_conv; ++i) {
         // stride-2 conv as a GEMM: output row r reads input rows 2r..2r+k-1 (contiguous K = k*512 floats)
@@ -634,7 +640,7 @@ void run_wav2vec(artalk_model* m, const float* audio, int c0, int n, float* out_
         // rows t >= conv_T[i] of every chunk are layout padding (computed from the padding rows below them): no range guard there
         layernorm(dst, dst, m->conv_lnw[i], m->conv_lnb[i], M, CD, 1e-5f, ACT_GELU_ERF, s, (p8 && i + 1 < c.w2v_n_conv) ? 1 : 0, w.status,
                   m->conv_S[i], m->conv_T[i], ex.conv[i]);
-        if (i + 1 < c.w2v_n_conv) audit(m, "w2v.conv", i, ".ln_gelu", dst, M, CD, CD, p8, s, &ex.conv[i], m->conv_S[i], m->conv_T[i]);
+        if (i + 1 < c.w2v_n_conv) audit(m, dst, M, CD, CD, p8, s, &ex.conv[i], m->conv_S[i], m->conv_T[i]);
         std::swap(src, dst);
     }
     stage_mark(m, s, PB_CONV);
@@ -648,10 +654,10 @@ void run_wav2vec(artalk_model* m, const float* audio, int c0, int n, float* out_
     const int JP = m->Ts, JF = m->Tw;
     // feature projection (hf:429-434)
     layernorm(src, dst, m->fp_lnw, m->fp_lnb, M, CD, c.w2v_ln_eps, ACT_NONE, s, p8, w.status, JP, JF, ex.fp_ln);
-    audit(m, "w2v.feature_projection.ln", -1, nullptr, dst, M, CD, CD, p8, s, &ex.fp_ln, JP, JF);
+    audit(m, dst, M, CD, CD, p8, s, &ex.fp_ln, JP, JF);
     linear(m, dst, CD, m->fp_w, m->fp_b, w.h0, Hs, M, Hs, CD, ACT_NONE, nullptr, s, AP, nullptr, ex.fp_ln);
     // positional conv embedding (hf:360-368): h1 = h0 + gelu(groupconv(h0) + b)
-    audit(m, "w2v.posconv.input(fp32 A)", -1, nullptr, w.h0, M, Hs, Hs, false, s, &ex.posconv_in, JP, JF);
+    audit(m, w.h0, M, Hs, Hs, false, s, &ex.posconv_in, JP, JF);
     {
         const int cg = Hs / c.w2v_pos_groups;
         GemmArgs g;
@@ -675,7 +681,7 @@ void run_wav2vec(artalk_model* m, const float* audio, int c0, int n, float* out_
         const W2VLayer& L = m->w2v[i];
         SiteExps::W2V& E = ex.w2v[i];
         layernorm(h, w.xln, L.ln1w, L.ln1b, M, Hs, c.w2v_ln_eps, ACT_NONE, s, p8, w.status, JP, JF, E.ln1);
-        audit(m, "w2v.layer", i, ".ln1", w.xln, M, Hs, Hs, p8, s, &E.ln1, JP, JF);
+        audit(m, w.xln, M, Hs, Hs, p8, s, &E.ln1, JP, JF);
         linear(m, w.xln, Hs, L.qkv_w, L.qkv_b, w.qkv, 3 * Hs, M, 3 * Hs, Hs, ACT_NONE, nullptr, s, AP | (p8 ? LF_C_P8 : 0), nullptr, E.ln1, E.qkv);   // q, k, v leave in P8
         AttnArgs a;
         a.qkv_p8 = p8; a.qkv_exp = E.qkv; a.o_exp = E.attn;
@@ -683,15 +689,15 @@ void run_wav2vec(artalk_model* m, const float* audio, int c0, int n, float* out_
         a.ldq = a.ldk = a.ldv = 3 * Hs; a.q_bstride = a.k_bstride = a.v_bstride = (long)m->Ts * 3 * Hs;
         a.O = w.att; a.ldo = Hs; a.o_bstride = (long)m->Ts * Hs;
         a.B = n; a.H = nh; a.HD = hd; a.Lq = m->Tw; a.Lk = m->Tw; a.scale = 1.0f / std::sqrt((float)hd);
-        audit(m, "w2v.layer", i, ".qkv", w.qkv, M, 3 * Hs, 3 * Hs, p8, s, &E.qkv, JP, JF);
+        audit(m, w.qkv, M, 3 * Hs, 3 * Hs, p8, s, &E.qkv, JP, JF);
         a.out_p8 = p8; a.split16 = p8; a.status = p8 ? w.status : nullptr; a.cus = m->n_cus;
         launch_attention(a, s);
-        audit(m, "w2v.layer", i, ".attn_out", w.att, M, Hs, Hs, p8, s, &E.attn, JP, JF);
+        audit(m, w.att, M, Hs, Hs, p8, s, &E.attn, JP, JF);
         linear(m, w.att, Hs, L.out_w, L.out_b, h, Hs, M, Hs, Hs, ACT_NONE, h, s, AP, nullptr, E.attn);
         layernorm(h, w.xln, L.ln2w, L.ln2b, M, Hs, c.w2v_ln_eps, ACT_NONE, s, p8, w.status, JP, JF, E.ln2);
-        audit(m, "w2v.layer", i, ".ln2", w.xln, M, Hs, Hs, p8, s, &E.ln2, JP, JF);
+        audit(m, w.xln, M, Hs, Hs, p8, s, &E.ln2, JP, JF);
         linear(m, w.xln, Hs, L.ff1_w, L.ff1_b, w.ffn, c.w2v_ffn, M, c.w2v_ffn, Hs, ACT_GELU_ERF, nullptr, s, AP | (p8 ? LF_C_P8 : 0), nullptr, E.ln2, E.ffn);
-        audit(m, "w2v.layer", i, ".ffn_hidden", w.ffn, M, c.w2v_ffn, c.w2v_ffn, p8, s, &E.ffn, JP, JF);
+        audit(m, w.ffn, M, c.w2v_ffn, c.w2v_ffn, p8, s, &E.ffn, JP, JF);
         linear(m, w.ffn, c.w2v_ffn, L.ff2_w, L.ff2_b, h, Hs, M, Hs, c.w2v_ffn, ACT_NONE, h, s, AP, nullptr, E.ffn);
     }
     layernorm(h, w.xln, m->enc_lnw, m->enc_lnb, M, Hs, c.w2v_ln_eps, ACT_NONE, s);
@@ -699,7 +705,7 @@ void run_wav2vec(artalk_model* m, const float* audio, int c0, int n, float* out_
         (void)hipMemcpy2DAsync(out_w2v + (long)c0 * m->Tw * Hs, (size_t)m->Tw * Hs * 4, w.xln, (size_t)m->Ts * Hs * 4,
                                (size_t)m->Tw * Hs * 4, n, hipMemcpyDeviceToDevice, s);
     launch_pool_silu(w.xln, m->Ts, m->Tw, w.silu_cond + (long)c0 * kNTok * kCond, n, m->pn, c.n_levels, kCond, s, p8, w.status, ex.silu_cond);
-    audit(m, "ar.silu_cond", -1, nullptr, w.silu_cond + (long)c0 * kNTok * kCond, n * kNTok, kCond, kCond, p8, s, &ex.silu_cond);
+    audit(m, w.silu_cond + (long)c0 * kNTok * kCond, n * kNTok, kCond, kCond, p8, s, &ex.silu_cond);
     stage_mark(m, s, PB_ENC);
 }
 
@@ -714,13 +720,13 @@ void run_style(artalk_model* m, const float* style_motion, int B, hipStream_t s,
     if (style_motion && encode) {
         launch_style_input(style_motion, m->st_mean, m->st_std, w.s_in, B, s);
         SiteExps& ex = m->ex;
-        audit(m, "style.input(fp32 A)", -1, nullptr, w.s_in, M, 128, 128, false, s, &ex.style_in);
+        audit(m, w.s_in, M, 128, 128, false, s, &ex.style_in);
         linear(m, w.s_in, 128, m->st_proj_w, m->st_proj_b, w.s_h, S, M, S, 128, ACT_NONE, nullptr, s, 0, nullptr, ex.style_in);
         launch_add_row(w.s_h, m->st_pe, M, S, s);   // PositionalEncoding quirk: pe[:, seq_len] added to every token
         for (int i = 0; i < c.style_layers; ++i) {
             const StyleLayer& Ly = m->style[i];
             SiteExps::ST& E = ex.style[i];
-            audit(m, "style.layer", i, ".in(fp32 A)", w.s_h, M, S, S, false, s, &E.h);
+            audit(m, w.s_h, M, S, S, false, s, &E.h);
             linear(m, w.s_h, S, Ly.in_w, Ly.in_b, w.s_qkv, 3 * S, M, 3 * S, S, ACT_NONE, nullptr, s, 0, nullptr, E.h);
             AttnArgs a;
             a.Q = w.s_qkv; a.K = w.s_qkv + S; a.V = w.s_qkv + 2 * S; a.ldq = a.ldk = a.ldv = 3 * S;
@@ -729,12 +735,12 @@ void run_style(artalk_model* m, const float* style_motion, int B, hipStream_t s,
             a.B = B; a.H = c.style_heads; a.HD = S / c.style_heads; a.Lq = L; a.Lk = L;
             a.scale = 1.0f / std::sqrt((float)(S / c.style_heads));
             launch_attention(a, s);
-            audit(m, "style.layer", i, ".attn_out(fp32 A)", w.s_att, M, S, S, false, s, &E.attn);
+            audit(m, w.s_att, M, S, S, false, s, &E.attn);
             linear(m, w.s_att, S, Ly.out_w, Ly.out_b, w.s_tmp, S, M, S, S, ACT_NONE, w.s_h, s, 0, nullptr, E.attn);
             layernorm(w.s_tmp, w.s_h, Ly.n1w, Ly.n1b, M, S, 1e-5f, ACT_NONE, s);
-            audit(m, "style.layer", i, ".norm1(fp32 A)", w.s_h, M, S, S, false, s, &E.h1);
+            audit(m, w.s_h, M, S, S, false, s, &E.h1);
             linear(m, w.s_h, S, Ly.l1_w, Ly.l1_b, w.s_ffn, c.style_ffn, M, c.style_ffn, S, ACT_GELU_ERF, nullptr, s, 0, nullptr, E.h1);
-            audit(m, "style.layer", i, ".ffn_hidden(fp32 A)", w.s_ffn, M, c.style_ffn, c.style_ffn, false, s, &E.ffn);
+            audit(m, w.s_ffn, M, c.style_ffn, c.style_ffn, false, s, &E.ffn);
             linear(m, w.s_ffn, c.style_ffn, Ly.l2_w, Ly.l2_b, w.s_tmp, S, M, S, c.style_ffn, ACT_NONE, w.s_h, s, 0, nullptr, E.ffn);
             layernorm(w.s_tmp, w.s_h, Ly.n2w, Ly.n2b, M, S, 1e-5f, ACT_NONE, s);
         }
@@ -751,12 +757,11 @@ void run_vae_stack(artalk_model* m, const VAESide& S, int B, int T, int split, h
     const int p8 = m->precision == 1 ? 1 : 0;      // GEMM-only activations in the P8 split format (see run_chunk_body)
     const int AP = p8 ? LF_A_P8 : 0;
     const int sd = &S == &m->enc ? 0 : 1;
-    const char* const an = sd == 0 ? "vae.encoder.layer" : "vae.decoder.layer";
     for (int i = 0; i < c.vae_depth; ++i) {
         const VAELayer& L = S.layers[i];
         SiteExps::VAE& E = m->ex.vae[sd][i];
         layernorm(w.vh, w.vln, L.lnw, L.lnb, M, H, 1e-5f, ACT_NONE, s, p8, w.status, 0, 0, E.ln);
-        audit(m, an, i, ".ln", w.vln, M, H, H, p8, s, &E.ln);
+        audit(m, w.vln, M, H, H, p8, s, &E.ln);
         linear(m, w.vln, H, L.qkv_w, nullptr, w.vqkv, 3 * H, M, 3 * H, H, ACT_NONE, nullptr, s, AP | (p8 ? LF_C_P8 : 0), nullptr, E.ln, E.qkv);   // q, k, v leave in P8
         AttnArgs a;
         a.qkv_p8 = p8; a.qkv_exp = E.qkv; a.o_exp = E.attn;
@@ -765,17 +770,17 @@ void run_vae_stack(artalk_model* m, const VAESide& S, int B, int T, int split, h
         a.O = w.vatt; a.ldo = H; a.o_bstride = (long)T * H;
         a.B = B; a.H = c.vae_heads; a.HD = H / c.vae_heads; a.Lq = T; a.Lk = T;
         a.scale = 1.0f / std::sqrt((float)H);      // hidden_dim**-0.5, NOT head_dim (bitwise_vae.py:198)
-        audit(m, an, i, ".qkv", w.vqkv, M, 3 * H, 3 * H, p8, s, &E.qkv);
+        audit(m, w.vqkv, M, 3 * H, 3 * H, p8, s, &E.qkv);
         a.split_q = split; a.split_k = split; a.out_p8 = p8; a.split16 = p8; a.status = p8 ? w.status : nullptr; a.cus = m->n_cus;
         launch_attention(a, s);
-        audit(m, an, i, ".attn_out", w.vatt, M, H, H, p8, s, &E.attn);
+        audit(m, w.vatt, M, H, H, p8, s, &E.attn);
         // the MLP reads the residual stream itself (no LayerNorm in front of it, bitwise_vae.py:139-145).  In f16x3 mode the
         // out-projection writes it a second time in P8 (w.vln) so that the MLP GEMM can stage it by LDS-DMA (the register-staged
         // kernel on fp32 rows took 36 us at M = 6400, a split pass + the small-grid kernel 4 + 15, the second copy from the epilogue 15)
         linear(m, w.vatt, H, L.out_w, L.out_b, w.vh, H, M, H, H, ACT_NONE, w.vh, s, AP, p8 ? w.vln : nullptr, E.attn, E.resid);
-        audit(m, an, i, ".residual", p8 ? w.vln : w.vh, M, H, H, p8, s, &E.resid);
+        audit(m, p8 ? w.vln : w.vh, M, H, H, p8, s, &E.resid);
         linear(m, p8 ? w.vln : w.vh, H, L.m1_w, L.m1_b, w.vmlp, F, M, F, H, ACT_GELU_TANH, nullptr, s, p8 ? (LF_A_P8 | LF_C_P8) : 0, nullptr, E.resid, E.mlp);
-        audit(m, an, i, ".mlp_hidden", w.vmlp, M, F, F, p8, s, &E.mlp);
+        audit(m, w.vmlp, M, F, F, p8, s, &E.mlp);
         linear(m, w.vmlp, F, L.m2_w, L.m2_b, w.vh, H, M, H, F, ACT_NONE, w.vh, s, AP, nullptr, E.mlp);
     }
 }
@@ -787,7 +792,7 @@ void run_reencode(artalk_model* m, int B, hipStream_t s) {
     const int H = c.vae_hidden, T = 100;
     Range r_re("artalk.vae.reencode_bsq");              // K16-K17: encoder, multi-scale BSQ, history features
     kbucket(m, KB_REENC);
-    audit(m, "vae.encoder.input(fp32 A)", -1, nullptr, w.enc_in, B * T, 128, 128, false, s, &m->ex.vae_enc_in);
+    audit(m, w.enc_in, B * T, 128, 128, false, s, &m->ex.vae_enc_in);
     linear(m, w.enc_in, 128, m->enc.in_w, m->enc.in_b, w.vh, H, B * T, H, 128, ACT_LEAKY02, nullptr, s, 0, nullptr, m->ex.vae_enc_in);
     run_vae_stack(m, m->enc, B, T, 0, s);
     linear(m, w.vh, H, m->enc.out_w, m->enc.out_b, w.enc_out, c.code_dim, B * T, c.code_dim, H, ACT_NONE, nullptr, s, LF_EXACT);
@@ -848,7 +853,7 @@ void run_chunk_body(artalk_model* m, int B, hipStream_t s, int n_reencode = -1) 
     roctxRangePushA("artalk.ar.history_kv");
     SiteExps& ex = m->ex;
     if (p8) launch_pack_split(w.prev_in, reinterpret_cast<unsigned int*>(w.prev_in_p8), (long)B * kNTok * kE, false, s, w.status, ex.hist_tok);   // one split for the 12 layers
-    audit(m, "ar.history_tokens", -1, nullptr, p8 ? w.prev_in_p8 : w.prev_in, B * kNTok, kE, kE, p8, s, &ex.hist_tok);
+    audit(m, p8 ? w.prev_in_p8 : w.prev_in, B * kNTok, kE, kE, p8, s, &ex.hist_tok);
     {
         // all blocks in one launch: N = depth x (E keys + E values), column group l = block l's weight rows / cache columns
         GemmArgs g;
@@ -903,7 +908,7 @@ void run_chunk_body(artalk_model* m, int B, hipStream_t s, int n_reencode = -1) 
             SiteExps::AR& E = ex.ar[l];
             if (l == 0) tap_copy(m, TAP_BLK0_IN, off, w.x, pn, kE, B, s);        // attn_feat entering attn_blocks[0] (app/models.py:100)
             if (!have_ln) launch_layernorm(ln_args(l, 0), s);
-            audit(m, "ar.block", l, ".ln1_mod", w.xmod, M, kE, kE, p8, s, &E.ln1);
+            audit(m, w.xmod, M, kE, kE, p8, s, &E.ln1);
             GemmArgs q;
             q.A = w.xmod; q.lda = kE; q.W = L.qkv_w; q.ldw = kE; q.bias = L.qkv_b; q.C = cache; q.ldc = 3 * kE;
             q.cmap = rowmap(pn, 2 * kNTok, kNTok + off); q.M = M; q.N = 3 * kE; q.K = kE; q.a_packed = p8; q.a_exp = E.ln1;
@@ -922,15 +927,15 @@ void run_chunk_body(artalk_model* m, int B, hipStream_t s, int n_reencode = -1) 
             a.B = B; a.H = c.ar_heads; a.HD = kE / c.ar_heads; a.Lq = pn; a.Lk = kNTok + off + pn; a.scale = 1.0f;
             a.l2norm = 1; a.qscale = L.qscale; a.out_p8 = p8; a.split16 = p8; a.status = p8 ? w.status : nullptr; a.o_exp = E.attn;
             launch_attention(a, s);
-            audit(m, "ar.block", l, ".attn_out", w.attn_out, M, kE, kE, p8, s, &E.attn);
+            audit(m, w.attn_out, M, kE, kE, p8, s, &E.attn);
             GemmArgs pj;
             pj.A = w.attn_out; pj.lda = kE; pj.W = L.proj_w; pj.ldw = kE; pj.bias = L.proj_b; pj.C = w.x; pj.ldc = kE;
             pj.gate = ada; pj.ldg = ldada; pj.gmap = amap; pj.R = w.x; pj.ldr = kE; pj.M = M; pj.N = kE; pj.K = kE; pj.a_packed = p8; pj.a_exp = E.attn;
             const LnArgs n2 = ln_args(l, 1);
             if (!gemm(m, pj, s, &n2)) launch_layernorm(n2, s);
-            audit(m, "ar.block", l, ".ln2_mod", w.xmod, M, kE, kE, p8, s, &E.ln2);
+            audit(m, w.xmod, M, kE, kE, p8, s, &E.ln2);
             linear(m, w.xmod, kE, L.ffn1_w, L.ffn1_b, w.ffn_h, 4 * kE, M, 4 * kE, kE, ACT_GELU_TANH, nullptr, s, p8 ? (LF_A_P8 | LF_C_P8) : 0, nullptr, E.ln2, E.ffn);
-            audit(m, "ar.block", l, ".ffn_hidden", w.ffn_h, M, 4 * kE, 4 * kE, p8, s, &E.ffn);
+            audit(m, w.ffn_h, M, 4 * kE, 4 * kE, p8, s, &E.ffn);
             GemmArgs f2;
             f2.A = w.ffn_h; f2.lda = 4 * kE; f2.W = L.ffn2_w; f2.ldw = 4 * kE; f2.bias = L.ffn2_b; f2.C = w.x; f2.ldc = kE;
             f2.gate = ada + kE; f2.ldg = ldada; f2.gmap = amap; f2.R = w.x; f2.ldr = kE; f2.M = M; f2.N = kE; f2.K = 4 * kE; f2.a_packed = p8; f2.a_exp = E.ffn;
@@ -953,10 +958,10 @@ void run_chunk_body(artalk_model* m, int B, hipStream_t s, int n_reencode = -1) 
     roctxRangePushA("artalk.vae.decode");               // K15
     kbucket(m, KB_VAE_DEC);
     launch_dec_input(w.prev_fdec, w.fhat, w.bits, m->dec_pos, w.dec_x, B, s);
-    audit(m, "vae.decoder.input(fp32 A)", -1, nullptr, w.dec_x, B * 200, c.code_dim, c.code_dim, false, s, &ex.vae_dec_in);
+    audit(m, w.dec_x, B * 200, c.code_dim, c.code_dim, false, s, &ex.vae_dec_in);
     linear(m, w.dec_x, c.code_dim, m->dec.in_w, m->dec.in_b, w.vh, H, B * 200, H, c.code_dim, ACT_LEAKY02, nullptr, s, 0, nullptr, ex.vae_dec_in);
     run_vae_stack(m, m->dec, B, 200, 100, s);
-    audit(m, "vae.decoder.output_head(fp32 A)", -1, nullptr, w.vh, B * 200, H, H, false, s, &ex.vae_dec_head);
+    audit(m, w.vh, B * 200, H, H, false, s, &ex.vae_dec_head);
     linear(m, w.vh, H, m->dec.out_w, m->dec.out_b, w.dec_out, c.motion_dim, B * 200, c.motion_dim, H, ACT_NONE, nullptr, s, 0, nullptr, ex.vae_dec_head);
     tap_copy(m, TAP_DEC_OUT, 0, w.dec_out, 200, c.motion_dim, B, s);               // dec_out before unnorm_with_stats (bitwise_vae.py:111)
     launch_dec_finish(w.dec_out, m->vae_mean, m->vae_std, m->enc_pos, w.motion_chunk, 100L * c.motion_dim, 0, w.enc_in, B, s, w.status);
@@ -1164,7 +1169,7 @@ int reserve(artalk_model* m, int maxB, int maxC) {
     for (void* p : m->ws_allocs) if (p) (void)hipFree(p);
     m->ws_allocs.clear();
     m->ws = Workspace();
-    m->stream_B = 0;          // the streaming history lived in the workspace that was just dropped: a session must begin again
+    m->stream_B = 0; m->stream_scales_ended = false;          // the streaming history lived in the workspace that was just dropped: a session must begin again
     m->status_pending = false;
     Workspace& w = m->ws;
     const int CD = c.w2v_conv_dim, Hs = c.w2v_hidden;
@@ -1207,6 +1212,68 @@ int reserve(artalk_model* m, int maxB, int maxC) {
     return ensure_stage(m, maxB, maxC);
 }
 
+// The P8 producer sites this configuration can run, named as the audit reports them.  Built once from the config (artalk_create):
+// unlike the audit's first-seen order it does not depend on which clips ran, so it is what a saved calibration is keyed by.
+void build_site_table(artalk_model* m) {
+    const artalk_config& c = m->cfg;
+    SiteExps& ex = m->ex;
+    auto add = [m](std::string name, int* e) {
+        m->site_of.emplace(e, (int)m->sites.size());
+        m->sites.push_back({std::move(name), e});
+    };
+    for (int i = 0; i + 1 < c.w2v_n_conv; ++i) add("w2v.conv" + std::to_string(i) + ".ln_gelu", &ex.conv[i]);
+    add("w2v.feature_projection.ln", &ex.fp_ln);
+    add("w2v.posconv.input(fp32 A)", &ex.posconv_in);
+    for (int i = 0; i < c.w2v_layers; ++i) {
+        const std::string p = "w2v.layer" + std::to_string(i);
+        SiteExps::W2V& E = ex.w2v[i];
+        add(p + ".ln1", &E.ln1); add(p + ".qkv", &E.qkv); add(p + ".attn_out", &E.attn); add(p + ".ln2", &E.ln2); add(p + ".ffn_hidden", &E.ffn);
+    }
+    add("ar.silu_cond", &ex.silu_cond);
+    add("ar.history_tokens", &ex.hist_tok);
+    for (int l = 0; l < c.ar_depth; ++l) {
+        const std::string p = "ar.block" + std::to_string(l);
+        SiteExps::AR& E = ex.ar[l];
+        add(p + ".ln1_mod", &E.ln1); add(p + ".attn_out", &E.attn); add(p + ".ln2_mod", &E.ln2); add(p + ".ffn_hidden", &E.ffn);
+    }
+    for (int sd = 0; sd < 2; ++sd)
+        for (int i = 0; i < c.vae_depth; ++i) {
+            const std::string p = std::string(sd == 0 ? "vae.encoder.layer" : "vae.decoder.layer") + std::to_string(i);
+            SiteExps::VAE& E = ex.vae[sd][i];
+            add(p + ".ln", &E.ln); add(p + ".qkv", &E.qkv); add(p + ".attn_out", &E.attn); add(p + ".residual", &E.resid); add(p + ".mlp_hidden", &E.mlp);
+        }
+    add("vae.encoder.input(fp32 A)", &ex.vae_enc_in);
+    add("vae.decoder.input(fp32 A)", &ex.vae_dec_in);
+    add("vae.decoder.output_head(fp32 A)", &ex.vae_dec_head);
+    add("style.input(fp32 A)", &ex.style_in);
+    for (int i = 0; i < c.style_layers; ++i) {
+        const std::string p = "style.layer" + std::to_string(i);
+        SiteExps::ST& E = ex.style[i];
+        add(p + ".in(fp32 A)", &E.h); add(p + ".attn_out(fp32 A)", &E.attn); add(p + ".norm1(fp32 A)", &E.h1); add(p + ".ffn_hidden(fp32 A)", &E.ffn);
+    }
+}
+
+// The one way new site exponents take effect (artalk_set_site_scales, artalk_calibrate): `next` is a complete SiteExps.  When anything
+// differs, the device is synchronised, the captured graphs (the exponents are kernel arguments of their launches) and the initial-history
+// cache are dropped, and an open streaming session ends - a session never mixes exponents.  Returns the number of sites changed.
+int commit_scales(artalk_model* m, const SiteExps& next) {
+    const int* a = reinterpret_cast<const int*>(&m->ex);
+    const int* b = reinterpret_cast<const int*>(&next);
+    int changed = 0;
+    for (size_t i = 0; i < sizeof(SiteExps) / sizeof(int); ++i) changed += a[i] != b[i];
+    if (changed) {
+        (void)hipSetDevice(m->device); (void)hipDeviceSynchronize();
+        for (auto& g : m->graphs) (void)hipGraphExecDestroy(g.second.exec);
+        m->graphs.clear();
+        m->init_hist[0].valid = m->init_hist[1].valid = false;
+        if (m->stream_B > 0) { m->stream_B = 0; m->stream_scales_ended = true; }
+        m->ex = next;
+    }
+    m->scales_changed = 0;
+    for (size_t i = 0; i < sizeof(SiteExps) / sizeof(int); ++i) m->scales_changed += a[i] != kActExp;
+    return changed;
+}
+
 }  // namespace
 
 // =================================================================================================== C ABI
@@ -1245,6 +1312,7 @@ int artalk_create(int device_id, const artalk_config* cfg, artalk_model** out) {
     if (init_ms_tables() != 0) { g_create_error = "uploading the interpolation tables to the device failed"; delete m; return ARTALK_EHIP; }
     attention_prepare();
     gemm_p8_prepare();
+    build_site_table(m);
     const int rc = build_registry(m);
     if (rc != ARTALK_OK) { g_create_error = m->err; artalk_destroy(m); return rc; }
     *out = m;
@@ -1456,9 +1524,10 @@ int artalk_set_audit(artalk_model* m, int enable) {
 // Per-site operand scales of the f16x3 format from the audit's maxima (SiteExps): after artalk_infer calls with the audit on - in EXACT-F32
 // mode, where no site can overflow on the way to a later one - every site whose max |x| * 2^e * headroom exceeds fp16's 65504 gets the
 // largest exponent e (<= the default 4, >= -8) that fits.  Exponents only go down (a later calibration on tamer inputs never undoes an
-// earlier one; artalk_reset_scales does).  Captured graphs and the initial-history cache are dropped when anything changed.
-// Returns the number of sites changed (>= 0), or a negative error: ARTALK_ESTATE without audit data, ARTALK_EINVAL for a non-finite
-// maximum (run the pass in f32 mode) or one that no exponent >= -8 can hold.
+// earlier one; artalk_reset_scales does).  All or nothing: the new exponents are computed into a copy and committed (commit_scales:
+// graphs, initial-history cache and streaming session dropped when anything changed) only after every site has passed.
+// Returns the number of sites changed (>= 0), or a negative error with the model untouched: ARTALK_ESTATE without audit data,
+// ARTALK_EINVAL for a non-finite maximum (run the pass in f32 mode) or one that no exponent >= -8 can hold.
 int artalk_calibrate(artalk_model* m, float headroom) {
     if (!m || !(headroom >= 1.0f)) return ARTALK_EINVAL;
     if (!m->audit_vals || m->audit_names.empty()) { m->err = "artalk_calibrate: no audit data (artalk_set_audit(1), then artalk_infer in f32 mode)"; return ARTALK_ESTATE; }
@@ -1467,10 +1536,12 @@ int artalk_calibrate(artalk_model* m, float headroom) {
     const int n = (int)m->audit_names.size();
     std::vector<unsigned int> bits((size_t)n);
     if (hipMemcpy(bits.data(), m->audit_vals, n * sizeof(unsigned int), hipMemcpyDeviceToHost) != hipSuccess) return ARTALK_EHIP;
-    int changed = 0;
+    SiteExps next = m->ex;
+    int* const base = reinterpret_cast<int*>(&m->ex);
+    int* const nbase = reinterpret_cast<int*>(&next);
     for (int i = 0; i < n; ++i) {
-        int* ex = m->audit_exp[i];
-        if (!ex) continue;
+        if (!m->audit_exp[i]) continue;
+        int* ex = nbase + (m->audit_exp[i] - base);      // the same member of the copy
         float mx;
         std::memcpy(&mx, &bits[i], sizeof(float));
         if (!std::isfinite(mx)) { m->err = "artalk_calibrate: site " + m->audit_names[i] + " is not finite (calibrate in f32 mode)"; return ARTALK_EINVAL; }
@@ -1478,17 +1549,9 @@ int artalk_calibrate(artalk_model* m, float headroom) {
         int e = *ex;
         while (e > -8 && (double)mx * std::ldexp(1.0, e) * headroom > 65504.0) --e;
         if ((double)mx * std::ldexp(1.0, e) > 65504.0) { m->err = "artalk_calibrate: site " + m->audit_names[i] + " exceeds every supported scale"; return ARTALK_EINVAL; }
-        if (e != *ex) { *ex = e; ++changed; }
+        *ex = e;
     }
-    if (changed) {
-        for (auto& g : m->graphs) (void)hipGraphExecDestroy(g.second.exec);      // the exponents are kernel arguments of the captured launches
-        m->graphs.clear();
-        m->init_hist[0].valid = m->init_hist[1].valid = false;
-    }
-    const int* p = reinterpret_cast<const int*>(&m->ex);
-    m->scales_changed = 0;
-    for (size_t i = 0; i < sizeof(SiteExps) / sizeof(int); ++i) m->scales_changed += p[i] != kActExp;
-    return changed;
+    return commit_scales(m, next);
 }
 int artalk_reset_scales(artalk_model* m) {
     if (!m) return ARTALK_EINVAL;
@@ -1506,6 +1569,37 @@ int artalk_get_scales(artalk_model* m, int* exps, int max_n) {
     const int n = std::min<int>((int)m->audit_names.size(), max_n);
     for (int i = 0; i < n; ++i) exps[i] = m->audit_exp[i] ? *m->audit_exp[i] : kActExp;
     return n;
+}
+// The static site table (build_site_table): names NUL-separated in table order; names_buf = NULL returns the count only.
+int artalk_scale_sites(const artalk_model* m, char* names_buf, int buf_len) {
+    if (!m) return ARTALK_EINVAL;
+    const int n = (int)m->sites.size();
+    if (!names_buf) return n;
+    int need = 0;
+    for (const auto& st : m->sites) need += (int)st.name.size() + 1;
+    if (buf_len < need) { const_cast<artalk_model*>(m)->err = "artalk_scale_sites: names need " + std::to_string(need) + " bytes"; return ARTALK_EINVAL; }
+    int pos = 0;
+    for (const auto& st : m->sites) { std::memcpy(names_buf + pos, st.name.c_str(), st.name.size() + 1); pos += (int)st.name.size() + 1; }
+    return n;
+}
+int artalk_get_site_scales(artalk_model* m, int* exps, int n) {
+    if (!m || !exps) return ARTALK_EINVAL;
+    if (n != (int)m->sites.size()) return fail(m, ARTALK_EINVAL, "artalk_get_site_scales: n must equal the site count " + std::to_string(m->sites.size()));
+    for (int i = 0; i < n; ++i) exps[i] = *m->sites[i].ex;
+    return ARTALK_OK;
+}
+// Validates every value before it changes anything, then commits through commit_scales (as artalk_calibrate does).
+int artalk_set_site_scales(artalk_model* m, const int* exps, int n) {
+    if (!m || !exps) return ARTALK_EINVAL;
+    if (n != (int)m->sites.size()) return fail(m, ARTALK_EINVAL, "artalk_set_site_scales: n must equal the site count " + std::to_string(m->sites.size()));
+    for (int i = 0; i < n; ++i)
+        if (exps[i] < -8 || exps[i] > kActExp)
+            return fail(m, ARTALK_EINVAL, "artalk_set_site_scales: exponent " + std::to_string(exps[i]) + " of site " + m->sites[i].name + " is outside [-8, 4]");
+    SiteExps next = m->ex;
+    int* const base = reinterpret_cast<int*>(&m->ex);
+    int* const nbase = reinterpret_cast<int*>(&next);
+    for (int i = 0; i < n; ++i) nbase[m->sites[i].ex - base] = exps[i];
+    return commit_scales(m, next);
 }
 int artalk_get_audit(artalk_model* m, char* names_buf, int buf_len, float* values, int max_n) {
     if (!m || !names_buf || !values || buf_len <= 0 || max_n <= 0) return ARTALK_EINVAL;
@@ -1611,7 +1705,7 @@ int artalk_infer(artalk_model* m, const float* audio_dev, int64_t audio_clip_str
     }
     HIPCHK(m, hipEventRecord(stg->done, s));   // pinned slot: no synchronisation, the slot is reused kStageSlots calls later
     stg->used = true;
-    m->stream_B = 0;   // the batch call reuses the workspace that holds the streaming history
+    m->stream_B = 0; m->stream_scales_ended = false;   // the batch call reuses the workspace that holds the streaming history
     HIPCHK(m, hipMemsetAsync(w.status, 0, 4 * sizeof(int), s));
     m->ev_used = 0; m->dom_events.clear(); m->marks.clear(); m->prof_stream = s;
     // level 3: every kernel of this call is launched with its own start / stop events (kernels.h ARTALK_LAUNCH) - on this thread, for the
@@ -1729,7 +1823,7 @@ int artalk_stream_begin(artalk_model* m, int B, const float* style_motion_dev, c
         run_style(m, (style_motion_dev && has_style) ? style_motion_dev : nullptr, B, s, encode_style);
         if (int rc = run_init_history(m, B, s)) return rc;
     }
-    m->stream_B = B;
+    m->stream_B = B; m->stream_scales_ended = false;
     if (int rc = publish_status(m, s)) return rc;
     HIPCHK(m, hipGetLastError());
     return ARTALK_OK;
@@ -1740,7 +1834,9 @@ int artalk_stream_begin(artalk_model* m, int B, const float* style_motion_dev, c
 int artalk_stream_chunk(artalk_model* m, const float* audio_dev, int64_t chunk_stride, float* out_motion_dev, int64_t out_stride,
                         void* stream) {
     if (!m || !audio_dev || !out_motion_dev) return ARTALK_EINVAL;
-    if (m->stream_B <= 0) return fail(m, ARTALK_ESTATE, "artalk_stream_chunk before artalk_stream_begin");
+    if (m->stream_B <= 0)
+        return fail(m, ARTALK_ESTATE, m->stream_scales_ended ? "the site scales changed since artalk_stream_begin; begin again"
+                                                             : "artalk_stream_chunk before artalk_stream_begin");
     (void)hipSetDevice(m->device);
     if (!stream && !m->own_stream) HIPCHK(m, hipStreamCreate(&m->own_stream));
     hipStream_t s = stream ? (hipStream_t)stream : m->own_stream;
@@ -1771,7 +1867,7 @@ int artalk_stream_chunk(artalk_model* m, const float* audio_dev, int64_t chunk_s
 
 int artalk_stream_end(artalk_model* m) {
     if (!m) return ARTALK_EINVAL;
-    m->stream_B = 0;      // the history in the workspace is dead; artalk_style_encode / artalk_reserve may use the workspace again
+    m->stream_B = 0; m->stream_scales_ended = false;      // the history in the workspace is dead; artalk_style_encode / artalk_reserve may use the workspace again
     return ARTALK_OK;
 }
 

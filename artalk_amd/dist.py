@@ -9,6 +9,7 @@ CPU tensors (tests/test_dist_gloo.py) and is what ``bench.py`` runs for N > 1.
 """
 from __future__ import annotations
 
+import hashlib
 import math
 import os
 import socket
@@ -92,7 +93,12 @@ def run_sharded(infer_fn, audios: Sequence[torch.Tensor], styles=None, gather: b
     ``audios`` only needs ``len()`` and indexing (a lazy sequence may build just the local clips); pass ``lengths`` (frames of
     EVERY clip of the job, e.g. ``seq_length(n_samples)``) or at least ``max_frames`` in that case.  With ``lengths`` - given, or
     derived here from every clip's sample count when neither is given - the gather is one collective and the host never waits
-    for the device (``gather_clips``); with only ``max_frames`` the lengths are exchanged and read back."""
+    for the device (``gather_clips``); with only ``max_frames`` the lengths are exchanged and read back.
+
+    The f16x3 site scales must be the same on every rank, else the bits of a clip depend on the rank that ran it: load one
+    ``save_scales`` file on every rank (``load_scales``), or calibrate on every rank and then call ``agree_scales``.  A model's
+    ``auto_calibrate`` recalibrates on its own rank's outlier batch alone, so inside a sharded job it too makes a clip's bits depend
+    on its rank (and on what that rank ran before); this function does not change the scales itself."""
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     if as_rank is not None:
@@ -136,3 +142,35 @@ def run_sharded(infer_fn, audios: Sequence[torch.Tensor], styles=None, gather: b
         k = len(shard_range(n, r, world))
         res.extend(allc[r * per: r * per + k])
     return res
+
+
+def agree_scales_dict(sites: dict, group=None, device: Optional[torch.device] = None) -> dict:
+    """Collective over ``{site name: exponent}``: the element-wise MIN over all ranks (a lower exponent holds everything a higher one
+    holds).  Every rank calls it.  The site lists are compared first (an all-gather of a hash of the names): if any rank's differs,
+    every rank raises ``RuntimeError`` before the reduction, so none is left waiting.  ``device``: where the int32 vector lives
+    (default: the current GPU for nccl, the CPU otherwise)."""
+    names = list(sites)
+    if device is None:
+        nccl = dist.get_backend(group) == "nccl"
+        device = torch.device("cuda", torch.cuda.current_device()) if nccl else torch.device("cpu")
+    digest = hashlib.sha256("\0".join(names).encode()).digest()
+    h = torch.tensor([int.from_bytes(digest[:8], "little", signed=True)], dtype=torch.int64, device=device)
+    world = dist.get_world_size(group)
+    all_h = torch.empty(world, dtype=torch.int64, device=device)
+    dist.all_gather_into_tensor(all_h, h, group=group)
+    all_h = all_h.cpu().tolist()
+    if len(set(all_h)) != 1:
+        bad = [r for r, v in enumerate(all_h) if v != all_h[0]]
+        raise RuntimeError(f"agree_scales: the site lists differ between ranks (ranks {bad} differ from rank 0): the models are not the "
+                           "same architecture")
+    v = torch.tensor([int(sites[n]) for n in names], dtype=torch.int32, device=device)
+    dist.all_reduce(v, op=dist.ReduceOp.MIN, group=group)
+    return dict(zip(names, [int(e) for e in v.cpu().tolist()]))
+
+
+def agree_scales(model, group=None) -> int:
+    """Give every rank's model the same f16x3 site scales: the element-wise minimum of all ranks' scales (``agree_scales_dict``), set
+    with ``model.load_scales``.  A collective: every rank calls it (after calibrating on its own clips, say).  Returns the number of
+    this rank's sites that changed."""
+    dev = model.device if dist.get_backend(group) == "nccl" else torch.device("cpu")
+    return model.load_scales(agree_scales_dict(model.scales(), group, dev))

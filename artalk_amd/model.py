@@ -21,6 +21,43 @@ import torch
 from . import capi
 from .config import ARTalkConfig
 
+SCALES_FORMAT = "artalk-site-scales/1"      # format tag of a save_scales file
+SCALE_EXP_MIN, SCALE_EXP_MAX = -8, 4          # the exponents artalk_calibrate can produce (2^4 = the default x16)
+
+
+def check_scales(sites, names: Sequence[str]) -> List[int]:
+    """``{site name: exponent}`` -> exponents in the order of ``names`` (a model's site table).  ``ValueError`` for a different set of
+    names (a few missing / extra ones are listed), an exponent that is not an int or one outside [-8, 4]; nothing else is touched."""
+    if not isinstance(sites, dict):
+        raise ValueError("site scales must be a {site name: exponent} dict")
+    missing = [n for n in names if n not in sites]
+    extra = [n for n in sites if n not in set(names)]
+    if missing or extra:
+        raise ValueError("the site scales do not match this model's site table ({} missing, e.g. {}; {} extra, e.g. {}): they belong to "
+                         "another architecture".format(len(missing), missing[:3], len(extra), extra[:3]))
+    exps = []
+    for n in names:
+        e = sites[n]
+        if isinstance(e, bool) or not isinstance(e, (int, np.integer)):
+            raise ValueError(f"site {n}: exponent {e!r} is not an int")
+        if not SCALE_EXP_MIN <= int(e) <= SCALE_EXP_MAX:
+            raise ValueError(f"site {n}: exponent {int(e)} is outside [{SCALE_EXP_MIN}, {SCALE_EXP_MAX}]")
+        exps.append(int(e))
+    return exps
+
+
+def read_scales_file(path) -> dict:
+    """The JSON document ``save_scales`` wrote; ``ValueError`` for another format tag or a document without ``sites``."""
+    import json
+    with open(path) as f:
+        doc = json.load(f)
+    if not isinstance(doc, dict) or doc.get("format") != SCALES_FORMAT:
+        raise ValueError("{}: not a site-scales file (format {!r}, expected {!r})".format(
+            path, doc.get("format") if isinstance(doc, dict) else None, SCALES_FORMAT))
+    if not isinstance(doc.get("sites"), dict):
+        raise ValueError(f"{path}: no 'sites' table")
+    return doc
+
 
 class _BasicVAE:
     """What the renderer side touches on ``model.basic_vae`` (reference ``inference.py:69``)."""
@@ -64,7 +101,10 @@ class BitwiseARModel:
         self.check_finite = True
         self._precision = "f16x3"   # default GEMM arithmetic (set_precision); applied when the weights are loaded
         self._latched_f32 = False   # an f16x3 call left fp16's range and recalibration did not cure it: the model stays in f32 mode from then on
-        self.auto_calibrate = True  # a tripped range guard first recalibrates the per-site operand scales on that batch (calibrate())
+        # a tripped range guard first recalibrates the per-site operand scales on that batch (inference_batch) or chunk (stream_chunk,
+        # which then raises: its session must begin again) and stays in f16x3 mode; f32 is latched only when nothing could be lowered
+        self.auto_calibrate = True
+        self._headroom = None       # headroom of the calibration the scales came from (save_scales), None = unknown / default scales
         self.style_cache_size = 64  # style conditions kept by style clip (set 0 to disable)
         self._style_cache = {}      # key -> (style tensor kept alive, (768,) condition on the device)
         self._stream = None      # dedicated HIP stream (hipGraph capture is not allowed on the legacy default stream)
@@ -183,9 +223,10 @@ class BitwiseARModel:
     def calibrate(self, audios, style_motions=None, headroom: float = 4.0) -> int:
         """Per-site operand scales of the f16x3 format from these clips (``artalk_calibrate``): one audit pass in exact-f32 mode
         (nothing can overflow there), then every site whose ``max|x| * scale * headroom`` would leave fp16's range gets the largest
-        power-of-two scale that fits - only those sites change.  Returns the number of sites changed.  ``inference_batch`` calls this
-        by itself, once, when a call trips the range guard; a serving setup calls it after ``load_state_dict`` with representative
-        clips (streaming sessions cannot recalibrate in flight)."""
+        power-of-two scale that fits - only those sites change.  Returns the number of sites changed.  All or nothing: if a site cannot
+        be held this raises ``RuntimeError`` and no scale changes.  ``inference_batch`` calls this by itself, once, when a call trips the
+        range guard, and ``stream_chunk`` on the chunk that tripped (the session then has to begin again).  A serving setup calls it
+        after ``load_state_dict`` with representative clips and keeps the result with ``save_scales``; later starts ``load_scales``."""
         L = capi.lib()
         prec, chk = self._precision, self.check_finite
         try:
@@ -203,12 +244,79 @@ class BitwiseARModel:
             self.set_precision(prec)
         self._style_cache = {}      # (conditions are keyed by precision only; the style encoder's GEMMs do not change, but stay safe)
         self._calibrations = getattr(self, "_calibrations", 0) + 1
+        self._headroom = float(headroom)
         return changed
+
+    # ------------------------------------------------------------------ portable site scales (artalk_scale_sites / *_site_scales)
+    def _site_names(self) -> List[str]:
+        """The model's site table: every P8 producer site the configuration can run, fixed at creation (artalk_scale_sites)."""
+        if getattr(self, "_site_table", None) is None:
+            L = capi.lib()
+            n = int(L.artalk_scale_sites(self._h, None, 0))
+            if n < 0:
+                raise RuntimeError("artalk_scale_sites failed: " + self._err())
+            buf = C.create_string_buffer(n * 64 + 1024)
+            if L.artalk_scale_sites(self._h, buf, len(buf)) != n:
+                raise RuntimeError("artalk_scale_sites failed: " + self._err())
+            self._site_table = [x.decode() for x in buf.raw.split(b"\0")[:n]]
+        return self._site_table
+
+    def _read_site_exps(self) -> List[int]:
+        names = self._site_names()
+        arr = (C.c_int * len(names))()
+        if capi.lib().artalk_get_site_scales(self._h, arr, len(names)) != capi.OK:
+            raise RuntimeError("artalk_get_site_scales failed: " + self._err())
+        return [int(v) for v in arr]
+
+    def _write_site_exps(self, exps: Sequence[int]) -> int:
+        arr = (C.c_int * len(exps))(*exps)
+        changed = int(capi.lib().artalk_set_site_scales(self._h, arr, len(exps)))
+        if changed < 0:
+            raise RuntimeError("artalk_set_site_scales failed: " + self._err())
+        return changed
+
+    def scales(self) -> dict:
+        """``{site name: exponent}`` of every site in table order (operand scale 2^e; 4 = the default x16)."""
+        if not self._loaded:
+            raise RuntimeError("load_state_dict must be called before scales")
+        return dict(zip(self._site_names(), self._read_site_exps()))
+
+    def load_scales(self, src) -> int:
+        """Restore site scales: ``src`` is a ``{site name: exponent}`` dict (``scales()``) or the path of a ``save_scales`` file.  Every
+        mismatch - another site set, an exponent that is not an int or lies outside [-8, 4], another format tag - raises ``ValueError``
+        before anything changes.  Returns the number of sites changed; when that is not 0 the captured graphs are dropped and an open
+        streaming session ends.  The file only proves the same architecture: matching it to its checkpoint is the caller's business."""
+        if not self._loaded:
+            raise RuntimeError("load_state_dict must be called before load_scales")
+        headroom = None
+        if isinstance(src, dict):
+            sites = src
+        else:
+            doc = read_scales_file(src)
+            sites, headroom = doc["sites"], doc.get("headroom")
+        exps = check_scales(sites, self._site_names())
+        changed = self._write_site_exps(exps)
+        if changed:
+            self._n_streams = 0                 # the library ended the session
+            self._style_cache = {}
+        if not isinstance(src, dict) or changed:
+            self._headroom = headroom
+        return changed
+
+    def save_scales(self, path):
+        """Write the site scales as JSON: ``format`` (``artalk-site-scales/1``), ``sites`` (every site, ``{name: exponent}``),
+        ``config`` (the ARTalkConfig fields, for humans) and the ``headroom`` of the last calibration (or null).  Data only."""
+        import dataclasses
+        import json
+        doc = {"format": SCALES_FORMAT, "sites": self.scales(), "config": dataclasses.asdict(self.cfg), "headroom": self._headroom}
+        with open(path, "w") as f:
+            json.dump(doc, f, indent=1)
 
     def reset_scales(self):
         """Back to the default scale (x16) at every site (``artalk_reset_scales``)."""
         if capi.lib().artalk_reset_scales(self._h) != capi.OK:
             raise RuntimeError("artalk_reset_scales failed: " + self._err())
+        self._headroom = None
 
     def _trip_to_f32(self, what: str):
         """An activation left fp16's range in f16x3 mode: switch to exact-f32 GEMMs for good (a checkpoint that trips once will
@@ -232,8 +340,9 @@ class BitwiseARModel:
 
     def set_precision(self, mode):
         """'f16x3' / 1 (default): fp16 operand-split MFMA GEMMs, fp32-class accuracy (more accurate than the fp32 MFMA chain on
-        every fixture) but operands must stay below fp16's 65504; 'f32' / 0: exact fp32 MFMA.  ``inference_batch`` falls back to
-        'f32' for a call whose f16x3 result is not finite (an fp16 overflow in some activation)."""
+        every fixture) but operands times their site's scale must stay below fp16's 65504; 'f32' / 0: exact fp32 MFMA.  When an f16x3
+        call trips the range guard, ``inference_batch`` (and ``stream_chunk``) first recalibrate the site scales (``auto_calibrate``)
+        and stay in f16x3 mode; only if nothing could be lowered do they switch to 'f32' and stay there."""
         code = {"f32": 0, "f16x3": 1}.get(mode, mode)
         if code not in (0, 1):
             raise ValueError("precision mode must be 'f32' or 'f16x3'")
@@ -370,7 +479,9 @@ class BitwiseARModel:
     @torch.no_grad()
     def stream_begin(self, n_streams: int, style_motions: Optional[Sequence[Optional[torch.Tensor]]] = None):
         """Open ``n_streams`` parallel streams: style condition + initial history (app/models.py:67-73,86-89).  The session
-        lasts until ``stream_end()``, the next ``stream_begin`` or any ``inference*`` call (they share the workspace)."""
+        lasts until ``stream_end()``, the next ``stream_begin`` or any ``inference*`` call (they share the workspace), or until the
+        site scales change (``calibrate``, ``load_scales``, a range trip in ``stream_chunk``): a session never mixes scales.  The
+        session's style rows are kept for a recalibration on a chunk that trips the range guard."""
         if not self._loaded:
             raise RuntimeError("load_state_dict must be called before inference")
         dev = self._device
@@ -402,7 +513,13 @@ class BitwiseARModel:
         number of real samples of each stream in this chunk (default: all 64000).  The call then also returns the number of
         valid frames per stream, ``ceil(total_samples * 25 / 16000) - 100 * chunks_before`` clipped to [0, 100] - the rows the
         reference keeps after its final truncation (app/models.py:115).  A stream whose clip has ended is fed zeros
-        (``n_valid = 0``) until the session ends; its rows are ignored."""
+        (``n_valid = 0``) until the session ends; its rows are ignored.
+
+        Range trip in f16x3 mode (status non-zero): the session's history already holds the damaged chunk, so the session ends and
+        this raises ``RuntimeError`` ("... begin the streaming session again").  With ``auto_calibrate`` on, the site scales are first
+        recalibrated on that chunk (each stream's 64 000 samples as a one-chunk clip, with the session's style rows): if sites changed
+        the model stays in f16x3 mode; if nothing could be lowered, or the calibration failed, it switches to f32 for good.  With
+        ``auto_calibrate`` off it switches to f32 at once."""
         B = getattr(self, "_n_streams", 0)
         if B <= 0:
             raise RuntimeError("stream_chunk before stream_begin")
@@ -423,6 +540,14 @@ class BitwiseARModel:
         if self._precision == "f16x3" and self.check_finite and self.status() != 0:
             # the history of the session already contains the damaged chunk: the session cannot be repaired in place
             self.stream_end()
+            if self.auto_calibrate:
+                try:
+                    changed = self.calibrate([x[b] for b in range(B)], self._stream_style)
+                except RuntimeError:
+                    changed = 0
+                if changed > 0:
+                    raise RuntimeError(f"artalk_amd: an activation left fp16's range during a streaming chunk; recalibrated {changed} "
+                                       "site scale(s) on that chunk and the model stays in f16x3 mode - begin the streaming session again")
             self._trip_to_f32("streaming chunk")
             raise RuntimeError("artalk_amd: an activation left fp16's range during a streaming chunk; the model is now in f32 "
                                "mode - begin the streaming session again")

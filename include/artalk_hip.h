@@ -123,8 +123,10 @@ const char* artalk_flame_last_error(const artalk_flame* f);
  * the one synchronisation on this boundary, paid only by callers that ask; `stream` is ignored); artalk_poll_status never
  * blocks and returns ARTALK_EBUSY while the call is still running.  Bits: 0 a logit was NaN/Inf (the pairwise argmax of
  * app/models.py:104 would silently turn it into a 0 bit), 1 a re-encoder output was NaN/Inf, 2 a FLAME code was NaN/Inf,
- * 3 an activation exceeded the range of the P8 split format (|x| >= 4094) where it was produced.  Non-zero in f16x3 mode
- * means an activation left fp16's range: redo the call in f32 mode (the Python host does, and stays in f32). */
+ * 3 an activation exceeded the range of its site's P8 scale where it was produced (|x| * 2^e >= 65504, e = the site's exponent,
+ * artalk_get_site_scales; |x| >= 4094 at the default e = 4).  Non-zero in f16x3 mode means an activation left fp16's range: the Python
+ * host first recalibrates the site scales on that batch (artalk_calibrate) and redoes the call in f16x3 mode; only when nothing could
+ * be lowered does it redo the call in f32 mode and stay there. */
 int artalk_get_status(artalk_model* m, int* flags, void* stream);
 int artalk_poll_status(artalk_model* m, int* flags);
 /* Several calls in flight (a serving loop that enqueues batch i+1 before it looks at batch i): every call that publishes a status
@@ -152,7 +154,7 @@ int artalk_get_profile(artalk_model* m, double* out, int n);
  * 4 history K/V + glue, 5..9 scale steps 0..4, 10 VAE decode, 11 re-encode, 12 other - and out[13] = kernels timed (n >= 14).
  * bench.py reports it next to the stages' event times as `budget_ms`. */
 int artalk_get_kernel_sums(artalk_model* m, double* out, int n);
-/* GEMM arithmetic: 0 (default) = exact fp32 on v_mfma_f32_32x32x2_f32; 1 = "f16x3": every fp32 operand split into two
+/* GEMM arithmetic: 0 (the library's default; the Python host selects 1) = exact fp32 on v_mfma_f32_32x32x2_f32; 1 = "f16x3": every fp32 operand split into two
  * fp16 values (22 significand bits), three fp16 MFMA products accumulated in fp32 - fp32-class accuracy (parity tests run in
  * both modes) at 5.3x the matrix-core rate; the logit / code heads stay on the fp32 path in both modes. */
 int artalk_set_precision(artalk_model* m, int mode);
@@ -178,11 +180,25 @@ int artalk_get_audit(artalk_model* m, char* names_buf, int buf_len, float* value
  * artalk_calibrate reads the maxima of an audit pass (artalk_set_audit(1) + artalk_infer in EXACT-F32 mode on representative clips)
  * and lowers e at every site where max|x| * 2^e * headroom would exceed fp16's 65504, per site, down to e = -8.  Only those sites change
  * (everything else stays bit-identical); exponents never go up again until artalk_reset_scales.  Returns the number of sites changed,
- * or a negative ARTALK_E* code.  artalk_get_scales: exps[i] = exponent of audit site i (the order of artalk_get_audit).
- * The Python host calls this by itself when a call trips the range guard (status bit 3) and re-runs the call in f16x3 mode. */
+ * or a negative ARTALK_E* code.  All or nothing: if any site fails (ARTALK_EINVAL: a non-finite maximum, or one no exponent can hold), no
+ * exponent changes and the captured graphs are kept.  artalk_get_scales: exps[i] = exponent of audit site i, in the order of artalk_get_audit
+ * (first seen during the audit pass: only the sites that ran, so it depends on the clips audited); artalk_*_site_scales below use the
+ * fixed table order instead.  The Python host calls this by itself when a call trips the range guard (status bit 3) and re-runs the call
+ * in f16x3 mode. */
 int artalk_calibrate(artalk_model* m, float headroom);
 int artalk_reset_scales(artalk_model* m);
 int artalk_get_scales(artalk_model* m, int* exps, int max_n);
+/* The site table: every P8 producer site this configuration can run, fixed at artalk_create from the config alone, with the names the
+ * audit reports (w2v.layer3.ffn_hidden, ar.block0.ln1_mod, ...).  It is the order a saved calibration is keyed by.  artalk_scale_sites
+ * returns the number of sites n and writes their names NUL-separated in table order (names_buf = NULL: only n; a buffer too small:
+ * ARTALK_EINVAL).  artalk_get_site_scales writes the n exponents in table order (n must equal the site count).
+ * artalk_set_site_scales restores them: n must equal the site count and every exponent must lie in [-8, 4] (what artalk_calibrate
+ * can produce), else ARTALK_EINVAL with nothing changed.  Returns the number of sites whose exponent changed; if any did, it
+ * synchronises the device, drops the captured graphs and the initial-history cache and ends an open streaming session (the next
+ * artalk_stream_chunk fails with ARTALK_ESTATE: a session never mixes exponents).  Setting the values the model holds changes nothing. */
+int artalk_scale_sites(const artalk_model* m, char* names_buf, int buf_len);
+int artalk_get_site_scales(artalk_model* m, int* exps, int n);
+int artalk_set_site_scales(artalk_model* m, const int* exps, int n);
 /* Intermediate taps: device buffers that correspond to intermediates of the reference, for parity tests that localise a difference to
  * a kernel group (tests/test_taps_gpu.py against tests/golden/taps_*.npz, captured from the reference by oracle/make_golden_taps.py).
  * While a tap buffer is set, artalk_infer runs the AR/VAE body eagerly as one clip group and copies, for chunk index j and clip
