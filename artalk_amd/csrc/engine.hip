@@ -135,9 +135,11 @@ struct artalk_model {
     std::vector<void*> allocs;      // weights (model lifetime)
     std::vector<void*> ws_allocs;   // workspace (re-allocated when a larger batch arrives)
     int64_t weight_bytes = 0;
-    struct PackRange { const float* base; int64_t n; unsigned int* packed; };
-    std::vector<PackRange> wranges;   // every weight allocation and its packed f16x3 copy (built at finalize)
-    int precision = 0;                // 0: fp32 MFMA everywhere, 1: f16x3 split GEMMs (heads stay fp32)
+    struct PackRange { const float* base; int64_t n; unsigned int* packed; uint16_t* bf16; };
+    std::vector<PackRange> wranges;   // every weight allocation, its packed f16x3 copy (built at finalize) and its bf16 copy (built on
+                                      // the first switch to precision mode 2: ensure_bf16_copy)
+    int precision = 0;                // 0: fp32 MFMA everywhere, 1: f16x3 split GEMMs, 2: bf16 GEMMs (heads stay fp32 in 1 and 2)
+    bool have_bf16 = false;           // the bf16 weight copy exists
     int splitk_tiles = 192, splitk_target = 384;   // split-K when the grid has fewer tiles than splitk_tiles; aim at splitk_target workgroups
     // headroom audit (artalk_set_audit): max |x| * 16 at every producer of a P8 operand, by site name
     bool audit = false;
@@ -156,8 +158,9 @@ struct artalk_model {
     // The INITIAL history of a clip (app/models.py:86-89: encode + quantise an all-zero motion) is a function of the weights only - the
     // same bits, decoder features and history tokens for every clip of every call.  It is computed once per precision mode (for ONE
     // clip, through the same run_reencode as every later history) and broadcast to the batch afterwards; only the style token in
-    // front of the history tokens differs per clip (launch_vq_embed).  [0] exact-f32 mode, [1] f16x3 mode.
-    struct InitHistory { uint8_t* bits = nullptr; float *fdec = nullptr, *msfeat = nullptr; bool valid = false; } init_hist[2];
+    // front of the history tokens differs per clip (launch_vq_embed).  Indexed by precision mode: [0] exact f32, [1] f16x3, [2] bf16.
+    struct InitHistory { uint8_t* bits = nullptr; float *fdec = nullptr, *msfeat = nullptr; bool valid = false; } init_hist[3];
+    void invalidate_init_hist() { for (auto& ih : init_hist) ih.valid = false; }
     // intermediate taps (artalk_set_tap): parity tests compare these device buffers with intermediates captured from the reference
     float* tap = nullptr; int tap_B = 0, tap_maxch = 0, tap_chunk = 0;
     std::vector<uint32_t> cu_mask;    // artalk_set_cu_mask: the library's own streams are restricted to these compute units
@@ -260,7 +263,7 @@ T* dalloc(artalk_model* m, int64_t n) { return dalloc_in<T>(m->allocs, n); }
 float* walloc(artalk_model* m, int64_t n) {
     m->weight_bytes += n * 4;
     float* p = dalloc<float>(m, n);
-    m->wranges.push_back({p, n, nullptr});
+    m->wranges.push_back({p, n, nullptr, nullptr});
     return p;
 }
 
@@ -268,6 +271,34 @@ const unsigned int* packed_of(const artalk_model* m, const float* w) {
     for (const auto& r : m->wranges)
         if (r.packed && w >= r.base && w < r.base + r.n) return r.packed + (w - r.base);
     return nullptr;
+}
+
+// the bf16 copy of a weight (same indexing), or null before ensure_bf16_copy / for a pointer that is no weight
+const void* bf16_of(const artalk_model* m, const float* w) {
+    for (const auto& r : m->wranges)
+        if (r.bf16 && w >= r.base && w < r.base + r.n) return r.bf16 + (w - r.base);
+    return nullptr;
+}
+
+// Precision mode 2 reads every weight from a bf16 copy: built once, on the first switch to the mode (a model that never runs bf16
+// allocates nothing for it).  One allocation, each weight at a 64-element aligned offset; weight_bytes counts 2 bytes per parameter.
+int ensure_bf16_copy(artalk_model* m) {
+    if (m->have_bf16) return ARTALK_OK;
+    int64_t total = 0;
+    for (const auto& r : m->wranges) total += (r.n + 63) / 64 * 64;
+    uint16_t* base = dalloc<uint16_t>(m, total);
+    if (!base) return fail(m, ARTALK_EHIP, "hipMalloc failed for the bf16 weight copy");
+    HIPCHK(m, hipDeviceSynchronize());      // (dalloc's zero fill runs on the null stream)
+    int64_t off = 0;
+    for (auto& r : m->wranges) {
+        r.bf16 = base + off;
+        launch_pack_bf16(r.base, r.bf16, r.n, nullptr);
+        off += (r.n + 63) / 64 * 64;
+    }
+    HIPCHK(m, hipDeviceSynchronize());
+    for (const auto& r : m->wranges) m->weight_bytes += r.n * 2;     // counted once the copy exists
+    m->have_bf16 = true;
+    return ARTALK_OK;
 }
 
 void add_slot(artalk_model* m, const std::string& key, std::vector<int64_t> shape, SlotKind kind, float* dst,
@@ -492,11 +523,19 @@ bool gemm(artalk_model* m, const GemmArgs& g0, hipStream_t s, const LnArgs* fuse
         g.Wp = packed_of(m, g.W);
         split = gemm_f16s_eligible(g);
     }
+    const bool bf16 = m->precision == 2 && !g.exact;
+    if (bf16) {
+        g.Wb = bf16_of(m, g.W);
+        if (!g.Wb || ((unsigned long long)g.Wb & 15) || (g.ldw & 7)) {
+            m->err = "internal: bf16 GEMM without an aligned bf16 weight copy"; m->sticky_error = true; return false;
+        }
+        if (g.a_packed) { m->err = "internal: P8 activation handed to a bf16 GEMM"; m->sticky_error = true; return false; }
+    }
     // split-K for grids that would leave most CUs idle (small-M scale steps): S workgroups per output tile
     const Workspace& cw = m->view ? *m->view : m->ws;
     const bool sm_path = split && g.a_packed && gemm_p8_sm_eligible(g) && !gemm_p8_eligible(g);
     if (g.batch == 1 && g.amode == 0 && cw.splitk && g.K >= 256) {
-        const int tiles = gemm_tile_count(g, split);
+        const int tiles = bf16 ? gemm_bf16_tile_count(g) : gemm_tile_count(g, split);
         const int lim = m->splitk_tiles, tgt = m->splitk_target;
         if (sm_path) {
             // Small-grid LDS-DMA kernel (64x64 tiles).  These launches are latency-bound: measured with cold weights, replayed from a
@@ -550,7 +589,8 @@ bool gemm(artalk_model* m, const GemmArgs& g0, hipStream_t s, const LnArgs* fuse
         }
     }
     const bool dominant = !m->in_body && g.M > 0 &&
-                          (split ? (g.a_packed ? (gemm_p8_eligible(g) && gemm_p8_variant(g) >= 1) : gemm_f16s_config(g) == 0) : gemm_config(g) == 4);
+                          (bf16 ? gemm_bf16_config(g) == 1 :
+                           split ? (g.a_packed ? (gemm_p8_eligible(g) && gemm_p8_variant(g) >= 1) : gemm_f16s_config(g) == 0) : gemm_config(g) == 4);
     size_t i0 = 0, i1 = 0;
     if (m->profiling && dominant) next_event(m, s, &i0);
     if (g.a_packed && !split) { m->err = "internal: P8 activation handed to an fp32 GEMM"; m->sticky_error = true; return false; }
@@ -562,7 +602,8 @@ bool gemm(artalk_model* m, const GemmArgs& g0, hipStream_t s, const LnArgs* fuse
                           !g.gate && (g.ldr % 4) == 0 &&      // (the epilogue's 16-byte path: every pointer and row start aligned)
                           (((unsigned long long)g.C | (unsigned long long)c2 | (unsigned long long)g.bias | (unsigned long long)g.R) & 15) == 0;
     if (!c2_fused) g.c2 = nullptr;
-    if (dma) launch_gemm_p8(g, s);
+    if (bf16) launch_gemm_bf16(g, s);
+    else if (dma) launch_gemm_p8(g, s);
     else if (split && gemm_p8_sm_eligible(g)) launch_gemm_p8_sm(g, s);     // P8 activation, small grid (AR/VAE scale steps)
     else if (split) launch_gemm_f16s(g, s);
     else launch_gemm(g, s);
@@ -806,7 +847,7 @@ int run_init_history(artalk_model* m, int B, hipStream_t s) {
     const artalk_config& c = m->cfg;
     struct Restore { artalk_model* m; ~Restore() { kbucket(m, KB_OTHER); } } restore{m};
     Workspace& w = m->ws;
-    artalk_model::InitHistory& ih = m->init_hist[m->precision == 1 ? 1 : 0];
+    artalk_model::InitHistory& ih = m->init_hist[m->precision];
     const long nb = (long)kNTok * c.code_dim, nf = 100L * c.code_dim * 4, nm = 180L * c.code_dim * 4;
     if (!ih.valid) {
         if (!ih.bits) {
@@ -1080,7 +1121,7 @@ int run_chunk_body_graphs(artalk_model* m, int B, hipStream_t s, int n_next = -1
         const int gsz = b0[h + 1] - b0[h];
         const int need = std::max(0, std::min(n_next - b0[h], gsz));      // clips of this group that have a next chunk
         nres[h] = std::min(gsz, (need + 7) / 8 * 8);
-        keys[h] = ((long long)(((B * 8 + NS) * 4 + h) * 2 + m->precision)) * 4096 + nres[h];
+        keys[h] = ((long long)(((B * 8 + NS) * 4 + h) * 3 + m->precision)) * 4096 + nres[h];     // (3 precision modes)
     }
     for (int h = 0; h < NS; ++h) {
         views[h] = clip_view(m, b0[h], h);
@@ -1265,7 +1306,7 @@ int commit_scales(artalk_model* m, const SiteExps& next) {
         (void)hipSetDevice(m->device); (void)hipDeviceSynchronize();
         for (auto& g : m->graphs) (void)hipGraphExecDestroy(g.second.exec);
         m->graphs.clear();
-        m->init_hist[0].valid = m->init_hist[1].valid = false;
+        m->invalidate_init_hist();
         if (m->stream_B > 0) { m->stream_B = 0; m->stream_scales_ended = true; }
         m->ex = next;
     }
@@ -1464,6 +1505,7 @@ int artalk_finalize_weights(artalk_model* m) {
         launch_pack_split(r.base, r.packed, r.n, true, nullptr);
     }
     HIPCHK(m, hipDeviceSynchronize());
+    if (m->precision == 2) { if (int rc = ensure_bf16_copy(m)) return rc; }
     m->finalized = true;
     return ARTALK_OK;
 }
@@ -1478,8 +1520,12 @@ int64_t artalk_weight_bytes(const artalk_model* m) { return m ? m->weight_bytes 
 
 int artalk_set_profiling(artalk_model* m, int level) { if (!m || level < 0 || level > 3) return ARTALK_EINVAL; m->profiling = level; return ARTALK_OK; }
 int artalk_set_precision(artalk_model* m, int mode) {
-    if (!m || (mode != 0 && mode != 1)) return ARTALK_EINVAL;
-    m->precision = mode;   // captured graphs are keyed by mode: switching costs nothing and keeps both sets
+    if (!m || mode < 0 || mode > 2) return ARTALK_EINVAL;
+    if (mode == 2 && m->finalized) {      // (before finalize: artalk_finalize_weights builds the copy)
+        (void)hipSetDevice(m->device);
+        if (int rc = ensure_bf16_copy(m)) return rc;
+    }
+    m->precision = mode;   // captured graphs are keyed by mode: switching costs nothing and keeps every set
     return ARTALK_OK;
 }
 int artalk_set_graphs(artalk_model* m, int enable) {
@@ -1493,7 +1539,7 @@ int artalk_set_graphs(artalk_model* m, int enable) {
     (void)hipSetDevice(m->device); (void)hipDeviceSynchronize();
     for (auto& g : m->graphs) (void)hipGraphExecDestroy(g.second.exec);
     m->graphs.clear();
-    m->init_hist[0].valid = m->init_hist[1].valid = false;      // "the same run_reencode as every later history": the split-K tuning changed
+    m->invalidate_init_hist();      // "the same run_reencode as every later history": the split-K tuning changed
     return ARTALK_OK;
 }
 // number of captured body graphs the model holds (bounded: run_chunk_body_graphs) / captures since the model was created
@@ -1560,7 +1606,7 @@ int artalk_reset_scales(artalk_model* m) {
     m->scales_changed = 0;
     for (auto& g : m->graphs) (void)hipGraphExecDestroy(g.second.exec);
     m->graphs.clear();
-    m->init_hist[0].valid = m->init_hist[1].valid = false;
+    m->invalidate_init_hist();
     return ARTALK_OK;
 }
 // exps[i] = exponent of audit site i (the order of artalk_get_audit); returns the number written
@@ -1657,7 +1703,7 @@ int artalk_set_cu_mask(artalk_model* m, const uint32_t* mask, int n_words) {
     }
     for (auto& g : m->graphs) (void)hipGraphExecDestroy(g.second.exec);      // the GEMM grids were captured for the old CU count
     m->graphs.clear();
-    m->init_hist[0].valid = m->init_hist[1].valid = false;
+    m->invalidate_init_hist();
     return ARTALK_OK;
 }
 
@@ -2004,6 +2050,44 @@ int artalk_op_gemm_f16s(const float* A, int64_t lda, const float* W, const float
     (void)hipStreamSynchronize(s);
     (void)hipFree(wp);
     if (ap) (void)hipFree(ap);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+
+// bf16 GEMM on fp32 inputs (W is converted into a temporary bf16 copy); C[m, n] = R + gate * act(bf16(A) bf16(W)^T + bias), ldc = ldg =
+// ldr = N; A and W 16-byte aligned.  force_cfg: -1 = the engine's own tile choice, else bits 0-7 = tile of gemm_bf16_kernel (0: 64x64, 1: 128x128, 2: 32x128, 0xff: own
+// choice), bits 8-15 = split-K factor (slabs in a temporary, finished by the split-K reduce pass), bits 16-23 = grid.z batch (A, W,
+// bias, R and C of batch z follow each other: strides M*lda, N*K, N, M*N, M*N), bit 24 = amode 1 (grouped positional-conv window:
+// pc_cin = 64, taps = K / 64, pad = taps / 2, rows of T = bits 25-30 frames each; the batch stride of A is then 64 columns).
+int artalk_op_gemm_bf16(const float* A, int64_t lda, const float* W, const float* bias, const float* gate, const float* R, float* C,
+                        int M, int N, int K, int act, int force_cfg, void* stream) {
+    if (!A || !W || !C || K % 32 != 0 || M < 0 || N <= 0 || lda <= 0 || lda % 4 != 0) return ARTALK_EINVAL;
+    if (((uintptr_t)A | (uintptr_t)W) & 15) return ARTALK_EINVAL;     // both are read with 16-byte vector loads (every batch's too: K % 32 == 0)
+    const int cfg = force_cfg < 0 ? 0xff : force_cfg & 0xff;
+    const int S = force_cfg < 0 ? 1 : std::max(1, (force_cfg >> 8) & 0xff);
+    const int nb = force_cfg < 0 ? 1 : std::max(1, (force_cfg >> 16) & 0xff);
+    const int am = force_cfg < 0 ? 0 : (force_cfg >> 24) & 1;
+    const int T = force_cfg < 0 ? 0 : (force_cfg >> 25) & 63;
+    if ((cfg > 2 && cfg != 0xff) || S > 16 || (am && (T <= 0 || M % T != 0 || K % 64 != 0 || nb * 64 > lda))) return ARTALK_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    void* wb = nullptr;
+    float* part = nullptr;
+    if (hipMalloc(&wb, (size_t)nb * N * K * 2) != hipSuccess) return ARTALK_EHIP;
+    if (S > 1 && hipMalloc(&part, (size_t)S * nb * M * N * 4) != hipSuccess) { (void)hipFree(wb); return ARTALK_EHIP; }
+    launch_pack_bf16(W, wb, (long)nb * N * K, s);
+    GemmArgs g;
+    g.A = A; g.lda = lda; g.W = W; g.Wb = wb; g.ldw = K; g.bias = bias; g.C = C; g.ldc = N; g.gate = gate; g.ldg = N; g.R = R; g.ldr = N;
+    g.M = M; g.N = N; g.K = K; g.act = act; g.force_cfg = cfg == 0xff ? -1 : cfg;
+    g.batch = nb; g.sA = am ? 64 : (long)M * lda; g.sW = (long)N * K; g.sBias = bias ? N : 0; g.sC = (long)M * N; g.sR = R ? (long)M * N : 0;
+    if (am) { g.amode = 1; g.pc_T = T; g.pc_tstride = T; g.pc_pad = K / 64 / 2; g.pc_cin = 64; }
+    if (S > 1) {
+        if (nb > 1 || am) { (void)hipFree(wb); (void)hipFree(part); return ARTALK_EINVAL; }     // (split-K is a batch-1 plain-window form)
+        g.splitk = S; g.partial = part;
+    }
+    launch_gemm_bf16(g, s);
+    if (S > 1) launch_splitk_reduce(g, s);
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(wb);
+    if (part) (void)hipFree(part);
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
 }
 

@@ -53,6 +53,7 @@ struct GemmArgs {
     const float* A = nullptr; long lda = 0;
     const float* W = nullptr; long ldw = 0;
     const unsigned int* Wp = nullptr;   // optional copy of W in the P8 split format (common.h), same ld: f16x3 split path
+    const void* Wb = nullptr;            // copy of W in bf16, same ld: bf16 path (gemm_bf16.hip)
     int c_p8 = 0;                        // 1: write C in the P8 split format (the consumer is a split GEMM); every split-GEMM epilogue and the split-K reduce
     int a_packed = 0;                    // 1: A is already in the P8 split format (written so by its producer kernel), f16x3 path only
     // site exponents of the P8 format (common.h): A was written (a_packed) or is split while staging (fp32 A) with scale 2^a_exp; a P8
@@ -104,6 +105,11 @@ int gemm_p8_variant(const GemmArgs& g);       // 0: gemm_p8_2wgp_kernel (persist
 bool gemm_p8_sm_eligible(const GemmArgs& g);   // both operands in P8, any grid (split-K capable): small-tile LDS-DMA kernel
 void launch_gemm_p8_sm(const GemmArgs& g, hipStream_t s);
 bool gemm_p8_pp_ok(const GemmArgs& g);      // operands within the 32-bit DMA offsets of the ping-pong kernel (launch_gemm_p8_sm cfg 30 / 31 / 33)
+// bf16 GEMM (precision mode 2, gemm_bf16.hip): bf16(A) * bf16(W)^T with fp32 accumulation; A is fp32, W is read from g.Wb
+void launch_gemm_bf16(const GemmArgs& g, hipStream_t s);
+int gemm_bf16_config(const GemmArgs& g);      // 0: 64x64, 1: 128x128 (large grids), 2: 32x128 (M <= 32)
+int gemm_bf16_tile_count(const GemmArgs& g);  // output tiles of that configuration
+void launch_pack_bf16(const float* in, void* out, long n, hipStream_t s);   // fp32 -> bf16 copy, same indexing
 // wav2vec2 positional convolution (16 groups of 64 channels, 128 taps) with the chunk's input window resident in LDS (gemm_f16s.hip)
 void launch_posconv_p8(const GemmArgs& g, int n_chunks, int T, int Ts, hipStream_t s);
 int gemm_config(const GemmArgs& g);   // 4: 128x128 BK16 (dominant kernel), 2: 64x64, 1: 128x64, 3: 32x128; 0,5,6,7 tuning variants

@@ -22,11 +22,12 @@ from .model import BitwiseARModel
 class ARTAvatarInferEngine:
     def __init__(self, load_gaga=False, fix_pose=False, clip_length=750, device="cuda",
                  ckpt_path="./assets/ARTalk_wav2vec.pt", config_path=None, state_dict=None, config=None, model=None,
-                 calibration=None):
+                 calibration=None, precision=None):
         """Arguments of the reference class, plus (all optional): ``state_dict`` / ``config`` instead of a checkpoint file, ``model``
         (an already loaded BitwiseARModel), and ``calibration`` - the f16x3 site scales to start from: a ``save_scales`` file or a
         ``{site: exponent}`` dict (``load_scales``), or a sequence of 16 kHz audio tensors to calibrate on once here (``calibrate``).
-        None keeps the model's scales (a checkpoint with outlier activations then recalibrates on its first outlier batch)."""
+        None keeps the model's scales (a checkpoint with outlier activations then recalibrates on its first outlier batch).
+        ``precision``: the GEMM arithmetic (``BitwiseARModel.set_precision``: 'f16x3', 'f32' or 'bf16'); None keeps the model's."""
         self.device = device
         self.fix_pose = fix_pose
         self.clip_length = clip_length
@@ -53,6 +54,8 @@ class ARTAvatarInferEngine:
                 self.ARTalk.load_scales(calibration)
             else:
                 self.ARTalk.calibrate(list(calibration))
+        if precision is not None:
+            self.ARTalk.set_precision(precision)
         # renderer-side attributes of the reference object; filled by whoever owns the (out of scope) renderers
         self.flame_model = None
         self.mesh_renderer = None

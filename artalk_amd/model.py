@@ -342,16 +342,23 @@ class BitwiseARModel:
         """'f16x3' / 1 (default): fp16 operand-split MFMA GEMMs, fp32-class accuracy (more accurate than the fp32 MFMA chain on
         every fixture) but operands times their site's scale must stay below fp16's 65504; 'f32' / 0: exact fp32 MFMA.  When an f16x3
         call trips the range guard, ``inference_batch`` (and ``stream_chunk``) first recalibrate the site scales (``auto_calibrate``)
-        and stay in f16x3 mode; only if nothing could be lowered do they switch to 'f32' and stay there."""
-        code = {"f32": 0, "f16x3": 1}.get(mode, mode)
-        if code not in (0, 1):
-            raise ValueError("precision mode must be 'f32' or 'f16x3'")
-        self._precision = "f16x3" if code == 1 else "f32"
+        and stay in f16x3 mode; only if nothing could be lowered do they switch to 'f32' and stay there.  'bf16' / 2: the throughput
+        mode - one bf16 MFMA product per GEMM product (operands rounded to bf16, fp32 accumulation; logit / code heads stay exact
+        fp32): chunk-0 FLAME error of a few 1e-2 and about 1 % of AR bits flipped against the fp32 reference; bf16 has fp32's range, so the mode never trips, recalibrates or falls back.  The
+        first switch to 'bf16' builds a bf16 copy of the weights (+2 bytes per parameter)."""
+        names = {0: "f32", 1: "f16x3", 2: "bf16"}
+        code = {"f32": 0, "f16x3": 1, "bf16": 2}.get(mode, mode)
+        if code not in names:
+            raise ValueError(f"precision mode must be 'f32', 'f16x3' or 'bf16' (got {mode!r})")
+        code = int(code)
+        self._precision = names[code]
         self._latched_f32 = False
         if self._h is not None and self._loaded:
             rc = capi.lib().artalk_set_precision(self._h, int(code))
-            if rc != capi.OK:
-                raise ValueError("precision mode must be 'f32' or 'f16x3'")
+            if rc == capi.EINVAL:
+                raise ValueError("precision mode must be 'f32', 'f16x3' or 'bf16'")
+            if rc != capi.OK:        # (mode 2 only: the bf16 weight copy could not be built)
+                raise RuntimeError(f"artalk_set_precision({code}) failed ({rc}): {self._err()}")
 
     def set_graphs(self, on: bool, branches: int = 0, splitk_tiles: int = 0, splitk_target: int = 0):
         """hipGraph replay of the AR/VAE body; ``branches`` (0 auto, 1, 2, 4) = concurrent clip groups; the split-K thresholds are

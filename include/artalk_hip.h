@@ -156,7 +156,14 @@ int artalk_get_profile(artalk_model* m, double* out, int n);
 int artalk_get_kernel_sums(artalk_model* m, double* out, int n);
 /* GEMM arithmetic: 0 (the library's default; the Python host selects 1) = exact fp32 on v_mfma_f32_32x32x2_f32; 1 = "f16x3": every fp32 operand split into two
  * fp16 values (22 significand bits), three fp16 MFMA products accumulated in fp32 - fp32-class accuracy (parity tests run in
- * both modes) at 5.3x the matrix-core rate; the logit / code heads stay on the fp32 path in both modes. */
+ * both modes) at 5.3x the matrix-core rate; the logit / code heads stay on the fp32 path in both modes.
+ * 2 = "bf16", the throughput mode: every GEMM except the logit / code heads computes bf16(A) * bf16(W) with fp32 accumulation
+ * (operands rounded to nearest even, one v_mfma_f32_32x32x16_bf16 per product); bias, activation, gate, residual and the split-K
+ * reduce stay fp32, and everything else (activations in HBM, LayerNorms, attention, pooling, conv0, quantiser) runs mode 0's
+ * schedule - what torch bf16 autocast does to linear / conv.  bf16 has fp32's exponent range: the site scales are not used and
+ * status bit 3 is never raised.  The first switch to mode 2 builds a bf16 copy of every weight (+2 bytes per parameter in
+ * artalk_weight_bytes); a model that never selects it allocates nothing.  Captured graphs and the cached initial history are kept
+ * per mode, so switching back and forth is free and never mixes modes. */
 int artalk_set_precision(artalk_model* m, int mode);
 /* Replay the AR/VAE part from hipGraphs captured per active-batch size (default 1 = on).  The batch is cut into 1/2/4 clip
  * groups whose graphs run concurrently on separate streams (automatic; enable | (groups << 8) forces a count, for tuning).
@@ -235,6 +242,14 @@ int artalk_op_mfma_f32_peak(float* out_dev, int blocks, int iters, int nacc, dou
 /* f16x3 split GEMM (mode 1 above) on fp32 inputs; cfg 0: 128x128 tiles, 1: 64x64, -1: heuristic.  M > 32, K % 32 == 0 */
 int artalk_op_gemm_f16s(const float* A, int64_t lda, const float* W, const float* bias, float* C, int M, int N, int K, int act,
                         int force_cfg, void* stream);
+/* bf16 GEMM on fp32 inputs (W converted to bf16 internally): C[m, n] = R + gate * act(bf16(A) bf16(W)^T + bias), ldc = ldg = ldr = N,
+ * K % 32 == 0, lda % 4 == 0 (lda < K: a convolution window), A and W 16-byte aligned.  force_cfg -1 = the engine's tile choice; otherwise
+ * bits 0-7 select the tile of the register-staged gemm_bf16_kernel (0: 64x64, 1: 128x128, 2: 32x128, 0xff: engine's choice), bits 8-15 a split-K factor (finished
+ * by the split-K reduce pass), bits 16-23 a grid.z batch (batch z at A + z*M*lda, W + z*N*K, bias + z*N, R / C + z*M*N), bit 24 the
+ * grouped positional-conv window (amode 1: 64 input channels per group at A + z*64, taps = K / 64, pad = taps / 2, clips of T = bits
+ * 25-30 rows).  Synchronises the stream. */
+int artalk_op_gemm_bf16(const float* A, int64_t lda, const float* W, const float* bias, const float* gate, const float* R, float* C,
+                        int M, int N, int K, int act, int force_cfg, void* stream);
 /* tuning helpers: fp32 -> packed split words; split GEMM on pre-packed W (and optionally pre-packed A) */
 int artalk_op_pack_split(const float* in, void* out_u32, int64_t n, int is_weight, void* stream);   /* operand scale: 0 activation, 1 weight */
 int artalk_op_gemm_f16s_packed(const void* A, int a_packed, int64_t lda, const void* Wp, const float* bias, float* C, int M, int N,
