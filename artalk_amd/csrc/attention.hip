@@ -200,8 +200,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const AttnArgs a) {
 // t = w, w+4, ...): K and V fragments go straight from global memory into MFMA operand registers (their lane maps are
 // row-contiguous: 64-byte pieces of a key row for K, whole 256-byte rows for V), the next tile's loads are issued before
 // the current tile's MFMAs, no LDS and no barrier in the loop; the four partial (m, l, O) are merged through LDS at the end.
-template <int HD, bool SLABS = false>      // SLABS: AttnArgs::slabs is set (its own instantiation: the slab path costs 27 registers, and the
-                                           // 25- / 50-query steps, which never take it, need three workgroups per CU)
+template <int HD>
 __global__ __launch_bounds__(256, 2) void attention_short_kernel(const AttnArgs a) {      // (2 blocks per CU: at most 256 registers per wave, which is what makes hipcc keep the MFMA accumulators in VGPRs - with the full 512 it put them in AGPRs and moved them out and back around the softmax and the rescale, 123 v_accvgpr moves and 66 hazard nops per tile pair)
     static_assert(HD == 64, "head dim");
     constexpr int NC = 4, NDT = 4;
@@ -223,36 +222,13 @@ __global__ __launch_bounds__(256, 2) void attention_short_kernel(const AttnArgs 
     const int qi = q0 + r;
     const bool qvalid = qi < a.Lq;
 
-    // Lq <= 16 with split-K slabs (AttnArgs::slabs): the q | k | v rows of the NEW tokens (the queries, and the last Lq keys) are not in
-    // the cache yet - a lane that needs four of their values sums them from the slabs itself, in splitk_reduce_kernel's order (0 + slab 0
-    // + slab 1 + ... + bias), straight into the fragment register the cache row would have been loaded into: no reduce launch, no trip
-    // through memory.  The lanes that own a new K / V row also write it to the cache (raw, before the L2 norm) for the later scale steps.
-    const int E = a.H * HD;
-    const int new0 = a.Lk - a.Lq;                                  // first new key row
-    auto from_slabs = [&](int t, int col) {                        // row t (0 .. Lq-1) of this clip, 4 columns from `col` of q | k | v
-        // every load of a batch of 8 slabs is issued before the first add (the slabs were written a moment ago by workgroups on other XCDs:
-        // each load is an L2 miss, and a run-time loop pays those latencies one after the other); the adds keep the slab order
-        const float* p = a.slabs + ((long)b * a.Lq + t) * a.slab_ld + col;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        const f32x4 bias = a.slab_bias ? *reinterpret_cast<const f32x4*>(a.slab_bias + col) : v;
-        for (int y0 = 0; y0 < a.n_slabs; y0 += 8) {
-            f32x4 tt[8];
-#pragma unroll
-            for (int y = 0; y < 8; ++y) tt[y] = *reinterpret_cast<const f32x4*>(p + (long)min(y0 + y, a.n_slabs - 1) * a.slab_stride);
-#pragma unroll
-            for (int y = 0; y < 8; ++y) if (y0 + y < a.n_slabs) v += tt[y];
-        }
-        if (a.slab_bias) v += bias;
-        return v;
-    };
     f32x4 qf[NC];
     {
         const float* qp = a.Q + (long)b * a.q_bstride + (long)qi * a.ldq + h * HD;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             f32x4 z = {0.f, 0.f, 0.f, 0.f};
-            if (SLABS) qf[c] = qvalid ? from_slabs(qi, h * HD + 4 * (g + 4 * c)) : z;
-            else qf[c] = qvalid ? *reinterpret_cast<const f32x4*>(qp + 4 * (g + 4 * c)) : z;
+            qf[c] = qvalid ? *reinterpret_cast<const f32x4*>(qp + 4 * (g + 4 * c)) : z;
         }
         if (a.l2norm) {
             float ss = 0.f;
@@ -284,27 +260,13 @@ __global__ __launch_bounds__(256, 2) void attention_short_kernel(const AttnArgs 
     f32x4 kf[2][NC], vf[2][4];
     auto load_tile = [&](int t, int slot) {
         const int kr = min(t * 16 + r, a.Lk - 1);
-        float* kp = const_cast<float*>(Kb) + (long)kr * a.ldk;
-        if (SLABS && kr >= new0) {
+        const float* kp = Kb + (long)kr * a.ldk;
 #pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                kf[slot][c] = from_slabs(kr - new0, E + h * HD + 4 * (g + 4 * c));
-                if (t * 16 + r < a.Lk) *reinterpret_cast<f32x4*>(kp + 4 * (g + 4 * c)) = kf[slot][c];
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < NC; ++c) kf[slot][c] = *reinterpret_cast<const f32x4*>(kp + 4 * (g + 4 * c));
-        }
+        for (int c = 0; c < NC; ++c) kf[slot][c] = *reinterpret_cast<const f32x4*>(kp + 4 * (g + 4 * c));
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int vr = min(t * 16 + 4 * g + j, a.Lk - 1);
-            float* vp = const_cast<float*>(Vb) + (long)vr * a.ldv + NDT * r;
-            if (SLABS && vr >= new0) {
-                vf[slot][j] = from_slabs(vr - new0, 2 * E + h * HD + NDT * r);
-                if (t * 16 + 4 * g + j < a.Lk) *reinterpret_cast<f32x4*>(vp) = vf[slot][j];
-            } else {
-                vf[slot][j] = *reinterpret_cast<const f32x4*>(vp);
-            }
+            vf[slot][j] = *reinterpret_cast<const f32x4*>(Vb + (long)vr * a.ldv + NDT * r);
         }
     };
 
@@ -410,9 +372,6 @@ __global__ __launch_bounds__(256, 2) void attention_short_kernel(const AttnArgs 
 // The V^T operand needs 8 consecutive KEYS per lane at one d: read by ds_read_b64_tr_b16 (4 keys x 16 d block per 16 lanes,
 // delivered column-major), two reads per operand.  The k slots of the PV MFMA are assigned so that the S^T accumulator is the
 // P^T operand without any data movement: slot (g, e) = key 32T + 4g + e for e < 4 (tile 2T), key 32T + 16 + 4g + (e - 4) (tile 2T+1).
-#ifndef ATT_ABL
-#define ATT_ABL 0
-#endif
 typedef _Float16 h8_t __attribute__((ext_vector_type(8)));
 typedef __fp16 fp16x4_raw __attribute__((__vector_size__(4 * sizeof(__fp16))));
 __device__ __forceinline__ void split4(const f32x4 x, f16x4_t& hi, f16x4_t& lo) {
@@ -679,14 +638,12 @@ __global__ __launch_bounds__(kWideMaxWaves * 64) void attention_f16_wide_kernel(
             const int row = idx >> 3, g8 = idx & 7;
             const h8_t z = {0, 0, 0, 0, 0, 0, 0, 0};
             kh[i] = z; kl[i] = z; vh[i] = z; vl[i] = z;
-#if ATT_ABL != 1      // (timing builds, results wrong: ATT_ABL 1 no K / V loads, 2 no softmax arithmetic, 3 one MFMA product of three, 4 no P split)
             if (row < a.Lk) {
                 const unsigned char* kp = reinterpret_cast<const unsigned char*>(Kb + (long)row * a.ldk) + g8 * 32;
                 const unsigned char* vp = reinterpret_cast<const unsigned char*>(Vb + (long)row * a.ldv) + g8 * 32;
                 kh[i] = *reinterpret_cast<const h8_t*>(kp); kl[i] = *reinterpret_cast<const h8_t*>(kp + 16);
                 vh[i] = *reinterpret_cast<const h8_t*>(vp); vl[i] = *reinterpret_cast<const h8_t*>(vp + 16);
             }
-#endif
         }
         // Q fragments (B operand of S^T): lane (r, g) holds Q[qi][8g + 32kb .. +7], hi | lo as stored
         h8_t qh_[2], ql_[2];
@@ -739,12 +696,8 @@ __global__ __launch_bounds__(kWideMaxWaves * 64) void attention_f16_wide_kernel(
                         const int off = (kb0 + t * 16 + r) * PB + (8 * g + 32 * kb) * 2;
                         const h8_t kh2 = *reinterpret_cast<const h8_t*>(Kh + off), kl2 = *reinterpret_cast<const h8_t*>(Kl + off);
                         acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh2, qh[kb], acc, 0, 0, 0);
-#if ATT_ABL != 3
                         acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kl2, qh[kb], acc, 0, 0, 0);
                         acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh2, ql[kb], acc, 0, 0, 0);
-#else
-                        acc[0] += (float)kl2[0] * (float)ql[kb][0];
-#endif
                     }
                 }
                 st[t] = acc;
@@ -772,9 +725,6 @@ __global__ __launch_bounds__(kWideMaxWaves * 64) void attention_f16_wide_kernel(
                         mx = fmaxf(mx, sv);
                     }
             }
-#if ATT_ABL == 2
-            l_part += mx;
-#else
             mx = fmaxf(mx, lane_xor<16>(mx));
             mx = fmaxf(mx, lane_xor<32>(mx));
             const float m_new = fmaxf(m_run, mx);
@@ -793,17 +743,12 @@ __global__ __launch_bounds__(kWideMaxWaves * 64) void attention_f16_wide_kernel(
             l_part = l_part * alpha + ps;
 #pragma unroll
             for (int d = 0; d < 4; ++d) ot[d] *= alpha;
-#endif
 #pragma unroll
             for (int T = 0; T < 2; ++T) {
                 if (2 * T < ntile) {
                     f16x4_t h0, l0, h1, l1;
-#if ATT_ABL == 4
-                    for (int e = 0; e < 4; ++e) { h0[e] = (_Float16)st[2 * T][e]; h1[e] = (_Float16)st[2 * T + 1][e]; l0[e] = h0[e]; l1[e] = h1[e]; }
-#else
                     split4(st[2 * T], h0, l0);
                     split4(st[2 * T + 1], h1, l1);
-#endif
                     const h8_t ph = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
                     const h8_t pl = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
                     const int row1 = kb0 + T * 32 + 4 * g + trq, row2 = row1 + 16;
@@ -821,12 +766,8 @@ __global__ __launch_bounds__(kWideMaxWaves * 64) void attention_f16_wide_kernel(
                         const h8_t vh2 = {a1[0], a1[1], a1[2], a1[3], a2[0], a2[1], a2[2], a2[3]};
                         const h8_t vl2 = {b1[0], b1[1], b1[2], b1[3], b2[0], b2[1], b2[2], b2[3]};
                         ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh2, ph, ot[dt], 0, 0, 0);
-#if ATT_ABL != 3
                         ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vl2, ph, ot[dt], 0, 0, 0);
                         ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh2, pl, ot[dt], 0, 0, 0);
-#else
-                        ot[dt][0] += (float)vl2[0] * (float)pl[0];
-#endif
                     }
                 }
             }
@@ -1375,9 +1316,7 @@ void launch_attention(const AttnArgs& a, hipStream_t s) {
     if (a.B <= 0 || a.Lq <= 0) return;
     if (a.HD == 64 && a.split_q == 0 && a.Lq <= 64 && a.Lk >= 64 && !a.qkv_p8) {      // AR scale steps 0-3: key-split kernel
         const dim3 grid(((a.H * a.B + 7) / 8) * 8 * ((a.Lq + 15) / 16));
-        if (a.slabs && a.Lq <= 16) ARTALK_LAUNCH((attention_short_kernel<64, true>), grid, dim3(256), 0, s, a);
-        else if (a.slabs) abort();      // (slabs are only handed over for one query tile per head: engine.hip run_chunk_body)
-        else ARTALK_LAUNCH((attention_short_kernel<64, false>), grid, dim3(256), 0, s, a);
+        ARTALK_LAUNCH((attention_short_kernel<64>), grid, dim3(256), 0, s, a);
         return;
     }
     dim3 grid((a.Lq + 63) / 64, a.H, a.B), block(256);
@@ -1397,11 +1336,11 @@ void launch_attention(const AttnArgs& a, hipStream_t s) {
         int& n_cu = n_cu_dev[dev];
         if (!n_cu && (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)) n_cu = 256;
         const int cus = a.cus > 0 ? (a.cus < n_cu ? a.cus : n_cu) : n_cu;
-        if (pp && wide != 2 && a.split_q <= 0 && a.Lk > kPPRowsA && a.Lk <= kPPRowsA + kPPRowsB && (long)a.B * a.H >= 2L * cus) {
+        if (pp && a.split_q <= 0 && a.Lk > kPPRowsA && a.Lk <= kPPRowsA + kPPRowsB && (long)a.B * a.H >= 2L * cus) {
             ARTALK_LAUNCH((attention_f16_pp_kernel<1>), dim3(cus), dim3(kPPWaves * 64), (size_t)4 * (kPPRowsA + kPPRowsB) * 160, s, a);
             return;
         }
-        if (wide == 2 || (long)a.B * a.H < 256) ARTALK_LAUNCH((attention_f16_wide_ar_kernel<1, 1, 7, 128>), dim3((a.Lq + 111) / 112, a.H, a.B), dim3(7 * 64), (size_t)4 * 128 * 160, s, a);
+        if ((long)a.B * a.H < 256) ARTALK_LAUNCH((attention_f16_wide_ar_kernel<1, 1, 7, 128>), dim3((a.Lq + 111) / 112, a.H, a.B), dim3(7 * 64), (size_t)4 * 128 * 160, s, a);
         else ARTALK_LAUNCH((attention_f16_wide_kernel<1>), dim3(1, a.H, a.B), dim3(kWideMaxWaves * 64), lds, s, a);
     } else if (a.HD == 64 && a.split16 && a.qkv_p8 && !a.l2norm)
         ARTALK_LAUNCH((attention_f16_kernel<1, 1>), grid, block, 0, s, a);

@@ -199,13 +199,6 @@ struct artalk_model {
     std::vector<std::pair<int, size_t>> marks;          // (bucket of the interval ending here, event index), caller's stream
     hipStream_t prof_stream = nullptr;
     hipStream_t side_stream[3] = {nullptr, nullptr, nullptr};   // extra branches of the AR body (run_chunk_body_graphs)
-    // The split-K reduce of the 1- / 5-token q|k|v GEMMs inside the short-query attention kernel (run_chunk_body): 12 launches fewer per
-    // scale step (113 -> 101), bit-identical (tests/test_edge_cases_gpu.py::test_fused_qkv_reduce_is_bit_identical) - and NOT faster: same
-    // box, alternating runs, body time 31.33 / 31.51 / 31.33 ms fused against 31.00 / 31.18 / 31.12 ms with the separate reduce pass
-    // (round 4).  The attention launch grows by what the reduce launch took: inside a graph a 4.8 us kernel costs less than its
-    // duration (the front end has the next dispatch ready), while the slab loads now sit on the attention kernel's own critical path.
-    // Off by default (ARTALK_FUSE_QKV_REDUCE=1 for an A/B run).
-    bool fuse_qkv_reduce = false;
     hipEvent_t fork_ev = nullptr, join_ev[3] = {nullptr, nullptr, nullptr};
     int branches = 0;                 // 0 = automatic (2 for B >= 8), else forced 1/2/4
     hipStream_t own_stream = nullptr;   // used when the caller passes stream == NULL (graph capture needs a real stream)
@@ -511,9 +504,7 @@ void audit(artalk_model* m, const float* buf, int rows, int cols, long ld, bool 
     launch_absmax(buf, rows, cols & ~7, ld, is_p8 ? 1 : 0, m->audit_vals + idx, s, junk_period, junk_from, ex ? *ex : kActExp);
 }
 
-// defer_reduce: the caller's next kernel sums the split-K slabs itself (the short-query attention kernel does, for the q|k|v rows of
-// its own head): if this GEMM is split, its reduce pass is NOT launched and *defer_reduce receives the slab count (else 0).
-bool gemm(artalk_model* m, const GemmArgs& g0, hipStream_t s, const LnArgs* fuse_ln = nullptr, int* defer_reduce = nullptr) {
+bool gemm(artalk_model* m, const GemmArgs& g0, hipStream_t s, const LnArgs* fuse_ln = nullptr) {
     GemmArgs g = g0;
     g.graph_tag = m->in_body ? 1 : 0;
     g.cus = m->n_cus;
@@ -531,90 +522,40 @@ bool gemm(artalk_model* m, const GemmArgs& g0, hipStream_t s, const LnArgs* fuse
         }
         if (g.a_packed) { m->err = "internal: P8 activation handed to a bf16 GEMM"; m->sticky_error = true; return false; }
     }
-    // split-K for grids that would leave most CUs idle (small-M scale steps): S workgroups per output tile
+    if (g.a_packed && !split) { m->err = "internal: P8 activation handed to an fp32 GEMM"; m->sticky_error = true; return false; }
     const Workspace& cw = m->view ? *m->view : m->ws;
-    const bool sm_path = split && g.a_packed && gemm_p8_sm_eligible(g) && !gemm_p8_eligible(g);
-    if (g.batch == 1 && g.amode == 0 && cw.splitk && g.K >= 256) {
+    const bool p8 = split && gemm_p8_sm_eligible(g);      // P8 activation: the f16x3 planner picks kernel, split-K and fetch policy
+    P8Plan plan;
+    if (p8) {
+        plan = plan_gemm_p8(g, cw.splitk ? cw.splitk_floats : 0);
+    } else if (g.batch == 1 && g.amode == 0 && cw.splitk && g.K >= 256) {
+        // split-K for grids that would leave most CUs idle (small-M scale steps): S workgroups per output tile
         const int tiles = bf16 ? gemm_bf16_tile_count(g) : gemm_tile_count(g, split);
-        const int lim = m->splitk_tiles, tgt = m->splitk_target;
-        if (sm_path) {
-            // Small-grid LDS-DMA kernel (64x64 tiles).  These launches are latency-bound: measured with cold weights, replayed from a
-            // graph, GEMM + reduce (profiles/r02_tiny_gemm_sweep.log): K = 3072 gains from a split below ~192 tiles (M = 400: 19.1 us
-            // split in 6 vs 27 unsplit); K = 768 gains only on the smallest grids, where the split workgroups' whole K slice fits the
-            // ring and is in flight at once (deep-ring configurations 23 / 24): proj at M = 80 7.8 us split in 6 vs 9.8, qkv 9.9 us
-            // split in 3 vs 13.2.  A split 768-wide result also gets its LayerNorm for free (fuse_ln).
-            int S = 1, cfg = -1;
-            if (g.K >= 2048) {
-                if (tiles <= 24) { S = 8; cfg = 23; }
-                else if (tiles < 192) S = tiles < 48 ? 6 : 3;
-            } else {
-                if (tiles <= 24) { S = 6; cfg = 24; }
-                else if (tiles <= 36) { S = 4; cfg = 24; }
-                else if (tiles <= 72) { S = 3; cfg = 23; }
-                else if (tiles <= 108) S = 2;
-            }
-            while (S > 1 && (int64_t)S * g.M * g.N > cw.splitk_floats) { --S; cfg = -1; }
-            if (S == 5 || S == 7) { --S; }        // the unrolled reduce kernels exist for 2, 3, 4, 6, 8 slabs
-            // Mid-grid kernel (128x128 tiles, one 8-wave workgroup per CU, 4-stage ring: gemm_p8_mid_kernel, cfg 28) where its grid
-            // fills most of the chip: these launches are bound by what an XCD pulls in per K step, and a 128x128 tile has four times
-            // the matrix work per fetched byte of the 64x64 tile (profiles/r03_mid_gemm_sweep.log, cold weights, graph replay:
-            // q|k|v at M = 1600 30.7 -> 24.6 us, FFN-in at M = 800 28.8 -> 22.2, FFN-out at M = 1600 split in 3 42.6 -> 35.0; below
-            // ~150 tiles the 64x64 kernel wins: projection at M = 1600 14.0 vs 19.0).  It has no second P8 copy of the result (c2).
-            if (S == 1 && g.force_cfg < 0 && !g.c2) {
-                const int t128 = ((g.M + 127) / 128) * ((g.N + 127) / 128);
-                // Ping-pong kernel (gemm_p8_pp_kernel, cfg 31: 256 x 128 tiles, the two waves of a SIMD one phase apart) where its grid is
-                // 120 .. 256 tiles: q|k|v and FFN-in of the 100-token step, q|k|v of the VAE decoder stack.  Measured (round 5,
-                // profiles/r05_pp_gemm_sweep.log, r05_pp_model_ab.log): FFN-in at M = 1600 39.0 -> 32.6 us (168 tiles in ONE round instead
-                // of 312 in two), VAE q|k|v at M = 3200 27.1 -> 24.2, q|k|v at M = 1600 slower alone (24.3 -> 30.8: half the chip) but not
-                // beside the other clip group's launches; body 31.75 / 31.92 -> 31.58 / 31.79 ms per step in same-box pairs.  The
-                // 128 x 128 form (cfg 33) equals the mid-grid kernel on every shape.  ARTALK_PP=0 switches it off (A/B), 2 / 3 add cfg 33.
-                static const int pp_mode = getenv("ARTALK_PP") ? atoi(getenv("ARTALK_PP")) : 1;
-                static const int pp_min = getenv("ARTALK_PP_MIN") ? atoi(getenv("ARTALK_PP_MIN")) : 120;
-                const int t256 = ((g.M + 255) / 256) * ((g.N + 127) / 128);
-                if ((pp_mode & 1) && t256 >= pp_min && t256 <= 256 && gemm_p8_pp_ok(g)) cfg = 31;
-                else if (t128 >= 150) cfg = ((pp_mode & 2) && gemm_p8_pp_ok(g)) ? 33 : 28;
-                if (cfg == 31 || cfg == 33) g.force_cfg = cfg;
-                else if (t128 < 150 && g.K >= 2048 && 3 * t128 >= 150 && (int64_t)3 * g.M * g.N <= cw.splitk_floats) { S = 3; cfg = 28; }
-                if (cfg == 28 && S == 1) g.force_cfg = 28;
-            }
-            if (S > 1) { g.splitk = S; g.partial = cw.splitk; if (g.force_cfg < 0) g.force_cfg = cfg; }
-            // weights of the narrowest steps (levels 0 and 1) are read once per launch by a handful of workgroups: fetched with the
-            // non-temporal policy they do not displace the resident history (A/B, cold weights: -0.2..-0.5 us of 8..16 us at M <= 80,
-            // +0.4 us at M = 400, where several row tiles re-read each weight tile through L2)
-            if (g.M <= 160) g.w_nt = 1;
-        } else if (tiles < lim) {
-            int S = std::min(std::min(g.K / 64, (tgt + tiles - 1) / tiles), 16);
+        if (tiles < m->splitk_tiles) {
+            int S = std::min(std::min(g.K / 64, (m->splitk_target + tiles - 1) / tiles), 16);
             while (S > 1 && (int64_t)S * g.M * g.N > cw.splitk_floats) --S;
-            if (S > 1) { g.splitk = S; g.partial = cw.splitk; }
+            if (S > 1) g.splitk = S;
         }
     }
+    if (g.splitk > 1) g.partial = cw.splitk;
     const bool dominant = !m->in_body && g.M > 0 &&
-                          (bf16 ? gemm_bf16_config(g) == 1 :
-                           split ? (g.a_packed ? (gemm_p8_eligible(g) && gemm_p8_variant(g) >= 1) : gemm_f16s_config(g) == 0) : gemm_config(g) == 4);
+                          (bf16 ? gemm_bf16_config(g) == 1 : p8 ? plan.dominant : split ? !g.a_packed && gemm_f16s_config(g) == 0 : gemm_config(g) == 4);
     size_t i0 = 0, i1 = 0;
     if (m->profiling && dominant) next_event(m, s, &i0);
-    if (g.a_packed && !split) { m->err = "internal: P8 activation handed to an fp32 GEMM"; m->sticky_error = true; return false; }
-    const bool dma = split && g.splitk == 1 && gemm_p8_eligible(g);
-    // second copy of the result in P8 (GemmArgs::c2): written by the small-grid kernel's epilogue when that kernel finishes the tiles
-    // itself, otherwise by a split pass over the fp32 result
+    // second copy of the result in P8 (GemmArgs::c2): written by the kernel's epilogue where the plan says so, otherwise by a split
+    // pass over the fp32 result
     float* const c2 = g.c2;
-    const bool c2_fused = c2 && !dma && split && gemm_p8_sm_eligible(g) && g.splitk == 1 && !g.c_p8 && (g.N % 8) == 0 && (g.ldc % 8) == 0 &&
-                          !g.gate && (g.ldr % 4) == 0 &&      // (the epilogue's 16-byte path: every pointer and row start aligned)
-                          (((unsigned long long)g.C | (unsigned long long)c2 | (unsigned long long)g.bias | (unsigned long long)g.R) & 15) == 0;
-    if (!c2_fused) g.c2 = nullptr;
+    if (!plan.c2_fused) g.c2 = nullptr;
     if (bf16) launch_gemm_bf16(g, s);
-    else if (dma) launch_gemm_p8(g, s);
-    else if (split && gemm_p8_sm_eligible(g)) launch_gemm_p8_sm(g, s);     // P8 activation, small grid (AR/VAE scale steps)
+    else if (p8) launch_gemm_p8(g, s);
     else if (split) launch_gemm_f16s(g, s);
     else launch_gemm(g, s);
     bool fused = false;
-    if (defer_reduce) *defer_reduce = 0;
     if (g.splitk > 1) {
         if (fuse_ln && splitk_reduce_ln_eligible(g, *fuse_ln)) { launch_splitk_reduce_ln(g, *fuse_ln, s); fused = true; }
-        else if (defer_reduce && !c2) *defer_reduce = g.splitk;
         else launch_splitk_reduce(g, s);
     }
-    if (c2 && !c2_fused) launch_pack_split(g.C, reinterpret_cast<unsigned int*>(c2), (long)g.M * g.N, false, s, g.status, g.c_exp);
+    if (c2 && !plan.c2_fused) launch_pack_split(g.C, reinterpret_cast<unsigned int*>(c2), (long)g.M * g.N, false, s, g.status, g.c_exp);
     if (m->profiling && dominant) {
         next_event(m, s, &i1);
         m->dom_events.emplace_back(i0, gemm_flops(g));
@@ -660,7 +601,7 @@ void run_wav2vec(artalk_model* m, const float* audio, int c0, int n, float* out_
     Workspace& w = m->ws;
     const int CD = c.w2v_conv_dim, Hs = c.w2v_hidden;
     // f16x3 mode: every activation whose only consumer is a GEMM is written by its producer directly in the P8 split
-    // format (same bytes), so the big GEMMs can stage both operands with LDS-DMA (gemm_p8_2wgp_kernel / gemm_p8_256_kernel).
+    // format (same bytes), so the big GEMMs can stage both operands with LDS-DMA (gemm_p8_2wgp_kernel / gemm_p8_big_kernel).
     const int p8 = m->precision == 1 ? 1 : 0;
     const int AP = p8 ? LF_A_P8 : 0;
     Range r_w2v("artalk.wav2vec2");
@@ -953,15 +894,8 @@ void run_chunk_body(artalk_model* m, int B, hipStream_t s, int n_reencode = -1) 
             GemmArgs q;
             q.A = w.xmod; q.lda = kE; q.W = L.qkv_w; q.ldw = kE; q.bias = L.qkv_b; q.C = cache; q.ldc = 3 * kE;
             q.cmap = rowmap(pn, 2 * kNTok, kNTok + off); q.M = M; q.N = 3 * kE; q.K = kE; q.a_packed = p8; q.a_exp = E.ln1;
-            // 1- and 5-token steps: a split q|k|v GEMM leaves its slabs to the attention kernel, whose workgroup (clip, head) sums the
-            // rows of its own head (same order: slabs ascending, then the bias), writes them to the KV cache and goes on - one launch
-            // less per block (ARTALK_FUSE_QKV_REDUCE=0: the separate reduce pass; a test compares both arms bit for bit)
-            int qkv_slabs = 0;
-            gemm(m, q, s, nullptr, (m->fuse_qkv_reduce && pn <= 16) ? &qkv_slabs : nullptr);
+            gemm(m, q, s);
             AttnArgs a;
-            if (qkv_slabs > 0) {
-                a.slabs = w.splitk; a.n_slabs = qkv_slabs; a.slab_stride = (long)M * 3 * kE; a.slab_ld = 3 * kE; a.slab_bias = L.qkv_b;
-            }
             a.Q = cache + (long)(kNTok + off) * 3 * kE; a.K = cache + kE; a.V = cache + 2 * kE;
             a.ldq = a.ldk = a.ldv = 3 * kE; a.q_bstride = a.k_bstride = a.v_bstride = (long)2 * kNTok * 3 * kE;
             a.O = w.attn_out; a.ldo = kE; a.o_bstride = (long)pn * kE;
@@ -1336,7 +1270,6 @@ int artalk_create(int device_id, const artalk_config* cfg, artalk_model** out) {
     if (hipSetDevice(device_id) != hipSuccess) { g_create_error = "hipSetDevice failed"; return ARTALK_EHIP; }
     artalk_model* m = new artalk_model();
     m->cfg = c; m->device = device_id;
-    if (const char* e = getenv("ARTALK_FUSE_QKV_REDUCE")) m->fuse_qkv_reduce = atoi(e) != 0;
     // conv stack geometry: T_l valid frames; row stride S_l per chunk with S_l = 2*S_{l+1} so that one GEMM covers all chunks
     int T = kSamplesPerChunk;
     for (int i = 0; i < c.w2v_n_conv; ++i) { T = (T - c.w2v_conv_kernel[i]) / c.w2v_conv_stride[i] + 1; m->conv_T[i] = T; }
@@ -2014,7 +1947,7 @@ int artalk_op_gemm(const float* A, int64_t lda, const float* W, const float* bia
 
 int artalk_op_gemm_ex(const float* A, int64_t lda, const float* W, const float* bias, float* C, int M, int N, int K, int act,
                       int force_cfg, void* stream) {
-    if (!A || !W || !C || K % 32 != 0 || M < 0 || N <= 0) return ARTALK_EINVAL;
+    if (!A || !W || !C || K % 32 != 0 || M < 0 || N <= 0 || force_cfg < -1 || force_cfg == 0 || force_cfg > 4) return ARTALK_EINVAL;
     GemmArgs g;
     g.A = A; g.lda = lda; g.W = W; g.ldw = K; g.bias = bias; g.C = C; g.ldc = N; g.M = M; g.N = N; g.K = K; g.act = act;
     g.force_cfg = force_cfg;
@@ -2119,14 +2052,20 @@ int artalk_op_gemm_f16s_packed(const void* A, int a_packed, int64_t lda, const v
     g.C = C; g.ldc = N; g.M = M; g.N = N; g.K = K; g.act = act & 0xff; g.force_cfg = force_cfg;
     g.c_p8 = (act >> 8) & 1;      // tuning: bit 8 of `act` = result in the P8 split format (same pitch)
     if ((act >> 9) & 1) { g.R = C; g.ldr = N; }      // tuning: bit 9 = residual read from C (in place, as the encoder's out-projection / FFN-out run)
-    if (force_cfg >= 2) {   // LDS-DMA kernels (both operands in P8): 7 / 12 = persistent 256x256 / 320x256 tiles, 8 = persistent 128x128, 13 = non-persistent 256x256 (17: with wall-clock stamps)
-        if (!a_packed) return ARTALK_EINVAL;
-        g.force_cfg = force_cfg == 99 ? -1 : force_cfg;   // 99: the engine's own choice between the production kernels
-        if (force_cfg == 17) { g.partial = (float*)bias; g.bias = nullptr; }     // (17: gemm_p8_256_kernel with stamps)   // timing build: `bias` carries the stamp buffer (8 x u64 per tile)
-        if (force_cfg != 99 && (force_cfg & 0xff) >= 20) {     // 20 / 23 / 24: small-grid LDS-DMA kernel; bits 8-15: split-K factor (slabs in a temporary)
-            g.force_cfg = force_cfg & 0xff;
+    if (force_cfg >= 2) {   // LDS-DMA kernels (both operands in P8): include/artalk_hip.h lists the configurations
+        int cfg = force_cfg & 0xff;
+        const int S = (force_cfg >> 8) & 0xff;
+        // retired configurations stay valid and run what replaced them (same accumulation order, same bits): 13 (the non-persistent
+        // 256x256 kernel) the plan, 29 (the 5-stage mid-grid ring) and 33 (the 128x128 ping-pong form) the mid-grid kernel, 30 (the
+        // one-barrier ping-pong form) the two-barrier one
+        if (cfg == 13) cfg = 99;
+        else if (cfg == 29 || cfg == 33) cfg = 28;
+        else if (cfg == 30) cfg = 31;
+        const bool small = cfg == 20 || cfg == 23 || cfg == 24 || cfg == 28 || cfg == 31;
+        if (!a_packed || !(small || cfg == 7 || cfg == 8 || cfg == 12 || cfg == 99)) return ARTALK_EINVAL;
+        g.force_cfg = cfg == 99 ? -1 : cfg;      // 99: the planner's own choice (without split-K)
+        if (small) {     // bits 8-15: split-K factor (slabs in a temporary)
             g.w_nt = (force_cfg >> 16) & 1;      // tuning: bit 16 = non-temporal weight pieces
-            const int S = (force_cfg >> 8) & 0xff;
             if (S > 1) {
                 const size_t need = (size_t)S * M * N * 4;
                 if (need > g_op_scratch_cap) {
@@ -2141,11 +2080,10 @@ int artalk_op_gemm_f16s_packed(const void* A, int a_packed, int64_t lda, const v
                 }
                 g.splitk = S; g.partial = g_op_scratch;
             }
-            launch_gemm_p8_sm(g, (hipStream_t)stream);
-            if (S > 1) launch_splitk_reduce(g, (hipStream_t)stream);
-        } else {
-            launch_gemm_p8(g, (hipStream_t)stream);
         }
+        plan_gemm_p8(g, 0);
+        launch_gemm_p8(g, (hipStream_t)stream);
+        if (g.splitk > 1) launch_splitk_reduce(g, (hipStream_t)stream);
     } else {
         launch_gemm_f16s(g, (hipStream_t)stream);
     }
@@ -2166,10 +2104,11 @@ int artalk_op_destroy_stream(void* stream) { return hipStreamDestroy((hipStream_
 
 int artalk_op_gemm_p8_plan(int M, int N, int K, int residual) {
     GemmArgs g;
-    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldc = N;
-    if (residual) { g.R = reinterpret_cast<const float*>(16); g.ldr = N; }     // only its presence and alignment are looked at
-    const int v = gemm_p8_variant(g);
-    return v == 1 ? 7 : (v == 2 ? 12 : 8);
+    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldc = N; g.a_packed = 1;
+    g.Wp = reinterpret_cast<const unsigned int*>(16);      // only its presence and alignment are looked at (so are R's)
+    if (residual) { g.R = reinterpret_cast<const float*>(16); g.ldr = N; }
+    plan_gemm_p8(g, 0);
+    return g.force_cfg;
 }
 
 int artalk_op_layernorm(const float* X, float* Y, const float* w, const float* b, const float* scale, const float* shift, int M,

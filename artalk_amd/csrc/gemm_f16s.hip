@@ -252,198 +252,12 @@ __device__ __forceinline__ void wait_vmcnt_units(int units) {   // at most `unit
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// 256x256 tile variant of the LDS-DMA kernel.  A 128x128 tile is bound by what the LDS-DMA path of a CU delivers
-// (~60 GB/s: 32 KiB per K step in 0.53 us with the MFMAs removed); a 256x256 tile needs half the operand
-// bytes per flop, which one fp32 accumulator per output (common.h: both operand halves share a scale) makes affordable:
-// 8 waves as 2 x 4, wave tile 128 x 64 = 4 x 2 MFMA tiles = 128 accumulator registers.
-//   LDS: 2 stages of 64 KiB (A 256 rows x 128 B, then W 256 rows x 128 B, same XOR swizzle as above).  One K step (32 deep)
-//   is 48 MFMAs per wave (~1.5 us per CU), long enough that a two-stage ring covers the L2/HBM latency:
-//     top of K step kt:  vmcnt(0) (stage kt, issued during step kt-1, has landed for this wave) + ONE barrier (landed for
-//                        all waves, and all waves are done reading stage kt-1, whose buffer is refilled next)
-//     body:              the 8 DMA pieces of stage kt+1 go out one per two MFMAs at the start of the step;
-//                        fragments roll through registers: B fragments of a k block (2 tiles) are double buffered, A tiles
-//                        (4 per k block) stream through two slots, each read issued 6 MFMAs before its first use and
-//                        waited for with a counted lgkmcnt.
-template <int ABL = 0>
-__global__ __launch_bounds__(512, 1) void gemm_p8_256_kernel(const GemmArgs g) {
-    constexpr int BM = 256, BN = 256, BK = 32;
-    constexpr int STAGE_BYTES = (BM + BN) * 128;     // 64 KiB
-    constexpr int NDMA = 8;                           // 1-KiB pieces per wave per stage: 4 of A, 4 of W
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_p8[];
-
-    const int tid = threadIdx.x;
-    unsigned long long* stamps = nullptr;
-    if constexpr (ABL == 6) {
-        stamps = reinterpret_cast<unsigned long long*>(g.partial) + (long)blockIdx.x * 8;
-        if (tid == 0) {
-            stamps[0] = wall_clock64();
-            stamps[4] = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));
-            stamps[5] = __builtin_amdgcn_s_getreg((20) | (0 << 6) | (31 << 11));
-        }
-    }
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int tiles_n = (g.N + BN - 1) / BN, tiles_m = (g.M + BM - 1) / BM;
-    int tm, tn;
-    {
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        const int idx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-        constexpr int GM = 8;      // row tiles per XCD tile group (8 x 4 tiles per XCD measured 0.27 ms per step better than 2 x 16)
-        const int width = GM * tiles_n;
-        const int group = idx / width, first_m = group * GM;
-        const int gsz = min(tiles_m - first_m, GM);
-        const int in_g = idx - group * width;
-        tn = in_g / gsz;
-        tm = first_m + (in_g - tn * gsz);
-    }
-    const int m0 = tm * BM, n0 = tn * BN;
-
-    // ---- DMA addressing: piece = 8 rows x 128 B; wave w owns A rows 32w..32w+31 and W rows 32w..32w+31 of the tile ----
-    const int prow = lane >> 3, pchunk = lane & 7;
-    const unsigned char* src[NDMA];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int ra = wave * 32 + q * 8 + prow;
-        const int gm = min(m0 + ra, g.M - 1);          // clamp: rows >= M are never stored
-        const int gn = min(n0 + ra, g.N - 1);
-        const int sw = (pchunk ^ ((ra >> 1) & 7)) << 4;
-        src[q] = reinterpret_cast<const unsigned char*>(g.A) + ((long)gm * g.lda) * 4 + sw;
-        src[4 + q] = reinterpret_cast<const unsigned char*>(g.Wp) + ((long)gn * g.ldw) * 4 + sw;
-    }
-    auto issue_piece = [&](int q, int kt, int buf) {
-        unsigned char* dst = smem_p8 + buf * STAGE_BYTES + (q < 4 ? 0 : BM * 128) + (wave * 4 + (q & 3)) * 1024;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[q] + (long)kt * (BK * 4)),
-                                         (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-    };
-
-    const int wm = wave >> 2, wn = wave & 3;
-    const int r = lane & 31, h = lane >> 5;
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem_p8;
-    unsigned a_off[2][2], w_off[2][2];               // [kb][hi/lo]; further tiles are +4096 B per 32 rows (same swizzle key)
-    {
-        const int arow = wm * 128 + r, wrow = wn * 64 + r;
-        const int akey = (arow >> 1) & 7, wkey = (wrow >> 1) & 7;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int lo = 0; lo < 2; ++lo) {
-                const int c = (kb * 2 + h) * 2 + lo;
-                a_off[kb][lo] = lds0 + arow * 128 + ((c ^ akey) << 4);
-                w_off[kb][lo] = lds0 + BM * 128 + wrow * 128 + ((c ^ wkey) << 4);
-            }
-    }
-
-    f32x16 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    const int nk = g.K / BK;
-#pragma unroll
-    for (int q = 0; q < NDMA; ++q) issue_piece(q, 0, 0);
-
-    f16x8 bh[2][2], bl[2][2];      // [k block parity][n tile]
-    f16x8 ah[2], al[2];            // two slots, m tile i lives in slot i & 1
-    auto read_b = [&](unsigned sb, int kb) {
-        bh[kb][0] = lds_read128<0>(w_off[kb][0] + sb);
-        bl[kb][0] = lds_read128<0>(w_off[kb][1] + sb);
-        bh[kb][1] = lds_read128<4096>(w_off[kb][0] + sb);
-        bl[kb][1] = lds_read128<4096>(w_off[kb][1] + sb);
-    };
-    auto read_a = [&](unsigned sb, int kb, int i) {
-        const unsigned hp = a_off[kb][0] + sb, lp = a_off[kb][1] + sb;
-        if (i == 0) { ah[0] = lds_read128<0>(hp); al[0] = lds_read128<0>(lp); }
-        else if (i == 1) { ah[1] = lds_read128<4096>(hp); al[1] = lds_read128<4096>(lp); }
-        else if (i == 2) { ah[0] = lds_read128<8192>(hp); al[0] = lds_read128<8192>(lp); }
-        else { ah[1] = lds_read128<12288>(hp); al[1] = lds_read128<12288>(lp); }
-    };
-    // one K step from ring buffer `buf`; ISSUE: fetch stage kt+1 into the other buffer meanwhile.  The eight (k block, m tile)
-    // sub-steps are spelled out with compile-time indices (fragment slots and DMA pieces are register arrays).
-    auto substep = [&](int kt, int buf, unsigned sb, auto issue_tag, auto kb_tag, auto i_tag) {
-        constexpr bool ISSUE = decltype(issue_tag)::value;
-        constexpr int kb = decltype(kb_tag)::value, i = decltype(i_tag)::value;
-        // prefetch the next fragments, then wait for everything older than them
-        if constexpr (i < 3) { read_a(sb, kb, i + 1); wait_lgkmcnt<2>(); }
-        else if constexpr (kb == 0) { read_b(sb, 1); read_a(sb, 1, 0); wait_lgkmcnt<6>(); }
-        else wait_lgkmcnt<0>();
-        constexpr int sl = i & 1;
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                if (t == 0) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[kb][j], ah[sl], acc[i][j], 0, 0, 0);
-                else if (t == 1) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[kb][j], ah[sl], acc[i][j], 0, 0, 0);
-                else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[kb][j], al[sl], acc[i][j], 0, 0, 0);
-                const int piece = i * 3 + t;     // one DMA piece per two MFMAs over the first 16 MFMAs of the step
-                if (ISSUE && kb == 0 && j == 1 && piece < NDMA) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    issue_piece(piece, kt + 1, buf ^ 1);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto kstep = [&](int kt, int buf, auto issue_tag) {
-        const unsigned sb = buf * STAGE_BYTES;
-        wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        read_b(sb, 0);
-        read_a(sb, 0, 0);
-        using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
-        using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
-        substep(kt, buf, sb, issue_tag, I0{}, I0{});
-        substep(kt, buf, sb, issue_tag, I0{}, I1{});
-        substep(kt, buf, sb, issue_tag, I0{}, I2{});
-        substep(kt, buf, sb, issue_tag, I0{}, I3{});
-        substep(kt, buf, sb, issue_tag, I1{}, I0{});
-        substep(kt, buf, sb, issue_tag, I1{}, I1{});
-        substep(kt, buf, sb, issue_tag, I1{}, I2{});
-        substep(kt, buf, sb, issue_tag, I1{}, I3{});
-    };
-    int kt = 0;
-    for (; kt + 1 < nk; ++kt) {
-        if (ABL == 6 && kt == 1) { if (tid == 0) stamps[1] = wall_clock64(); }
-        kstep(kt, kt & 1, std::true_type{});
-    }
-    kstep(kt, kt & 1, std::false_type{});
-    if constexpr (ABL == 6) { if (tid == 0) stamps[2] = wall_clock64(); }
-
-    const EpiCtx epi = make_epi(g, g.bias, g.C, g.R);
-    if (epi.vec && ABL != 1) {      // coalesced: two passes (m tiles 0-1, then 2-3) through this wave's 17 KiB slice of LDS (ABL 1: tuning, direct stores)
-        __builtin_amdgcn_s_barrier();      // every wave has consumed its last fragments
-        constexpr int SLICE = 64 * 68;
-        float* lds = reinterpret_cast<float*>(smem_p8) + wave * SLICE;
-        f32x16 (&lo2)[2][2] = *reinterpret_cast<f32x16 (*)[2][2]>(&acc[0]);
-        f32x16 (&hi2)[2][2] = *reinterpret_cast<f32x16 (*)[2][2]>(&acc[2]);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] *= p8_out_scale_of(g.a_exp);
-        epilogue_wave_lds<2, 2>(g, epi, lds, m0 + wm * 128, n0 + wn * 64, lane, lo2);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        epilogue_wave_lds<2, 2>(g, epi, lds, m0 + wm * 128 + 64, n0 + wn * 64, lane, hi2);
-    } else {
-        epilogue_tiles<true, false, 4, 2>(g, epi, m0 + wm * 128 + r, n0 + wn * 64, h, acc, p8_out_scale_of(g.a_exp));
-    }
-    if constexpr (ABL == 6) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (tid == 0) stamps[3] = wall_clock64();
-    }
-}
-
-
-// ------------------------------------------------------------------------------------------------------------------
-// Persistent big-tile kernel: (64 TM) x 256 tiles, TM = 4 (256 x 256, the tile of gemm_p8_256_kernel) or 5 (320 x 256), one
-// workgroup of 8 waves (2 x 4, wave tile 32 TM x 64 = TM x 2 MFMA tiles = 128 / 160 accumulator registers) per CU walking the
-// tile list with stride gridDim.x.  What it adds to gemm_p8_256_kernel:
+// Persistent big-tile kernel: (64 TM) x 256 tiles, TM = 4 (256 x 256) or 5 (320 x 256), one workgroup of 8 waves (2 x 4, wave tile
+// 32 TM x 64 = TM x 2 MFMA tiles = 128 / 160 accumulator registers) per CU walking the tile list with stride gridDim.x.  A 128x128
+// tile is bound by what the LDS-DMA path of a CU delivers (~60 GB/s: 32 KiB per K step in 0.53 us with the MFMAs removed); a
+// 256-row tile needs half the operand bytes per flop, which one fp32 accumulator per output (common.h: both operand halves share a
+// scale) makes affordable.  A K step (32 deep) is long enough that a two-stage ring of (BM + BN) x 128 B covers the L2 / HBM
+// latency.  What it adds to a plain (non-persistent) tile kernel of that shape:
 //   * the LDS-DMA ring runs ACROSS tile boundaries: stage 0 of the next tile is fetched during the last K step of this one and its
 //     stage 1 right after that step's barrier, so a tile has no prologue (3.3 us of 90) and the DMA latency of the first two stages
 //     sits under the epilogue;
@@ -583,11 +397,9 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_big_kernel(const GemmArgs g) {
         else wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-#ifndef BIG_ABL_NOLDS
         read_b(sb, 0);
         ah[0] = lds_read128<0>(a_off[0] + sb);
         al[0] = lds_read128<0>(a_off[1] + sb);
-#endif
     };
     // One K step out of ring buffer `buf`; its top() has run.  The pieces of K tile kt_issue of the tile `src` points at go into the
     // other buffer meanwhile, one per two MFMAs - in EVERY step, so that the step is straight-line code (ONE copy serves the whole
@@ -602,52 +414,34 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_big_kernel(const GemmArgs g) {
             constexpr int u = decltype(u_tag)::value, kb = u / TM, i = u % TM, sl = u & 1;
             if constexpr (u + 1 < NSUB) {       // prefetch the next sub-step's fragments, then wait for everything older than them
                 constexpr int nkb = (u + 1) / TM, ni = (u + 1) % TM, nsl = (u + 1) & 1;
-#ifndef BIG_ABL_NOLDS      // (timing builds, results wrong: BIG_ABL_NOLDS no fragment reads, BIG_ABL_NODMA no DMA pieces, BIG_ABL_ONEPROD one MFMA product of three, BIG_ABL_NOSTORE stores masked)
                 if constexpr (ni == 0) read_b(sb, nkb);
                 ah[nsl] = lds_read128<ni * 4096>((a_off[0] + sb) ^ (nkb << 6));
                 al[nsl] = lds_read128<ni * 4096>((a_off[1] + sb) ^ (nkb << 6));
-#endif
                 if constexpr (ni == 0) wait_lgkmcnt<6>(); else wait_lgkmcnt<2>();
             } else {
                 wait_lgkmcnt<0>();
                 if (next_top) top(buf ^ 1, next_pre);      // (slot 0 and the k-block-0 weight fragments are free: this sub-step uses slot 1 / k block 1)
             }
-#ifdef BIG_SETPRIO      // (experiment: the wave whose fragments are in gets the issue slots for its six MFMAs)
-            __builtin_amdgcn_s_setprio(BIG_SETPRIO);
-#endif
 #pragma unroll
             for (int t = 0; t < 3; ++t)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     if (t == 0) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[kb][j], ah[sl], acc[i][j], 0, 0, 0);
-#ifndef BIG_ABL_ONEPROD
                     else if (t == 1) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[kb][j], ah[sl], acc[i][j], 0, 0, 0);
                     else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[kb][j], al[sl], acc[i][j], 0, 0, 0);
-#endif
                     const int piece = u * 3 + t;     // one DMA piece per two MFMAs from the start of the step
-#ifdef BIG_ABL_NODMA
-                    if (false) {
-#else
                     if (j == 1 && piece < NDMA) {
-#endif
                         __builtin_amdgcn_sched_barrier(0);
                         issue_piece(piece, kt_issue, buf ^ 1);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
-#ifdef BIG_SETPRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
             __builtin_amdgcn_sched_barrier(0);
         });
     };
 
     int t = blockIdx.x;
     if (t >= ntiles) return;
-#ifdef BIG_ABL_NOLDS
-    read_b(0, 0); read_b(0, 1);
-    ah[0] = lds_read128<0>(a_off[0]); al[0] = lds_read128<0>(a_off[1]); ah[1] = lds_read128<4096>(a_off[0]); al[1] = lds_read128<4096>(a_off[1]);
-#endif
     int m0, n0;
     tile_origin(t, m0, n0);
     set_src(m0, n0);
@@ -670,11 +464,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_big_kernel(const GemmArgs g) {
 #pragma unroll
                 for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
         const int t_next = t + gridDim.x;
-#ifdef BIG_NO_NEXT
-        const bool has_next = false;
-#else
         const bool has_next = t_next < ntiles;
-#endif
         int nm0 = 0, nn0 = 0;
         if (has_next) tile_origin(t_next, nm0, nn0);
         // Stages 0 and 1 of a tile are in the ring when it starts.  Step kt reads buffer gs & 1 and fetches K tile kt + 1 into the
@@ -683,15 +473,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_big_kernel(const GemmArgs g) {
         // traffic buys a branch-free step.  The last step runs the ring on into the next tile: its stage 0 goes into the buffer of the
         // step before; the very last step of the workgroup re-fetches K tile 0 of its own tile into that (free) buffer.
         top(gs & 1, nk > 1 ? pre0 : 0);      // (nk == 1: stage 0 only, waited for in full)
-#ifdef BIG_PHASE      // timing build (results wrong): the first tile of a workgroup runs a phase-dependent share of its K steps, so the CUs' epilogues stop coinciding
-#ifdef BIG_PHASE_XCD     // the CUs of an XCD stay in phase (they share operand fetches through their L2), the eight XCDs are spread over a tile period
-        const int nk_cur = tile_no == 0 ? max(2, (nk * ((int)(blockIdx.x & 7) + 1)) / 8) : nk;
-#else
-        const int nk_cur = tile_no == 0 ? max(2, (nk * ((int)((blockIdx.x >> 3) % BIG_PHASE) + 1)) / BIG_PHASE) : nk;
-#endif
-#else
         const int nk_cur = nk;
-#endif
 #pragma nounroll
         for (int kt = 0; kt < nk_cur; ++kt) {
             const bool last = kt + 1 == nk_cur;
@@ -735,11 +517,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_big_kernel(const GemmArgs g) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) acc[i][j][4 * q + e] += res[q][e];
             }
-#ifdef BIG_ABL_NOSTORE
-            epilogue_tile32_store<false>(g, g.C, row, n0 + wn * 64 + j * 32, h, acc[i][j], nullptr, row < (g.force_cfg == 12345 ? g.M : -1));
-#else
             epilogue_tile32_store<false>(g, g.C, row, n0 + wn * 64 + j * 32, h, acc[i][j], nullptr, row < g.M);
-#endif
         };
         using J0 = std::integral_constant<int, 0>; using J1 = std::integral_constant<int, 1>;
         // Residual tiles (the encoder's out-projection and FFN-out, x += ... in place; fp32 result): the residual runs of sub-tile s + 1
@@ -1153,32 +931,24 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_mid_kernel(const GemmArgs g) {
     auto read_frags = [&](int buf, int kb, f16x8 (&ah)[2], f16x8 (&al)[2], f16x8 (&bh)[TN], f16x8 (&bl)[TN]) {
         const unsigned sb = buf * STAGE_BYTES;
         const unsigned ahp = a_off[kb][0] + sb, alp = a_off[kb][1] + sb, whp = w_off[kb][0] + sb, wlp = w_off[kb][1] + sb;
-#ifndef MID_ABL_NOB      // (timing build: the weight operand neither fetched nor read from LDS after the first K step)
         bh[0] = lds_read128<0>(whp);
         bl[0] = lds_read128<0>(wlp);
-#endif
         ah[0] = lds_read128<0>(ahp);
         al[0] = lds_read128<0>(alp);
         ah[1] = lds_read128<4096>(ahp);
         al[1] = lds_read128<4096>(alp);
-#ifndef MID_ABL_NOB
         if constexpr (TN == 2) {
             bh[TN - 1] = lds_read128<4096>(whp);
             bl[TN - 1] = lds_read128<4096>(wlp);
         }
-#endif
     };
     constexpr int NMF = 2 * TN * 3;    // MFMAs per half step
     auto mfma_slot = [&](int sidx, const f16x8 (&ah)[2], const f16x8 (&al)[2], const f16x8 (&bh)[TN], const f16x8 (&bl)[TN]) {
         // term-major order: consecutive MFMAs go to different accumulators.  Weight fragment = A operand: C^T, see epilogue_tile32
         const int t = sidx / (2 * TN), i = (sidx / TN) % 2, j = sidx % TN;
-#ifdef MID_ABL_NOMFMA      // (timing builds, results wrong: MID_ABL_NOMFMA one MFMA of twelve per half step, MID_ABL_NODMA no DMA after the prologue, MID_ABL_NOBAR no barriers)
-        if (sidx == 0) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[j], ah[i], acc[i][j], 0, 0, 0);
-#else
         if (t == 0) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[j], ah[i], acc[i][j], 0, 0, 0);
         else if (t == 1) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[j], ah[i], acc[i][j], 0, 0, 0);
         else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[j], al[i], acc[i][j], 0, 0, 0);
-#endif
     };
     auto mfmas = [&](const f16x8 (&ah)[2], const f16x8 (&al)[2], const f16x8 (&bh)[TN], const f16x8 (&bl)[TN]) {
 #pragma unroll
@@ -1189,9 +959,6 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_mid_kernel(const GemmArgs g) {
     wait_vmcnt_units<NDMA>(min(STAGES - 2, nk - 1));   // stage 0 landed (the prologue left up to STAGES-2 younger stages in flight)
     __builtin_amdgcn_s_barrier();
     read_frags(0, 0, ah0, al0, bh0, bl0);
-#ifdef MID_ABL_NOB
-    bh0[0] = lds_read128<0>(w_off[0][0]); bl0[0] = lds_read128<0>(w_off[0][1]); bh1[0] = lds_read128<0>(w_off[1][0]); bl1[0] = lds_read128<0>(w_off[1][1]);
-#endif
     int kt = 0, buf = 0;                               // buf = kt % STAGES
     for (; kt + STAGES - 1 < nk; ++kt) {               // steady state: stage kt+S-1 still to be fetched
         const int nbuf = (buf + 1 == STAGES) ? 0 : buf + 1;
@@ -1200,27 +967,15 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_mid_kernel(const GemmArgs g) {
         wait_lgkmcnt<NRD>();                           // the kb=0 fragments (issued half a step ago) are in; the kb=1 reads fly on
         mfmas(ah0, al0, bh0, bl0);
         __builtin_amdgcn_sched_barrier(0);
-#ifdef MID_ABL_NOB
-        wait_vmcnt<(STAGES - 3) * APIECES>();
-#else
         wait_vmcnt<(STAGES - 3) * NDMA>();             // stage kt+1 landed for this wave (stages kt+2 .. kt+S-2 may still fly)
-#endif
-#ifndef MID_ABL_NOBAR
         __builtin_amdgcn_s_barrier();                  // ... and for every wave; every wave is done with stage kt-1
-#endif
         __builtin_amdgcn_sched_barrier(0);
         read_frags(nbuf, 0, ah0, al0, bh0, bl0);
         wait_lgkmcnt<NRD>();                           // kb=1 fragments of stage kt
 #pragma unroll
         for (int sidx = 0; sidx < NMF; ++sidx) {
             mfma_slot(sidx, ah1, al1, bh1, bl1);
-#ifdef MID_ABL_NODMA
-            if (false) {
-#elif defined(MID_ABL_NOB)
-            if (sidx < APIECES) {
-#else
             if (sidx < NDMA) {
-#endif
                 __builtin_amdgcn_sched_barrier(0);
                 issue_piece(sidx, kt + STAGES - 1, fbuf);
                 __builtin_amdgcn_sched_barrier(0);
@@ -1291,10 +1046,11 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_mid_kernel(const GemmArgs g) {
 //     stages keeps two K steps in flight (the in-phase structure reads a stage over a whole step and needs 4 buffers for that), which
 //     is what makes a 256 x 128 tile (48 KB per stage: 0.75 of the operand bytes per flop of 128 x 128) fit the 160 KB of LDS;
 //   * DMA pieces are buffer loads to LDS (descriptor in SGPRs, 32-bit lane offsets, hardware range check instead of a row clamp).
-// Synchronisation per K step: ONE mandatory barrier O_k (behind a counted vmcnt wait: stage k + 1 has landed for every wave, every wave
-// has read stage k) and, with BAR2, a second one E_k between the two phases of a step (keeps the groups exactly one phase apart;
-// without it they pair up by themselves).  Accumulation order per output element is that of every other split kernel.
-template <int BM, int BN, int WMW, int WNW, int STAGES, int BAR2, int TAG>
+// Synchronisation per K step: a barrier O_k (behind a counted vmcnt wait: stage k + 1 has landed for every wave, every wave has read
+// stage k) and a second one E_k between the two phases of a step, which keeps the groups exactly one phase apart (with O_k alone they
+// pair up by themselves; one barrier per step measured no better: profiles/r05_pp_gemm_sweep.log).  Accumulation order per output
+// element is that of every other split kernel.
+template <int BM, int BN, int WMW, int WNW, int STAGES, int TAG>
 __global__ __launch_bounds__(512, 1) void gemm_p8_pp_kernel(const GemmArgs g) {
     constexpr int BK = 32;
     static_assert(WMW * WNW == 8, "8 waves");
@@ -1382,16 +1138,9 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_pp_kernel(const GemmArgs g) {
     constexpr int NRD_KB = 2 * (TMW + TNW);                       // ds_read_b128 per k block (lgkmcnt is a 4-bit counter: with 16 reads of a phase in flight the 16th waits at issue)
     // LOAD phase of K step k: the pieces of stage k + S - 1 first (a Y wave's pieces have three phases to land, an X wave's four), then
     // every fragment of stage k, k block 0 first
-    // (timing builds, results wrong: PP_ABL_NOMFMA one MFMA of a phase's 6 TMW TNW, PP_ABL_NODMA no DMA behind the prologue, PP_ABL_NOLDS
-    // fragments read in the first K step only; tools/pp_ablation.sh)
     auto load_phase = [&](int k) __attribute__((always_inline)) {
-#ifndef PP_ABL_NODMA
         if (k >= 1 && k + STAGES - 1 < nk) issue_stage(k + STAGES - 1, (k - 1) % STAGES);
-#endif
         __builtin_amdgcn_sched_barrier(0);
-#ifdef PP_ABL_NOLDS
-        if (k > 0) return;
-#endif
         const unsigned sb = (unsigned)((k % STAGES) * STAGE_BYTES);
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
@@ -1421,9 +1170,6 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_pp_kernel(const GemmArgs g) {
                 for (int i = 0; i < TMW; ++i)
 #pragma unroll
                     for (int j = 0; j < TNW; ++j) {      // weight fragment = A operand: C^T, see epilogue_tile32
-#ifdef PP_ABL_NOMFMA
-                        if (t + i + j + kb > 0) continue;
-#endif
                         if (t == 0) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[kb][j], ah[kb][i], acc[i][j], 0, 0, 0);
                         else if (t == 1) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[kb][j], ah[kb][i], acc[i][j], 0, 0, 0);
                         else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[kb][j], al[kb][i], acc[i][j], 0, 0, 0);
@@ -1440,34 +1186,29 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_pp_kernel(const GemmArgs g) {
         __builtin_amdgcn_sched_barrier(0);
     }
     // ONE program for both groups (no divergent path around the fragment and accumulator registers: the asm reads' results may not cross
-    // a control-flow join before their wait): L(k) | C(k) per K step; what differs is where a group's barriers sit.
-    //   BAR2 = 0: X has its barrier O_k behind C(k), Y behind L(k) - so Y runs C(k - 1) | L(k) between two barriers while X runs L(k) | C(k);
-    //   BAR2 = 1: a barrier behind every phase; Y takes one extra barrier first (it starts one phase late), X one extra at the end.
+    // a control-flow join before their wait): L(k) | C(k) per K step, a barrier behind every phase; Y takes one extra barrier first (it
+    // starts one phase late), X one extra at the end.
     // O_k (X: behind C(k), Y: behind L(k)) is taken behind the wait for this wave's pieces of stage k + 1: at most the stages issued
     // behind it, k + 2 .. min(k + S - 1, nk - 1), stay in flight.  A load phase's reads have returned before its barrier, so that
     // nobody's DMA can overwrite a buffer under a read in flight.
-    if (BAR2 && grp_y) __builtin_amdgcn_s_barrier();
+    if (grp_y) __builtin_amdgcn_s_barrier();
 #pragma nounroll
     for (int k = 0; k < nk; ++k) {
         const bool more = k + 1 < nk;
         const int units = min(STAGES - 2, nk - 2 - k);
         load_phase(k);
-        if (BAR2 || (grp_y && more)) {
-            if (grp_y) {
-                wait_lgkmcnt<0>();
-                if (more) wait_vmcnt_units<NP>(units);
-            }
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
+        if (grp_y) {
+            wait_lgkmcnt<0>();
+            if (more) wait_vmcnt_units<NP>(units);
         }
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
         compute_phase();
-        if (BAR2 || (!grp_y && more)) {
-            if (!grp_y && more) wait_vmcnt_units<NP>(units);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        if (!grp_y && more) wait_vmcnt_units<NP>(units);
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
     }
-    if (BAR2 && !grp_y) __builtin_amdgcn_s_barrier();
+    if (!grp_y) __builtin_amdgcn_s_barrier();
 
 #pragma unroll
     for (int i = 0; i < TMW; ++i)
@@ -1889,11 +1630,6 @@ static void launch_p8_sm_cfg(const GemmArgs& g, hipStream_t s) {
 bool gemm_p8_sm_eligible(const GemmArgs& g) {
     return g.Wp != nullptr && g.a_packed && g.amode == 0 && g.batch == 1 && g.K % 32 == 0 && (g.lda % 8) == 0;
 }
-// force_cfg 20: 64x64 x 4 stages (default); deep rings for the split-K launches of the small scale steps, where a workgroup's whole K
-// slice should be in flight at once (the launch then costs one memory latency instead of one per K step): 23: 64x64 x 8 stages
-// (128 KiB, one workgroup per CU), 24: 64x64 x 5 stages (80 KiB, two per CU).  (128x64, 64x128 and 128x128 tiles and a 3-stage ring
-// were measured on the unsplit grids of the 50- / 100-token steps and never won: DESIGN.md section 6.)
-void gemm_p8_prepare();
 template <int STAGES>
 static void launch_p8_mid(const GemmArgs& g, hipStream_t s) {
     const int tiles = ((g.M + 127) / 128) * ((g.N + 127) / 128);
@@ -1901,37 +1637,19 @@ static void launch_p8_mid(const GemmArgs& g, hipStream_t s) {
     if (g.graph_tag) ARTALK_LAUNCH((gemm_p8_mid_kernel<STAGES, 1>), dim3(tiles, g.splitk), dim3(512), STAGES * 256 * 128, s, g);
     else ARTALK_LAUNCH((gemm_p8_mid_kernel<STAGES, 0>), dim3(tiles, g.splitk), dim3(512), STAGES * 256 * 128, s, g);
 }
-template <int BM, int BN, int WMW, int WNW, int STAGES, int BAR2>
+template <int BM, int BN, int WMW, int WNW, int STAGES>
 static void launch_p8_pp(const GemmArgs& g, hipStream_t s) {
     const int tiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
     gemm_p8_prepare();
     const size_t lds = STAGES * (BM + BN) * 128;
-    if (g.graph_tag) ARTALK_LAUNCH((gemm_p8_pp_kernel<BM, BN, WMW, WNW, STAGES, BAR2, 1>), dim3(tiles, g.splitk), dim3(512), lds, s, g);
-    else ARTALK_LAUNCH((gemm_p8_pp_kernel<BM, BN, WMW, WNW, STAGES, BAR2, 0>), dim3(tiles, g.splitk), dim3(512), lds, s, g);
+    if (g.graph_tag) ARTALK_LAUNCH((gemm_p8_pp_kernel<BM, BN, WMW, WNW, STAGES, 1>), dim3(tiles, g.splitk), dim3(512), lds, s, g);
+    else ARTALK_LAUNCH((gemm_p8_pp_kernel<BM, BN, WMW, WNW, STAGES, 0>), dim3(tiles, g.splitk), dim3(512), lds, s, g);
 }
 // what gemm_p8_pp_kernel's 32-bit DMA offsets need: operands below 4 GiB
-bool gemm_p8_pp_ok(const GemmArgs& g) {
+static bool gemm_p8_pp_ok(const GemmArgs& g) {
     return (double)g.M * g.lda * 4.0 < 4294967296.0 && (double)g.N * g.ldw * 4.0 < 4294967296.0;
 }
-void launch_gemm_p8_sm(const GemmArgs& g, hipStream_t s) {
-    if (g.M <= 0 || g.N <= 0) return;
-    int cfg = g.force_cfg;
-    if (cfg >= 30 && cfg <= 33 && !gemm_p8_pp_ok(g)) cfg = 28;
-    switch (cfg) {
-        // ping-pong kernel (round 5): 30 / 31 = 256 x 128 tile, 3 stages, one / two barriers per K step; 33 = 128 x 128, 4 stages, two barriers
-        // (one barrier per step and the 128 x 256 tile measured no better: profiles/r05_pp_gemm_sweep.log)
-        case 30: launch_p8_pp<256, 128, 4, 2, 3, 0>(g, s); break;
-        case 31: launch_p8_pp<256, 128, 4, 2, 3, 1>(g, s); break;
-        case 33: launch_p8_pp<128, 128, 2, 4, 4, 1>(g, s); break;
-        case 28: launch_p8_mid<4>(g, s); break;
-        case 29: launch_p8_mid<5>(g, s); break;      // (experiment: the whole 160 KiB of LDS as a ring of 5 stages, four K tiles in flight)
-        case 23: launch_p8_sm_cfg<64, 64, 8>(g, s); break;
-        case 24: launch_p8_sm_cfg<64, 64, 5>(g, s); break;
-        default: launch_p8_sm_cfg<64, 64, 4>(g, s); break;
-    }
-}
 
-int gemm_p8_variant(const GemmArgs& g);
 // host-side copy of make_epi()'s test: every row start and every run of 4 columns of C / bias / R / gate is 16-byte aligned
 static bool epi_vec_host(const GemmArgs& g) {
     unsigned long long bits = (unsigned long long)(g.N | g.ldc) | ((unsigned long long)g.C >> 2);
@@ -1955,21 +1673,10 @@ void gemm_p8_prepare() {      // more than the default 64 KB of dynamic LDS (out
     for (const void* f : big5) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 576 * 128 + 4096);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_p8_mid_kernel<4, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 256 * 128);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_p8_mid_kernel<4, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 256 * 128);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_p8_mid_kernel<5, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 5 * 256 * 128);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_p8_mid_kernel<5, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 5 * 256 * 128);
-    {
-        const void* pp[] = {reinterpret_cast<const void*>(&gemm_p8_pp_kernel<256, 128, 4, 2, 3, 0, 0>), reinterpret_cast<const void*>(&gemm_p8_pp_kernel<256, 128, 4, 2, 3, 0, 1>),
-                            reinterpret_cast<const void*>(&gemm_p8_pp_kernel<256, 128, 4, 2, 3, 1, 0>), reinterpret_cast<const void*>(&gemm_p8_pp_kernel<256, 128, 4, 2, 3, 1, 1>)};
-        for (const void* f : pp) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 384 * 128);
-        const void* pq[] = {reinterpret_cast<const void*>(&gemm_p8_pp_kernel<128, 128, 2, 4, 4, 1, 0>), reinterpret_cast<const void*>(&gemm_p8_pp_kernel<128, 128, 2, 4, 4, 1, 1>)};
-        for (const void* f : pq) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 256 * 128);
-    }
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_p8_pp_kernel<256, 128, 4, 2, 3, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 384 * 128);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_p8_pp_kernel<256, 128, 4, 2, 3, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 384 * 128);
     done[dev] = true;
 }
-// Production kernels: force_cfg 7 / 12 = gemm_p8_big_kernel with 256 x 256 / 320 x 256 tiles (persistent, one workgroup per CU),
-// 8 = gemm_p8_2wgp_kernel (persistent 128 x 128, two workgroups per CU, deferred epilogue), -1 = gemm_p8_variant()'s choice;
-// 13 = gemm_p8_256_kernel (the non-persistent 256 x 256 kernel, kept as the A/B baseline of the persistent one), 17 = 13 with
-// wall-clock stamps (tools/gemm_p8_stamps.py).  cfg 8 needs the 16-byte epilogue path (epi_vec_host).
 static int gemm_p8_cus() {      // workgroups of the one-per-CU persistent kernel
     static int n[64] = {};
     int dev = 0;
@@ -2004,6 +1711,7 @@ static void launch_p8_big(const GemmArgs& g, hipStream_t s) {
     const int cus = p8_cus_of(g);
     const size_t lds = 2 * (64 * TM + 256) * 128 + 4096;
     const dim3 grid(tiles < cus ? tiles : cus);
+    gemm_p8_prepare();
     if (g.R) {
         if (g.graph_tag) ARTALK_LAUNCH((gemm_p8_big_kernel<TM, true, 1>), grid, dim3(512), lds, s, g);
         else ARTALK_LAUNCH((gemm_p8_big_kernel<TM, true, 0>), grid, dim3(512), lds, s, g);
@@ -2012,81 +1720,26 @@ static void launch_p8_big(const GemmArgs& g, hipStream_t s) {
         else ARTALK_LAUNCH((gemm_p8_big_kernel<TM, false, 0>), grid, dim3(512), lds, s, g);
     }
 }
-void launch_gemm_p8(const GemmArgs& g0, hipStream_t s) {
-    if (g0.M <= 0 || g0.N <= 0) return;
-    // No range guard in the epilogues of the large-grid kernels (compiled out: epilogue_tile32<.., GUARD = false>; with it the dominant
-    // kernel lost registers to it): their P8 results (q|k|v, FFN hidden) are consumed by the attention kernel and by the next GEMM +
-    // LayerNorm, an out-of-range value turns into inf / NaN there, and those producers (attention output, LayerNorm) carry the
-    // guard - one kernel later instead of in place.
-    GemmArgs g = g0;
-    g.status = nullptr;
-    const int t128 = ((g.M + 127) / 128) * ((g.N + 127) / 128), t256sq = ((g.M + 255) / 256) * ((g.N + 255) / 256);
-    int cfg = g.force_cfg;
-    if (cfg != 7 && cfg != 8 && cfg != 12 && cfg != 13 && cfg != 17) {
-        const int v = gemm_p8_variant(g);
-        cfg = v == 1 ? 7 : (v == 2 ? 12 : 8);
-    }
-    if ((cfg == 7 || cfg == 12) && !p8_big_ok(g)) cfg = epi_vec_host(g) ? 8 : 13;      // (tuning / tests only: the dispatch checks p8_big_ok itself)
-    if (cfg == 8 && !epi_vec_host(g)) cfg = 13;     // (no launch of the path gets here: every large-grid result is 16-byte aligned)
-    if (cfg == 7 || cfg == 12) {
-        gemm_p8_prepare();
-        // Round quantisation, the dispatch-only answer (round 5): a launch of 320-row tiles whose LAST round is partial
-        // goes out as two launches when the rows of that round fit ONE round of 256-row tiles - whole rounds of 320 x 256 first, then the
-        // remaining rows as 256 x 256 tiles (0.8 of a round's time).  With the shapes of batch 32 that is the encoder's FFN-in GEMM only
-        // (960 tiles = 3.75 rounds -> 768 tiles + 240 tiles of 256 rows: 3.8 rounds of time instead of 4); q|k|v (2.81 rounds) has no such
-        // split: 504 + 276 tiles, the second launch would spill into a second round.  Row ranges are independent and an element's K order
-        // does not depend on its tile: bit-identical.  MEASURED, NO GAIN (same box, three alternating pairs, profiles/r05_split2_ab.log:
-        // encoder 36.08 / 36.01 / 36.00 ms without, 36.03 / 36.09 / 35.98 ms with): in the partial last round of the single launch a quarter
-        // of the CUs are idle and the power-managed clock of the others rises, which already recovers most of what
-        // the quantisation costs on paper (5 % of the launch).  Off by default; ARTALK_P8_SPLIT2=1 switches it on (A/B).
-        static const int split2 = getenv("ARTALK_P8_SPLIT2") ? atoi(getenv("ARTALK_P8_SPLIT2")) : 0;
-        if (cfg == 12 && split2 && g0.force_cfg < 0 && g.cmap.rpb == INT_MAX && !g.gate) {
-            const int cus = p8_cus_of(g), tn = (g.N + 255) / 256, tm5 = (g.M + 319) / 320;
-            const int tiles5 = tm5 * tn, full = tiles5 / cus * cus;
-            if (full > 0 && tiles5 > full) {
-                const int rows1 = full / tn;                       // row tiles of the first launch (whole rounds or a little less)
-                const int M1 = rows1 * 320, M2 = g.M - M1;
-                const int tiles2 = ((M2 + 255) / 256) * tn;
-                const double t_one = std::ceil((double)tiles5 / cus), t_two = std::ceil((double)rows1 * tn / cus) + 0.8 * std::ceil((double)tiles2 / cus) + 0.04;
-                if (rows1 > 0 && M2 > 0 && tiles2 <= cus && t_two < t_one) {
-                    GemmArgs a = g, b = g;
-                    a.M = M1;
-                    b.M = M2; b.A = g.A + (long)M1 * g.lda; b.C = g.C + (long)M1 * g.ldc;
-                    if (g.R) b.R = g.R + (long)M1 * g.ldr;
-                    launch_p8_big<5>(a, s);
-                    launch_p8_big<4>(b, s);
-                    return;
-                }
-            }
-        }
-        if (cfg == 7) launch_p8_big<4>(g, s); else launch_p8_big<5>(g, s);
-    } else if (cfg == 13) {
-        ARTALK_LAUNCH((gemm_p8_256_kernel<0>), dim3(t256sq), dim3(512), 8 * 64 * 68 * 4, s, g);
-    } else if (cfg == 17) {
-        ARTALK_LAUNCH((gemm_p8_256_kernel<6>), dim3(t256sq), dim3(512), 8 * 64 * 68 * 4, s, g);
-    } else {
-        // residual tiles deferred too (ARTALK_P8_RES_DEFER=0 finishes them at once; tests compare both): 16 KiB more LDS, still two
-        // workgroups per CU
-        static const int res_defer = getenv("ARTALK_P8_RES_DEFER") ? atoi(getenv("ARTALK_P8_RES_DEFER")) : 1;
-        g.res_lds = (res_defer && g.R && !g.gate && !g.c_p8) ? 1 : 0;
-        if (g.res_lds) gemm_p8_prepare();
-        const size_t lds = 2 * 256 * 128 + (g.res_lds ? 16384 : 0);
-        const int slots = 2 * p8_cus_of(g);      // two workgroups per CU
-        if (g.graph_tag) ARTALK_LAUNCH((gemm_p8_2wgp_kernel<1>), dim3(t128 < slots ? t128 : slots), dim3(256), lds, s, g);
-        else ARTALK_LAUNCH((gemm_p8_2wgp_kernel<0>), dim3(t128 < slots ? t128 : slots), dim3(256), lds, s, g);
-    }
+static void launch_p8_2wgp(GemmArgs g, hipStream_t s) {
+    // residual tiles deferred too (ARTALK_P8_RES_DEFER=0 finishes them at once; tests compare both): 16 KiB more LDS, still two
+    // workgroups per CU
+    static const int res_defer = getenv("ARTALK_P8_RES_DEFER") ? atoi(getenv("ARTALK_P8_RES_DEFER")) : 1;
+    g.res_lds = (res_defer && g.R && !g.gate && !g.c_p8) ? 1 : 0;
+    if (g.res_lds) gemm_p8_prepare();
+    const int t128 = ((g.M + 127) / 128) * ((g.N + 127) / 128);
+    const size_t lds = 2 * 256 * 128 + (g.res_lds ? 16384 : 0);
+    const int slots = 2 * p8_cus_of(g);      // two workgroups per CU
+    if (g.graph_tag) ARTALK_LAUNCH((gemm_p8_2wgp_kernel<1>), dim3(t128 < slots ? t128 : slots), dim3(256), lds, s, g);
+    else ARTALK_LAUNCH((gemm_p8_2wgp_kernel<0>), dim3(t128 < slots ? t128 : slots), dim3(256), lds, s, g);
 }
 // 0: persistent two-workgroup 128x128 kernel, 1 / 2: persistent big-tile kernel with 256x256 / 320x256 tiles.  A cost model picks the
 // configuration with the shortest critical path: rounds x (K steps x time per step + epilogue), calibrated on the encoder shapes of
 // batch 32 (profiles/r03_gemm_f16s_bench.log): a 64-row slab of a 256-column tile takes 0.58 us per 32-deep K step and ~3 us of
 // epilogue, a pair of co-resident 128x128 tiles 1.1 - 1.5 us per K step (1.3 taken).  At M = 19200 this gives 320x256 everywhere: N = 1024 (out-projection,
 // FFN-out) is ONE round of 240 tiles on 256 CUs where the 128x128 kernel's 512 workgroups need 2.34 rounds (FFN-out 482 -> 406 us),
-// q|k|v 2.81 rounds instead of the 256x256 tile's 3.52 (403 -> 328 us).  ARTALK_P8_BIG = 0 / 1 / 2 forces a variant (A/B runs).
-int gemm_p8_variant(const GemmArgs& g) {
-    static const int forced = getenv("ARTALK_P8_BIG") ? atoi(getenv("ARTALK_P8_BIG")) : -1;
-    const bool big_ok = p8_big_ok(g);
-    if (forced >= 0) return big_ok ? forced : 0;
-    if (!big_ok) return 0;
+// q|k|v 2.81 rounds instead of the 256x256 tile's 3.52 (403 -> 328 us).
+static int gemm_p8_variant(const GemmArgs& g) {
+    if (!p8_big_ok(g)) return 0;
     const double nk = g.K / 32, cus = p8_cus_of(g);
     auto big = [&](int TM) {
         const double tiles = (double)((g.M + 64 * TM - 1) / (64 * TM)) * ((g.N + 255) / 256);
@@ -2099,7 +1752,103 @@ int gemm_p8_variant(const GemmArgs& g) {
 }
 bool gemm_p8_eligible(const GemmArgs& g) {
     return g.Wp != nullptr && g.a_packed && g.amode == 0 && g.batch == 1 && g.splitk == 1 && g.K % 32 == 0 && (g.lda % 8) == 0 &&
-           (long)((g.M + 127) / 128) * ((g.N + 127) / 128) >= 384 && (g.ngrp == 0 || (g.ngrp % 128 == 0 && g.N % g.ngrp == 0));
+           (long)((g.M + 127) / 128) * ((g.N + 127) / 128) >= 384 && (g.ngrp == 0 || (g.ngrp % 128 == 0 && g.N % g.ngrp == 0)) &&
+           epi_vec_host(g);
+}
+
+// Small-grid plan (the AR / VAE scale steps).  Small-grid LDS-DMA kernel (64x64 tiles).  These launches are latency-bound: measured
+// with cold weights, replayed from a graph, GEMM + reduce (profiles/r02_tiny_gemm_sweep.log): K = 3072 gains from a split below ~192
+// tiles (M = 400: 19.1 us split in 6 vs 27 unsplit); K = 768 gains only on the smallest grids, where the split workgroups' whole K
+// slice fits the ring and is in flight at once (deep-ring configurations 23 / 24): proj at M = 80 7.8 us split in 6 vs 9.8, qkv 9.9 us
+// split in 3 vs 13.2.  A split 768-wide result also gets its LayerNorm for free (the engine's fused reduce + LayerNorm).
+static int plan_gemm_p8_small(GemmArgs& g, int64_t splitk_floats) {
+    if (g.K < 256) return 20;
+    const int tiles = gemm_tile_count(g, true);
+    int S = 1, cfg = -1;
+    if (g.K >= 2048) {
+        if (tiles <= 24) { S = 8; cfg = 23; }
+        else if (tiles < 192) S = tiles < 48 ? 6 : 3;
+    } else {
+        if (tiles <= 24) { S = 6; cfg = 24; }
+        else if (tiles <= 36) { S = 4; cfg = 24; }
+        else if (tiles <= 72) { S = 3; cfg = 23; }
+        else if (tiles <= 108) S = 2;
+    }
+    while (S > 1 && (int64_t)S * g.M * g.N > splitk_floats) { --S; cfg = -1; }
+    if (S == 5 || S == 7) { --S; }        // the unrolled reduce kernels exist for 2, 3, 4, 6, 8 slabs
+    // Mid-grid kernel (128x128 tiles, one 8-wave workgroup per CU, 4-stage ring: gemm_p8_mid_kernel, cfg 28) where its grid
+    // fills most of the chip: these launches are bound by what an XCD pulls in per K step, and a 128x128 tile has four times
+    // the matrix work per fetched byte of the 64x64 tile (profiles/r03_mid_gemm_sweep.log, cold weights, graph replay:
+    // q|k|v at M = 1600 30.7 -> 24.6 us, FFN-in at M = 800 28.8 -> 22.2, FFN-out at M = 1600 split in 3 42.6 -> 35.0; below
+    // ~150 tiles the 64x64 kernel wins: projection at M = 1600 14.0 vs 19.0).  It has no second P8 copy of the result (c2).
+    if (S == 1 && !g.c2) {
+        const int t128 = ((g.M + 127) / 128) * ((g.N + 127) / 128);
+        // Ping-pong kernel (gemm_p8_pp_kernel, cfg 31: 256 x 128 tiles, the two waves of a SIMD one phase apart) where its grid is
+        // 120 .. 256 tiles: q|k|v and FFN-in of the 100-token step, q|k|v of the VAE decoder stack.  Measured (round 5,
+        // profiles/r05_pp_gemm_sweep.log, r05_pp_model_ab.log): FFN-in at M = 1600 39.0 -> 32.6 us (168 tiles in ONE round instead
+        // of 312 in two), VAE q|k|v at M = 3200 27.1 -> 24.2, q|k|v at M = 1600 slower alone (24.3 -> 30.8: half the chip) but not
+        // beside the other clip group's launches; body 31.75 / 31.92 -> 31.58 / 31.79 ms per step in same-box pairs.
+        const int t256 = ((g.M + 255) / 256) * ((g.N + 127) / 128);
+        if (t256 >= 120 && t256 <= 256 && gemm_p8_pp_ok(g)) cfg = 31;
+        else if (t128 >= 150) cfg = 28;
+        else if (g.K >= 2048 && 3 * t128 >= 150 && (int64_t)3 * g.M * g.N <= splitk_floats) { S = 3; cfg = 28; }
+    }
+    g.splitk = S;
+    // weights of the narrowest steps (levels 0 and 1) are read once per launch by a handful of workgroups: fetched with the
+    // non-temporal policy they do not displace the resident history (A/B, cold weights: -0.2..-0.5 us of 8..16 us at M <= 80,
+    // +0.4 us at M = 400, where several row tiles re-read each weight tile through L2)
+    if (g.M <= 160) g.w_nt = 1;
+    return cfg < 0 ? 20 : cfg;
+}
+P8Plan plan_gemm_p8(GemmArgs& g, int64_t splitk_floats) {
+    int cfg = g.force_cfg;
+    // a forced configuration the shape cannot take: the big tiles fall back to the persistent 128x128 kernel, that one (it needs the
+    // 16-byte epilogue path) to the plan, the ping-pong kernel to the mid-grid one
+    if ((cfg == 7 || cfg == 12) && !p8_big_ok(g)) cfg = 8;
+    if (cfg == 8 && !epi_vec_host(g)) cfg = -1;
+    if (cfg == 31 && !gemm_p8_pp_ok(g)) cfg = 28;
+    if (cfg < 0 && gemm_p8_eligible(g)) {
+        const int v = gemm_p8_variant(g);
+        cfg = v == 1 ? 7 : (v == 2 ? 12 : 8);
+    }
+    if (cfg < 0) { g.force_cfg = -1; cfg = plan_gemm_p8_small(g, splitk_floats); }
+    g.force_cfg = cfg;
+    P8Plan p;
+    p.dominant = cfg == 7 || cfg == 12;
+    // the second P8 copy of the result (GemmArgs::c2) comes from the small-grid kernel's epilogue when that kernel finishes the tiles
+    // itself, through the epilogue's 16-byte path (every pointer and row start aligned)
+    p.c2_fused = g.c2 && (cfg == 20 || cfg == 23 || cfg == 24) && g.splitk == 1 && !g.c_p8 && (g.N % 8) == 0 && (g.ldc % 8) == 0 &&
+                 !g.gate && (g.ldr % 4) == 0 &&
+                 (((unsigned long long)g.C | (unsigned long long)g.c2 | (unsigned long long)g.bias | (unsigned long long)g.R) & 15) == 0;
+    return p;
+}
+
+// Launches the planned configuration (g.force_cfg, plan_gemm_p8):
+//   large grid: 7 / 12 = gemm_p8_big_kernel with 256 x 256 / 320 x 256 tiles (persistent, one workgroup per CU), 8 = gemm_p8_2wgp_kernel
+//     (persistent 128 x 128, two workgroups per CU, deferred epilogue);
+//   small grid: 20 = gemm_p8_sm_kernel, 64x64 x 4 stages; deep rings for the split-K launches of the small scale steps, where a
+//     workgroup's whole K slice should be in flight at once (the launch then costs one memory latency instead of one per K step):
+//     23 = 64x64 x 8 stages (128 KiB, one workgroup per CU), 24 = 64x64 x 5 stages (80 KiB, two per CU).  (128x64, 64x128 and
+//     128x128 tiles and a 3-stage ring were measured on the unsplit grids of the 50- / 100-token steps and never won: DESIGN.md
+//     section 6.)  28 = gemm_p8_mid_kernel (128 x 128, 4 stages), 31 = gemm_p8_pp_kernel (256 x 128, 3 stages, two barriers per K
+//     step; profiles/r05_pp_gemm_sweep.log).
+// No range guard in the epilogues of the large-grid kernels (compiled out: epilogue_tile32<.., GUARD = false>; with it the dominant
+// kernel lost registers to it): their P8 results (q|k|v, FFN hidden) are consumed by the attention kernel and by the next GEMM +
+// LayerNorm, an out-of-range value turns into inf / NaN there, and those producers (attention output, LayerNorm) carry the
+// guard - one kernel later instead of in place.
+void launch_gemm_p8(const GemmArgs& g0, hipStream_t s) {
+    if (g0.M <= 0 || g0.N <= 0) return;
+    GemmArgs g = g0;
+    switch (g.force_cfg) {
+        case 7: g.status = nullptr; launch_p8_big<4>(g, s); break;
+        case 12: g.status = nullptr; launch_p8_big<5>(g, s); break;
+        case 8: g.status = nullptr; launch_p8_2wgp(g, s); break;
+        case 31: launch_p8_pp<256, 128, 4, 2, 3>(g, s); break;
+        case 28: launch_p8_mid<4>(g, s); break;
+        case 23: launch_p8_sm_cfg<64, 64, 8>(g, s); break;
+        case 24: launch_p8_sm_cfg<64, 64, 5>(g, s); break;
+        default: launch_p8_sm_cfg<64, 64, 4>(g, s); break;
+    }
 }
 
 template <int BM, int BN, int WM, int WN>

@@ -175,7 +175,6 @@ static void launch_cfg(const GemmArgs& g, hipStream_t s) {
 //   2: 64x64,   BK=32   smaller grids with M > 32 (AR / VAE steps; 4 workgroups/CU)                                  50-100 TF/s
 //   1: 128x64,  BK=32   grouped positional conv (N = 64 per group)
 //   3: 32x128,  BK=32   M <= 32 (first scale step at small batch)
-//   0,5,6,7: kept for tuning (128x128 BK=32; 128x64, 64x128, 64x64 with BK=16)
 int gemm_config(const GemmArgs& g) {
     if (g.force_cfg >= 0) return g.force_cfg;
     if (g.amode == 1) return 1;
@@ -188,15 +187,9 @@ int gemm_config(const GemmArgs& g) {
 void launch_gemm(const GemmArgs& g, hipStream_t s) {
     if (g.M <= 0 || g.N <= 0) return;
     switch (gemm_config(g)) {
-        case 0: launch_cfg<128, 128, 2, 2>(g, s); break;
         case 1: launch_cfg<128, 64, 2, 2>(g, s); break;
         case 2: launch_cfg<64, 64, 2, 2>(g, s); break;
-        case 3: launch_cfg<32, 128, 1, 4>(g, s); break;
-        // experimental BK=16 variants (more workgroups per CU)
-        case 4: launch_cfg<128, 128, 2, 2, 16>(g, s); break;
-        case 5: launch_cfg<128, 64, 2, 2, 16>(g, s); break;
-        case 6: launch_cfg<64, 128, 2, 2, 16>(g, s); break;
-        case 7: launch_cfg<64, 64, 2, 2, 16>(g, s); break;
+        case 4: launch_cfg<128, 128, 2, 2, 16>(g, s); break;      // BK = 16 (more workgroups per CU)
         default: launch_cfg<32, 128, 1, 4>(g, s); break;
     }
 }
@@ -348,10 +341,9 @@ int gemm_tile_count(const GemmArgs& g, bool f16s) {
     int bm, bn;
     if (f16s) { if (gemm_f16s_config(g) == 0) { bm = 128; bn = 128; } else { bm = 64; bn = 64; } }
     else switch (gemm_config(g)) {
-        case 0: case 4: bm = 128; bn = 128; break;
-        case 1: case 5: bm = 128; bn = 64; break;
-        case 6: bm = 64; bn = 128; break;
-        case 2: case 7: bm = 64; bn = 64; break;
+        case 4: bm = 128; bn = 128; break;
+        case 1: bm = 128; bn = 64; break;
+        case 2: bm = 64; bn = 64; break;
         default: bm = 32; bn = 128; break;
     }
     return ((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn);

@@ -98,13 +98,18 @@ void launch_pack_split(const float* w, unsigned int* out, long n, bool is_weight
 bool gemm_f16s_eligible(const GemmArgs& g);
 int gemm_f16s_config(const GemmArgs& g);     // register-staged kernel: 0: 128x128, 1: 64x64
 void launch_gemm_f16s(const GemmArgs& g, hipStream_t s);
-bool gemm_p8_eligible(const GemmArgs& g);      // both operands in P8 and a large grid: the LDS-DMA kernels (gemm_p8_2wgp / _256)
+bool gemm_p8_eligible(const GemmArgs& g);      // both operands in P8 and a large grid: the persistent LDS-DMA kernels (gemm_p8_big / _2wgp)
+bool gemm_p8_sm_eligible(const GemmArgs& g);   // both operands in P8, any grid: what plan_gemm_p8 / launch_gemm_p8 take
+// The f16x3 GEMM planner, the one place the kernel of a GEMM with a P8 activation is chosen: sets g.force_cfg (a forced configuration
+// the shape cannot take falls back), and for an unforced small grid g.splitk (its slabs, S x M x N floats, within splitk_floats; the
+// caller points g.partial at them) and g.w_nt.  launch_gemm_p8 launches the planned configuration.
+struct P8Plan {
+    bool c2_fused = false;      // the kernel's epilogue writes GemmArgs::c2 (otherwise a split pass over the fp32 result must)
+    bool dominant = false;      // a big-tile kernel (the step's dominant GEMMs, for profiling)
+};
+P8Plan plan_gemm_p8(GemmArgs& g, int64_t splitk_floats);
 void launch_gemm_p8(const GemmArgs& g, hipStream_t s);
 void gemm_p8_prepare();      // one-time kernel attributes (call once per process before the first captured launch)
-int gemm_p8_variant(const GemmArgs& g);       // 0: gemm_p8_2wgp_kernel (persistent 128x128, two workgroups per CU), 1: gemm_p8_256_kernel
-bool gemm_p8_sm_eligible(const GemmArgs& g);   // both operands in P8, any grid (split-K capable): small-tile LDS-DMA kernel
-void launch_gemm_p8_sm(const GemmArgs& g, hipStream_t s);
-bool gemm_p8_pp_ok(const GemmArgs& g);      // operands within the 32-bit DMA offsets of the ping-pong kernel (launch_gemm_p8_sm cfg 30 / 31 / 33)
 // bf16 GEMM (precision mode 2, gemm_bf16.hip): bf16(A) * bf16(W)^T with fp32 accumulation; A is fp32, W is read from g.Wb
 void launch_gemm_bf16(const GemmArgs& g, hipStream_t s);
 int gemm_bf16_config(const GemmArgs& g);      // 0: 64x64, 1: 128x128 (large grids), 2: 32x128 (M <= 32)
@@ -112,7 +117,7 @@ int gemm_bf16_tile_count(const GemmArgs& g);  // output tiles of that configurat
 void launch_pack_bf16(const float* in, void* out, long n, hipStream_t s);   // fp32 -> bf16 copy, same indexing
 // wav2vec2 positional convolution (16 groups of 64 channels, 128 taps) with the chunk's input window resident in LDS (gemm_f16s.hip)
 void launch_posconv_p8(const GemmArgs& g, int n_chunks, int T, int Ts, hipStream_t s);
-int gemm_config(const GemmArgs& g);   // 4: 128x128 BK16 (dominant kernel), 2: 64x64, 1: 128x64, 3: 32x128; 0,5,6,7 tuning variants
+int gemm_config(const GemmArgs& g);   // 4: 128x128 BK16 (dominant kernel), 2: 64x64, 1: 128x64, 3: 32x128
 // Average kernel time helper for benches: FLOPs of one launch
 static inline double gemm_flops(const GemmArgs& g) { return 2.0 * g.M * (double)g.N * g.K * g.batch; }
 
@@ -150,10 +155,6 @@ struct AttnArgs {
     int qkv_exp = 4, o_exp = 4;                      // site exponents of the P8 format: Q / K / V rows (qkv_p8), O rows (out_p8)
     int* status = nullptr;                           // out_p8: range guard (see GemmArgs::status)
     int cus = 0;                                     // compute units of the model's partition (0 = the whole device): grid of the persistent kernel
-    // short-query kernel, Lq <= 16: the q | k | v rows of the NEW tokens (the last Lq keys) are still split-K slabs [n_slabs][B * Lq][slab_ld]
-    // (row b * Lq + t; columns q | k | v x heads x 64): the workgroup sums its head's rows (slabs ascending, then slab_bias), writes them to
-    // Q / K / V and reads them back from there
-    const float* slabs = nullptr; int n_slabs = 0; long slab_stride = 0; int slab_ld = 0; const float* slab_bias = nullptr;
 };
 void launch_attention(const AttnArgs& a, hipStream_t s);
 void attention_prepare();      // one-time kernel attributes (call once per process before the first captured launch)

@@ -234,7 +234,7 @@ int artalk_set_cu_mask(artalk_model* m, const uint32_t* mask, int n_words);
 /* C[M,N] = R + gate * act(A[M,K] W[N,K]^T + bias); act: 0 none, 1 gelu(erf), 2 gelu(tanh), 3 leaky_relu(0.2). K % 32 == 0 */
 int artalk_op_gemm(const float* A, int64_t lda, const float* W, const float* bias, const float* gate, const float* R,
                    float* C, int M, int N, int K, int act, void* stream);
-/* same, with an explicit tile configuration (4: 128x128 BK16, 2: 64x64, 1: 128x64, 3: 32x128, 0/5/6/7: tuning variants; -1: heuristic) for tuning */
+/* same, with an explicit tile configuration (4: 128x128 BK16, 2: 64x64, 1: 128x64, 3: 32x128; -1: heuristic) for tuning */
 int artalk_op_gemm_ex(const float* A, int64_t lda, const float* W, const float* bias, float* C, int M, int N, int K, int act,
                       int force_cfg, void* stream);
 /* calibration: register-only fp32 MFMA loop (blocks x 256 threads, 32*iters MFMAs per wave, nacc = 1 or 4 independent accumulators); *flops = FLOPs of the launch */
@@ -250,16 +250,22 @@ int artalk_op_gemm_f16s(const float* A, int64_t lda, const float* W, const float
  * 25-30 rows).  Synchronises the stream. */
 int artalk_op_gemm_bf16(const float* A, int64_t lda, const float* W, const float* bias, const float* gate, const float* R, float* C,
                         int M, int N, int K, int act, int force_cfg, void* stream);
-/* tuning helpers: fp32 -> packed split words; split GEMM on pre-packed W (and optionally pre-packed A) */
+/* tuning helpers: fp32 -> packed split words; split GEMM on pre-packed W (and optionally pre-packed A).  force_cfg -1 / 0 / 1: the
+ * register-staged kernel (heuristic / 128x128 / 64x64); with a_packed the LDS-DMA kernels of the f16x3 planner: 7 / 12 = gemm_p8_big_kernel
+ * (256x256 / 320x256 tiles), 8 = gemm_p8_2wgp_kernel (a forced 7 / 12 / 8 the shape cannot take falls back: 7 / 12 to 8, 8 to the plan),
+ * 20 / 23 / 24 = gemm_p8_sm_kernel (64x64, 4 / 8 / 5 stages), 28 = gemm_p8_mid_kernel, 31 = gemm_p8_pp_kernel; for 20 .. 31 bits 8-15
+ * are a split-K factor and bit 16 fetches the weights non-temporally; 99 = the planner's own choice (no split-K).  Retired values run
+ * what replaced them: 13 as 99, 29 and 33 as 28, 30 as 31.  Other values: EINVAL. */
 int artalk_op_pack_split(const float* in, void* out_u32, int64_t n, int is_weight, void* stream);   /* operand scale: 0 activation, 1 weight */
 int artalk_op_gemm_f16s_packed(const void* A, int a_packed, int64_t lda, const void* Wp, const float* bias, float* C, int M, int N,
                                int K, int act, int force_cfg, void* stream);
 /* frees the split-K scratch artalk_op_gemm_f16s_packed grows on demand (the buffers it outgrew are kept until this call, because
  * graphs captured from earlier launches still write to them): call it when no such graph will be replayed again */
 int artalk_op_release_scratch(void);
-/* which production LDS-DMA kernel launch_gemm_p8 picks for an M x N x K product (dense rows, with or without a residual) with both
- * operands in P8 and no forced configuration (what the model path calls): 7 / 12 = gemm_p8_big_kernel with 256x256 / 320x256 tiles,
- * 8 = gemm_p8_2wgp_kernel; force_cfg 99 of artalk_op_gemm_f16s_packed launches exactly that choice */
+/* which production LDS-DMA kernel the f16x3 planner picks for an M x N x K product (dense rows, with or without a residual) with both
+ * operands in P8 and no forced configuration (what the model path calls): on a large grid 7 / 12 = gemm_p8_big_kernel with 256x256 /
+ * 320x256 tiles, 8 = gemm_p8_2wgp_kernel; otherwise the small-grid configuration without split-K (20, 28, 31: see
+ * artalk_op_gemm_f16s_packed); force_cfg 99 of artalk_op_gemm_f16s_packed launches exactly that choice */
 int artalk_op_gemm_p8_plan(int M, int N, int K, int residual);
 /* a HIP stream restricted to the compute units whose bits are set in mask[0 .. n_words) (hipExtStreamCreateWithCUMask; on MI355X bit i =
  * CU i / 8 of XCD i % 8): the stream a model with artalk_set_cu_mask is driven on */

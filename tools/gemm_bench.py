@@ -16,7 +16,7 @@ SHAPES = [  # (name, M, N, K)
 only = os.environ.get("GEMM_ONLY")
 if only:
     SHAPES = [x for x in SHAPES if x[0] in only.split(",")]
-cfgs = [int(c) for c in (sys.argv[1].split(",") if len(sys.argv) > 1 else "0,1,2,3".split(","))]
+cfgs = [int(c) for c in (sys.argv[1].split(",") if len(sys.argv) > 1 else "1,2,3,4".split(","))]      # artalk_op_gemm_ex configurations
 # correctness of every requested configuration on an awkward shape first
 A = torch.randn(777, 96, device='cuda'); W = torch.randn(333, 96, device='cuda'); b = torch.randn(333, device='cuda')
 ref = (A.double() @ W.double().t() + b.double()).float()
@@ -32,7 +32,7 @@ for name, M, N, K in SHAPES:
     for rnd in range(3):
         for cfg in cfgs:
             if cfg == 3 and M > 4096: continue
-            if cfg == 0 and M * N < 128 * 128 * 8: continue
+            if cfg == 4 and M * N < 128 * 128 * 8: continue
             s = torch.cuda.current_stream().cuda_stream
             n = 3 if M * N * K > 1e11 else 10
             L.artalk_op_gemm_ex(p(A), K, p(W), p(b), p(Cc), M, N, K, 0, cfg, C.c_void_p(s))

@@ -25,8 +25,9 @@ SHAPES += [("e qkv", 1600, 1536, 512), ("e proj", 1600, 512, 512), ("e mlp1", 16
 # row counts whose 128x128 tile counts are whole multiples of the 512 persistent workgroups (round-quantisation check)
 for _M in (8192, 16384):
     SHAPES += [(f"q{_M} qkv", _M, 3072, 1024), (f"q{_M} out", _M, 1024, 1024), (f"q{_M} ff1", _M, 4096, 1024), (f"q{_M} ff2", _M, 1024, 4096)]
-variants = [(1, 1), (7, 1), (8, 1), (99, 1)]   # (cfg, A packed): 0/1 register-staged 128x128 / 64x64; LDS-DMA kernels: 7 256x256, 8 persistent
-                                                # two-workgroup 128x128, 99 the dispatch's own choice; small-grid 64x64: 20 (4 stages), 23 (8), 24 (5); cfg | S << 8 = split-K S (20, 23, 24)
+variants = [(1, 1), (7, 1), (8, 1), (99, 1)]   # (cfg, A packed): 0/1 register-staged 128x128 / 64x64; LDS-DMA kernels: 7 / 12 256x256 / 320x256,
+                                                # 8 persistent two-workgroup 128x128, 99 the planner's own choice; small-grid 64x64: 20 (4 stages), 23 (8),
+                                                # 24 (5); 28 mid-grid 128x128, 31 ping-pong 256x128; cfg | S << 8 = split-K S (20 .. 31)
 # one-round launches of the 320x256 kernel on 30 / 60 / 120 / 240 of the 256 CUs (same work per CU): is the per-CU rate load-dependent?
 for _M in (2400, 4800, 9600, 19200):
     SHAPES += [(f"p{_M} ff2", _M, 1024, 4096)]
