@@ -23,6 +23,7 @@ SYMBOLS = [
     "artalk_set_profiling", "artalk_get_profile", "artalk_get_kernel_sums", "artalk_set_graphs", "artalk_graph_count", "artalk_set_cu_mask", "artalk_set_audit", "artalk_get_audit", "artalk_calibrate", "artalk_reset_scales", "artalk_get_scales", "artalk_scale_sites", "artalk_get_site_scales", "artalk_set_site_scales", "artalk_set_tap", "artalk_tap_layout", "artalk_set_precision",
     "artalk_op_gemm", "artalk_op_gemm_ex", "artalk_op_gemm_bf16", "artalk_op_gemm_f16s", "artalk_op_pack_split", "artalk_op_gemm_f16s_packed", "artalk_op_release_scratch", "artalk_op_gemm_p8_plan", "artalk_op_create_masked_stream", "artalk_op_destroy_stream", "artalk_op_mfma_f32_peak", "artalk_op_layernorm", "artalk_op_attention", "artalk_op_w2v_front", "artalk_op_resample_mean", "artalk_op_pool_silu",
     "artalk_op_bsq_history",
+    "artalk_op_pack_split_ex", "artalk_op_layernorm_ex", "artalk_op_gemm_f16s_packed_ex", "artalk_op_gemm_f16s_ex", "artalk_op_attention_ex", "artalk_op_w2v_front_ex", "artalk_op_pool_silu_ex", "artalk_op_posconv_p8_ex",
 ]
 
 
@@ -201,6 +202,23 @@ def lib() -> C.CDLL:
     L.artalk_op_pool_silu.restype = i32
     L.artalk_op_bsq_history.argtypes = [vp, vp, vp, vp, i32, vp]
     L.artalk_op_bsq_history.restype = i32
+    if hasattr(L, "artalk_op_pack_split_ex"):      # (an older build loaded through ARTALK_LIB lacks the entry points with site exponents)
+        L.artalk_op_pack_split_ex.argtypes = [vp, vp, i64, i32, i32, vp, vp]
+        L.artalk_op_pack_split_ex.restype = i32
+        L.artalk_op_layernorm_ex.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, f32, i32, i32, i32, i32, vp, vp]
+        L.artalk_op_layernorm_ex.restype = i32
+        L.artalk_op_gemm_f16s_packed_ex.argtypes = [vp, i32, i64, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
+        L.artalk_op_gemm_f16s_packed_ex.restype = i32
+        L.artalk_op_gemm_f16s_ex.argtypes = [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
+        L.artalk_op_gemm_f16s_ex.restype = i32
+        L.artalk_op_attention_ex.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp, i32, i32, i32, i32, vp, vp]
+        L.artalk_op_attention_ex.restype = i32
+        L.artalk_op_w2v_front_ex.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]
+        L.artalk_op_w2v_front_ex.restype = i32
+        L.artalk_op_pool_silu_ex.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, vp]
+        L.artalk_op_pool_silu_ex.restype = i32
+        L.artalk_op_posconv_p8_ex.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
+        L.artalk_op_posconv_p8_ex.restype = i32
     _lib = L
     return L
 

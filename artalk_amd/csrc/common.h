@@ -128,7 +128,7 @@ __device__ __forceinline__ void apply_act4(f32x4& v, int act) {
 // [8 x f16 hi][8 x f16 lo] with hi = f16(S x) and lo = f16(S x - hi) (UNSCALED residual; gfx950's f16 MFMA honours subnormal inputs -
 // tools/mfma_subnormal_probe.py - so a residual below 2^-14 still carries 2^-25 absolute precision).  Same pitch as fp32.  Because
 // both halves are in one scale, hi*hi + hi*lo + lo*hi accumulate in ONE fp32 accumulator; the GEMM epilogue multiplies by
-// 1 / (SA * SW) (exact: powers of two).  Range: |x| < 65504 / S (4094 at the default 16) for activations, < 255 for weights; an
+// 1 / (SA * SW) (exact: powers of two).  Range: |x| <= 65504 / S (4094 at the default 16; the guard below compares with >) for activations, < 255 for weights; an
 // overflow raises the status word at the producer (the host recalibrates the site scales, or falls back to exact f32).
 // Producers and consumers carry the exponent e (an int: kernels.h GemmArgs::a_exp / c_exp, LnArgs::p8_exp, AttnArgs::qkv_exp / o_exp):
 // scale, 1 / scale and the guard threshold are two scalar integer operations away from it.

@@ -1963,9 +1963,16 @@ int artalk_op_mfma_f32_peak(float* out_dev, int blocks, int iters, int nacc, dou
 }
 
 // f16x3 split GEMM on fp32 inputs (W is packed into a temporary): same contract as artalk_op_gemm_ex; cfg 0: 128x128, 1: 64x64, -1: heuristic
+static bool op_exp_ok(int e) { return e >= -8 && e <= kActExp; }      // what artalk_set_site_scales accepts
+
 int artalk_op_gemm_f16s(const float* A, int64_t lda, const float* W, const float* bias, float* C, int M, int N, int K, int act,
                         int force_cfg, void* stream) {
-    if (!A || !W || !C || K % 32 != 0 || M <= 32 || N <= 0) return ARTALK_EINVAL;
+    return artalk_op_gemm_f16s_ex(A, lda, W, bias, C, M, N, K, act, force_cfg, kActExp, nullptr, stream);
+}
+// the same with the site exponent of A (split while staging, or packed with it under force_cfg | 0x100) and the model status word
+int artalk_op_gemm_f16s_ex(const float* A, int64_t lda, const float* W, const float* bias, float* C, int M, int N, int K, int act,
+                           int force_cfg, int a_exp, int* status_dev, void* stream) {
+    if (!A || !W || !C || K % 32 != 0 || M <= 32 || N <= 0 || !op_exp_ok(a_exp)) return ARTALK_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     unsigned int* wp = nullptr;
     if (hipMalloc(&wp, (size_t)N * K * 4) != hipSuccess) return ARTALK_EHIP;
@@ -1973,10 +1980,11 @@ int artalk_op_gemm_f16s(const float* A, int64_t lda, const float* W, const float
     GemmArgs g;
     g.A = A; g.lda = lda; g.W = W; g.Wp = wp; g.ldw = K; g.bias = bias; g.C = C; g.ldc = N; g.M = M; g.N = N; g.K = K; g.act = act;
     g.force_cfg = force_cfg & 0xff;
+    g.a_exp = a_exp; g.status = status_dev;
     unsigned int* ap = nullptr;
     if (force_cfg >= 0 && (force_cfg & 0x100)) {   // tuning: pre-packed A (what a fused producer would hand over)
-        if (hipMalloc(&ap, (size_t)M * lda * 4) != hipSuccess) return ARTALK_EHIP;
-        launch_pack_split(A, ap, (long)M * lda, false, s);
+        if (hipMalloc(&ap, (size_t)M * lda * 4) != hipSuccess) { (void)hipFree(wp); return ARTALK_EHIP; }
+        launch_pack_split(A, ap, (long)M * lda, false, s, status_dev, a_exp);
         g.A = reinterpret_cast<const float*>(ap); g.a_packed = 1;
     }
     launch_gemm_f16s(g, s);
@@ -2040,14 +2048,24 @@ int artalk_op_release_scratch(void) {
 }
 // building blocks for tuning the split GEMM without allocation noise: pack once, then launch on packed operands
 int artalk_op_pack_split(const float* in, void* out_u32, int64_t n, int is_weight, void* stream) {
-    if (!in || !out_u32 || n <= 0) return ARTALK_EINVAL;
-    launch_pack_split(in, (unsigned int*)out_u32, n, is_weight != 0, (hipStream_t)stream);
+    return artalk_op_pack_split_ex(in, out_u32, n, is_weight, kActExp, nullptr, stream);
+}
+int artalk_op_pack_split_ex(const float* in, void* out_u32, int64_t n, int is_weight, int p8_exp, int* status_dev, void* stream) {
+    if (!in || !out_u32 || n <= 0 || !op_exp_ok(p8_exp)) return ARTALK_EINVAL;
+    launch_pack_split(in, (unsigned int*)out_u32, n, is_weight != 0, (hipStream_t)stream, status_dev, p8_exp);
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
 }
 int artalk_op_gemm_f16s_packed(const void* A, int a_packed, int64_t lda, const void* Wp, const float* bias, float* C, int M, int N,
                                int K, int act, int force_cfg, void* stream) {
+    return artalk_op_gemm_f16s_packed_ex(A, a_packed, lda, Wp, bias, C, M, N, K, act, force_cfg, kActExp, kActExp, nullptr, nullptr, stream);
+}
+int artalk_op_gemm_f16s_packed_ex(const void* A, int a_packed, int64_t lda, const void* Wp, const float* bias, float* C, int M, int N,
+                                  int K, int act, int force_cfg, int a_exp, int c_exp, void* c2_u32, int* status_dev, void* stream) {
     if (!A || !Wp || !C || K % 32 != 0 || M <= 0 || N <= 0 || (M <= 32 && (force_cfg & 0xff) < 20)) return ARTALK_EINVAL;
+    if (!op_exp_ok(a_exp) || !op_exp_ok(c_exp)) return ARTALK_EINVAL;
+    if (c2_u32 && (force_cfg < 2 || ((act >> 8) & 1) || N % 8 != 0)) return ARTALK_EINVAL;      // the second copy: LDS-DMA kernels, fp32 C
     GemmArgs g;
+    g.a_exp = a_exp; g.c_exp = c_exp; g.status = status_dev; g.c2 = (float*)c2_u32;
     g.A = (const float*)A; g.a_packed = a_packed; g.lda = lda; g.W = nullptr; g.Wp = (const unsigned int*)Wp; g.ldw = K; g.bias = bias;
     g.C = C; g.ldc = N; g.M = M; g.N = N; g.K = K; g.act = act & 0xff; g.force_cfg = force_cfg;
     g.c_p8 = (act >> 8) & 1;      // tuning: bit 8 of `act` = result in the P8 split format (same pitch)
@@ -2081,9 +2099,13 @@ int artalk_op_gemm_f16s_packed(const void* A, int a_packed, int64_t lda, const v
                 g.splitk = S; g.partial = g_op_scratch;
             }
         }
-        plan_gemm_p8(g, 0);
+        const P8Plan plan = plan_gemm_p8(g, 0);
+        // the second copy as the model's gemm() makes it: by the kernel's epilogue where the plan says so, otherwise by a split pass
+        if (!plan.c2_fused) g.c2 = nullptr;
         launch_gemm_p8(g, (hipStream_t)stream);
         if (g.splitk > 1) launch_splitk_reduce(g, (hipStream_t)stream);
+        if (c2_u32 && !plan.c2_fused)
+            launch_pack_split(g.C, (unsigned int*)c2_u32, (long)g.M * g.N, false, (hipStream_t)stream, g.status, g.c_exp);
     } else {
         launch_gemm_f16s(g, (hipStream_t)stream);
     }
@@ -2113,8 +2135,15 @@ int artalk_op_gemm_p8_plan(int M, int N, int K, int residual) {
 
 int artalk_op_layernorm(const float* X, float* Y, const float* w, const float* b, const float* scale, const float* shift, int M,
                         int D, float eps, int act, void* stream) {
-    if (!X || !Y || (D != 128 && D != 512 && D != 768 && D != 1024)) return ARTALK_EINVAL;
+    return artalk_op_layernorm_ex(X, Y, w, b, scale, shift, M, D, eps, act, kActExp, 0, 0, nullptr, stream);
+}
+int artalk_op_layernorm_ex(const float* X, float* Y, const float* w, const float* b, const float* scale, const float* shift, int M,
+                           int D, float eps, int act, int p8_exp, int junk_period, int junk_from, int* status_dev, void* stream) {
+    if (!X || !Y || (D != 128 && D != 512 && D != 768 && D != 1024) || !op_exp_ok(p8_exp)) return ARTALK_EINVAL;
+    if (junk_period < 0 || junk_from < 0 || (junk_period > 0 && junk_from > junk_period)) return ARTALK_EINVAL;
+    if ((act & 0x100) && D == 128) return ARTALK_EINVAL;      // the 128-wide kernel (style encoder: fp32 A sites) has no P8 store
     LnArgs a;
+    a.p8_exp = p8_exp; a.junk_period = junk_period; a.junk_from = junk_from; a.status = (act & 0x100) ? status_dev : nullptr;
     a.X = X; a.ldx = D; a.Y = Y; a.ldy = D; a.w = w; a.b = b; a.scale = scale; a.shift = shift; a.ldm = D; a.M = M; a.D = D;
     a.eps = eps; a.act = act & 0xff; a.out_p8 = (act & 0x100) ? 1 : 0;   // act | 0x100: write Y in the P8 split format
     launch_layernorm(a, (hipStream_t)stream);
@@ -2123,8 +2152,14 @@ int artalk_op_layernorm(const float* X, float* Y, const float* w, const float* b
 
 int artalk_op_attention(const float* Q, const float* K, const float* V, float* O, int B, int H, int HD, int Lq, int Lk, float scale,
                         int l2norm, const float* qscale, int split, void* stream) {
+    return artalk_op_attention_ex(Q, K, V, O, B, H, HD, Lq, Lk, scale, l2norm, qscale, split, kActExp, kActExp, 0, nullptr, stream);
+}
+int artalk_op_attention_ex(const float* Q, const float* K, const float* V, float* O, int B, int H, int HD, int Lq, int Lk, float scale,
+                           int l2norm, const float* qscale, int split, int qkv_exp, int o_exp, int out_p8, int* status_dev, void* stream) {
     if (!Q || !K || !V || !O || (HD != 64 && HD != 32) || ((l2norm & 1) && !qscale)) return ARTALK_EINVAL;
+    if (!op_exp_ok(qkv_exp) || !op_exp_ok(o_exp)) return ARTALK_EINVAL;
     AttnArgs a;
+    a.qkv_exp = qkv_exp; a.o_exp = o_exp; a.out_p8 = out_p8 ? 1 : 0; a.status = out_p8 ? status_dev : nullptr;
     a.split16 = (l2norm >> 1) & 1;      // l2norm | 2: the fp16 operand-split kernel of f16x3 mode
     a.qkv_p8 = (l2norm >> 2) & 1;       // l2norm | 4 (with | 2, without L2 norm): Q, K, V are given in the P8 split format
     l2norm &= 1;
@@ -2139,7 +2174,11 @@ int artalk_op_attention(const float* Q, const float* K, const float* V, float* O
 
 int artalk_op_w2v_front(const float* audio, int C, int n, const float* w, const float* bias, const float* lnw, const float* lnb,
                         float* xnorm_out, float* Y, void* stream) {
-    if (!audio || !xnorm_out || !Y || C <= 0 || n < 10) return ARTALK_EINVAL;
+    return artalk_op_w2v_front_ex(audio, C, n, w, bias, lnw, lnb, xnorm_out, Y, 0, kActExp, nullptr, stream);
+}
+int artalk_op_w2v_front_ex(const float* audio, int C, int n, const float* w, const float* bias, const float* lnw, const float* lnb,
+                           float* xnorm_out, float* Y, int out_p8, int p8_exp, int* status_dev, void* stream) {
+    if (!audio || !xnorm_out || !Y || C <= 0 || n < 10 || !op_exp_ok(p8_exp)) return ARTALK_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     std::vector<long> off(C);
     for (int i = 0; i < C; ++i) off[i] = (long)i * n;
@@ -2148,7 +2187,7 @@ int artalk_op_w2v_front(const float* audio, int C, int n, const float* w, const 
     (void)hipMemcpy(doff, off.data(), C * sizeof(long), hipMemcpyHostToDevice);
     const int T = (n - 10) / 5 + 1;
     launch_audio_normalize(audio, doff, xnorm_out, C, n, s);
-    launch_conv0(xnorm_out, n, w, bias, lnw, lnb, Y, C, T, T, s);
+    launch_conv0(xnorm_out, n, w, bias, lnw, lnb, Y, C, T, T, s, out_p8 ? 1 : 0, out_p8 ? status_dev : nullptr, p8_exp);
     (void)hipStreamSynchronize(s);
     (void)hipFree(doff);
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
@@ -2162,9 +2201,25 @@ int artalk_op_resample_mean(const float* x, int nch, int n, const float* taps, i
 }
 
 int artalk_op_pool_silu(const float* X, int C, int T, int D, float* Y, void* stream) {
-    if (!X || !Y || D % 4 != 0) return ARTALK_EINVAL;
+    return artalk_op_pool_silu_ex(X, C, T, D, Y, 0, kActExp, nullptr, stream);
+}
+int artalk_op_pool_silu_ex(const float* X, int C, int T, int D, float* Y, int out_p8, int p8_exp, int* status_dev, void* stream) {
+    if (!X || !Y || D % 4 != 0 || (out_p8 && D % 8 != 0) || !op_exp_ok(p8_exp)) return ARTALK_EINVAL;
     static const int pn[5] = {1, 5, 25, 50, 100};
-    launch_pool_silu(X, T, T, Y, C, pn, 5, D, (hipStream_t)stream);
+    launch_pool_silu(X, T, T, Y, C, pn, 5, D, (hipStream_t)stream, out_p8 ? 1 : 0, out_p8 ? status_dev : nullptr, p8_exp);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+
+// wav2vec2 positional convolution of f16x3 mode (launch_posconv_p8): X [n_chunks * Ts][1024] fp32 rows (frames t < T of a chunk are read),
+// Wp [1024][128 * 64] packed weights (k = tap * 64 + input channel of the group), C = R + act(conv + bias), rows t < Ts of every chunk
+int artalk_op_posconv_p8_ex(const float* X, const void* Wp, const float* bias, const float* R, float* C, int n_chunks, int T, int Ts,
+                            int act, int a_exp, int* status_dev, void* stream) {
+    if (!X || !Wp || !C || n_chunks <= 0 || T <= 0 || T > Ts || Ts > 256 || act < 0 || act > 3 || !op_exp_ok(a_exp)) return ARTALK_EINVAL;
+    if (((uintptr_t)X | (uintptr_t)Wp | (uintptr_t)C | (uintptr_t)bias | (uintptr_t)R) & 15) return ARTALK_EINVAL;
+    GemmArgs g;
+    g.A = X; g.lda = 1024; g.Wp = (const unsigned int*)Wp; g.ldw = 128 * 64; g.bias = bias; g.C = C; g.ldc = 1024; g.R = R; g.ldr = 1024;
+    g.M = n_chunks * Ts; g.N = 1024; g.K = 128 * 64; g.act = act; g.a_exp = a_exp; g.status = status_dev;
+    launch_posconv_p8(g, n_chunks, T, Ts, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
 }
 

@@ -123,8 +123,8 @@ const char* artalk_flame_last_error(const artalk_flame* f);
  * the one synchronisation on this boundary, paid only by callers that ask; `stream` is ignored); artalk_poll_status never
  * blocks and returns ARTALK_EBUSY while the call is still running.  Bits: 0 a logit was NaN/Inf (the pairwise argmax of
  * app/models.py:104 would silently turn it into a 0 bit), 1 a re-encoder output was NaN/Inf, 2 a FLAME code was NaN/Inf,
- * 3 an activation exceeded the range of its site's P8 scale where it was produced (|x| * 2^e >= 65504, e = the site's exponent,
- * artalk_get_site_scales; |x| >= 4094 at the default e = 4).  Non-zero in f16x3 mode means an activation left fp16's range: the Python
+ * 3 an activation exceeded the range of its site's P8 scale where it was produced (|x| * 2^e > 65504, fp16's largest finite value, or
+ * x is NaN; e = the site's exponent, artalk_get_site_scales; |x| > 4094 at the default e = 4: exactly 65504 / 2^e is still stored finite).  Non-zero in f16x3 mode means an activation left fp16's range: the Python
  * host first recalibrates the site scales on that batch (artalk_calibrate) and redoes the call in f16x3 mode; only when nothing could
  * be lowered does it redo the call in f32 mode and stay there. */
 int artalk_get_status(artalk_model* m, int* flags, void* stream);
@@ -287,6 +287,39 @@ int artalk_op_resample_mean(const float* x, int nch, int n, const float* taps, i
                             void* stream);
 /* X [C][T][D] -> Y [C][181][D]: area pooling to {1,5,25,50,100} then SiLU */
 int artalk_op_pool_silu(const float* X, int C, int T, int D, float* Y, void* stream);
+/* ---- the same entry points with the site exponents of the P8 format and a status word (tests/test_p8_exps_ops_gpu.py) ----
+ * Every P8 producer writes hi = f16(x * 2^e), lo = f16(x * 2^e - hi) and raises bit 3 of *status_dev (device int, may be NULL: no guard)
+ * when |x| * 2^e > 65504 or x is NaN; every consumer removes the 2^e of the buffer it reads.  The entry points above call these with
+ * e = 4 and no status word.  Any exponent outside [-8, 4] (what artalk_set_site_scales accepts): ARTALK_EINVAL before the device is touched.
+ *   pack_split_ex        p8_exp: exponent of the packed activation (ignored for weights, which have no guard either)
+ *   layernorm_ex         p8_exp: exponent of a P8 result (act | 0x100; D = 128 has no P8 form: ARTALK_EINVAL); rows r with
+ *                        r % junk_period >= junk_from (junk_period > 0) are layout padding: stored as zeros, exempt from the guard
+ *   gemm_f16s_packed_ex  a_exp: exponent A was packed with, or is split with while staging (fp32 A: force_cfg < 2, guarded); c_exp: exponent
+ *                        of a P8 result (act bit 8) and of c2_u32, an optional second copy of an fp32 result in P8, same pitch (N % 8 == 0,
+ *                        LDS-DMA configurations only): written by the kernel's epilogue where the planner fuses it (20 / 23 / 24 without
+ *                        split-K), by a split pass over the result otherwise - as the model does
+ *   gemm_f16s_ex         a_exp: exponent the fp32 A rows are split with while staging (or packed with, force_cfg | 0x100)
+ *   attention_ex         qkv_exp: exponent of P8 Q / K / V rows (l2norm bit 2); out_p8 != 0: O is written in P8 with o_exp
+ *   w2v_front_ex, pool_silu_ex   out_p8 != 0: Y is written in P8 with p8_exp (pool: D % 8 == 0)
+ *   posconv_p8_ex        the grouped positional convolution of f16x3 mode (16 groups of 64 channels, 128 taps, padding 64): X
+ *                        [n_chunks * Ts][1024] fp32, frames t < T of a chunk are read (split with a_exp while staged into LDS, guarded),
+ *                        Wp [1024][128 * 64] packed weights with k = tap * 64 + input channel, C = R + act(conv + bias) for the rows
+ *                        t < Ts <= 256 of every chunk (R may be NULL or C); pointers 16-byte aligned */
+int artalk_op_pack_split_ex(const float* in, void* out_u32, int64_t n, int is_weight, int p8_exp, int* status_dev, void* stream);
+int artalk_op_layernorm_ex(const float* X, float* Y, const float* w, const float* b, const float* scale, const float* shift,
+                           int M, int D, float eps, int act, int p8_exp, int junk_period, int junk_from, int* status_dev, void* stream);
+int artalk_op_gemm_f16s_packed_ex(const void* A, int a_packed, int64_t lda, const void* Wp, const float* bias, float* C, int M, int N,
+                                  int K, int act, int force_cfg, int a_exp, int c_exp, void* c2_u32, int* status_dev, void* stream);
+int artalk_op_gemm_f16s_ex(const float* A, int64_t lda, const float* W, const float* bias, float* C, int M, int N, int K, int act,
+                           int force_cfg, int a_exp, int* status_dev, void* stream);
+int artalk_op_attention_ex(const float* Q, const float* K, const float* V, float* O, int B, int H, int HD, int Lq, int Lk,
+                           float scale, int l2norm, const float* qscale, int split, int qkv_exp, int o_exp, int out_p8,
+                           int* status_dev, void* stream);
+int artalk_op_w2v_front_ex(const float* audio, int C, int n, const float* w, const float* bias, const float* lnw,
+                           const float* lnb, float* xnorm_out, float* Y, int out_p8, int p8_exp, int* status_dev, void* stream);
+int artalk_op_pool_silu_ex(const float* X, int C, int T, int D, float* Y, int out_p8, int p8_exp, int* status_dev, void* stream);
+int artalk_op_posconv_p8_ex(const float* X, const void* Wp, const float* bias, const float* R, float* C, int n_chunks, int T, int Ts,
+                            int act, int a_exp, int* status_dev, void* stream);
 /* enc_out [B][100][32] -> hist_bits [B][181][32] u8, prev_fdec [B][100][32], msfeat [B][180][32] */
 int artalk_op_bsq_history(const float* enc_out, uint8_t* hist_bits, float* prev_fdec, float* msfeat, int B, void* stream);
 
