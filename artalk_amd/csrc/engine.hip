@@ -198,11 +198,11 @@ struct artalk_model {
     std::vector<std::pair<size_t, double>> dom_events;   // (event index of start, flops)
     std::vector<std::pair<int, size_t>> marks;          // (bucket of the interval ending here, event index), caller's stream
     hipStream_t prof_stream = nullptr;
-    hipStream_t side_stream[3] = {nullptr, nullptr, nullptr};   // extra branches of the AR body (run_chunk_body_graphs)
+    hipStream_t side_stream[3] = {nullptr, nullptr, nullptr};   // extra branches of the AR body (run_body)
     hipEvent_t fork_ev = nullptr, join_ev[3] = {nullptr, nullptr, nullptr};
     int branches = 0;                 // 0 = automatic (2 for B >= 8), else forced 1/2/4
     hipStream_t own_stream = nullptr;   // used when the caller passes stream == NULL (graph capture needs a real stream)
-    // graphs: one per (active batch size, clip group, precision, re-encoded clips), LRU-bounded (run_chunk_body_graphs)
+    // graphs: one per (active batch size, clip group, precision, re-encoded clips), LRU-bounded (run_body)
     struct GraphEntry { hipGraphExec_t exec = nullptr; long long last_use = 0; };
     std::map<long long, GraphEntry> graphs;
     long long graph_clock = 0, graph_captures = 0;
@@ -967,42 +967,10 @@ Workspace clip_view(const artalk_model* m, int b0, int branch) {
     return v;
 }
 
-// The AR/VAE body of one chunk index for B clips.  The small scale steps leave most CUs idle, and clips are independent, so
-// for B >= 8 the batch is cut into two halves that run as parallel branches (stream s and m->side_stream; inside a capture this
-// becomes a fork/join in the hipGraph): one half's GPU-filling step overlaps the other half's latency-bound ones.
-int ensure_side_streams(artalk_model* m, int n);
-int body_branches(const artalk_model* m, int B);
-int run_chunk_body_split(artalk_model* m, int B, hipStream_t s, int n_next = -1) {
-    if (n_next < 0 || n_next > B) n_next = B;
-    if (m->profiling == 3 && B >= 8 && m->branches != 1 && !m->audit && !m->tap) {
-        // kernel timer: the SAME clip groups (and therefore the same kernels, tiles and split-K factors) as the graphs replay, one
-        // after the other on one stream - the sums are then those of the production launches, without their overlap
-        const int NS = body_branches(m, B);
-        for (int h = 0; h < NS; ++h) {
-            const int lo = (int)((long)B * h / NS), hi = (int)((long)B * (h + 1) / NS);
-            Workspace v = clip_view(m, lo, h);
-            m->view = &v;
-            run_chunk_body(m, hi - lo, s, std::max(0, std::min(n_next - lo, hi - lo)));
-            m->view = nullptr;
-        }
-        return ARTALK_OK;
-    }
-    if (B < 8 || m->profiling >= 2 || m->branches == 1 || m->audit || m->tap) { run_chunk_body(m, B, s, n_next); return ARTALK_OK; }
-    if (int rc = ensure_side_streams(m, 1)) return rc;
-    const int B0 = (B + 1) / 2, B1 = B - B0;
-    Workspace v0 = clip_view(m, 0, 0), v1 = clip_view(m, B0, 1);
-    HIPCHK(m, hipEventRecord(m->fork_ev, s));
-    HIPCHK(m, hipStreamWaitEvent(m->side_stream[0], m->fork_ev, 0));
-    m->view = &v0; run_chunk_body(m, B0, s, std::min(n_next, B0));
-    m->view = &v1; run_chunk_body(m, B1, m->side_stream[0], std::max(0, n_next - B0));
-    m->view = nullptr;
-    HIPCHK(m, hipEventRecord(m->join_ev[0], m->side_stream[0]));
-    HIPCHK(m, hipStreamWaitEvent(s, m->join_ev[0], 0));
-    return ARTALK_OK;
-}
-
-// Body of one chunk index through hipGraphs: the batch is cut into NS clip groups (1, 2 or 4), one graph per (active batch, group),
-// launched on NS streams so that they really run concurrently (a single captured graph with a fork/join ran almost serially).
+// The AR/VAE body of one chunk index for B clips.  The small scale steps leave most CUs idle, and clips are independent, so the
+// batch is cut into n clip groups (1, 2 or 4: body_branches), each with its own workspace view and split-K scratch, that run as
+// parallel branches on stream s and m->side_stream: one group's GPU-filling step overlaps the others' latency-bound ones.  With
+// graphs on every group is one hipGraph (a single captured graph with a fork/join ran almost serially).
 // HIP multiplexes streams onto a few hardware queues (4 by default): every extra stream a process creates can end up sharing a
 // queue with the caller's stream and serialise the branches, so side streams are created lazily and only as many as are used.
 int ensure_side_streams(artalk_model* m, int n) {
@@ -1019,6 +987,13 @@ int body_branches(const artalk_model* m, int B) {
     // measured at batch 32: 1 branch 54.9 ms, 2 branches 49.5 ms, 4 branches 77-120 ms (queue sharing / contention)
     const int want = m->branches > 0 ? m->branches : (B >= 8 ? 2 : 1);
     return B >= 2 * want ? want : (B >= 8 ? 2 : 1);
+}
+// Replay captured graphs, or launch eagerly?  The one rule, for the batch call and the streaming calls alike: the audit and the taps
+// are launches of their own that a replay would not make (or would make forever), profiling levels 2 and 3 time the single launches.
+bool body_uses_graphs(const artalk_model* m) { return m->use_graphs && m->profiling < 2 && !m->audit && !m->tap; }
+void drop_graphs(artalk_model* m) {
+    for (auto& g : m->graphs) (void)hipGraphExecDestroy(g.second.exec);
+    m->graphs.clear();
 }
 // Graph cache: one hipGraphExec per (active clips, clip group, precision, re-encoded clips of the group).  The key space is bounded
 // (ADVICE r4): the re-encode count of a group is rounded UP to a multiple of 8 (re-encoding a clip without a next chunk is what the
@@ -1041,47 +1016,62 @@ int evict_graphs(artalk_model* m, const long long* keep, int n_keep) {
     }
     return ARTALK_OK;
 }
-int run_chunk_body_graphs(artalk_model* m, int B, hipStream_t s, int n_next = -1) {
+// The clip groups of one chunk index: group h holds clips [b0[h], b0[h + 1]) and re-encodes its first nre[h] (n_next = clips of the B,
+// a prefix, that have a next chunk; < 0 = all).  The only place that cuts a batch: graph replay, the eager streams and the kernel
+// timer run the same groups, so the body's GEMMs get the same M - the same tiles, split-K and summation order - in all three.
+struct BodyGroups { bool graphs; int n; int b0[5]; int nre[4]; long long key[4]; };
+BodyGroups plan_body(const artalk_model* m, int B, int n_next) {
+    BodyGroups g;
     if (n_next < 0 || n_next > B) n_next = B;
-    if (B > 4095) { run_chunk_body(m, B, s, n_next); return ARTALK_OK; }      // (graph keys hold 12 bits of clip counts)
-    const int NS = body_branches(m, B);
-    if (NS > 1) { if (int rc = ensure_side_streams(m, NS - 1)) return rc; }
-    Workspace views[4];
-    int b0[5], nres[4];
-    for (int h = 0; h <= NS; ++h) b0[h] = (int)((long)B * h / NS);
-    hipStream_t st[4] = {s, m->side_stream[0], m->side_stream[1], m->side_stream[2]};
-    long long keys[4];
-    for (int h = 0; h < NS; ++h) {
-        const int gsz = b0[h + 1] - b0[h];
-        const int need = std::max(0, std::min(n_next - b0[h], gsz));      // clips of this group that have a next chunk
-        nres[h] = std::min(gsz, (need + 7) / 8 * 8);
-        keys[h] = ((long long)(((B * 8 + NS) * 4 + h) * 3 + m->precision)) * 4096 + nres[h];     // (3 precision modes)
+    g.graphs = body_uses_graphs(m) && B <= 4095;      // (graph keys hold 12 bits of clip counts)
+    // one group: the audit and the taps address the batch as a whole, level 2 times whole stages; body_branches covers m->branches == 1
+    const bool whole = m->audit || m->tap || m->profiling == 2 || (body_uses_graphs(m) && !g.graphs);
+    g.n = whole ? 1 : body_branches(m, B);
+    for (int h = 0; h <= g.n; ++h) g.b0[h] = (int)((long)B * h / g.n);
+    for (int h = 0; h < g.n; ++h) {
+        const int gsz = g.b0[h + 1] - g.b0[h];
+        const int need = std::max(0, std::min(n_next - g.b0[h], gsz));      // clips of this group that have a next chunk
+        g.nre[h] = g.graphs ? std::min(gsz, (need + 7) / 8 * 8) : need;     // rounded only where it bounds the key space
+        g.key[h] = ((long long)(((B * 8 + g.n) * 4 + h) * 3 + m->precision)) * 4096 + g.nre[h];     // (3 precision modes)
     }
-    for (int h = 0; h < NS; ++h) {
-        views[h] = clip_view(m, b0[h], h);
-        auto hit = m->graphs.find(keys[h]);
+    return g;
+}
+// Runs the groups: replay of their graphs on n streams (captured on a miss), eagerly on n streams (graphs off), or - kernel timer,
+// profiling level 3 - eagerly one after the other on s: the sums are then those of the production launches, without their overlap.
+int run_body(artalk_model* m, int B, hipStream_t s, int n_next) {
+    const BodyGroups g = plan_body(m, B, n_next);
+    const bool fork = g.n > 1 && m->profiling != 3;
+    if (fork) { if (int rc = ensure_side_streams(m, g.n - 1)) return rc; }
+    hipStream_t st[4] = {s, s, s, s};
+    for (int h = 1; fork && h < g.n; ++h) st[h] = m->side_stream[h - 1];
+    Workspace views[4];
+    for (int h = 0; h < g.n; ++h) views[h] = clip_view(m, g.b0[h], h);
+    auto launch_group = [&](int h) { m->view = &views[h]; run_chunk_body(m, g.b0[h + 1] - g.b0[h], st[h], g.nre[h]); m->view = nullptr; };
+    for (int h = 0; g.graphs && h < g.n; ++h) {      // capture what the cache lacks, before anything of this chunk index is launched
+        auto hit = m->graphs.find(g.key[h]);
         if (hit != m->graphs.end()) { hit->second.last_use = ++m->graph_clock; continue; }
-        if (int rc = evict_graphs(m, keys, NS)) return rc;
+        if (int rc = evict_graphs(m, g.key, g.n)) return rc;
         hipGraph_t graph = nullptr;
         hipGraphExec_t exec = nullptr;
         HIPCHK(m, hipStreamBeginCapture(st[h], hipStreamCaptureModeThreadLocal));
         m->in_graph_body = true;
-        m->view = &views[h];
-        run_chunk_body(m, b0[h + 1] - b0[h], st[h], nres[h]);
-        m->view = nullptr;
+        launch_group(h);
         m->in_graph_body = false;
         HIPCHK(m, hipStreamEndCapture(st[h], &graph));
         HIPCHK(m, hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
         (void)hipGraphDestroy(graph);
-        m->graphs.emplace(keys[h], artalk_model::GraphEntry{exec, ++m->graph_clock});
+        m->graphs.emplace(g.key[h], artalk_model::GraphEntry{exec, ++m->graph_clock});
         ++m->graph_captures;
     }
-    if (NS > 1) {
+    if (fork) {
         HIPCHK(m, hipEventRecord(m->fork_ev, s));
-        for (int h = 1; h < NS; ++h) HIPCHK(m, hipStreamWaitEvent(st[h], m->fork_ev, 0));
+        for (int h = 1; h < g.n; ++h) HIPCHK(m, hipStreamWaitEvent(st[h], m->fork_ev, 0));
     }
-    for (int h = 0; h < NS; ++h) HIPCHK(m, hipGraphLaunch(m->graphs[keys[h]].exec, st[h]));
-    for (int h = 1; h < NS; ++h) {
+    for (int h = 0; h < g.n; ++h) {
+        if (g.graphs) HIPCHK(m, hipGraphLaunch(m->graphs[g.key[h]].exec, st[h]));
+        else launch_group(h);
+    }
+    for (int h = 1; fork && h < g.n; ++h) {
         HIPCHK(m, hipEventRecord(m->join_ev[h - 1], st[h]));
         HIPCHK(m, hipStreamWaitEvent(s, m->join_ev[h - 1], 0));
     }
@@ -1130,6 +1120,7 @@ int publish_status(artalk_model* m, hipStream_t s) {
     HIPCHK(m, hipEventRecord(m->status_ev[slot], s));
     ++m->ticket;
     m->status_pending = true;
+    HIPCHK(m, hipGetLastError());
     return ARTALK_OK;
 }
 
@@ -1139,8 +1130,7 @@ int reserve(artalk_model* m, int maxB, int maxC) {
     // grow: drop the old workspace (and the graphs that captured its pointers) and allocate the larger one
     maxB = std::max(maxB, m->ws.maxB); maxC = std::max(maxC, m->ws.maxC);
     (void)hipDeviceSynchronize();
-    for (auto& g : m->graphs) (void)hipGraphExecDestroy(g.second.exec);
-    m->graphs.clear();
+    drop_graphs(m);
     for (void* p : m->ws_allocs) if (p) (void)hipFree(p);
     m->ws_allocs.clear();
     m->ws = Workspace();
@@ -1238,8 +1228,7 @@ int commit_scales(artalk_model* m, const SiteExps& next) {
     for (size_t i = 0; i < sizeof(SiteExps) / sizeof(int); ++i) changed += a[i] != b[i];
     if (changed) {
         (void)hipSetDevice(m->device); (void)hipDeviceSynchronize();
-        for (auto& g : m->graphs) (void)hipGraphExecDestroy(g.second.exec);
-        m->graphs.clear();
+        drop_graphs(m);
         m->invalidate_init_hist();
         if (m->stream_B > 0) { m->stream_B = 0; m->stream_scales_ended = true; }
         m->ex = next;
@@ -1247,6 +1236,67 @@ int commit_scales(artalk_model* m, const SiteExps& next) {
     m->scales_changed = 0;
     for (size_t i = 0; i < sizeof(SiteExps) / sizeof(int); ++i) m->scales_changed += a[i] != kActExp;
     return changed;
+}
+
+// ---------------------------------------------------------------------------------- shared by the batch call and the streaming calls
+// device of the model and the stream of this call: the caller's, or the model's own (graph capture needs a real stream)
+int call_stream(artalk_model* m, void* stream, hipStream_t* s) {
+    (void)hipSetDevice(m->device);
+    if (!stream && !m->own_stream) HIPCHK(m, hipStreamCreate(&m->own_stream));
+    *s = stream ? (hipStream_t)stream : m->own_stream;
+    return ARTALK_OK;
+}
+// the style flags of a call, checked before anything is enqueued or any state changes; *encode = some clip brings a style clip (flag 1)
+int check_has_style(artalk_model* m, const float* style_motion_dev, const uint8_t* has_style, int B, bool* encode) {
+    *encode = false;
+    for (int b = 0; style_motion_dev && has_style && b < B; ++b) {
+        if (has_style[b] > 2) return fail(m, ARTALK_EINVAL, "has_style entries must be 0, 1 or 2");
+        *encode |= has_style[b] == 1;
+    }
+    return ARTALK_OK;
+}
+// Start of a call for B clips: the style flags go through the pinned slot `stg` (its event then covers every copy the caller staged
+// in it before), the status word is reset, the style conditions are computed.
+int begin_clips(artalk_model* m, hipStream_t s, int B, const float* style_motion_dev, const uint8_t* has_style, bool encode_style,
+                artalk_model::Stage* stg) {
+    Workspace& w = m->ws;
+    if (!has_style) style_motion_dev = nullptr;
+    if (style_motion_dev) {
+        std::memcpy(stg->has, has_style, (size_t)B);
+        HIPCHK(m, hipMemcpyAsync(w.has_style, stg->has, B, hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(m, hipEventRecord(stg->done, s));   // pinned slot: no synchronisation, the slot is reused kStageSlots calls later
+    stg->used = true;
+    HIPCHK(m, hipMemsetAsync(w.status, 0, 4 * sizeof(int), s));
+    stage_mark(m, s, PB_OTHER);
+    run_style(m, style_motion_dev, B, s, encode_style);
+    stage_mark(m, s, PB_STYLE);
+    return ARTALK_OK;
+}
+// One chunk index of Bn clips whose SiLU(cond) rows start at row cond_row0 * 181 of w.silu_cond: the AdaLN table of all blocks + head,
+// SiLU(cond) @ [W_0;...;W_11;W_head]^T, in line in front of the body that reads it, the body, and the chunk's motion to the caller
+// ([Bn][out_stride] floats).  tap_chunk = the chunk's row of slots in the tap buffer (m->tap_maxch: none).
+// (The table of chunk index j + 1 on a stream of its own beside body j was measured in round 4 and removed in round 5: the bodies slow
+// down by what the table GEMM takes, profiles/r04_ada_overlap_sweep.log.)
+int chunk_step(artalk_model* m, hipStream_t s, int cond_row0, int Bn, int n_next, int tap_chunk, float* out_motion_dev, int64_t out_stride) {
+    Workspace& w = m->ws;
+    m->tap_chunk = tap_chunk;
+    roctxRangePushA("artalk.ar.adaln_table");
+    kbucket(m, KB_ADA);
+    linear(m, w.silu_cond + (long)cond_row0 * kNTok * kCond, kCond, m->ada_w, m->ada_b, w.ada, m->ada_n, Bn * kNTok, m->ada_n, kCond,
+           ACT_NONE, nullptr, s, m->precision == 1 ? LF_A_P8 : 0, nullptr, m->ex.silu_cond);
+    roctxRangePop();
+    stage_mark(m, s, PB_ADA);
+    if (body_uses_graphs(m)) {
+        Range r_body("artalk.body.graph");
+        if (int rc = run_body(m, Bn, s, n_next)) return rc;
+        stage_mark(m, s, PB_AR);   // light profiling: the whole captured body (AR steps + VAE) is charged to the AR bucket
+    } else {
+        if (int rc = run_body(m, Bn, s, n_next)) return rc;
+    }
+    const size_t mrow = (size_t)100 * m->cfg.motion_dim * 4;
+    HIPCHK(m, hipMemcpy2DAsync(out_motion_dev, (size_t)out_stride * 4, w.motion_chunk, mrow, mrow, Bn, hipMemcpyDeviceToDevice, s));
+    return ARTALK_OK;
 }
 
 }  // namespace
@@ -1297,7 +1347,7 @@ void artalk_destroy(artalk_model* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
     (void)hipDeviceSynchronize();
-    for (auto& g : m->graphs) (void)hipGraphExecDestroy(g.second.exec);
+    drop_graphs(m);
     for (auto e : m->ev_pool) (void)hipEventDestroy(e);
     for (auto e : m->ktimer.pool) (void)hipEventDestroy(e);
     if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
@@ -1470,12 +1520,11 @@ int artalk_set_graphs(artalk_model* m, int enable) {
         m->splitk_tiles = ((enable >> 16) & 0xff) * 16; m->splitk_target = ((enable >> 24) & 0xff) * 16;
     }
     (void)hipSetDevice(m->device); (void)hipDeviceSynchronize();
-    for (auto& g : m->graphs) (void)hipGraphExecDestroy(g.second.exec);
-    m->graphs.clear();
+    drop_graphs(m);
     m->invalidate_init_hist();      // "the same run_reencode as every later history": the split-K tuning changed
     return ARTALK_OK;
 }
-// number of captured body graphs the model holds (bounded: run_chunk_body_graphs) / captures since the model was created
+// number of captured body graphs the model holds (bounded: run_body) / captures since the model was created
 int artalk_graph_count(const artalk_model* m, long long* captures) {
     if (!m) return ARTALK_EINVAL;
     if (captures) *captures = m->graph_captures;
@@ -1537,8 +1586,7 @@ int artalk_reset_scales(artalk_model* m) {
     (void)hipSetDevice(m->device); (void)hipDeviceSynchronize();
     m->ex = SiteExps();
     m->scales_changed = 0;
-    for (auto& g : m->graphs) (void)hipGraphExecDestroy(g.second.exec);
-    m->graphs.clear();
+    drop_graphs(m);
     m->invalidate_init_hist();
     return ARTALK_OK;
 }
@@ -1634,8 +1682,7 @@ int artalk_set_cu_mask(artalk_model* m, const uint32_t* mask, int n_words) {
         if (m->side_stream[i]) { (void)hipStreamDestroy(m->side_stream[i]); m->side_stream[i] = nullptr; }
         if (m->join_ev[i]) { (void)hipEventDestroy(m->join_ev[i]); m->join_ev[i] = nullptr; }
     }
-    for (auto& g : m->graphs) (void)hipGraphExecDestroy(g.second.exec);      // the GEMM grids were captured for the old CU count
-    m->graphs.clear();
+    drop_graphs(m);      // the GEMM grids were captured for the old CU count
     m->invalidate_init_hist();
     return ARTALK_OK;
 }
@@ -1645,22 +1692,16 @@ int artalk_infer(artalk_model* m, const float* audio_dev, int64_t audio_clip_str
                  uint8_t* out_bits_dev, uint8_t* out_hist_bits_dev, float* out_w2v_dev, void* stream) {
     if (!m || !audio_dev || !n_chunks || !out_motion_dev || B <= 0) return ARTALK_EINVAL;
     if (!m->finalized) return fail(m, ARTALK_ESTATE, "artalk_infer before artalk_finalize_weights");
-    (void)hipSetDevice(m->device);
-    if (!stream && !m->own_stream) HIPCHK(m, hipStreamCreate(&m->own_stream));
-    hipStream_t s = stream ? (hipStream_t)stream : m->own_stream;
+    hipStream_t s;
+    if (int rc = call_stream(m, stream, &s)) return rc;
     const artalk_config& c = m->cfg;
     int64_t C = 0, maxch = n_chunks[0];
     for (int b = 0; b < B; ++b) {
         if (n_chunks[b] <= 0 || (b > 0 && n_chunks[b] > n_chunks[b - 1])) return fail(m, ARTALK_EINVAL, "n_chunks must be positive and non-increasing");
         C += n_chunks[b];
     }
-    bool encode_style = false;      // validated before anything is enqueued or any state changes
-    if (style_motion_dev && has_style) {
-        for (int b = 0; b < B; ++b) {
-            if (has_style[b] > 2) return fail(m, ARTALK_EINVAL, "has_style entries must be 0, 1 or 2");
-            encode_style |= has_style[b] == 1;
-        }
-    }
+    bool encode_style;
+    if (int rc = check_has_style(m, style_motion_dev, has_style, B, &encode_style)) return rc;
     if (m->tap && (B > m->tap_B || maxch > m->tap_maxch)) return fail(m, ARTALK_EINVAL, "the tap buffer (artalk_set_tap) is smaller than this call");
     if (B > m->ws.maxB || C > m->ws.maxC) { if (int rc = reserve(m, B, (int)C)) return rc; }
     Workspace& w = m->ws;
@@ -1678,22 +1719,13 @@ int artalk_infer(artalk_model* m, const float* audio_dev, int64_t audio_clip_str
         base[maxch] = idx;
     }
     HIPCHK(m, hipMemcpyAsync(w.src_off, src, C * sizeof(long), hipMemcpyHostToDevice, s));
-    if (style_motion_dev && has_style) {
-        std::memcpy(stg->has, has_style, (size_t)B);
-        HIPCHK(m, hipMemcpyAsync(w.has_style, stg->has, B, hipMemcpyHostToDevice, s));
-    }
-    HIPCHK(m, hipEventRecord(stg->done, s));   // pinned slot: no synchronisation, the slot is reused kStageSlots calls later
-    stg->used = true;
     m->stream_B = 0; m->stream_scales_ended = false;   // the batch call reuses the workspace that holds the streaming history
-    HIPCHK(m, hipMemsetAsync(w.status, 0, 4 * sizeof(int), s));
     m->ev_used = 0; m->dom_events.clear(); m->marks.clear(); m->prof_stream = s;
     // level 3: every kernel of this call is launched with its own start / stop events (kernels.h ARTALK_LAUNCH) - on this thread, for the
-    // duration of the call; the body then runs eagerly as ONE clip group, like level 2
+    // duration of the call; the body then runs eagerly, its clip groups one after the other (run_body)
     struct TimerScope { bool on; TimerScope(artalk_model* x) : on(x->profiling == 3) { if (on) { x->ktimer.used = 0; x->ktimer.recs.clear(); x->ktimer.bucket = KB_OTHER; g_ktimer = &x->ktimer; } }
                         ~TimerScope() { if (on) g_ktimer = nullptr; } } timer_scope(m);
-    stage_mark(m, s, PB_OTHER);
-    run_style(m, (style_motion_dev && has_style) ? style_motion_dev : nullptr, B, s, encode_style);
-    stage_mark(m, s, PB_STYLE);
+    if (int rc = begin_clips(m, s, B, style_motion_dev, has_style, encode_style, stg)) return rc;
     // (wav2vec2 of chunk index j + 1 on a stream of its own beside the AR/VAE body of index j was an option until round 3: with the
     // persistent one-workgroup-per-CU GEMM kernels, whose workgroups hold a CU's LDS for a whole launch, the body's short kernels wait
     // behind them - 82 -> 128 ms per step; removed)
@@ -1705,35 +1737,12 @@ int artalk_infer(artalk_model* m, const float* audio_dev, int64_t audio_clip_str
         HIPCHK(m, hipMemcpy2DAsync(out_hist_bits_dev, (size_t)(maxch + 1) * bits_row, w.hist_bits, bits_row, bits_row, B,
                                    hipMemcpyDeviceToDevice, s));
     stage_mark(m, s, PB_VAE);
-    const bool graphs = m->use_graphs && m->profiling < 2 && !m->audit && !m->tap;
-    // AdaLN table of a chunk index for all blocks + head: SiLU(cond) @ [W_0;...;W_11;W_head]^T, in line in front of the body that reads it.
-    // (The table of chunk index j + 1 on a stream of its own beside body j was measured in round 4 and removed in round 5: the bodies slow
-    // down by what the table GEMM takes, profiles/r04_ada_overlap_sweep.log.)
-    auto ada_table = [&](int64_t j) {
-        roctxRangePushA("artalk.ar.adaln_table");
-        kbucket(m, KB_ADA);
-        linear(m, w.silu_cond + (long)base[j] * kNTok * kCond, kCond, m->ada_w, m->ada_b, w.ada, m->ada_n, Bj[j] * kNTok, m->ada_n, kCond,
-               ACT_NONE, nullptr, s, m->precision == 1 ? LF_A_P8 : 0, nullptr, m->ex.silu_cond);
-        roctxRangePop();
-    };
     for (int64_t j = 0; j < maxch; ++j) {
         const int Bn = Bj[j];
-        m->tap_chunk = (int)j;
         // clips whose motion must be re-encoded into a history: those with a chunk j + 1 (a prefix: clips are sorted by length) - all of
         // them when the caller asked for the history bits of every chunk (the reference computes the trailing ones too and drops them)
         const int n_next = out_hist_bits_dev ? Bn : (j + 1 < maxch ? Bj[j + 1] : 0);
-        ada_table(j);
-        stage_mark(m, s, PB_ADA);
-        if (graphs) {
-            Range r_body("artalk.body.graph");
-            if (int brc = run_chunk_body_graphs(m, Bn, s, n_next)) return brc;
-            stage_mark(m, s, PB_AR);   // light profiling: the whole captured body (AR steps + VAE) is charged to the AR bucket
-        } else {
-            if (int brc = run_chunk_body_split(m, Bn, s, n_next)) return brc;
-        }
-        const size_t mrow = (size_t)100 * c.motion_dim * 4;
-        HIPCHK(m, hipMemcpy2DAsync(out_motion_dev + j * 100 * c.motion_dim, (size_t)out_clip_stride * 4, w.motion_chunk, mrow, mrow, Bn,
-                                   hipMemcpyDeviceToDevice, s));
+        if (int rc = chunk_step(m, s, base[j], Bn, n_next, (int)j, out_motion_dev + j * 100 * c.motion_dim, out_clip_stride)) return rc;
         if (out_bits_dev)
             HIPCHK(m, hipMemcpy2DAsync(out_bits_dev + j * bits_row, (size_t)maxch * bits_row, w.bits, bits_row, bits_row, Bn,
                                        hipMemcpyDeviceToDevice, s));
@@ -1743,7 +1752,6 @@ int artalk_infer(artalk_model* m, const float* audio_dev, int64_t audio_clip_str
     }
     stage_mark(m, s, PB_OTHER);
     if (int rc = publish_status(m, s)) return rc;
-    HIPCHK(m, hipGetLastError());
     if (m->sticky_error) { m->sticky_error = false; return ARTALK_ESTATE; }
     return ARTALK_OK;
 }
@@ -1754,9 +1762,8 @@ int artalk_infer(artalk_model* m, const float* audio_dev, int64_t audio_clip_str
 int artalk_style_encode(artalk_model* m, const float* style_motion_dev, int n, float* out_cond_dev, void* stream) {
     if (!m || !style_motion_dev || !out_cond_dev || n <= 0) return ARTALK_EINVAL;
     if (!m->finalized) return fail(m, ARTALK_ESTATE, "artalk_style_encode before artalk_finalize_weights");
-    (void)hipSetDevice(m->device);
-    if (!stream && !m->own_stream) HIPCHK(m, hipStreamCreate(&m->own_stream));
-    hipStream_t s = stream ? (hipStream_t)stream : m->own_stream;
+    hipStream_t s;
+    if (int rc = call_stream(m, stream, &s)) return rc;
     if (m->stream_B > 0) return fail(m, ARTALK_ESTATE, "artalk_style_encode during a streaming session (it shares the workspace)");
     if (n > m->ws.maxB) { if (int rc = reserve(m, n, std::max(n, m->ws.maxC))) return rc; }
     Workspace& w = m->ws;
@@ -1776,35 +1783,21 @@ int artalk_style_encode(artalk_model* m, const float* style_motion_dev, int n, f
 int artalk_stream_begin(artalk_model* m, int B, const float* style_motion_dev, const uint8_t* has_style, void* stream) {
     if (!m || B <= 0) return ARTALK_EINVAL;
     if (!m->finalized) return fail(m, ARTALK_ESTATE, "artalk_stream_begin before artalk_finalize_weights");
-    bool encode_style = false;
-    if (style_motion_dev && has_style)
-        for (int b = 0; b < B; ++b) {
-            if (has_style[b] > 2) return fail(m, ARTALK_EINVAL, "has_style entries must be 0, 1 or 2");
-            encode_style |= has_style[b] == 1;
-        }
-    (void)hipSetDevice(m->device);
-    if (!stream && !m->own_stream) HIPCHK(m, hipStreamCreate(&m->own_stream));
-    hipStream_t s = stream ? (hipStream_t)stream : m->own_stream;
+    bool encode_style;
+    if (int rc = check_has_style(m, style_motion_dev, has_style, B, &encode_style)) return rc;
+    hipStream_t s;
+    if (int rc = call_stream(m, stream, &s)) return rc;
     if (B > m->ws.maxB || B > m->ws.maxC) { if (int rc = reserve(m, B, B)) return rc; }
     if (int rc = ensure_stage(m, m->ws.maxB, m->ws.maxC)) return rc;
-    Workspace& w = m->ws;
-    if (style_motion_dev && has_style) {
-        artalk_model::Stage* stg = nullptr;
-        if (int rc = next_stage(m, &stg)) return rc;
-        std::memcpy(stg->has, has_style, (size_t)B);
-        HIPCHK(m, hipMemcpyAsync(w.has_style, stg->has, B, hipMemcpyHostToDevice, s));
-        HIPCHK(m, hipEventRecord(stg->done, s));
-        stg->used = true;
-    }
-    HIPCHK(m, hipMemsetAsync(w.status, 0, 4 * sizeof(int), s));   // the status word covers the whole streaming session
+    artalk_model::Stage* stg = nullptr;
+    if (int rc = next_stage(m, &stg)) return rc;
     {
         ProfilingOff quiet(m);
-        run_style(m, (style_motion_dev && has_style) ? style_motion_dev : nullptr, B, s, encode_style);
+        if (int rc = begin_clips(m, s, B, style_motion_dev, has_style, encode_style, stg)) return rc;   // the status word covers the whole session
         if (int rc = run_init_history(m, B, s)) return rc;
     }
     m->stream_B = B; m->stream_scales_ended = false;
     if (int rc = publish_status(m, s)) return rc;
-    HIPCHK(m, hipGetLastError());
     return ARTALK_OK;
 }
 
@@ -1816,9 +1809,8 @@ int artalk_stream_chunk(artalk_model* m, const float* audio_dev, int64_t chunk_s
     if (m->stream_B <= 0)
         return fail(m, ARTALK_ESTATE, m->stream_scales_ended ? "the site scales changed since artalk_stream_begin; begin again"
                                                              : "artalk_stream_chunk before artalk_stream_begin");
-    (void)hipSetDevice(m->device);
-    if (!stream && !m->own_stream) HIPCHK(m, hipStreamCreate(&m->own_stream));
-    hipStream_t s = stream ? (hipStream_t)stream : m->own_stream;
+    hipStream_t s;
+    if (int rc = call_stream(m, stream, &s)) return rc;
     const int B = m->stream_B;
     Workspace& w = m->ws;
     if (B > w.maxB) return fail(m, ARTALK_ESTATE, "workspace was re-reserved since artalk_stream_begin; begin again");
@@ -1830,17 +1822,9 @@ int artalk_stream_chunk(artalk_model* m, const float* audio_dev, int64_t chunk_s
     stg->used = true;
     ProfilingOff quiet(m);      // restored on every exit path
     for (int c0 = 0; c0 < B; c0 += w.G) run_wav2vec(m, audio_dev, c0, std::min(w.G, B - c0), nullptr, s);
-    linear(m, w.silu_cond, kCond, m->ada_w, m->ada_b, w.ada, m->ada_n, B * kNTok, m->ada_n, kCond, ACT_NONE, nullptr, s,
-           m->precision == 1 ? LF_A_P8 : 0, nullptr, m->ex.silu_cond);
-    if (m->use_graphs) {
-        if (int brc = run_chunk_body_graphs(m, B, s)) return brc;
-    } else {
-        if (int brc = run_chunk_body_split(m, B, s)) return brc;
-    }
-    const size_t mrow = (size_t)100 * m->cfg.motion_dim * 4;
-    HIPCHK(m, hipMemcpy2DAsync(out_motion_dev, (size_t)out_stride * 4, w.motion_chunk, mrow, mrow, B, hipMemcpyDeviceToDevice, s));
+    // every stream has a next chunk; no taps: their slots belong to the chunk indices of a batch call
+    if (int rc = chunk_step(m, s, 0, B, B, m->tap_maxch, out_motion_dev, out_stride)) return rc;
     if (int rc = publish_status(m, s)) return rc;
-    HIPCHK(m, hipGetLastError());
     return ARTALK_OK;
 }
 

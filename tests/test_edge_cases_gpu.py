@@ -334,3 +334,86 @@ def test_kernel_timer_budget_matches_the_graph_path():
     finally:
         m.set_profiling(0)
         m.set_precision("f32")
+
+
+def test_graphs_off_equals_graphs_on_at_an_odd_batch():
+    """Graph replay and the eager run of the body (artalk_set_graphs(0)) cut a batch into the same clip groups, so the GEMM planner sees
+    the same M and every bit agrees.  9 clips of 1 / 2 / 3 chunks: the active batch decays 9 -> 6 -> 3 (two groups of 4 + 5, then one
+    group below 8 clips); 9 is the smallest batch where a cut at (B + 1) / 2 differs from B * h / n (5 + 4 against 4 + 5), and the
+    smallest that four groups accept.  The forced four-group eager run is compared with the four-group replay: another cut."""
+    from artalk_amd.synth import synth_audio
+    m = get_gpu_model("tiny")
+    audios = [torch.from_numpy(synth_audio(600 + i, (2.0, 5.5, 9.0)[i % 3])) for i in range(9)]
+
+    def run():
+        outs = [o.clone() for o in m.inference_batch(audios, return_aux=True)]
+        return outs, [b.clone() for b in m.last_aux["bits"]]
+
+    def same(a, b):
+        return all(torch.equal(x, y) for x, y in zip(a[0] + a[1], b[0] + b[1]))
+
+    m.set_precision("f16x3")
+    try:
+        want = run()
+        assert m.graph_count()[0] > 0
+        m.set_graphs(False)
+        assert same(run(), want) and m.graph_count()[0] == 0
+        m.set_graphs(True, branches=4)
+        want4 = run()
+        m.set_graphs(False, branches=4)
+        assert same(run(), want4)
+    finally:
+        m.set_graphs(True)
+        m.set_precision("f32")
+
+
+def test_streaming_shares_the_batch_calls_graphs():
+    """A streaming chunk of B streams is the chunk step of a batch call of B clips: it replays the graphs that call captured and gives
+    the same codes."""
+    from artalk_amd.synth import synth_audio
+    m = get_gpu_model("tiny")
+    audios = [torch.from_numpy(synth_audio(620 + i, 8.0)) for i in range(9)]
+    m.set_precision("f16x3")
+    try:
+        want = torch.stack(m.inference_batch(audios))
+        captures = m.graph_count()[1]
+        m.stream_begin(9)
+        got = []
+        for j in range(2):
+            got.append(m.stream_chunk(torch.stack([a[j * 64000:(j + 1) * 64000] for a in audios]).cuda()))
+            assert m.graph_count()[1] == captures      # the streams always have a next chunk: the keys of the call's first chunk index
+        got = torch.cat(got, dim=1)
+        print(f"streaming vs batch call, 9 clips x 2 chunks: max-abs difference {(got - want).abs().max().item():.3e}")
+        assert torch.equal(got, want)
+    finally:
+        m.stream_end()
+        m.set_precision("f32")
+
+
+def test_streaming_under_the_audit_runs_eagerly():
+    """With the audit on a streaming chunk runs eagerly and records its sites, as a batch call does: nothing is captured (a graph
+    captured then would replay the audit's launches for ever), and with the audit off again the session's output is what it was."""
+    import ctypes as C
+    from artalk_amd import capi
+    from artalk_amd.synth import synth_audio
+    m = get_gpu_model("tiny")
+    L = capi.lib()
+    chunk = torch.stack([torch.from_numpy(synth_audio(640 + i, 4.0)) for i in range(9)]).cuda()
+    m.set_precision("f32")
+    try:
+        m.stream_begin(9)
+        before = m.stream_chunk(chunk).clone()
+        captures = m.graph_count()[1]
+        assert L.artalk_set_audit(m._h, 1) == capi.OK
+        m.stream_begin(9)
+        m.stream_chunk(chunk)
+        assert m.graph_count()[1] == captures
+        buf = C.create_string_buffer(1 << 16)
+        vals = (C.c_float * 1024)()
+        assert L.artalk_get_audit(m._h, buf, len(buf), vals, 1024) > 0
+        L.artalk_set_audit(m._h, 0)
+        m.stream_begin(9)
+        assert torch.equal(m.stream_chunk(chunk), before)
+    finally:
+        L.artalk_set_audit(m._h, 0)
+        m.stream_end()
