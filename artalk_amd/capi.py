@@ -23,6 +23,7 @@ SYMBOLS = [
     "artalk_set_profiling", "artalk_get_profile", "artalk_get_kernel_sums", "artalk_set_graphs", "artalk_graph_count", "artalk_set_cu_mask", "artalk_set_audit", "artalk_get_audit", "artalk_calibrate", "artalk_reset_scales", "artalk_get_scales", "artalk_scale_sites", "artalk_get_site_scales", "artalk_set_site_scales", "artalk_set_tap", "artalk_tap_layout", "artalk_set_precision",
     "artalk_op_gemm", "artalk_op_gemm_ex", "artalk_op_gemm_bf16", "artalk_op_gemm_f16s", "artalk_op_pack_split", "artalk_op_gemm_f16s_packed", "artalk_op_release_scratch", "artalk_op_gemm_p8_plan", "artalk_op_create_masked_stream", "artalk_op_destroy_stream", "artalk_op_mfma_f32_peak", "artalk_op_layernorm", "artalk_op_attention", "artalk_op_w2v_front", "artalk_op_resample_mean", "artalk_op_pool_silu",
     "artalk_op_bsq_history",
+    "artalk_sessions_reserve", "artalk_session_open", "artalk_session_step", "artalk_session_close", "artalk_session_count",
     "artalk_op_pack_split_ex", "artalk_op_layernorm_ex", "artalk_op_gemm_f16s_packed_ex", "artalk_op_gemm_f16s_ex", "artalk_op_attention_ex", "artalk_op_w2v_front_ex", "artalk_op_pool_silu_ex", "artalk_op_posconv_p8_ex",
 ]
 
@@ -117,6 +118,17 @@ def lib() -> C.CDLL:
     L.artalk_stream_end.restype = i32
     L.artalk_stream_chunk.argtypes = [vp, vp, i64, vp, i64, vp]
     L.artalk_stream_chunk.restype = i32
+    if hasattr(L, "artalk_session_open"):      # (an older build loaded through ARTALK_LIB for an A/B run lacks the session entry points)
+        L.artalk_sessions_reserve.argtypes = [vp, i32]
+        L.artalk_sessions_reserve.restype = i32
+        L.artalk_session_open.argtypes = [vp, i32, vp, vp, C.POINTER(i64), vp]
+        L.artalk_session_open.restype = i32
+        L.artalk_session_step.argtypes = [vp, C.POINTER(i64), i32, vp, i64, vp, i64, vp, vp, vp]
+        L.artalk_session_step.restype = i32
+        L.artalk_session_close.argtypes = [vp, C.POINTER(i64), i32]
+        L.artalk_session_close.restype = i32
+        L.artalk_session_count.argtypes = [vp]
+        L.artalk_session_count.restype = i32
     L.artalk_flame_create.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, C.POINTER(vp)]
     L.artalk_flame_create.restype = i32
     L.artalk_flame_verts.argtypes = [vp, vp, vp, i32, vp, vp]

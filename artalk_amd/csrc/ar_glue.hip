@@ -293,6 +293,45 @@ void launch_enc_input_zero(const float* mean, const float* stdv, const float* ep
     ARTALK_LAUNCH(enc_input_zero_kernel, dim3(B), dim3(256), 0, s, mean, stdv, epos, E, 106, 128);
 }
 
+// Independent streaming sessions (engine.hip, session pool): the state of a session that crosses a chunk boundary - style condition,
+// history tokens, decoder features of the previous chunk - lives in a pool slot, [style | prev_in | prev_fdec] in 16-byte units.  Block
+// (piece, i) moves piece `piece` of session i between the slot slots[i] and row i of the three workspace buffers, one uint4 per lane
+// and trip; which buffer a unit belongs to is uniform per wavefront except at the two field boundaries.
+__global__ __launch_bounds__(256) void session_gather_kernel(const uint4* const* __restrict__ slots, SessionRows w) {
+    const uint4* __restrict__ src = slots[blockIdx.y];
+    const long row = blockIdx.y;
+    const int p0 = w.s16, f0 = w.s16 + w.p16, n16 = f0 + w.f16;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n16; i += gridDim.x * 256) {
+        const uint4 v = src[i];
+        if (i < p0) w.style[row * w.s16 + i] = v;
+        else if (i < f0) w.prev_in[row * w.p16 + (i - p0)] = v;
+        else w.prev_fdec[row * w.f16 + (i - f0)] = v;
+    }
+}
+// the way back; the style condition never changes after the session was opened, so only the open writes it (with_style)
+__global__ __launch_bounds__(256) void session_scatter_kernel(uint4* const* __restrict__ slots, SessionRows w, int with_style) {
+    uint4* __restrict__ dst = slots[blockIdx.y];
+    const long row = blockIdx.y;
+    const int p0 = w.s16, f0 = w.s16 + w.p16, n16 = f0 + w.f16;
+    for (int i = (with_style ? 0 : p0) + blockIdx.x * 256 + threadIdx.x; i < n16; i += gridDim.x * 256) {
+        uint4 v;
+        if (i < p0) v = w.style[row * w.s16 + i];
+        else if (i < f0) v = w.prev_in[row * w.p16 + (i - p0)];
+        else v = w.prev_fdec[row * w.f16 + (i - f0)];
+        dst[i] = v;
+    }
+}
+static inline unsigned session_pieces(const SessionRows& w) { return (unsigned)((w.s16 + w.p16 + w.f16 + 1023) / 1024); }   // 4 trips per lane
+void launch_session_gather(const float* const* slots, const SessionRows& w, int n, hipStream_t s) {
+    if (n <= 0) return;
+    ARTALK_LAUNCH(session_gather_kernel, dim3(session_pieces(w), n), dim3(256), 0, s, reinterpret_cast<const uint4* const*>(slots), w);
+}
+void launch_session_scatter(float* const* slots, const SessionRows& w, int n, bool with_style, hipStream_t s) {
+    if (n <= 0) return;
+    ARTALK_LAUNCH(session_scatter_kernel, dim3(session_pieces(w), n), dim3(256), 0, s, reinterpret_cast<uint4* const*>(slots), w,
+                  with_style ? 1 : 0);
+}
+
 // ------------------------------------------------------------------------------------------------
 // One workgroup per clip.  Sequential over the 5 scales (each needs the residual left by the previous one); 1024 threads: the kernel is a
 // chain of passes over the clip's 3 200 values between barriers, 3 trips per pass instead of 13 (41 -> ~20 us per launch).

@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -116,6 +117,7 @@ struct Workspace {
     float* splitk_b[4] = {nullptr, nullptr, nullptr, nullptr};   // one scratch per concurrent branch of the AR body (splitk_b[0] == splitk)
     uint8_t *bits = nullptr, *hist_bits = nullptr, *has_style = nullptr;
     int* status = nullptr;           // device word: bit 0 non-finite logit, bit 1 non-finite re-encoder output (see artalk_get_status)
+    float** sess_slots = nullptr;    // [maxB] pool slots of the sessions of the current artalk_session_open / _step, row order (launch_session_gather)
     // VAE
     float *prev_fdec = nullptr, *msfeat = nullptr, *dec_x = nullptr, *vh = nullptr, *vln = nullptr, *vqkv = nullptr;
     float *vatt = nullptr, *vmlp = nullptr, *dec_out = nullptr, *enc_in = nullptr, *enc_out = nullptr, *motion_chunk = nullptr;
@@ -166,6 +168,22 @@ struct artalk_model {
     std::vector<uint32_t> cu_mask;    // artalk_set_cu_mask: the library's own streams are restricted to these compute units
     int n_cus = 0;                    // their number (0 = the whole device): grid of the persistent one-workgroup-per-CU kernels
     int stream_B = 0;                 // streams opened by artalk_stream_begin (history lives in the workspace)
+    // Independent streaming sessions (artalk_session_*).  What a stream carries from chunk to chunk - style condition [768], history
+    // tokens prev_in [181][768], decoder features prev_fdec [100][32], plain fp32 in every precision mode - lives in a pool slot, OUTSIDE
+    // the workspace: device memory in blocks of kSessBlock slots that are never moved or freed before artalk_destroy, so growing the
+    // pool touches no open session.  A step gathers the listed sessions into workspace rows 0..n-1, runs the chunk step of lockstep
+    // streaming there and scatters the new history back.  INVARIANT: between library calls the workspace holds nothing a session
+    // needs - it is scratch, and the batch call, lockstep streaming, artalk_style_encode and workspace growth may use it freely.
+    static constexpr int kSessBlock = 32;
+    struct Sessions {
+        std::vector<float*> blocks;                // device blocks of kSessBlock slots
+        std::vector<int64_t> owner;                // per slot: the id of the session that holds it, 0 = free
+        std::map<int64_t, int> open;               // id -> slot
+        std::set<int64_t> ended_by_scales;         // ids a change of site scales closed (a step on one says so; artalk_session_close forgets it)
+        int64_t next_id = 1;                       // ids are never reused during the model's life
+    } sess;
+    int64_t sess_slot_floats() const { return kE + (int64_t)kNTok * kE + 100LL * cfg.code_dim; }
+    float* sess_slot(int i) const { return sess.blocks[i / kSessBlock] + (int64_t)(i % kSessBlock) * sess_slot_floats(); }
     Workspace* view = nullptr;        // workspace view (clip sub-range) the body launchers currently work on; null = m->ws
     bool sticky_error = false;        // set by internal consistency checks inside the launch sequence; reported by artalk_infer
     // derived sizes
@@ -210,7 +228,7 @@ struct artalk_model {
     // recorded after its H2D copies, so artalk_infer never has to wait for its own copies (it blocks only if kStageSlots calls
     // are still in flight).  h_status receives the device status word at the end of every call (async), status_ev marks it.
     static constexpr int kStageSlots = 4;
-    struct Stage { long* src = nullptr; uint8_t* has = nullptr; hipEvent_t done = nullptr; bool used = false; };
+    struct Stage { long* src = nullptr; uint8_t* has = nullptr; float** slots = nullptr; hipEvent_t done = nullptr; bool used = false; };
     Stage stage[kStageSlots];
     int stage_cap_c = 0, stage_cap_b = 0, stage_next = 0;
     // one slot per call in flight (ring of kStatusSlots, indexed by the call's ticket): a caller that keeps several calls queued reads
@@ -1082,7 +1100,8 @@ void free_stage(artalk_model* m) {
     for (auto& st : m->stage) {
         if (st.src) (void)hipHostFree(st.src);
         if (st.has) (void)hipHostFree(st.has);
-        st.src = nullptr; st.has = nullptr; st.used = false;
+        if (st.slots) (void)hipHostFree(st.slots);
+        st.src = nullptr; st.has = nullptr; st.slots = nullptr; st.used = false;
     }
     m->stage_cap_c = m->stage_cap_b = 0;
 }
@@ -1098,6 +1117,7 @@ int ensure_stage(artalk_model* m, int maxB, int maxC) {
     for (auto& st : m->stage) {
         HIPCHK(m, hipHostMalloc(reinterpret_cast<void**>(&st.src), (size_t)maxC * sizeof(long), hipHostMallocDefault));
         HIPCHK(m, hipHostMalloc(reinterpret_cast<void**>(&st.has), (size_t)maxB, hipHostMallocDefault));
+        HIPCHK(m, hipHostMalloc(reinterpret_cast<void**>(&st.slots), (size_t)maxB * sizeof(float*), hipHostMallocDefault));
         if (!st.done) HIPCHK(m, hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
     }
     m->stage_cap_b = maxB; m->stage_cap_c = maxC;
@@ -1161,6 +1181,7 @@ int reserve(artalk_model* m, int maxB, int maxC) {
     w.hist_bits = dalloc_in<uint8_t>(m->ws_allocs, (int64_t)maxB * kNTok * c.code_dim);
     w.has_style = dalloc_in<uint8_t>(m->ws_allocs, maxB);
     w.status = dalloc_in<int>(m->ws_allocs, 4);
+    w.sess_slots = dalloc_in<float*>(m->ws_allocs, maxB);
     w.prev_fdec = F((int64_t)maxB * 100 * c.code_dim); w.msfeat = F((int64_t)maxB * 180 * c.code_dim);
     const int H = c.vae_hidden;
     w.dec_x = F((int64_t)maxB * 200 * c.code_dim); w.vh = F((int64_t)maxB * 200 * H); w.vln = F((int64_t)maxB * 200 * H);
@@ -1218,6 +1239,12 @@ void build_site_table(artalk_model* m) {
     }
 }
 
+// A change of site scales closes every open session (the device is idle: the caller synchronised): their history was written under the
+// old exponents' arithmetic, and a session never mixes exponents.  The ids are remembered so that a later step can say why it fails.
+void end_sessions_by_scales(artalk_model* m) {
+    for (const auto& kv : m->sess.open) { m->sess.ended_by_scales.insert(kv.first); m->sess.owner[kv.second] = 0; }
+    m->sess.open.clear();
+}
 // The one way new site exponents take effect (artalk_set_site_scales, artalk_calibrate): `next` is a complete SiteExps.  When anything
 // differs, the device is synchronised, the captured graphs (the exponents are kernel arguments of their launches) and the initial-history
 // cache are dropped, and an open streaming session ends - a session never mixes exponents.  Returns the number of sites changed.
@@ -1231,6 +1258,7 @@ int commit_scales(artalk_model* m, const SiteExps& next) {
         drop_graphs(m);
         m->invalidate_init_hist();
         if (m->stream_B > 0) { m->stream_B = 0; m->stream_scales_ended = true; }
+        end_sessions_by_scales(m);
         m->ex = next;
     }
     m->scales_changed = 0;
@@ -1299,6 +1327,33 @@ int chunk_step(artalk_model* m, hipStream_t s, int cond_row0, int Bn, int n_next
     return ARTALK_OK;
 }
 
+// ---------------------------------------------------------------------------------- session pool (artalk_session_*)
+SessionRows session_rows(const artalk_model* m) {
+    const Workspace& w = m->ws;
+    SessionRows r;
+    r.style = reinterpret_cast<uint4*>(w.style_cond); r.prev_in = reinterpret_cast<uint4*>(w.prev_in); r.prev_fdec = reinterpret_cast<uint4*>(w.prev_fdec);
+    r.s16 = kE / 4; r.p16 = kNTok * kE / 4; r.f16 = 100 * m->cfg.code_dim / 4;
+    return r;
+}
+// at least n_slots slots: new blocks only, nothing is moved (the slots are written by a scatter before anything reads them: no fill)
+int grow_sessions(artalk_model* m, int64_t n_slots) {
+    artalk_model::Sessions& ss = m->sess;
+    if (m->cfg.code_dim % 4) return fail(m, ARTALK_EINVAL, "sessions need a code_dim that is a multiple of 4 (16-byte rows)");
+    while ((int64_t)ss.owner.size() < n_slots) {
+        void* p = nullptr;
+        HIPCHK(m, hipMalloc(&p, (size_t)artalk_model::kSessBlock * m->sess_slot_floats() * sizeof(float)));
+        ss.blocks.push_back(static_cast<float*>(p));
+        ss.owner.resize(ss.owner.size() + artalk_model::kSessBlock, 0);
+    }
+    return ARTALK_OK;
+}
+// the device table of this call's slots (row i = slot[i]) through the pinned slot `stg`; the caller records stg->done afterwards
+int stage_session_slots(artalk_model* m, hipStream_t s, artalk_model::Stage* stg, const int* slot, int n) {
+    for (int i = 0; i < n; ++i) stg->slots[i] = m->sess_slot(slot[i]);
+    HIPCHK(m, hipMemcpyAsync(m->ws.sess_slots, stg->slots, (size_t)n * sizeof(float*), hipMemcpyHostToDevice, s));
+    return ARTALK_OK;
+}
+
 }  // namespace
 
 // =================================================================================================== C ABI
@@ -1362,6 +1417,7 @@ void artalk_destroy(artalk_model* m) {
     for (auto& e : m->status_ev) if (e) (void)hipEventDestroy(e);
     for (void* p : m->allocs) if (p) (void)hipFree(p);
     for (void* p : m->ws_allocs) if (p) (void)hipFree(p);
+    for (float* p : m->sess.blocks) if (p) (void)hipFree(p);
     delete m;
 }
 
@@ -1584,6 +1640,7 @@ int artalk_calibrate(artalk_model* m, float headroom) {
 int artalk_reset_scales(artalk_model* m) {
     if (!m) return ARTALK_EINVAL;
     (void)hipSetDevice(m->device); (void)hipDeviceSynchronize();
+    if (m->scales_changed) end_sessions_by_scales(m);      // (the lockstep session keeps its old rule)
     m->ex = SiteExps();
     m->scales_changed = 0;
     drop_graphs(m);
@@ -1831,6 +1888,109 @@ int artalk_stream_chunk(artalk_model* m, const float* audio_dev, int64_t chunk_s
 int artalk_stream_end(artalk_model* m) {
     if (!m) return ARTALK_EINVAL;
     m->stream_B = 0; m->stream_scales_ended = false;      // the history in the workspace is dead; artalk_style_encode / artalk_reserve may use the workspace again
+    return ARTALK_OK;
+}
+
+// ---------------------------------------------------------------------------------- independent sessions
+// The same chunk step for streams that join and leave between steps: the history of every session lives in the session pool
+// (artalk_model::Sessions) and visits the workspace only for the duration of a call.
+int artalk_sessions_reserve(artalk_model* m, int max_sessions) {
+    if (!m || max_sessions <= 0) return ARTALK_EINVAL;
+    (void)hipSetDevice(m->device);
+    return grow_sessions(m, max_sessions);
+}
+
+int artalk_session_count(const artalk_model* m) { return m ? (int)m->sess.open.size() : ARTALK_EINVAL; }
+
+int artalk_session_open(artalk_model* m, int n, const float* style_motion_dev, const uint8_t* has_style, int64_t* ids_out, void* stream) {
+    if (!m || n <= 0 || !ids_out) return ARTALK_EINVAL;
+    if (!m->finalized) return fail(m, ARTALK_ESTATE, "artalk_session_open before artalk_finalize_weights");
+    bool encode_style;
+    if (int rc = check_has_style(m, style_motion_dev, has_style, n, &encode_style)) return rc;
+    hipStream_t s;
+    if (int rc = call_stream(m, stream, &s)) return rc;
+    artalk_model::Sessions& ss = m->sess;
+    if (int rc = grow_sessions(m, (int64_t)ss.open.size() + n)) return rc;
+    if (n > m->ws.maxB || n > m->ws.maxC) { if (int rc = reserve(m, n, n)) return rc; }
+    if (int rc = ensure_stage(m, m->ws.maxB, m->ws.maxC)) return rc;
+    std::vector<int> slot;
+    for (int i = 0; i < (int)ss.owner.size() && (int)slot.size() < n; ++i)
+        if (!ss.owner[i]) slot.push_back(i);
+    artalk_model::Stage* stg = nullptr;
+    if (int rc = next_stage(m, &stg)) return rc;
+    if (int rc = stage_session_slots(m, s, stg, slot.data(), n)) return rc;
+    m->stream_B = 0; m->stream_scales_ended = false;      // rows 0..n-1 of the workspace are rewritten: a lockstep session ends, as under artalk_infer
+    {
+        ProfilingOff quiet(m);
+        if (int rc = begin_clips(m, s, n, style_motion_dev, has_style, encode_style, stg)) return rc;
+        if (int rc = run_init_history(m, n, s)) return rc;
+    }
+    launch_session_scatter(m->ws.sess_slots, session_rows(m), n, true, s);
+    if (int rc = publish_status(m, s)) return rc;
+    for (int i = 0; i < n; ++i) {
+        ids_out[i] = ss.next_id++;
+        ss.owner[slot[i]] = ids_out[i];
+        ss.open.emplace(ids_out[i], slot[i]);
+    }
+    return ARTALK_OK;
+}
+
+int artalk_session_step(artalk_model* m, const int64_t* ids, int n, const float* audio_dev, int64_t chunk_stride, float* out_motion_dev,
+                        int64_t out_stride, uint8_t* out_bits_dev, uint8_t* out_hist_bits_dev, void* stream) {
+    if (!m || !ids || n <= 0 || !audio_dev || !out_motion_dev) return ARTALK_EINVAL;
+    artalk_model::Sessions& ss = m->sess;
+    // every id is checked before anything is enqueued or any session changes
+    std::vector<int> slot((size_t)n);
+    std::set<int64_t> seen;
+    for (int i = 0; i < n; ++i) {
+        const auto it = ss.open.find(ids[i]);
+        if (it == ss.open.end()) {
+            if (ss.ended_by_scales.count(ids[i]))
+                return fail(m, ARTALK_ESTATE, "session " + std::to_string(ids[i]) + ": the site scales changed since artalk_session_open; open the session again");
+            return fail(m, ARTALK_EINVAL, "artalk_session_step: " + std::to_string(ids[i]) + " is not an open session");
+        }
+        if (!seen.insert(ids[i]).second) return fail(m, ARTALK_EINVAL, "artalk_session_step: session " + std::to_string(ids[i]) + " is listed twice");
+        slot[i] = it->second;
+    }
+    hipStream_t s;
+    if (int rc = call_stream(m, stream, &s)) return rc;
+    if (n > m->ws.maxB || n > m->ws.maxC) { if (int rc = reserve(m, n, n)) return rc; }
+    Workspace& w = m->ws;
+    artalk_model::Stage* stg = nullptr;
+    if (int rc = next_stage(m, &stg)) return rc;
+    for (int b = 0; b < n; ++b) stg->src[b] = (long)b * chunk_stride;
+    HIPCHK(m, hipMemcpyAsync(w.src_off, stg->src, n * sizeof(long), hipMemcpyHostToDevice, s));
+    if (int rc = stage_session_slots(m, s, stg, slot.data(), n)) return rc;
+    HIPCHK(m, hipEventRecord(stg->done, s));
+    stg->used = true;
+    m->stream_B = 0; m->stream_scales_ended = false;      // (see artalk_session_open)
+    HIPCHK(m, hipMemsetAsync(w.status, 0, 4 * sizeof(int), s));      // every step has a status word, and a ticket, of its own
+    const SessionRows rows = session_rows(m);
+    ProfilingOff quiet(m);      // restored on every exit path
+    launch_session_gather(w.sess_slots, rows, n, s);
+    for (int c0 = 0; c0 < n; c0 += w.G) run_wav2vec(m, audio_dev, c0, std::min(w.G, n - c0), nullptr, s);
+    // the chunk step of artalk_stream_chunk for n streams: same rows, same graphs; every session has a next chunk
+    if (int rc = chunk_step(m, s, 0, n, n, m->tap_maxch, out_motion_dev, out_stride)) return rc;
+    launch_session_scatter(w.sess_slots, rows, n, false, s);
+    const size_t bits_n = (size_t)n * kNTok * m->cfg.code_dim;
+    if (out_bits_dev) HIPCHK(m, hipMemcpyAsync(out_bits_dev, w.bits, bits_n, hipMemcpyDeviceToDevice, s));
+    if (out_hist_bits_dev) HIPCHK(m, hipMemcpyAsync(out_hist_bits_dev, w.hist_bits, bits_n, hipMemcpyDeviceToDevice, s));
+    if (int rc = publish_status(m, s)) return rc;
+    return ARTALK_OK;
+}
+
+int artalk_session_close(artalk_model* m, const int64_t* ids, int n) {
+    if (!m || !ids || n <= 0) return ARTALK_EINVAL;
+    artalk_model::Sessions& ss = m->sess;
+    std::set<int64_t> seen;
+    for (int i = 0; i < n; ++i)
+        if ((!ss.open.count(ids[i]) && !ss.ended_by_scales.count(ids[i])) || !seen.insert(ids[i]).second)
+            return fail(m, ARTALK_EINVAL, "artalk_session_close: " + std::to_string(ids[i]) + " is not an open session (or is listed twice)");
+    for (int i = 0; i < n; ++i) {
+        const auto it = ss.open.find(ids[i]);
+        if (it != ss.open.end()) { ss.owner[it->second] = 0; ss.open.erase(it); }
+        ss.ended_by_scales.erase(ids[i]);      // a session the scale change closed: only the note is dropped
+    }
     return ARTALK_OK;
 }
 

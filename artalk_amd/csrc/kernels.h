@@ -187,6 +187,16 @@ void launch_dec_finish(const float* dec /*[B*200,106]*/, const float* mean, cons
 // zero motion encoder input (initial history): E[b*100+t] = (0-mean)/std + epos[t]
 void launch_enc_input_zero(const float* mean, const float* stdv, const float* epos, float* E, int B, hipStream_t s);
 void launch_broadcast16(const void* src, void* dst, long bytes, int B, hipStream_t s);      // dst[b] = src for b < B (bytes % 16 == 0)
+// Streaming sessions: rows of the three workspace buffers that hold the state a session carries from chunk to chunk, and the size of
+// one row of each in 16-byte units (a pool slot is the three rows back to back: s16 + p16 + f16 units)
+struct SessionRows {
+    uint4* style; uint4* prev_in; uint4* prev_fdec;      // w.style_cond [n][768], w.prev_in [n][181][768], w.prev_fdec [n][100][32]
+    int s16, p16, f16;
+};
+// session_gather_kernel: slot slots[i] -> row i of the three buffers, i < n (slots: device table of n slot pointers, 16-byte aligned)
+void launch_session_gather(const float* const* slots, const SessionRows& w, int n, hipStream_t s);
+// session_scatter_kernel: row i of prev_in and prev_fdec (and of style with with_style: the open) -> slot slots[i]
+void launch_session_scatter(float* const* slots, const SessionRows& w, int n, bool with_style, hipStream_t s);
 // multi-scale BSQ of enc_out [B*100,32] -> hist bits [B,181,32], prev_fdec [B,100,32], ms feats [B,180,32]
 void launch_bsq_history(const float* enc_out, uint8_t* hist_bits, float* prev_fdec, float* msfeat, int B, hipStream_t s,
                         int* status = nullptr);    // status |= 2 if an encoder output is not finite

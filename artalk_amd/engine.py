@@ -92,6 +92,26 @@ class ARTAvatarInferEngine:
         pred_motions[..., 104:] *= 0.0
         return pred_motions
 
+    # ------------------------------------------------------------------ live streams (independent sessions)
+    def open_stream(self, style_motion=None):
+        """One live stream (``BitwiseARModel.open_session``) with the engine's style clip unless ``style_motion`` ((50, 106)) is given.
+        Streams join and leave independently: ``stream_step`` takes any subset of them, ``stream.close()`` frees one."""
+        if style_motion is None and self.style_motion is not None:
+            style_motion = self.style_motion[0]
+        return self.ARTalk.open_session(style_motion)
+
+    def stream_step(self, streams, chunks, n_valid=None):
+        """Next 4 seconds of the listed streams: ``chunks`` (n, 64000) -> (n, 100, 106) (with ``n_valid`` also the valid frame counts,
+        ``BitwiseARModel.step_sessions``), with ``fix_pose`` applied and dims 104: zeroed as ``inference`` does.  The Savitzky-Golay
+        smoothing of ``inference`` is NOT applied: its window reaches 4 frames into the future, which a live block does not have yet
+        (a streaming smoother is a separate piece of work)."""
+        res = self.ARTalk.step_sessions(streams, chunks, n_valid=n_valid)
+        pred = res[0] if n_valid is not None else res
+        if self.fix_pose:
+            pred[..., 100:103] *= 0.0
+        pred[..., 104:] *= 0.0
+        return (pred, res[1]) if n_valid is not None else pred
+
     def smooth_motion_savgol(self, motion_codes):
         """``smooth_motion_savgol`` (inference.py:89-95) without the host round trip: Savitzky-Golay (5, 2) on all dims,
         (9, 3) on dims 100:103 of the unsmoothed signal, scipy's mode='interp' edges, as a device kernel (artalk_savgol)."""

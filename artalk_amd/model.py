@@ -81,6 +81,27 @@ class _BasicVAE:
         raise ValueError("Invalid shape of shape_params: {}".format(shape_params.shape))
 
 
+class StreamSession:
+    """One independent stream of ``BitwiseARModel.open_session``: ``id`` (the library's session id, never reused), ``fed`` (real samples
+    fed so far), ``style_motion`` (kept for a recalibration on a step that trips the range guard), ``closed`` and ``close()``.  A session
+    is closed by ``close()``, by a range trip in ``step_sessions`` and by any change of the site scales (``why`` says which)."""
+
+    def __init__(self, model, sid: int, style_motion=None):
+        self._model = model
+        self.id = int(sid)
+        self.fed = 0
+        self.style_motion = style_motion
+        self.closed = False
+        self.why = None
+
+    def close(self):
+        if not self.closed:
+            self._model.close_sessions([self])
+
+    def __repr__(self):
+        return f"StreamSession(id={self.id}, fed={self.fed}, closed={self.closed})"
+
+
 class BitwiseARModel:
     def __init__(self, model_cfg=None, w2v_config: Optional[dict] = None, **kwargs):
         if isinstance(model_cfg, ARTalkConfig):
@@ -109,6 +130,7 @@ class BitwiseARModel:
         self._style_cache = {}      # key -> (style tensor kept alive, (768,) condition on the device)
         self._stream = None      # dedicated HIP stream (hipGraph capture is not allowed on the legacy default stream)
         self._h2d_stream = None  # uploads of host clips (inference_batch)
+        self._sessions = {}      # id -> StreamSession of every open independent session (open_session)
         self.last_aux = {}
 
     # ------------------------------------------------------------------ nn.Module-like surface
@@ -152,6 +174,7 @@ class BitwiseARModel:
         if self._h is not None and self._loaded:      # reloading: derived layouts/packed copies belong to the old weights
             L.artalk_destroy(self._h)
             self._h, self._loaded, self._stream, self._h2d_stream = None, False, None, None
+            self._mark_sessions_closed("the model's weights were reloaded")
         self._style_cache = {}
         if self._h is None:
             h = C.c_void_p()
@@ -243,6 +266,7 @@ class BitwiseARModel:
             self.check_finite = chk
             self.set_precision(prec)
         self._style_cache = {}      # (conditions are keyed by precision only; the style encoder's GEMMs do not change, but stay safe)
+        self._sync_sessions()
         self._calibrations = getattr(self, "_calibrations", 0) + 1
         self._headroom = float(headroom)
         return changed
@@ -299,6 +323,7 @@ class BitwiseARModel:
         if changed:
             self._n_streams = 0                 # the library ended the session
             self._style_cache = {}
+            self._sync_sessions()
         if not isinstance(src, dict) or changed:
             self._headroom = headroom
         return changed
@@ -317,6 +342,7 @@ class BitwiseARModel:
         if capi.lib().artalk_reset_scales(self._h) != capi.OK:
             raise RuntimeError("artalk_reset_scales failed: " + self._err())
         self._headroom = None
+        self._sync_sessions()
 
     def _trip_to_f32(self, what: str):
         """An activation left fp16's range in f16x3 mode: switch to exact-f32 GEMMs for good (a checkpoint that trips once will
@@ -576,6 +602,156 @@ class BitwiseARModel:
         self._n_streams = 0
         if self._h is not None:
             capi.lib().artalk_stream_end(self._h)
+
+    # ------------------------------------------------------------------ independent sessions (join and leave between steps)
+    def _mark_sessions_closed(self, why: str):
+        for sess in self._sessions.values():
+            sess.closed, sess.why = True, why
+        self._sessions = {}
+
+    def _sync_sessions(self):
+        """The library closes sessions by itself in one case only, and then all of them: a change of site scales."""
+        if self._sessions and self._h is not None and capi.lib().artalk_session_count(self._h) == 0:
+            self._mark_sessions_closed("the site scales changed")
+
+    def session_count(self) -> int:
+        """Open sessions of the model (artalk_session_count)."""
+        return int(capi.lib().artalk_session_count(self._h)) if self._h is not None else 0
+
+    def reserve_sessions(self, max_sessions: int):
+        """Pre-allocate the session pool (optional: ``open_session`` grows it on demand, 32 sessions at a time)."""
+        if capi.lib().artalk_sessions_reserve(self._h, int(max_sessions)) != capi.OK:
+            raise RuntimeError("artalk_sessions_reserve failed: " + self._err())
+
+    @torch.no_grad()
+    def open_sessions(self, styles: Sequence[Optional[torch.Tensor]]) -> List[StreamSession]:
+        """Open ``len(styles)`` independent sessions (``None`` = no style clip): style condition + initial history
+        (app/models.py:67-73,86-89), kept in the model's session pool - outside the workspace, so a session lives through batch calls,
+        lockstep streaming, ``style_encode`` and workspace growth, and through ``set_precision`` / ``set_graphs``.  Only a change of the
+        site scales closes it.  Opening (and stepping) sessions ends a lockstep ``stream_begin`` session: that one lives in the workspace."""
+        if not self._loaded:
+            raise RuntimeError("load_state_dict must be called before inference")
+        n = len(styles)
+        assert n > 0, "open_sessions needs at least one session"
+        dev = self._device
+        ids = (C.c_int64 * n)()
+        with torch.cuda.device(dev):
+            if self._stream is None:
+                self._stream = torch.cuda.Stream(device=dev)
+            caller = torch.cuda.current_stream()
+            self._stream.wait_stream(caller)
+            self.stream_end()          # artalk_style_encode refuses to run inside a lockstep session, which the open ends anyway
+            style_t, has = self._style_rows(list(styles), list(range(n)), n)
+            self._stream.wait_stream(caller)
+            rc = capi.lib().artalk_session_open(self._h, n, capi.ptr(style_t), C.cast(has, C.c_void_p) if has is not None else None,
+                                                ids, C.c_void_p(self._stream.cuda_stream))
+            caller.wait_stream(self._stream)
+            if style_t is not None:
+                style_t.record_stream(self._stream)
+        if rc != capi.OK:
+            raise RuntimeError("artalk_session_open failed: " + self._err())
+        out = [StreamSession(self, ids[i], styles[i]) for i in range(n)]
+        for sess in out:
+            self._sessions[sess.id] = sess
+        return out
+
+    def open_session(self, style_motion: Optional[torch.Tensor] = None) -> StreamSession:
+        """One independent streaming session (see ``open_sessions``); feed it with ``step_sessions``."""
+        return self.open_sessions([style_motion])[0]
+
+    def close_sessions(self, sessions: Sequence[StreamSession]):
+        """Free the sessions' pool slots (artalk_session_close); sessions that are closed already are skipped."""
+        live = [s_ for s_ in sessions if not s_.closed]
+        if live and self._h is not None:
+            ids = (C.c_int64 * len(live))(*[s_.id for s_ in live])
+            if capi.lib().artalk_session_close(self._h, ids, len(live)) != capi.OK:
+                raise RuntimeError("artalk_session_close failed: " + self._err())
+        for s_ in live:
+            s_.closed, s_.why = True, "closed"
+            self._sessions.pop(s_.id, None)
+
+    @torch.no_grad()
+    def step_sessions(self, sessions: Sequence[StreamSession], audio_chunks: torch.Tensor, n_valid: Optional[Sequence[int]] = None,
+                      return_aux: bool = False):
+        """Next 4 seconds of the listed sessions - any subset of the open ones, in the caller's order: ``(n, 64000)`` float32 ->
+        ``(n, 100, 106)``, row i for ``sessions[i]``.  A session that is not listed simply does not advance.  End of a clip as in
+        ``stream_chunk``: zero-pad the last chunk and pass ``n_valid``; the call then returns ``(codes, valid frame counts)``.  With
+        ``return_aux`` the chunk's AR bits and the new history bits, ``(n, 181, 32)`` uint8 each, are appended to the result.
+
+        The step is the chunk step of lockstep streaming for n streams (same workspace rows, same captured graphs), between one gather
+        and one scatter of the sessions' state.  A closed session, or one listed twice, raises before anything runs.
+
+        Range trip in f16x3 mode (status bit 3): ``stream_chunk``'s policy on this step's chunks and styles - with ``auto_calibrate``
+        the site scales are recalibrated on them and the model stays in f16x3 mode when sites changed, otherwise (or when nothing could
+        be lowered) it switches to f32 for good.  Either way EVERY session of the model is closed (the stepped ones hold the damaged
+        chunk, and a session never mixes scales) and this raises ``RuntimeError``: open the sessions again."""
+        n = len(sessions)
+        assert n > 0, "step_sessions needs at least one session"
+        for sess in sessions:
+            if sess.closed:
+                raise RuntimeError(f"session {sess.id} is closed ({sess.why}); open it again")
+        assert len({sess.id for sess in sessions}) == n, "a session is listed twice"
+        assert tuple(audio_chunks.shape) == (n, self.cfg.samples_per_chunk), f"expected ({n}, {self.cfg.samples_per_chunk}) samples"
+        dev = self._device
+        ids = (C.c_int64 * n)(*[sess.id for sess in sessions])
+        with torch.cuda.device(dev):
+            x = audio_chunks.to(device=dev, dtype=torch.float32).contiguous()
+            out = torch.empty(n, 100, self.cfg.motion_dim, dtype=torch.float32, device=dev)
+            bits = hist = None
+            if return_aux:
+                bits = torch.empty(n, 181, self.cfg.code_dim, dtype=torch.uint8, device=dev)
+                hist = torch.empty(n, 181, self.cfg.code_dim, dtype=torch.uint8, device=dev)
+            if self._stream is None:      # (set_cu_mask(None) dropped the masked stream; the sessions live on)
+                self._stream = torch.cuda.Stream(device=dev)
+            caller = torch.cuda.current_stream()
+            self._stream.wait_stream(caller)
+            rc = capi.lib().artalk_session_step(self._h, ids, n, capi.ptr(x), x.stride(0), capi.ptr(out), out.stride(0),
+                                                capi.ptr(bits), capi.ptr(hist), C.c_void_p(self._stream.cuda_stream))
+            caller.wait_stream(self._stream)
+            for t in (x, out, bits, hist):
+                if t is not None:
+                    t.record_stream(self._stream)
+        if rc != capi.OK:
+            msg = self._err()
+            self._sync_sessions()
+            raise RuntimeError("artalk_session_step failed: " + msg)
+        self._n_streams = 0             # the step used the workspace rows a lockstep session lives in
+        if self._precision == "f16x3" and self.check_finite and self.status() != 0:
+            styles = [sess.style_motion for sess in sessions]
+            changed = 0
+            if self.auto_calibrate:
+                try:
+                    changed = self.calibrate([x[b] for b in range(n)], styles)
+                except RuntimeError:
+                    changed = 0
+            every = list(self._sessions.values())
+            self.close_sessions(every)
+            for sess in every:
+                sess.why = "an activation left fp16's range during a session step"
+            if changed > 0:
+                raise RuntimeError(f"artalk_amd: an activation left fp16's range during a session step; recalibrated {changed} site "
+                                   "scale(s) on that step and the model stays in f16x3 mode - open the sessions again")
+            self._trip_to_f32("session step")
+            raise RuntimeError("artalk_amd: an activation left fp16's range during a session step; the model is now in f32 mode - "
+                               "open the sessions again")
+        res = [out]
+        if n_valid is not None:
+            frames = []
+            spc = self.cfg.samples_per_chunk
+            for b, sess in enumerate(sessions):
+                before = sess.fed
+                sess.fed = before + int(n_valid[b])
+                if int(n_valid[b]) <= 0:
+                    frames.append(0)
+                    continue
+                frames.append(max(0, min(100, self.seq_length(sess.fed) - 100 * (before // spc))))
+            res.append(frames)
+        else:
+            for sess in sessions:
+                sess.fed += self.cfg.samples_per_chunk
+        if return_aux:
+            res += [bits, hist]
+        return res[0] if len(res) == 1 else tuple(res)
 
     # ------------------------------------------------------------------ geometry of app/models.py:66,78-80
     def seq_length(self, n_samples: int) -> int:

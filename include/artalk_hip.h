@@ -106,6 +106,46 @@ int artalk_stream_begin(artalk_model* m, int B, const float* style_motion_dev, c
 int artalk_stream_chunk(artalk_model* m, const float* audio_dev, int64_t chunk_stride, float* out_motion_dev, int64_t out_stride,
                         void* stream);
 
+/* Independent streaming sessions: the same chunk step for streams that join and leave between steps (a server with live users).
+ * What a stream carries from chunk to chunk - style condition [768], history tokens [181][768], decoder features of the previous
+ * chunk [100][32], fp32 in every precision mode: 571 904 bytes - lives in a session pool owned by the model, outside the workspace:
+ * device blocks of 32 slots that are never moved or freed before artalk_destroy.  A step gathers the listed sessions into workspace
+ * rows 0..n-1 (one copy kernel), runs there what artalk_stream_chunk runs for n streams - the same rows, hence the same captured
+ * graphs and the same bits - and scatters the new history back (one copy kernel); nothing synchronises.  Between library calls the
+ * workspace holds nothing a session needs.
+ *   Lifetime: sessions survive artalk_infer, artalk_style_encode, artalk_stream_begin / _chunk / _end and workspace growth
+ * (artalk_reserve, a larger call); artalk_set_precision (the state is fp32 and every mode reads it the same way; a session may change
+ * mode between steps); artalk_set_graphs, artalk_set_cu_mask, the audit, tap and profiling switches (while one of them forbids
+ * graphs, a step runs eagerly, by the rule of every other call).  A change of site scales - artalk_calibrate, artalk_set_site_scales
+ * or artalk_reset_scales that changed an exponent - closes ALL sessions (a session never mixes exponents): the next artalk_session_step
+ * with such an id fails with ARTALK_ESTATE and a message that says so.  In the other direction artalk_session_open and
+ * artalk_session_step end a lockstep session (artalk_stream_begin), as artalk_infer does: they rewrite the workspace rows it lives in.
+ * Calls for one model are ordered by the caller, as for artalk_infer (a step reads what the previous step of the same session wrote).
+ *
+ * artalk_sessions_reserve  allocates pool blocks for at least max_sessions sessions (optional: artalk_session_open grows the pool on
+ *                          demand, one hipMalloc per 32 sessions).
+ * artalk_session_open      opens n sessions: style arguments and validation of artalk_stream_begin (style_motion_dev [n][50][106] or
+ *                          NULL, has_style host [n] with flags 0, 1, 2); computes style condition and initial history in the workspace and
+ *                          stores them in n free slots.  ids_out host [n] receives the ids: positive, never reused during the model's
+ *                          life (a freed slot is reused under a new id).  Publishes a status word (a ticket) like artalk_stream_begin.
+ * artalk_session_step      the next 64000 samples of the n listed sessions, any subset of the open ones in any order: row i of audio_dev
+ *                          [n][chunk_stride] and of every output belongs to ids[i].  out_motion_dev [n][out_stride] receives 100 x 106
+ *                          codes per session; out_bits_dev (optional) [n][181][32] u8 this chunk's AR decisions, out_hist_bits_dev
+ *                          (optional) [n][181][32] u8 the bits of the new history.  The status word is reset at the start of every step
+ *                          and published at its end: each step has its own ticket.  The workspace grows when n exceeds it.  ARTALK_EINVAL
+ *                          for n <= 0, an id that is not open (never issued, closed) or listed twice: nothing is enqueued, no session
+ *                          changes.  The caller zero-pads the last chunk of a clip, as for artalk_stream_chunk.
+ * artalk_session_close     frees the slots of the n listed sessions (host bookkeeping only; ordered by the caller against the steps
+ *                          that still use them).  ARTALK_EINVAL, with nothing changed, for an id that is not open or listed twice; an id
+ *                          that a scale change closed is accepted.
+ * artalk_session_count     number of open sessions. */
+int artalk_sessions_reserve(artalk_model* m, int max_sessions);
+int artalk_session_open(artalk_model* m, int n, const float* style_motion_dev, const uint8_t* has_style, int64_t* ids_out, void* stream);
+int artalk_session_step(artalk_model* m, const int64_t* ids, int n, const float* audio_dev, int64_t chunk_stride, float* out_motion_dev,
+                        int64_t out_stride, uint8_t* out_bits_dev, uint8_t* out_hist_bits_dev, void* stream);
+int artalk_session_close(artalk_model* m, const int64_t* ids, int n);
+int artalk_session_count(const artalk_model* m);
+
 /* FLAME linear blend skinning: the consumer behind BITWISE_VAE.get_flame_verts (bitwise_vae.py:43-57) ->
  * FLAMEModel.forward(no_lmks=True) (app/flame_model/FLAME.py:117-142) -> lbs (app/flame_model/lbs.py:142-233).  Host arrays in
  * the layouts of the reference's buffers: v_template [V][3], shapedirs [V][3][NB], posedirs_t [V*3][36] (the reference buffer
