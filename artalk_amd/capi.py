@@ -25,6 +25,7 @@ SYMBOLS = [
     "artalk_op_bsq_history",
     "artalk_sessions_reserve", "artalk_session_open", "artalk_session_step", "artalk_session_close", "artalk_session_count",
     "artalk_op_pack_split_ex", "artalk_op_layernorm_ex", "artalk_op_gemm_f16s_packed_ex", "artalk_op_gemm_f16s_ex", "artalk_op_attention_ex", "artalk_op_w2v_front_ex", "artalk_op_pool_silu_ex", "artalk_op_posconv_p8_ex",
+    "artalk_op_bsq_history_ex", "artalk_op_ar_bits_next", "artalk_op_vq_embed", "artalk_op_ar_begin", "artalk_op_dec_input", "artalk_op_dec_finish", "artalk_op_enc_input_zero", "artalk_op_style_input", "artalk_op_add_row", "artalk_op_style_finish", "artalk_op_broadcast16", "artalk_op_session_gather", "artalk_op_session_scatter", "artalk_op_absmax",
 ]
 
 
@@ -231,6 +232,24 @@ def lib() -> C.CDLL:
         L.artalk_op_pool_silu_ex.restype = i32
         L.artalk_op_posconv_p8_ex.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
         L.artalk_op_posconv_p8_ex.restype = i32
+    if hasattr(L, "artalk_op_ar_bits_next"):      # (an older build loaded through ARTALK_LIB lacks the single-kernel glue entry points)
+        for name, args in (
+                ("bsq_history_ex", [vp, vp, vp, vp, i32, vp, vp]),
+                ("ar_bits_next", [vp, vp, vp, vp, i32, i32, vp, vp]),
+                ("vq_embed", [vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp]),
+                ("ar_begin", [vp, vp, vp, vp, i32, vp]),
+                ("dec_input", [vp, vp, vp, vp, vp, i32, vp]),
+                ("dec_finish", [vp, vp, vp, vp, vp, i64, i32, vp, i32, vp, vp]),
+                ("enc_input_zero", [vp, vp, vp, vp, i32, vp]),
+                ("style_input", [vp, vp, vp, vp, i32, vp]),
+                ("add_row", [vp, vp, i32, i32, vp]),
+                ("style_finish", [vp, vp, vp, vp, vp, vp, i32, vp, i64, vp]),
+                ("broadcast16", [vp, vp, i64, i32, vp]),
+                ("session_gather", [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+                ("session_scatter", [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+                ("absmax", [vp, i32, i32, i64, i32, i32, i32, i32, vp, vp])):
+            f = getattr(L, "artalk_op_" + name)
+            f.argtypes, f.restype = args, i32
     _lib = L
     return L
 

@@ -2368,9 +2368,106 @@ int artalk_op_posconv_p8_ex(const float* X, const void* Wp, const float* bias, c
 }
 
 int artalk_op_bsq_history(const float* enc_out, uint8_t* hist_bits, float* prev_fdec, float* msfeat, int B, void* stream) {
+    return artalk_op_bsq_history_ex(enc_out, hist_bits, prev_fdec, msfeat, B, nullptr, stream);
+}
+int artalk_op_bsq_history_ex(const float* enc_out, uint8_t* hist_bits, float* prev_fdec, float* msfeat, int B, int* status_dev, void* stream) {
     if (!enc_out || !hist_bits || !prev_fdec || !msfeat || B <= 0) return ARTALK_EINVAL;
     if (init_ms_tables() != 0) return ARTALK_EHIP;
-    launch_bsq_history(enc_out, hist_bits, prev_fdec, msfeat, B, (hipStream_t)stream);
+    launch_bsq_history(enc_out, hist_bits, prev_fdec, msfeat, B, (hipStream_t)stream, status_dev);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+
+// ---- the glue kernels of ar_glue.hip, one launch each (tests/test_glue_ops_gpu.py); the sizes the kernels fix (768, 181, 100, 32, 106 ->
+// 128, 50) are the model's
+int artalk_op_ar_bits_next(const float* logits, uint8_t* bits, float* fhat, float* nextfeat, int B, int level, int* status_dev, void* stream) {
+    if (!logits || !bits || B <= 0 || level < 0 || level > 4 || (level < 4 && (!fhat || !nextfeat))) return ARTALK_EINVAL;
+    if (init_ms_tables() != 0) return ARTALK_EHIP;
+    launch_ar_bits_next(logits, bits, fhat, nextfeat, B, level, (hipStream_t)stream, status_dev);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+int artalk_op_vq_embed(const float* feat, int n, const float* We, const float* be, const float* pos, float* X, int xrows, int xoff,
+                       const float* style_cond, const float* pos0, int B, void* stream) {
+    if (!feat || !We || !be || !pos || !X || n <= 0 || B <= 0 || xoff < 0 || xrows < xoff + n) return ARTALK_EINVAL;
+    if (style_cond && (!pos0 || xoff < 1)) return ARTALK_EINVAL;      // the style row is row 0 of each clip's block
+    if (((uintptr_t)We) & 15) return ARTALK_EINVAL;                     // weight rows are read as float4
+    launch_vq_embed(feat, n, We, be, pos, X, xrows, xoff, style_cond, pos0, B, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+int artalk_op_ar_begin(const float* style_cond, const float* lvlpos, float* x0, float* fhat, int B, void* stream) {
+    if (!style_cond || !lvlpos || !x0 || !fhat || B <= 0) return ARTALK_EINVAL;
+    launch_ar_begin(style_cond, lvlpos, x0, fhat, B, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+int artalk_op_dec_input(const float* prev_fdec, const float* fhat, const uint8_t* bits, const float* dpos, float* X, int B, void* stream) {
+    if (!prev_fdec || !fhat || !bits || !dpos || !X || B <= 0) return ARTALK_EINVAL;
+    if (init_ms_tables() != 0) return ARTALK_EHIP;
+    launch_dec_input(prev_fdec, fhat, bits, dpos, X, B, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+int artalk_op_dec_finish(const float* dec, const float* mean, const float* std_, const float* epos, float* out, int64_t out_bstride,
+                         int chunk, float* E, int B, int* status_dev, void* stream) {
+    if (!dec || !mean || !std_ || !epos || !out || !E || B <= 0 || chunk < 0) return ARTALK_EINVAL;
+    if (out_bstride < ((int64_t)chunk + 1) * 100 * 106) return ARTALK_EINVAL;      // a clip's rows would run into the next clip's
+    launch_dec_finish(dec, mean, std_, epos, out, (long)out_bstride, chunk, E, B, (hipStream_t)stream, status_dev);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+int artalk_op_enc_input_zero(const float* mean, const float* std_, const float* epos, float* E, int B, void* stream) {
+    if (!mean || !std_ || !epos || !E || B <= 0) return ARTALK_EINVAL;
+    launch_enc_input_zero(mean, std_, epos, E, B, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+int artalk_op_style_input(const float* motion, const float* mean, const float* std_, float* X, int B, void* stream) {
+    if (!motion || !mean || !std_ || !X || B <= 0) return ARTALK_EINVAL;
+    launch_style_input(motion, mean, std_, X, B, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+int artalk_op_add_row(float* X, const float* v, int M, int D, void* stream) {
+    if (!X || !v || M <= 0 || D <= 0) return ARTALK_EINVAL;
+    launch_add_row(X, v, M, D, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+int artalk_op_style_finish(const float* feat, const float* Ws, const float* bs, const float* null_cond, const uint8_t* has_style,
+                           float* style_cond, int B, const float* cached, int64_t cached_stride, void* stream) {
+    if (!feat || !Ws || !bs || !null_cond || !style_cond || B <= 0) return ARTALK_EINVAL;
+    if (cached && cached_stride < 768) return ARTALK_EINVAL;
+    launch_style_finish(feat, Ws, bs, null_cond, has_style, style_cond, B, (hipStream_t)stream, cached, (long)cached_stride);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+int artalk_op_broadcast16(const void* src, void* dst, int64_t bytes, int B, void* stream) {
+    if (!src || !dst || B <= 0 || bytes <= 0 || bytes % 16 != 0 || bytes / 16 > 0x7fffffff) return ARTALK_EINVAL;
+    if (((uintptr_t)src | (uintptr_t)dst) & 15) return ARTALK_EINVAL;
+    launch_broadcast16(src, dst, (long)bytes, B, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+static bool op_session_rows(float* style, float* prev_in, float* prev_fdec, int s16, int p16, int f16, SessionRows* w) {
+    if (!style || !prev_in || !prev_fdec || s16 <= 0 || p16 <= 0 || f16 <= 0) return false;
+    if (((uintptr_t)style | (uintptr_t)prev_in | (uintptr_t)prev_fdec) & 15) return false;
+    if ((int64_t)s16 + p16 + f16 > 0x7fffffff) return false;
+    w->style = reinterpret_cast<uint4*>(style); w->prev_in = reinterpret_cast<uint4*>(prev_in); w->prev_fdec = reinterpret_cast<uint4*>(prev_fdec);
+    w->s16 = s16; w->p16 = p16; w->f16 = f16;
+    return true;
+}
+int artalk_op_session_gather(const float* const* slots_dev, float* style, float* prev_in, float* prev_fdec, int s16, int p16, int f16, int n,
+                             void* stream) {
+    SessionRows w;
+    if (!slots_dev || n <= 0 || !op_session_rows(style, prev_in, prev_fdec, s16, p16, f16, &w)) return ARTALK_EINVAL;
+    launch_session_gather(slots_dev, w, n, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+int artalk_op_session_scatter(float* const* slots_dev, const float* style, const float* prev_in, const float* prev_fdec, int s16, int p16,
+                              int f16, int n, int with_style, void* stream) {
+    SessionRows w;      // (the scatter kernel only reads the three buffers)
+    if (!slots_dev || n <= 0 ||
+        !op_session_rows(const_cast<float*>(style), const_cast<float*>(prev_in), const_cast<float*>(prev_fdec), s16, p16, f16, &w))
+        return ARTALK_EINVAL;
+    launch_session_scatter(slots_dev, w, n, with_style != 0, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+int artalk_op_absmax(const float* buf, int rows, int cols, int64_t ld, int is_p8, int p8_exp, int junk_period, int junk_from,
+                     unsigned int* slot_dev, void* stream) {
+    if (!buf || !slot_dev || rows < 0 || cols <= 0 || cols % 8 != 0 || ld < cols || !op_exp_ok(p8_exp)) return ARTALK_EINVAL;
+    if (junk_period < 0 || junk_from < 0 || (junk_period > 0 && junk_from > junk_period)) return ARTALK_EINVAL;
+    launch_absmax(buf, rows, cols, (long)ld, is_p8 ? 1 : 0, slot_dev, (hipStream_t)stream, junk_period, junk_from, p8_exp);
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
 }
 

@@ -362,6 +362,55 @@ int artalk_op_posconv_p8_ex(const float* X, const void* Wp, const float* bias, c
                             int act, int a_exp, int* status_dev, void* stream);
 /* enc_out [B][100][32] -> hist_bits [B][181][32] u8, prev_fdec [B][100][32], msfeat [B][180][32] */
 int artalk_op_bsq_history(const float* enc_out, uint8_t* hist_bits, float* prev_fdec, float* msfeat, int B, void* stream);
+/* the same with the status word: bit 1 of *status_dev (device int, may be NULL) is raised when an element of enc_out is NaN/Inf */
+int artalk_op_bsq_history_ex(const float* enc_out, uint8_t* hist_bits, float* prev_fdec, float* msfeat, int B, int* status_dev,
+                             void* stream);
+/* ---- the small kernels between the GEMMs of the AR / VAE / style stages, one launch each (tests/test_glue_ops_gpu.py) ----
+ * Device pointers; sizes are the model's: 181 tokens of 32 bits per clip at levels of 1, 5, 25, 50, 100 tokens, embedding width 768,
+ * 106 motion dims padded to 128 columns, 50 style frames.  NULL required pointers, B <= 0, n <= 0 and the cases named below:
+ * ARTALK_EINVAL before the device is touched. */
+/* logits [B * pn[level]][64] -> bits[b][off[level] + i][c] = logit pair c of token i has l1 > l0 (a tie gives 0); level < 4: fhat [B][100][32]
+ * += the level's +-1/sqrt(32) upsampled to 100 frames, nextfeat [B][pn[level + 1]][32] = fhat area-pooled; level 4 leaves both alone (they
+ * may be NULL).  Bit 0 of *status_dev (may be NULL) is raised for a NaN/Inf logit.  level outside 0..4: ARTALK_EINVAL. */
+int artalk_op_ar_bits_next(const float* logits, uint8_t* bits, float* fhat, float* nextfeat, int B, int level, int* status_dev,
+                           void* stream);
+/* X[b * xrows + xoff + i][:] = We [768][32] . feat[b][i][:] + be + pos[i][:] for i < n; with style_cond: X[b * xrows][:] = style_cond[b] + pos0
+ * (then xoff >= 1).  xrows >= xoff + n; We 16-byte aligned. */
+int artalk_op_vq_embed(const float* feat, int n, const float* We, const float* be, const float* pos, float* X, int xrows, int xoff,
+                       const float* style_cond, const float* pos0, int B, void* stream);
+/* x0[b][:768] = style_cond[b] + lvlpos[:768]; fhat [B][100][32] = 0 */
+int artalk_op_ar_begin(const float* style_cond, const float* lvlpos, float* x0, float* fhat, int B, void* stream);
+/* X [B][200][32]: rows t < 100 = prev_fdec[b][t] + dpos[t]; rows 100 + t = fhat[b][t] + (+-1/sqrt(32) of bits[b][81 + t]) + dpos[100 + t] */
+int artalk_op_dec_input(const float* prev_fdec, const float* fhat, const uint8_t* bits, const float* dpos, float* X, int B, void* stream);
+/* m = dec[b][100 + t][:106] * std + mean -> out[b * out_bstride + (chunk * 100 + t) * 106 ..]; E [B][100][128] = (m - mean) / std + epos[t], columns
+ * >= 106 zero.  Rows t < 100 of dec are not read.  Bit 2 of *status_dev (may be NULL) for a NaN/Inf m.  out_bstride (floats) must hold
+ * chunk + 1 chunks. */
+int artalk_op_dec_finish(const float* dec, const float* mean, const float* std_, const float* epos, float* out, int64_t out_bstride,
+                         int chunk, float* E, int B, int* status_dev, void* stream);
+/* E [B][100][128] = (0 - mean) / std + epos[t], columns >= 106 zero: the re-encoder input of the all-zero initial motion */
+int artalk_op_enc_input_zero(const float* mean, const float* std_, const float* epos, float* E, int B, void* stream);
+/* X [B * 50][128] = (motion [B * 50][106] - mean) / std, columns >= 106 zero */
+int artalk_op_style_input(const float* motion, const float* mean, const float* std_, float* X, int B, void* stream);
+/* X [M][D] += v [D] on every row */
+int artalk_op_add_row(float* X, const float* v, int M, int D, void* stream);
+/* style_cond [B][768]: has_style[b] == 1: 1.1 * (Ws [768][128] . mean over the 50 frames of feat [B * 50][128] + bs) - 0.1 * null_cond; == 2: a copy of
+ * cached[b * cached_stride ..] (cached_stride >= 768 floats); else, or with has_style NULL: null_cond */
+int artalk_op_style_finish(const float* feat, const float* Ws, const float* bs, const float* null_cond, const uint8_t* has_style,
+                           float* style_cond, int B, const float* cached, int64_t cached_stride, void* stream);
+/* dst[b * bytes ..] = src[0 .. bytes) for b < B; bytes % 16 == 0 and both pointers 16-byte aligned, else ARTALK_EINVAL */
+int artalk_op_broadcast16(const void* src, void* dst, int64_t bytes, int B, void* stream);
+/* Session pool moves.  A slot is [style | prev_in | prev_fdec] of s16 + p16 + f16 16-byte units; slots_dev: device table of n slot pointers.
+ * gather: slot slots_dev[i] -> row i of the three buffers (rows of s16, p16, f16 units); scatter: the way back, the style field only
+ * with with_style != 0.  All pointers 16-byte aligned, unit counts > 0. */
+int artalk_op_session_gather(const float* const* slots_dev, float* style, float* prev_in, float* prev_fdec, int s16, int p16, int f16, int n,
+                             void* stream);
+int artalk_op_session_scatter(float* const* slots_dev, const float* style, const float* prev_in, const float* prev_fdec, int s16, int p16,
+                              int f16, int n, int with_style, void* stream);
+/* *slot_dev = max(*slot_dev, bit pattern of max |x|) over rows x cols of an fp32 buffer of row pitch ld floats, or (is_p8) of the hi halves
+ * of a P8 buffer times 2^-p8_exp; a NaN counts as +inf; rows r with r % junk_period >= junk_from (junk_period > 0) are skipped; rows == 0
+ * changes nothing.  cols % 8 != 0, ld < cols or p8_exp outside [-8, 4]: ARTALK_EINVAL.  What artalk_calibrate reads its maxima with. */
+int artalk_op_absmax(const float* buf, int rows, int cols, int64_t ld, int is_p8, int p8_exp, int junk_period, int junk_from,
+                     unsigned int* slot_dev, void* stream);
 
 #ifdef __cplusplus
 }
