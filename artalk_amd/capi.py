@@ -26,6 +26,7 @@ SYMBOLS = [
     "artalk_sessions_reserve", "artalk_session_open", "artalk_session_step", "artalk_session_close", "artalk_session_count",
     "artalk_op_pack_split_ex", "artalk_op_layernorm_ex", "artalk_op_gemm_f16s_packed_ex", "artalk_op_gemm_f16s_ex", "artalk_op_attention_ex", "artalk_op_w2v_front_ex", "artalk_op_pool_silu_ex", "artalk_op_posconv_p8_ex",
     "artalk_op_bsq_history_ex", "artalk_op_ar_bits_next", "artalk_op_vq_embed", "artalk_op_ar_begin", "artalk_op_dec_input", "artalk_op_dec_finish", "artalk_op_enc_input_zero", "artalk_op_style_input", "artalk_op_add_row", "artalk_op_style_finish", "artalk_op_broadcast16", "artalk_op_session_gather", "artalk_op_session_scatter", "artalk_op_absmax",
+    "artalk_op_gemm_rows", "artalk_op_layernorm_rows", "artalk_op_attention_rows", "artalk_op_gemm_rows_layout", "artalk_op_rows_dry_run",
 ]
 
 
@@ -43,6 +44,40 @@ class ArtalkConfigStruct(C.Structure):
         ("style_dim", C.c_int32), ("style_heads", C.c_int32), ("style_layers", C.c_int32), ("style_ffn", C.c_int32),
         ("style_len", C.c_int32),
     ]
+
+
+ROWMAP_IDENTITY = (2 ** 31 - 1, 0, 0)      # row(m) = (m // rpb) * bstride + off + m % rpb; rpb = INT32_MAX: row(m) = m
+
+
+class GemmRowsArgs(C.Structure):
+    """artalk_op_gemm_rows_args of include/artalk_hip.h (field for field).  A new object holds identity maps, no forced configuration,
+    no split and the default exponents; sizes (*_elems) count 4-byte elements from the pointer of their buffer."""
+    _fields_ = [
+        ("mode", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("act", C.c_int32),
+        ("A", C.c_void_p), ("lda", C.c_int64), ("a_elems", C.c_int64), ("a_exp", C.c_int32),
+        ("W", C.c_void_p), ("ldw", C.c_int64), ("w_elems", C.c_int64),
+        ("bias", C.c_void_p), ("bias_elems", C.c_int64),
+        ("C", C.c_void_p), ("ldc", C.c_int64), ("c_elems", C.c_int64), ("cmap", C.c_int32 * 3),
+        ("gate", C.c_void_p), ("ldg", C.c_int64), ("gate_elems", C.c_int64), ("gmap", C.c_int32 * 3),
+        ("R", C.c_void_p), ("ldr", C.c_int64), ("r_elems", C.c_int64),
+        ("c_p8", C.c_int32), ("c_exp", C.c_int32),
+        ("force_cfg", C.c_int32), ("splitk", C.c_int32),
+        ("ngrp", C.c_int32), ("grpW", C.c_int64), ("grpB", C.c_int64), ("grpC", C.c_int64),
+        ("status_dev", C.c_void_p),
+        ("ln_Y", C.c_void_p), ("ln_ldy", C.c_int64), ("ln_y_elems", C.c_int64),
+        ("ln_scale", C.c_void_p), ("ln_shift", C.c_void_p), ("ln_ldm", C.c_int64), ("ln_mod_elems", C.c_int64), ("ln_mmap", C.c_int32 * 3),
+        ("ln_eps", C.c_float), ("ln_out_p8", C.c_int32), ("ln_p8_exp", C.c_int32),
+        ("used_cfg", C.POINTER(C.c_int32)), ("used_splitk", C.POINTER(C.c_int32)), ("fused_ln", C.POINTER(C.c_int32)),
+    ]
+
+    def __init__(self, **kw):
+        super().__init__()
+        self.a_exp = self.c_exp = self.ln_p8_exp = 4
+        self.force_cfg, self.splitk, self.ln_eps = -1, 1, 1e-6
+        for name in ("cmap", "gmap", "ln_mmap"):
+            setattr(self, name, (C.c_int32 * 3)(*ROWMAP_IDENTITY))
+        for k, v in kw.items():
+            setattr(self, k, (C.c_int32 * 3)(*v) if k in ("cmap", "gmap", "ln_mmap") else v)
 
 
 def config_struct(cfg: ARTalkConfig) -> ArtalkConfigStruct:
@@ -250,6 +285,19 @@ def lib() -> C.CDLL:
                 ("absmax", [vp, i32, i32, i64, i32, i32, i32, i32, vp, vp])):
             f = getattr(L, "artalk_op_" + name)
             f.argtypes, f.restype = args, i32
+    if hasattr(L, "artalk_op_gemm_rows"):      # (an older build loaded through ARTALK_LIB lacks the row-mapped entry points)
+        L.artalk_op_gemm_rows.argtypes = [C.POINTER(GemmRowsArgs), vp]
+        L.artalk_op_gemm_rows.restype = i32
+        L.artalk_op_layernorm_rows.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, f32, i32, i32, i32, i32, vp,
+                                               i64, i64, i64, C.POINTER(C.c_int32), i64, i64, i64, vp]
+        L.artalk_op_layernorm_rows.restype = i32
+        L.artalk_op_attention_rows.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp, i32, i32, i32, i32, vp,
+                                               i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, vp]
+        L.artalk_op_attention_rows.restype = i32
+        L.artalk_op_gemm_rows_layout.argtypes = [C.POINTER(i64), i32]
+        L.artalk_op_gemm_rows_layout.restype = i32
+        L.artalk_op_rows_dry_run.argtypes = [i32]
+        L.artalk_op_rows_dry_run.restype = i32
     _lib = L
     return L
 

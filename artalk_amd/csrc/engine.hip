@@ -2316,6 +2316,246 @@ int artalk_op_attention_ex(const float* Q, const float* K, const float* V, float
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
 }
 
+// ---- the launchers in the forms the AR / VAE / style bodies use them (include/artalk_hip.h).  Everything is checked on the host first:
+// a launch is made only when every row, column group and batch it addresses lies inside the sizes the caller states.
+static bool op_map_ok(const int32_t* m) { return m[0] > 0 && m[1] >= 0 && m[2] >= 0; }
+// the largest row a map sends rows 0 .. M-1 to (the last row of the last batch, or of the one before it when the last is short)
+static int64_t op_map_last(const int32_t* m, int M) {
+    if (m[0] == INT_MAX) return (int64_t)M - 1;
+    const int64_t rpb = m[0], bs = m[1], off = m[2], qb = (M - 1) / rpb, rem = (M - 1) % rpb;
+    int64_t last = qb * bs + off + rem;
+    if (qb > 0) last = std::max(last, (qb - 1) * bs + off + rpb - 1);
+    return last;
+}
+static bool op_al(const void* p, int bytes) { return ((uintptr_t)p & (uintptr_t)(bytes - 1)) == 0; }
+// rows 0 .. last of pitch ld, `width` elements each, inside `elems` (all in 4-byte elements)
+static bool op_fits(int64_t last, int64_t ld, int64_t width, int64_t elems) {
+    return last >= 0 && ld >= 0 && width > 0 && last <= INT_MAX && last * ld + width <= elems;
+}
+// two buffers of na / nb 4-byte elements share a byte
+static bool op_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a && b && a0 < b0 + (uintptr_t)nb * 4 && b0 < a0 + (uintptr_t)na * 4;
+}
+// distance in elements between the scale and shift rows of one modulation table (-1: not a whole number of elements)
+static int64_t op_mod_gap(const float* scale, const float* shift) {
+    const uintptr_t a = (uintptr_t)scale, b = (uintptr_t)shift, d = a < b ? b - a : a - b;
+    return d % 4 == 0 ? (int64_t)(d / 4) : -1;
+}
+// artalk_op_rows_dry_run: the three entry points below return ARTALK_OK where they would touch the device
+static thread_local bool g_rows_dry_run = false;
+int artalk_op_rows_dry_run(int enable) { g_rows_dry_run = enable != 0; return ARTALK_OK; }
+
+#define ROWS_FIELD(f) (int64_t)offsetof(artalk_op_gemm_rows_args, f)
+int artalk_op_gemm_rows_layout(int64_t* out, int n) {
+    static const int64_t lay[] = {
+        (int64_t)sizeof(artalk_op_gemm_rows_args),
+        ROWS_FIELD(mode), ROWS_FIELD(M), ROWS_FIELD(N), ROWS_FIELD(K), ROWS_FIELD(act), ROWS_FIELD(A), ROWS_FIELD(lda), ROWS_FIELD(a_elems),
+        ROWS_FIELD(a_exp), ROWS_FIELD(W), ROWS_FIELD(ldw), ROWS_FIELD(w_elems), ROWS_FIELD(bias), ROWS_FIELD(bias_elems), ROWS_FIELD(C),
+        ROWS_FIELD(ldc), ROWS_FIELD(c_elems), ROWS_FIELD(cmap), ROWS_FIELD(gate), ROWS_FIELD(ldg), ROWS_FIELD(gate_elems), ROWS_FIELD(gmap),
+        ROWS_FIELD(R), ROWS_FIELD(ldr), ROWS_FIELD(r_elems), ROWS_FIELD(c_p8), ROWS_FIELD(c_exp), ROWS_FIELD(force_cfg), ROWS_FIELD(splitk),
+        ROWS_FIELD(ngrp), ROWS_FIELD(grpW), ROWS_FIELD(grpB), ROWS_FIELD(grpC), ROWS_FIELD(status_dev), ROWS_FIELD(ln_Y), ROWS_FIELD(ln_ldy),
+        ROWS_FIELD(ln_y_elems), ROWS_FIELD(ln_scale), ROWS_FIELD(ln_shift), ROWS_FIELD(ln_ldm), ROWS_FIELD(ln_mod_elems), ROWS_FIELD(ln_mmap),
+        ROWS_FIELD(ln_eps), ROWS_FIELD(ln_out_p8), ROWS_FIELD(ln_p8_exp), ROWS_FIELD(used_cfg), ROWS_FIELD(used_splitk), ROWS_FIELD(fused_ln)};
+    const int total = (int)(sizeof(lay) / sizeof(lay[0]));
+    if (!out || n < total) return ARTALK_EINVAL;
+    for (int i = 0; i < total; ++i) out[i] = lay[i];
+    return total;
+}
+#undef ROWS_FIELD
+
+int artalk_op_gemm_rows(const artalk_op_gemm_rows_args* a, void* stream) {
+    if (!a || !a->A || !a->W || !a->C || a->mode < 0 || a->mode > 2) return ARTALK_EINVAL;
+    const int M = a->M, N = a->N, K = a->K;
+    if (M <= 0 || N <= 0 || K <= 0 || K % 32 != 0 || a->act < 0 || a->act > 3) return ARTALK_EINVAL;
+    if (!op_exp_ok(a->a_exp) || !op_exp_ok(a->c_exp) || !op_exp_ok(a->ln_p8_exp)) return ARTALK_EINVAL;
+    if (!op_map_ok(a->cmap) || !op_map_ok(a->gmap) || !op_map_ok(a->ln_mmap)) return ARTALK_EINVAL;
+    if (a->lda <= 0 || a->ldw < K || a->ldc <= 0) return ARTALK_EINVAL;
+    const bool p8 = a->mode == 1, ident_c = a->cmap[0] == INT_MAX;
+    if (a->c_p8 && (!p8 || N % 8 != 0 || a->ldc % 8 != 0)) return ARTALK_EINVAL;
+    // alignment: A and W rows are read as 16-byte vectors (P8 rows as 32-byte groups); the f16x3 kernels take the 16-byte epilogue only
+    const int ka = p8 ? 8 : 4, kw = a->mode == 0 ? 4 : 8;
+    if (!op_al(a->A, 16) || !op_al(a->W, 16) || a->lda % ka != 0 || a->ldw % kw != 0) return ARTALK_EINVAL;
+    if (p8) {
+        if (!op_al(a->C, 16) || !op_al(a->bias, 16) || !op_al(a->gate, 16) || !op_al(a->R, 16) || N % 4 != 0 || a->ldc % 4 != 0) return ARTALK_EINVAL;
+        if ((a->R && a->ldr % 4 != 0) || (a->gate && a->ldg % 4 != 0)) return ARTALK_EINVAL;
+    }
+    // tile configuration and split
+    int cfg = (a->force_cfg == -1 || a->force_cfg == 99) ? -1 : a->force_cfg;
+    if (cfg != -1) {
+        const bool ok = a->mode == 0 ? (cfg >= 1 && cfg <= 4) : a->mode == 2 ? (cfg >= 0 && cfg <= 2)
+                        : (cfg == 7 || cfg == 8 || cfg == 12 || cfg == 20 || cfg == 23 || cfg == 24 || cfg == 28 || cfg == 31);
+        if (!ok) return ARTALK_EINVAL;
+    }
+    if (a->splitk < 0 || a->splitk > 16 || (a->splitk > 1 && 32 * a->splitk > K)) return ARTALK_EINVAL;
+    // column groups
+    const int G = a->ngrp ? N / a->ngrp : 1;
+    if (a->ngrp) {
+        if (!p8 || a->ngrp < 0 || a->ngrp % 128 != 0 || N % a->ngrp != 0 || a->grpW < 0 || a->grpB < 0 || a->grpC < 0 || a->grpW % 8 != 0 ||
+            a->grpB % 4 != 0 || a->grpC % 4 != 0 || a->gate || a->R || a->ln_Y || a->splitk > 1 || (cfg != -1 && cfg != 8))
+            return ARTALK_EINVAL;
+    }
+    const int64_t gw = a->ngrp ? a->ngrp : N;      // columns one group (or the whole launch) touches from its base
+    // sizes: A, W, bias, C, R, gate
+    if (!op_fits(M - 1, a->lda, K, a->a_elems)) return ARTALK_EINVAL;
+    const int64_t w_last = (int64_t)(G - 1) * a->grpW + (gw - 1) * a->ldw + K;      // elements of W the launch reads (and the copy holds)
+    if (w_last > a->w_elems) return ARTALK_EINVAL;
+    if (a->bias && (int64_t)(G - 1) * a->grpB + gw > a->bias_elems) return ARTALK_EINVAL;
+    const int64_t c_last = op_map_last(a->cmap, M);
+    if (!ident_c && M > a->cmap[0] && a->cmap[1] < a->cmap[0]) return ARTALK_EINVAL;      // result rows of two batches would collide
+    if (a->ldc < gw || !op_fits(c_last, a->ldc, (int64_t)(G - 1) * a->grpC + gw, a->c_elems)) return ARTALK_EINVAL;
+    if (a->R && (a->ldr < N || !op_fits(c_last, a->ldr, N, a->r_elems))) return ARTALK_EINVAL;
+    // a residual in place is read and written by the same lane; any other overlap of R and C would race between rows
+    if (a->R && !((const void*)a->R == (const void*)a->C && a->ldr == a->ldc) &&
+        op_overlap(a->R, c_last * a->ldr + N, a->C, c_last * a->ldc + N))
+        return ARTALK_EINVAL;
+    if (a->gate && (a->ldg < N || !op_fits(op_map_last(a->gmap, M), a->ldg, N, a->gate_elems))) return ARTALK_EINVAL;
+    // the LayerNorm that follows
+    LnArgs ln;
+    if (a->ln_Y) {
+        if (N != kE || a->c_p8 || !a->ln_scale || !a->ln_shift || a->ln_ldm < kE || a->ln_ldy < kE || a->ln_ldm % 4 != 0 || a->ln_ldy % 4 != 0 ||
+            a->ldc % 4 != 0 || !op_al(a->C, 16) || !op_al(a->ln_Y, 16) || !op_al(a->ln_scale, 16) || !op_al(a->ln_shift, 16))
+            return ARTALK_EINVAL;
+        if (a->ln_out_p8 && a->ln_ldy % 8 != 0) return ARTALK_EINVAL;
+        if (!op_fits(M - 1, a->ln_ldy, kE, a->ln_y_elems)) return ARTALK_EINVAL;
+        const int64_t gap = op_mod_gap(a->ln_scale, a->ln_shift);
+        if (gap < 0 || !op_fits(op_map_last(a->ln_mmap, M), a->ln_ldm, gap + kE, a->ln_mod_elems)) return ARTALK_EINVAL;
+        if (op_overlap(a->ln_Y, (int64_t)(M - 1) * a->ln_ldy + kE, a->C, c_last * a->ldc + N)) return ARTALK_EINVAL;
+        ln.X = (const float*)a->C; ln.ldx = a->ldc; ln.Y = (float*)a->ln_Y; ln.ldy = a->ln_ldy; ln.scale = a->ln_scale; ln.shift = a->ln_shift;
+        ln.ldm = a->ln_ldm; ln.mmap = RowMap{a->ln_mmap[0], a->ln_mmap[1], a->ln_mmap[2]}; ln.M = M; ln.D = kE; ln.eps = a->ln_eps;
+        ln.out_p8 = a->ln_out_p8 ? 1 : 0; ln.p8_exp = a->ln_p8_exp; ln.status = a->ln_out_p8 ? a->status_dev : nullptr;
+    }
+    GemmArgs g;
+    g.A = (const float*)a->A; g.lda = a->lda; g.a_packed = p8 ? 1 : 0; g.a_exp = a->a_exp; g.W = a->W; g.ldw = a->ldw; g.bias = a->bias;
+    g.C = (float*)a->C; g.ldc = a->ldc; g.cmap = RowMap{a->cmap[0], a->cmap[1], a->cmap[2]}; g.c_p8 = a->c_p8 ? 1 : 0; g.c_exp = a->c_exp;
+    g.gate = a->gate; g.ldg = a->ldg; g.gmap = RowMap{a->gmap[0], a->gmap[1], a->gmap[2]}; g.R = a->R; g.ldr = a->ldr;
+    g.M = M; g.N = N; g.K = K; g.act = a->act; g.force_cfg = cfg; g.status = a->status_dev;
+    g.ngrp = a->ngrp; g.grpW = a->grpW; g.grpB = a->grpB; g.grpC = a->grpC;
+    int S = a->splitk > 1 ? a->splitk : 1;
+    if (p8) {
+        g.Wp = reinterpret_cast<const unsigned int*>(16);      // the planner looks at its presence only; the copy is made below
+        if (a->ngrp && cfg == -1 && !gemm_p8_eligible(g)) return ARTALK_EINVAL;
+        const bool own_split = a->splitk == 0 && cfg == -1;
+        g.splitk = 1;
+        plan_gemm_p8(g, own_split ? (int64_t)8 * M * N : 0);
+        const bool small = g.force_cfg == 20 || g.force_cfg == 23 || g.force_cfg == 24 || g.force_cfg == 28 || g.force_cfg == 31;
+        if (a->ngrp && g.force_cfg != 8) return ARTALK_EINVAL;
+        if (S > 1 && !small) return ARTALK_EINVAL;
+        if (own_split) S = g.splitk;
+        g.splitk = S;
+    } else {
+        g.splitk = S;
+    }
+    bool fused = false;
+    if (a->ln_Y) {
+        g.partial = reinterpret_cast<float*>(16);      // (eligibility looks at its alignment; hipMalloc's is at least that)
+        fused = S > 1 && splitk_reduce_ln_eligible(g, ln);
+        if (!fused && !ident_c) return ARTALK_EINVAL;      // launch_layernorm reads x as dense rows
+    }
+    if (g_rows_dry_run) {
+        if (a->used_cfg) *a->used_cfg = a->mode == 0 ? gemm_config(g) : a->mode == 2 ? gemm_bf16_config(g) : g.force_cfg;
+        if (a->used_splitk) *a->used_splitk = S;
+        if (a->fused_ln) *a->fused_ln = fused ? 1 : 0;
+        return ARTALK_OK;
+    }
+    // ---- the device from here on
+    hipStream_t s = (hipStream_t)stream;
+    void* wcopy = nullptr;
+    float* part = nullptr;
+    if (a->mode != 0 && hipMalloc(&wcopy, (size_t)w_last * (p8 ? 4 : 2)) != hipSuccess) return ARTALK_EHIP;
+    if (S > 1 && hipMalloc(&part, (size_t)S * M * N * 4) != hipSuccess) { if (wcopy) (void)hipFree(wcopy); return ARTALK_EHIP; }
+    g.partial = part;
+    if (p8) { launch_pack_split(a->W, (unsigned int*)wcopy, w_last, true, s); g.Wp = (const unsigned int*)wcopy; }
+    if (a->mode == 2) { launch_pack_bf16(a->W, wcopy, w_last, s); g.Wb = wcopy; }
+    if (a->mode == 0) launch_gemm(g, s);
+    else if (p8) launch_gemm_p8(g, s);
+    else launch_gemm_bf16(g, s);
+    if (S > 1) {
+        if (fused) launch_splitk_reduce_ln(g, ln, s);
+        else launch_splitk_reduce(g, s);
+    }
+    if (a->ln_Y && !fused) launch_layernorm(ln, s);
+    const hipError_t e1 = hipStreamSynchronize(s);
+    if (wcopy) (void)hipFree(wcopy);
+    if (part) (void)hipFree(part);
+    if (a->used_cfg) *a->used_cfg = a->mode == 0 ? gemm_config(g) : a->mode == 2 ? gemm_bf16_config(g) : g.force_cfg;
+    if (a->used_splitk) *a->used_splitk = S;
+    if (a->fused_ln) *a->fused_ln = fused ? 1 : 0;
+    return (e1 == hipSuccess && hipGetLastError() == hipSuccess) ? ARTALK_OK : ARTALK_EHIP;
+}
+
+int artalk_op_layernorm_rows(const float* X, float* Y, const float* w, const float* b, const float* scale, const float* shift, int M,
+                             int D, float eps, int act, int p8_exp, int junk_period, int junk_from, int* status_dev, int64_t ldx,
+                             int64_t ldy, int64_t ldm, const int32_t* mmap, int64_t x_elems, int64_t y_elems, int64_t mod_elems,
+                             void* stream) {
+    if (!X || !Y || !mmap || M <= 0 || (D != 128 && D != 512 && D != 768 && D != 1024) || !op_exp_ok(p8_exp)) return ARTALK_EINVAL;
+    if (junk_period < 0 || junk_from < 0 || (junk_period > 0 && junk_from > junk_period)) return ARTALK_EINVAL;
+    if ((act & 0x100) && D == 128) return ARTALK_EINVAL;      // the 128-wide kernel has no P8 store
+    if ((w == nullptr) != (b == nullptr) || (scale == nullptr) != (shift == nullptr) || !op_map_ok(mmap)) return ARTALK_EINVAL;
+    const int vb = D == 128 ? 8 : 16, ve = vb / 4;      // bytes / elements of one access of the kernel (float2 at D = 128, 16 bytes otherwise)
+    if (!op_al(X, vb) || !op_al(Y, vb) || !op_al(w, vb) || !op_al(b, vb) || !op_al(scale, vb) || !op_al(shift, vb)) return ARTALK_EINVAL;
+    if (ldx < D || ldy < D || ldx % ve != 0 || ldy % ve != 0 || ((act & 0x100) && ldy % 8 != 0)) return ARTALK_EINVAL;
+    if (!op_fits(M - 1, ldx, D, x_elems) || !op_fits(M - 1, ldy, D, y_elems)) return ARTALK_EINVAL;
+    if (scale) {
+        if (ldm < D || ldm % ve != 0) return ARTALK_EINVAL;
+        const int64_t gap = op_mod_gap(scale, shift);
+        if (gap < 0 || !op_fits(op_map_last(mmap, M), ldm, gap + D, mod_elems)) return ARTALK_EINVAL;
+    }
+    // in place only row on row (a wave reads its row before it writes it); any other overlap of X and Y would race between rows
+    if (!((const void*)X == (const void*)Y && ldx == ldy) && op_overlap(X, (int64_t)(M - 1) * ldx + D, Y, (int64_t)(M - 1) * ldy + D))
+        return ARTALK_EINVAL;
+    if (g_rows_dry_run) return ARTALK_OK;
+    LnArgs a;
+    a.p8_exp = p8_exp; a.junk_period = junk_period; a.junk_from = junk_from; a.status = (act & 0x100) ? status_dev : nullptr;
+    a.X = X; a.ldx = ldx; a.Y = Y; a.ldy = ldy; a.w = w; a.b = b; a.scale = scale; a.shift = shift; a.ldm = ldm;
+    a.mmap = RowMap{mmap[0], mmap[1], mmap[2]}; a.M = M; a.D = D;
+    a.eps = eps; a.act = act & 0xff; a.out_p8 = (act & 0x100) ? 1 : 0;
+    hipStream_t s = (hipStream_t)stream;
+    launch_layernorm(a, s);
+    const hipError_t e1 = hipStreamSynchronize(s);
+    return (e1 == hipSuccess && hipGetLastError() == hipSuccess) ? ARTALK_OK : ARTALK_EHIP;
+}
+
+int artalk_op_attention_rows(const float* Q, const float* K, const float* V, float* O, int B, int H, int HD, int Lq, int Lk,
+                             float scale, int l2norm, const float* qscale, int split, int qkv_exp, int o_exp, int out_p8,
+                             int* status_dev, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bstride, int64_t k_bstride,
+                             int64_t v_bstride, int64_t o_bstride, int64_t q_elems, int64_t k_elems, int64_t v_elems, int64_t o_elems,
+                             void* stream) {
+    if (!Q || !K || !V || !O || (HD != 64 && HD != 32) || ((l2norm & 1) && !qscale)) return ARTALK_EINVAL;
+    if (!op_exp_ok(qkv_exp) || !op_exp_ok(o_exp)) return ARTALK_EINVAL;
+    if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0 || split < 0 || l2norm < 0 || l2norm > 7) return ARTALK_EINVAL;
+    const int split16 = (l2norm >> 1) & 1, qkv_p8 = (l2norm >> 2) & 1;
+    if ((split16 || qkv_p8 || out_p8) && HD != 64) return ARTALK_EINVAL;      // the f16 kernels and the P8 rows are 64-wide heads
+    if (qkv_p8 && (!split16 || (l2norm & 1))) return ARTALK_EINVAL;
+    const int64_t D = (int64_t)H * HD;
+    // rows are read and written as 16-byte vectors, P8 rows as 32-byte groups
+    const int kin = qkv_p8 ? 8 : 4, kout = out_p8 ? 8 : 4;
+    if (!op_al(Q, 4 * kin) || !op_al(K, 4 * kin) || !op_al(V, 4 * kin) || !op_al(O, 4 * kout)) return ARTALK_EINVAL;
+    if (ldq % kin != 0 || ldk % kin != 0 || ldv % kin != 0 || ldo % kout != 0 || q_bstride % kin != 0 || k_bstride % kin != 0 ||
+        v_bstride % kin != 0 || o_bstride % kout != 0)
+        return ARTALK_EINVAL;
+    if (ldq < D || ldk < D || ldv < D || ldo < D || q_bstride < 0 || k_bstride < 0 || v_bstride < 0) return ARTALK_EINVAL;
+    if (B > 1 && o_bstride < (int64_t)(Lq - 1) * ldo + D) return ARTALK_EINVAL;      // output batches would overlap
+    auto fits = [&](int64_t bstride, int64_t ld, int L, int64_t elems) {
+        return (int64_t)(B - 1) * bstride + (int64_t)(L - 1) * ld + D <= elems;
+    };
+    if (!fits(q_bstride, ldq, Lq, q_elems) || !fits(k_bstride, ldk, Lk, k_elems) || !fits(v_bstride, ldv, Lk, v_elems) ||
+        !fits(o_bstride, ldo, Lq, o_elems))
+        return ARTALK_EINVAL;
+    AttnArgs a;
+    a.qkv_exp = qkv_exp; a.o_exp = o_exp; a.out_p8 = out_p8 ? 1 : 0; a.status = out_p8 ? status_dev : nullptr;
+    a.split16 = split16; a.qkv_p8 = qkv_p8;
+    a.Q = Q; a.K = K; a.V = V; a.O = O; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
+    a.q_bstride = q_bstride; a.k_bstride = k_bstride; a.v_bstride = v_bstride; a.o_bstride = o_bstride;
+    a.B = B; a.H = H; a.HD = HD; a.Lq = Lq; a.Lk = Lk; a.scale = scale; a.l2norm = l2norm & 1; a.qscale = qscale;
+    a.split_q = split; a.split_k = split;
+    if (g_rows_dry_run) return ARTALK_OK;
+    hipStream_t s = (hipStream_t)stream;
+    launch_attention(a, s);
+    const hipError_t e1 = hipStreamSynchronize(s);
+    return (e1 == hipSuccess && hipGetLastError() == hipSuccess) ? ARTALK_OK : ARTALK_EHIP;
+}
+
 int artalk_op_w2v_front(const float* audio, int C, int n, const float* w, const float* bias, const float* lnw, const float* lnb,
                         float* xnorm_out, float* Y, void* stream) {
     return artalk_op_w2v_front_ex(audio, C, n, w, bias, lnw, lnb, xnorm_out, Y, 0, kActExp, nullptr, stream);

@@ -411,6 +411,73 @@ int artalk_op_session_scatter(float* const* slots_dev, const float* style, const
  * changes nothing.  cols % 8 != 0, ld < cols or p8_exp outside [-8, 4]: ARTALK_EINVAL.  What artalk_calibrate reads its maxima with. */
 int artalk_op_absmax(const float* buf, int rows, int cols, int64_t ld, int is_p8, int p8_exp, int junk_period, int junk_from,
                      unsigned int* slot_dev, void* stream);
+/* ---- the GEMM, LayerNorm and attention launchers in the forms the AR / VAE / style bodies use them: row maps, pitches wider than a row,
+ * column groups, batch strides, split-K finished by the plain or the LayerNorm-fused reduce (tests/test_rows_ops_gpu.py, tests/test_rows_ops_cpu.py) ----
+ * A row map is int32 {rpb, bstride, off}: row(m) = (m / rpb) * bstride + off + m % rpb; rpb = INT32_MAX is the identity; rpb <= 0,
+ * bstride < 0 or off < 0: ARTALK_EINVAL.  Every buffer that is addressed through a pitch, a map, a group stride or a batch stride comes
+ * with its size in 4-byte elements counted from the pointer given; the entry point works out the furthest element the launch would touch
+ * and returns ARTALK_EINVAL when it lies outside, as for every other bad argument (NULL required pointer, K % 32 != 0, an exponent outside
+ * [-8, 4], a pointer or pitch the kernels' 16-byte accesses cannot take), before the device is touched.  All three synchronise the stream. */
+/* C[cmap(m), n] = R[cmap(m), n] + gate[gmap(m), n] * act(sum_k A[m, k] W[n, k] + bias[n]), then optionally
+ * Y[m, :] = LN(C[cmap(m), :]) * (1 + ln_scale[ln_mmap(m), :]) + ln_shift[ln_mmap(m), :] (N = 768, fp32 C): the order of the engine's gemm()
+ * and its callers.
+ *   mode       0: fp32 MFMA kernels (launch_gemm); 1: f16x3 LDS-DMA kernels with A already in P8 at a_exp (plan_gemm_p8 / launch_gemm_p8);
+ *              2: bf16 kernels (launch_gemm_bf16).  W is fp32 [N][ldw]; the packed / bf16 copy is made internally.  Mode 1 needs every
+ *              pointer 16-byte aligned, lda, ldw % 8 == 0 and N, ldc, ldr, ldg % 4 == 0 (the 16-byte epilogue); modes 0 and 2 need that of
+ *              A, W, lda and ldw (% 4; mode 2: ldw % 8) only.
+ *   force_cfg  -1 or 99: the launcher's / planner's own choice; mode 0: 1, 2, 3, 4 (artalk_op_gemm_ex); mode 1: 7, 8, 12, 20, 23, 24, 28, 31
+ *              (artalk_op_gemm_f16s_packed); mode 2: 0, 1, 2 (artalk_op_gemm_bf16).
+ *   splitk     1: none; S > 1 (S <= 16, 32 S <= K): S slabs in a temporary, finished by the reduce pass (mode 1: small-grid
+ *              configurations only); 0: mode 1 with force_cfg -1 / 99: the planner's own split; otherwise none.
+ *   ngrp       mode 1, column groups of the persistent 128x128 kernel (configuration 8): group j = columns [j ngrp, (j + 1) ngrp) reads weight
+ *              rows at W + j grpW and bias at bias + j grpB and writes C + j grpC.  Taken with force_cfg 8, or with -1 / 99 where
+ *              gemm_p8_eligible holds; no gate, residual, split-K or LayerNorm; otherwise ARTALK_EINVAL.
+ *   ln_Y       non-NULL: the LayerNorm that follows, D = 768, no affine, Y dense rows of pitch ln_ldy, fp32 or (ln_out_p8) P8 at ln_p8_exp;
+ *              ln_mod_elems counts from the lower of ln_scale and ln_shift.  With a split the reduce is launch_splitk_reduce_ln where
+ *              splitk_reduce_ln_eligible holds (S in 2, 3, 4, 6, 8, every pointer 16-byte aligned and ln_ldy % 8 == 0 - also for an fp32 Y,
+ *              for which the entry point itself takes ln_ldy % 4 == 0: such a pitch runs unfused and fused_ln says so), otherwise the
+ *              plain reduce (or no reduce) and launch_layernorm, which reads C as dense rows: a cmap other than the identity is then
+ *              ARTALK_EINVAL.  Y must not overlap C.
+ *   R          may be C with ldr == ldc (the residual in place); any other overlap of R and C is ARTALK_EINVAL.
+ *   used_cfg, used_splitk, fused_ln   host, nullable: the configuration and split that ran, whether the fused reduce did (0 / 1). */
+typedef struct artalk_op_gemm_rows_args {
+    int32_t mode, M, N, K, act;
+    const void* A; int64_t lda, a_elems; int32_t a_exp;
+    const float* W; int64_t ldw, w_elems;
+    const float* bias; int64_t bias_elems;
+    void* C; int64_t ldc, c_elems; int32_t cmap[3];
+    const float* gate; int64_t ldg, gate_elems; int32_t gmap[3];
+    const float* R; int64_t ldr, r_elems;          /* addressed with cmap; may be C */
+    int32_t c_p8, c_exp;
+    int32_t force_cfg, splitk;
+    int32_t ngrp; int64_t grpW, grpB, grpC;
+    int32_t* status_dev;
+    void* ln_Y; int64_t ln_ldy, ln_y_elems;
+    const float* ln_scale; const float* ln_shift; int64_t ln_ldm, ln_mod_elems; int32_t ln_mmap[3];
+    float ln_eps; int32_t ln_out_p8, ln_p8_exp;
+    int32_t* used_cfg; int32_t* used_splitk; int32_t* fused_ln;
+} artalk_op_gemm_rows_args;
+int artalk_op_gemm_rows(const artalk_op_gemm_rows_args* a, void* stream);
+/* sizeof(artalk_op_gemm_rows_args) followed by the offset of every field in declaration order (49 values; returns the count, ARTALK_EINVAL
+ * for n below it): what a binding checks its mirror of the struct against */
+int artalk_op_gemm_rows_layout(int64_t* out, int n);
+/* enable != 0: on the calling thread the three *_rows entry points validate as usual and return ARTALK_OK where they would first touch the
+ * device (artalk_op_gemm_rows still reports used_cfg, used_splitk, fused_ln): what separates "accepted" from "refused" without a GPU */
+int artalk_op_rows_dry_run(int enable);
+/* artalk_op_layernorm_ex with row pitches ldx, ldy >= D, the modulation rows at scale / shift + mmap(m) * ldm (ldm >= D; mod_elems counts
+ * from the lower of the two pointers) and the sizes of X, Y and the modulation table.  Y may be X with ldy == ldx; any other overlap is
+ * ARTALK_EINVAL */
+int artalk_op_layernorm_rows(const float* X, float* Y, const float* w, const float* b, const float* scale, const float* shift, int M,
+                             int D, float eps, int act, int p8_exp, int junk_period, int junk_from, int* status_dev, int64_t ldx,
+                             int64_t ldy, int64_t ldm, const int32_t* mmap, int64_t x_elems, int64_t y_elems, int64_t mod_elems,
+                             void* stream);
+/* artalk_op_attention_ex with row pitches (>= H * HD), batch strides (>= 0; O's batches must not overlap) and buffer sizes: clip b, row i,
+ * head h of Q is at Q + b * q_bstride + i * ldq + h * HD, likewise K, V (Lk rows) and O */
+int artalk_op_attention_rows(const float* Q, const float* K, const float* V, float* O, int B, int H, int HD, int Lq, int Lk,
+                             float scale, int l2norm, const float* qscale, int split, int qkv_exp, int o_exp, int out_p8,
+                             int* status_dev, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bstride, int64_t k_bstride,
+                             int64_t v_bstride, int64_t o_bstride, int64_t q_elems, int64_t k_elems, int64_t v_elems, int64_t o_elems,
+                             void* stream);
 
 #ifdef __cplusplus
 }

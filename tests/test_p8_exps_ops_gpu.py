@@ -8,9 +8,8 @@ restatement of the format (tests/p8_format.py, itself checked in test_p8_format_
 stored value, plus the bars test_ops_gpu.py already uses for the arithmetic (2e-6 of the largest result for the split GEMMs, 2e-5
 absolute for attention outputs of magnitude ~1 - relative to the largest value here - and LayerNorm).  Guard tests feed inf / NaN as data.
 
-Not covered here, only by the scrambled model runs of test_site_exps_gpu.py: the split-K reduce fused with the AdaLN LayerNorm
-(launch_splitk_reduce_ln takes a GemmArgs and an LnArgs of the AR residual stream; it has no single-kernel entry point) - the plain
-split-K reduce and the LayerNorm kernel it combines are both covered."""
+The split-K reduce fused with the AdaLN LayerNorm (launch_splitk_reduce_ln takes a GemmArgs and an LnArgs of the AR residual stream) is
+covered by test_rows_ops_gpu.py through artalk_op_gemm_rows, at ln_p8_exp 4, 0 and -8."""
 import ctypes as C
 import math
 
