@@ -27,6 +27,7 @@ SYMBOLS = [
     "artalk_op_pack_split_ex", "artalk_op_layernorm_ex", "artalk_op_gemm_f16s_packed_ex", "artalk_op_gemm_f16s_ex", "artalk_op_attention_ex", "artalk_op_w2v_front_ex", "artalk_op_pool_silu_ex", "artalk_op_posconv_p8_ex",
     "artalk_op_bsq_history_ex", "artalk_op_ar_bits_next", "artalk_op_vq_embed", "artalk_op_ar_begin", "artalk_op_dec_input", "artalk_op_dec_finish", "artalk_op_enc_input_zero", "artalk_op_style_input", "artalk_op_add_row", "artalk_op_style_finish", "artalk_op_broadcast16", "artalk_op_session_gather", "artalk_op_session_scatter", "artalk_op_absmax",
     "artalk_op_gemm_rows", "artalk_op_layernorm_rows", "artalk_op_attention_rows", "artalk_op_gemm_rows_layout", "artalk_op_rows_dry_run",
+    "artalk_op_w2v_front_rows", "artalk_op_pool_silu_rows", "artalk_op_posconv_rows",
 ]
 
 
@@ -298,6 +299,13 @@ def lib() -> C.CDLL:
         L.artalk_op_gemm_rows_layout.restype = i32
         L.artalk_op_rows_dry_run.argtypes = [i32]
         L.artalk_op_rows_dry_run.restype = i32
+    if hasattr(L, "artalk_op_w2v_front_rows"):      # (an older build loaded through ARTALK_LIB lacks the chunk-strided wav2vec2 entry points)
+        L.artalk_op_w2v_front_rows.argtypes = [vp, i64, C.POINTER(i64), i32, i32, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, vp]
+        L.artalk_op_w2v_front_rows.restype = i32
+        L.artalk_op_pool_silu_rows.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, i64, i64, i64, vp]
+        L.artalk_op_pool_silu_rows.restype = i32
+        L.artalk_op_posconv_rows.argtypes = [i32, vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]
+        L.artalk_op_posconv_rows.restype = i32
     _lib = L
     return L
 

@@ -2607,6 +2607,86 @@ int artalk_op_posconv_p8_ex(const float* X, const void* Wp, const float* bias, c
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
 }
 
+// ---- the wav2vec2 stage's kernels in the chunk-strided forms run_wav2vec launches them (include/artalk_hip.h): checked on the host
+// like the *_rows entry points above, dry run included
+int artalk_op_w2v_front_rows(const float* audio, int64_t audio_elems, const int64_t* chunk_off, int C, int n, const float* w,
+                             const float* bias, const float* lnw, const float* lnb, float* xnorm_out, float* Y, int64_t row_stride,
+                             int64_t y_elems, int out_p8, int p8_exp, int* status_dev, void* stream) {
+    if (!audio || !chunk_off || !w || !bias || !lnw || !lnb || !xnorm_out || !Y || C <= 0 || n < 10 || !op_exp_ok(p8_exp)) return ARTALK_EINVAL;
+    const int T = (n - 10) / 5 + 1;
+    if (row_stride < T || row_stride > INT_MAX) return ARTALK_EINVAL;
+    if (!op_al(Y, out_p8 ? 32 : 16)) return ARTALK_EINVAL;      // rows are stored as 16-byte vectors, P8 rows as 32-byte groups
+    for (int i = 0; i < C; ++i)
+        if (chunk_off[i] < 0 || chunk_off[i] > audio_elems - n) return ARTALK_EINVAL;
+    if (!op_fits((int64_t)(C - 1) * row_stride + T - 1, 512, 512, y_elems)) return ARTALK_EINVAL;
+    if (g_rows_dry_run) return ARTALK_OK;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<long> off(chunk_off, chunk_off + C);
+    long* doff = nullptr;
+    if (hipMalloc(&doff, C * sizeof(long)) != hipSuccess) return ARTALK_EHIP;
+    if (hipMemcpy(doff, off.data(), C * sizeof(long), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(doff); return ARTALK_EHIP; }
+    launch_audio_normalize(audio, doff, xnorm_out, C, n, s);
+    launch_conv0(xnorm_out, n, w, bias, lnw, lnb, Y, C, T, (int)row_stride, s, out_p8 ? 1 : 0, out_p8 ? status_dev : nullptr, p8_exp);
+    const hipError_t e1 = hipStreamSynchronize(s);
+    (void)hipFree(doff);
+    return (e1 == hipSuccess && hipGetLastError() == hipSuccess) ? ARTALK_OK : ARTALK_EHIP;
+}
+
+int artalk_op_pool_silu_rows(const float* X, int C, int T, int D, float* Y, int out_p8, int p8_exp, int* status_dev, int64_t x_tstride,
+                             int64_t x_elems, int64_t y_elems, void* stream) {
+    if (!X || !Y || C <= 0 || T < 1 || D <= 0 || D % 4 != 0 || (out_p8 && D % 8 != 0) || !op_exp_ok(p8_exp)) return ARTALK_EINVAL;
+    if (x_tstride < T || x_tstride > INT_MAX) return ARTALK_EINVAL;
+    if (!op_al(X, 16) || !op_al(Y, out_p8 ? 32 : 16)) return ARTALK_EINVAL;
+    if (!op_fits((int64_t)(C - 1) * x_tstride + T - 1, D, D, x_elems) || !op_fits((int64_t)C * kNTok - 1, D, D, y_elems)) return ARTALK_EINVAL;
+    if (g_rows_dry_run) return ARTALK_OK;
+    static const int pn[5] = {1, 5, 25, 50, 100};
+    hipStream_t s = (hipStream_t)stream;
+    launch_pool_silu(X, (int)x_tstride, T, Y, C, pn, 5, D, s, out_p8 ? 1 : 0, out_p8 ? status_dev : nullptr, p8_exp);
+    const hipError_t e1 = hipStreamSynchronize(s);
+    return (e1 == hipSuccess && hipGetLastError() == hipSuccess) ? ARTALK_OK : ARTALK_EHIP;
+}
+
+int artalk_op_posconv_rows(int mode, const float* X, int64_t x_elems, const float* W, const float* bias, const float* R, float* C,
+                           int64_t c_elems, int n_chunks, int T, int Ts, int groups, int cg, int taps, int act, int a_exp, int force_cfg,
+                           int* status_dev, void* stream) {
+    if (mode < 0 || mode > 2 || !X || !W || !C || (R && R != C)) return ARTALK_EINVAL;
+    if (n_chunks <= 0 || T < 1 || T > Ts || groups <= 0 || cg <= 0 || taps <= 0 || act < 0 || act > 3 || !op_exp_ok(a_exp)) return ARTALK_EINVAL;
+    if (cg % 4 != 0 || ((int64_t)cg * taps) % 32 != 0 || (int64_t)cg * taps > INT_MAX || (int64_t)groups * cg > INT_MAX) return ARTALK_EINVAL;
+    if (mode == 1 ? (groups != 16 || cg != 64 || taps != 128 || Ts > 256 || force_cfg != -1)
+                  : (force_cfg != -1 && (mode == 0 ? (force_cfg < 1 || force_cfg > 4) : (force_cfg < 0 || force_cfg > 2))))
+        return ARTALK_EINVAL;
+    // X and W rows are read as 16-byte vectors in every mode; the f16x3 kernel takes the 16-byte epilogue only
+    if (!op_al(X, 16) || !op_al(W, 16)) return ARTALK_EINVAL;
+    if (mode == 1 && (!op_al(C, 16) || !op_al(bias, 16))) return ARTALK_EINVAL;
+    const int64_t H = (int64_t)groups * cg, M = (int64_t)n_chunks * Ts, K = (int64_t)cg * taps;
+    if (M > INT_MAX) return ARTALK_EINVAL;
+    // frames t < T of every chunk are read, rows t < Ts of every chunk are written
+    if (!op_fits((int64_t)(n_chunks - 1) * Ts + T - 1, H, H, x_elems) || !op_fits(M - 1, H, H, c_elems)) return ARTALK_EINVAL;
+    if (op_overlap(X, (int64_t)(n_chunks - 1) * Ts * H + (int64_t)T * H, C, M * H)) return ARTALK_EINVAL;      // a row of X is read by many rows of C
+    if (g_rows_dry_run) return ARTALK_OK;
+    hipStream_t s = (hipStream_t)stream;
+    void* wcopy = nullptr;
+    if (mode != 0 && hipMalloc(&wcopy, (size_t)(H * K) * (mode == 1 ? 4 : 2)) != hipSuccess) return ARTALK_EHIP;
+    GemmArgs g;
+    g.A = X; g.lda = H; g.W = W; g.ldw = K; g.bias = bias; g.C = C; g.ldc = H; g.R = R; g.ldr = H;
+    g.M = (int)M; g.act = act; g.a_exp = a_exp; g.K = (int)K;
+    if (mode == 1) {
+        launch_pack_split(W, (unsigned int*)wcopy, H * K, true, s);
+        g.N = (int)H; g.Wp = (const unsigned int*)wcopy; g.status = status_dev;
+        launch_posconv_p8(g, n_chunks, T, Ts, s);
+    } else {
+        // the grouped GEMM over grid.z of run_wav2vec (amode 1)
+        g.amode = 1; g.pc_T = T; g.pc_tstride = Ts; g.pc_pad = taps / 2; g.pc_cin = cg;
+        g.N = cg; g.force_cfg = force_cfg;
+        g.batch = groups; g.sA = cg; g.sW = (long)cg * K; g.sBias = bias ? cg : 0; g.sC = cg; g.sR = R ? cg : 0;
+        if (mode == 2) { launch_pack_bf16(W, wcopy, H * K, s); g.Wb = wcopy; launch_gemm_bf16(g, s); }
+        else launch_gemm(g, s);
+    }
+    const hipError_t e1 = hipStreamSynchronize(s);
+    if (wcopy) (void)hipFree(wcopy);
+    return (e1 == hipSuccess && hipGetLastError() == hipSuccess) ? ARTALK_OK : ARTALK_EHIP;
+}
+
 int artalk_op_bsq_history(const float* enc_out, uint8_t* hist_bits, float* prev_fdec, float* msfeat, int B, void* stream) {
     return artalk_op_bsq_history_ex(enc_out, hist_bits, prev_fdec, msfeat, B, nullptr, stream);
 }

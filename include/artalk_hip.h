@@ -478,6 +478,34 @@ int artalk_op_attention_rows(const float* Q, const float* K, const float* V, flo
                              int* status_dev, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bstride, int64_t k_bstride,
                              int64_t v_bstride, int64_t o_bstride, int64_t q_elems, int64_t k_elems, int64_t v_elems, int64_t o_elems,
                              void* stream);
+/* ---- the wav2vec2 stage's kernels in the chunk-strided forms run_wav2vec launches them (tests/test_w2v_ops_gpu.py, tests/test_w2v_ops_cpu.py).
+ * Conventions of the *_rows entry points above: every buffer reached through an offset, a pitch or a stride comes with its size in 4-byte
+ * elements, the furthest element of the launch is worked out on the host, any bad argument is ARTALK_EINVAL before the device is touched,
+ * artalk_op_rows_dry_run is honoured, the stream is synchronised.  (The conv layers 1-6 are artalk_op_gemm_rows with lda < K, the encoder
+ * attention is artalk_op_attention_rows with its strides: they need no entry point of their own.) */
+/* artalk_op_w2v_front_ex with the chunk table and the row stride of the model: chunk c is read at audio + chunk_off[c] (host table of C
+ * offsets in samples; they may overlap and come in any order) and frame t < T = (n - 10) / 5 + 1 of chunk c is written to row
+ * c * row_stride + t of Y (512 wide); rows t >= T of a chunk are not written.  xnorm_out stays [C][n].  ARTALK_EINVAL: a NULL pointer, a negative
+ * offset, chunk_off[c] + n > audio_elems, row_stride < T, a Y too small or not 16-byte (out_p8: 32-byte) aligned, p8_exp outside [-8, 4]. */
+int artalk_op_w2v_front_rows(const float* audio, int64_t audio_elems, const int64_t* chunk_off, int C, int n, const float* w,
+                             const float* bias, const float* lnw, const float* lnb, float* xnorm_out, float* Y, int64_t row_stride,
+                             int64_t y_elems, int out_p8, int p8_exp, int* status_dev, void* stream);
+/* artalk_op_pool_silu_ex with the frame stride of the model: frame t < T of chunk c is read at row c * x_tstride + t of X (D wide, D % 4 == 0;
+ * out_p8: D % 8 == 0), x_tstride >= T >= 1; Y [C][181][D].  X 16-byte, Y 16-byte (out_p8: 32-byte) aligned. */
+int artalk_op_pool_silu_rows(const float* X, int C, int T, int D, float* Y, int out_p8, int p8_exp, int* status_dev, int64_t x_tstride,
+                             int64_t x_elems, int64_t y_elems, void* stream);
+/* The grouped positional convolution as run_wav2vec sets it up: X [n_chunks * Ts][groups * cg] fp32, frames t < T of a chunk are read and
+ * everything outside [0, T) of the chunk counts as zero (padding taps / 2, the last output frame dropped); W fp32 [groups * cg][taps * cg]
+ * with k = tap * cg + input channel of the group (packed / converted internally); C = R + act(conv + bias) for the rows t < Ts of every
+ * chunk, pitch groups * cg; R is NULL or C (the residual in place); X must not overlap C.
+ *   mode 0: the fp32 grouped GEMM over grid.z (amode 1 of launch_gemm), force_cfg -1 or 1, 2, 3, 4;
+ *   mode 1: launch_posconv_p8 (the window split with 2^a_exp while staged, guarded through status_dev): groups = 16, cg = 64, taps = 128,
+ *           Ts <= 256, force_cfg -1, X, W, bias and C 16-byte aligned;
+ *   mode 2: the bf16 grouped GEMM (amode 1 of launch_gemm_bf16), force_cfg -1 or 0, 1, 2.
+ * Modes 0 and 2 take any cg % 4 == 0 with (cg * taps) % 32 == 0, X and W 16-byte aligned. */
+int artalk_op_posconv_rows(int mode, const float* X, int64_t x_elems, const float* W, const float* bias, const float* R, float* C,
+                           int64_t c_elems, int n_chunks, int T, int Ts, int groups, int cg, int taps, int act, int a_exp, int force_cfg,
+                           int* status_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -28,7 +28,7 @@ def _p(t):
 
 
 @pytest.mark.parametrize("M,N,K,act,use_bias,use_gate,use_res", [
-    (1000, 512, 1536, 0, True, False, False),     # conv-as-GEMM shape, 128x128 tiles
+    (1000, 512, 1536, 0, True, False, False),     # N and K of a conv layer, dense rows (lda = K; the window form, lda = 1024 < K: test_w2v_ops_gpu.py)
     (2000, 1024, 1024, 1, True, False, True),     # gelu(erf) + residual
     (333, 768, 3072, 2, True, True, True),        # ragged M, gelu(tanh), gate, residual; 64x64 tiles
     (32, 2304, 768, 0, True, False, False),       # tiny M: 32x128 tiles
