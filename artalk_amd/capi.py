@@ -24,6 +24,7 @@ SYMBOLS = [
     "artalk_op_gemm", "artalk_op_gemm_ex", "artalk_op_gemm_bf16", "artalk_op_gemm_f16s", "artalk_op_pack_split", "artalk_op_gemm_f16s_packed", "artalk_op_release_scratch", "artalk_op_gemm_p8_plan", "artalk_op_create_masked_stream", "artalk_op_destroy_stream", "artalk_op_mfma_f32_peak", "artalk_op_layernorm", "artalk_op_attention", "artalk_op_w2v_front", "artalk_op_resample_mean", "artalk_op_pool_silu",
     "artalk_op_bsq_history",
     "artalk_sessions_reserve", "artalk_session_open", "artalk_session_step", "artalk_session_close", "artalk_session_count",
+    "artalk_session_smooth", "artalk_op_savgol_stream", "artalk_op_session_smooth_check",
     "artalk_op_pack_split_ex", "artalk_op_layernorm_ex", "artalk_op_gemm_f16s_packed_ex", "artalk_op_gemm_f16s_ex", "artalk_op_attention_ex", "artalk_op_w2v_front_ex", "artalk_op_pool_silu_ex", "artalk_op_posconv_p8_ex",
     "artalk_op_bsq_history_ex", "artalk_op_ar_bits_next", "artalk_op_vq_embed", "artalk_op_ar_begin", "artalk_op_dec_input", "artalk_op_dec_finish", "artalk_op_enc_input_zero", "artalk_op_style_input", "artalk_op_add_row", "artalk_op_style_finish", "artalk_op_broadcast16", "artalk_op_session_gather", "artalk_op_session_scatter", "artalk_op_absmax",
     "artalk_op_gemm_rows", "artalk_op_layernorm_rows", "artalk_op_attention_rows", "artalk_op_gemm_rows_layout", "artalk_op_rows_dry_run",
@@ -166,6 +167,15 @@ def lib() -> C.CDLL:
         L.artalk_session_close.restype = i32
         L.artalk_session_count.argtypes = [vp]
         L.artalk_session_count.restype = i32
+    if hasattr(L, "artalk_session_smooth"):    # (an older build loaded through ARTALK_LIB lacks the streaming smoother)
+        pi32, pu8 = C.POINTER(i32), C.POINTER(C.c_uint8)
+        L.artalk_session_smooth.argtypes = [vp, C.POINTER(i64), i32, vp, i64, pi32, pu8, vp, i64, pi32, pi32, vp]
+        L.artalk_session_smooth.restype = i32
+        L.artalk_op_savgol_stream.argtypes = [vp, vp, i64, pi32, pi32, pu8, vp, i64, i32, vp]
+        L.artalk_op_savgol_stream.restype = i32
+        L.artalk_op_session_smooth_check.argtypes = [C.POINTER(i64), C.POINTER(i64), pu8, i32, C.POINTER(i64), i32, C.POINTER(i64), i32, i32, i64,
+                                                     pi32, pu8, i64, pi32, pi32, C.c_char_p, i32]
+        L.artalk_op_session_smooth_check.restype = i32
     L.artalk_flame_create.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, C.POINTER(vp)]
     L.artalk_flame_create.restype = i32
     L.artalk_flame_verts.argtypes = [vp, vp, vp, i32, vp, vp]

@@ -8,7 +8,7 @@
 //   dec_finish     bitwise_vae.py:63-65,111-113 ; :59-61,87 for the re-encode input
 //   bsq_history    bitwise_vae.py:227-242,316-334 (MultiScaleBSQ/BSQ forward) + :269-288 (features from bits)
 //   style_*        app/modules/style_encoder.py:26-38,58-60 ; app/models.py:67-73
-//   savgol         inference.py:89-95 (scipy.signal.savgol_filter, mode='interp')
+//   savgol         inference.py:89-95 (scipy.signal.savgol_filter, mode='interp'); savgol_stream: the same for a live session, 4 frames late
 #include "common.h"
 #include <cmath>
 #include <mutex>
@@ -492,30 +492,77 @@ static void polyfit_edge(int window, int order, int n_edge, double* out /*[n_edg
     for (int j = 0; j < window; ++j) fir[j] = H(window / 2, j);
 }
 
+// One output of the filter: frame t, dim d of a clip of T frames (T >= 9).  in(j) is raw frame j of the clip, dim d.  Both kernels below
+// go through this one function, so a frame costs the same operations in the same order whichever of them emits it.
+template <typename In>
+__device__ __forceinline__ float savgol_point(const In& in, int t, int T, int d, const SavgolCoef& k) {
+    double acc = 0.0;
+    if (d >= 100 && d < 103) {
+        if (t < 4) { for (int j = 0; j < 9; ++j) acc += k.edge9[t][j] * (double)in(j); }
+        else if (t >= T - 4) { const int i = T - 1 - t; for (int j = 0; j < 9; ++j) acc += k.edge9[i][j] * (double)in(T - 1 - j); }
+        else { for (int j = 0; j < 9; ++j) acc += k.fir9[j] * (double)in(t - 4 + j); }
+    } else {
+        if (t < 2) { for (int j = 0; j < 5; ++j) acc += k.edge5[t][j] * (double)in(j); }
+        else if (t >= T - 2) { const int i = T - 1 - t; for (int j = 0; j < 5; ++j) acc += k.edge5[i][j] * (double)in(T - 1 - j); }
+        else { for (int j = 0; j < 5; ++j) acc += k.fir5[j] * (double)in(t - 2 + j); }
+    }
+    return (float)acc;
+}
+
 __global__ __launch_bounds__(128) void savgol_kernel(const float* __restrict__ in, float* __restrict__ out, int T, int D, SavgolCoef k) {
     const int t = blockIdx.x, d = threadIdx.x;
     if (d >= D) return;
-    double acc = 0.0;
-    if (d >= 100 && d < 103) {
-        if (t < 4) { for (int j = 0; j < 9; ++j) acc += k.edge9[t][j] * (double)in[(long)j * D + d]; }
-        else if (t >= T - 4) { const int i = T - 1 - t; for (int j = 0; j < 9; ++j) acc += k.edge9[i][j] * (double)in[(long)(T - 1 - j) * D + d]; }
-        else { for (int j = 0; j < 9; ++j) acc += k.fir9[j] * (double)in[(long)(t - 4 + j) * D + d]; }
-    } else {
-        if (t < 2) { for (int j = 0; j < 5; ++j) acc += k.edge5[t][j] * (double)in[(long)j * D + d]; }
-        else if (t >= T - 2) { const int i = T - 1 - t; for (int j = 0; j < 5; ++j) acc += k.edge5[i][j] * (double)in[(long)(T - 1 - j) * D + d]; }
-        else { for (int j = 0; j < 5; ++j) acc += k.fir5[j] * (double)in[(long)(t - 2 + j) * D + d]; }
-    }
-    out[(long)t * D + d] = (float)acc;
+    out[(long)t * D + d] = savgol_point([&](int j) { return in[(long)j * D + d]; }, t, T, d, k);
 }
-void launch_savgol(const float* in, float* out, int T, int D, hipStream_t s) {
+
+static const SavgolCoef& savgol_coef() {
     static SavgolCoef k;
     static std::once_flag once;
     std::call_once(once, [] {
         polyfit_edge(5, 2, 2, &k.edge5[0][0], k.fir5);
         polyfit_edge(9, 3, 4, &k.edge9[0][0], k.fir9);
     });
+    return k;
+}
+void launch_savgol(const float* in, float* out, int T, int D, hipStream_t s) {
     if (T < 9) abort();   // the Python host raises ValueError first (scipy does the same for mode='interp')
-    ARTALK_LAUNCH(savgol_kernel, dim3(T), dim3(128), 0, s, in, out, T, D, k);
+    ARTALK_LAUNCH(savgol_kernel, dim3(T), dim3(128), 0, s, in, out, T, D, savgol_coef());
+}
+
+// The filter on a live session (kernels.h).  The window [carry | new frames] = stream frames [base, T') sits in LDS; an emitted frame t
+// reads frames t - 4 .. t + 4 (FIR), 0 .. 8 (head: then base == 0) or T' - 9 .. T' - 1 (tail, last call only), all inside the window.
+// Only this workgroup touches the session's carry: it is read before the first barrier and written after the second.
+constexpr int SGS_NT = 256, SGS_D = 106, SGS_WIN = kSavgolCarry + T100;
+__global__ __launch_bounds__(SGS_NT) void savgol_stream_kernel(float* const* __restrict__ slots, const int4* __restrict__ meta, long carry_off,
+                                                               const float* __restrict__ raw, long raw_stride, float* __restrict__ out,
+                                                               long out_stride, SavgolCoef k) {
+    __shared__ float win[SGS_WIN * SGS_D];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const int4 mt = meta[i];
+    const int seen = mt.x, nf = mt.y, last = mt.z;
+    float* __restrict__ carry = slots[i] + carry_off;
+    const int nc = seen < kSavgolCarry ? seen : kSavgolCarry;      // carried frames: stream frames [seen - nc, seen)
+    const int base = seen - nc, rows = nc + nf, T = seen + nf;
+    for (int idx = tid; idx < nc * SGS_D; idx += SGS_NT) win[idx] = carry[idx];
+    const float* __restrict__ src = raw + (long)i * raw_stride;
+    for (int idx = tid; idx < nf * SGS_D; idx += SGS_NT) win[nc * SGS_D + idx] = src[idx];
+    __syncthreads();
+    const int first = seen > kSavgolLag ? seen - kSavgolLag : 0;
+    const int count = (last ? T : T - kSavgolLag) - first;
+    float* __restrict__ dst = out + (long)i * out_stride;
+    for (int idx = tid; idx < count * SGS_D; idx += SGS_NT) {
+        const int r = idx / SGS_D, d = idx - r * SGS_D;
+        dst[idx] = savgol_point([&](int j) { return win[(j - base) * SGS_D + d]; }, first + r, T, d, k);
+    }
+    __syncthreads();
+    const int keep = T < kSavgolCarry ? T : kSavgolCarry;
+    for (int idx = tid; idx < keep * SGS_D; idx += SGS_NT) carry[idx] = win[(rows - keep) * SGS_D + idx];
+}
+void launch_savgol_stream(float* const* slots, const int4* meta, long carry_off, const float* raw, long raw_stride, float* out,
+                          long out_stride, int n, int D, hipStream_t s) {
+    if (n <= 0) return;
+    if (D != SGS_D) abort();   // artalk_create accepts no other motion_dim
+    ARTALK_LAUNCH(savgol_stream_kernel, dim3(n), dim3(SGS_NT), 0, s, slots, meta, carry_off, raw, raw_stride, out, out_stride, savgol_coef());
 }
 
 }  // namespace artalk

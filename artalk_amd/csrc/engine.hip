@@ -128,6 +128,10 @@ struct Workspace {
 
 }  // namespace
 
+// where the smoother's carry starts in a pool slot, in floats: behind [style kE | prev_in kNTok x kE | prev_fdec 100 x code_dim]
+constexpr int64_t slot_carry_off(int code_dim) { return kE + (int64_t)kNTok * kE + 100LL * code_dim; }
+constexpr int kOpCodeDim = 32, kOpMotionDim = 106;      // the only widths artalk_create accepts: what the model-free entry points assume
+
 struct artalk_model {
     artalk_config cfg{};
     int device = 0;
@@ -178,11 +182,18 @@ struct artalk_model {
     struct Sessions {
         std::vector<float*> blocks;                // device blocks of kSessBlock slots
         std::vector<int64_t> owner;                // per slot: the id of the session that holds it, 0 = free
-        std::map<int64_t, int> open;               // id -> slot
+        // an open session: its slot, and where its streaming smoother stands (artalk_session_smooth): raw frames consumed, and whether
+        // a `last` call has emitted the tail.  Born zero with the id, dropped with it: a slot reused under a new id starts clean.
+        struct Open { int slot = 0; int64_t seen = 0; bool smooth_done = false; };
+        std::map<int64_t, Open> open;              // id -> state
         std::set<int64_t> ended_by_scales;         // ids a change of site scales closed (a step on one says so; artalk_session_close forgets it)
         int64_t next_id = 1;                       // ids are never reused during the model's life
+        void* smooth_tab = nullptr; int64_t smooth_cap = 0;      // device table of one artalk_session_smooth call: [cap slot pointers | cap int4]
     } sess;
-    int64_t sess_slot_floats() const { return kE + (int64_t)kNTok * kE + 100LL * cfg.code_dim; }
+    // slot: [style | prev_in | prev_fdec | smoother carry]; the carry (the last 9 raw frames, padded to 16 bytes) is read and written in
+    // place by savgol_stream_kernel and never visits the workspace: SessionRows and the gather / scatter cover the first three fields only
+    int64_t sess_carry_off() const { return slot_carry_off(cfg.code_dim); }
+    int64_t sess_slot_floats() const { return sess_carry_off() + (kSavgolCarry * (int64_t)cfg.motion_dim + 3) / 4 * 4; }
     float* sess_slot(int i) const { return sess.blocks[i / kSessBlock] + (int64_t)(i % kSessBlock) * sess_slot_floats(); }
     Workspace* view = nullptr;        // workspace view (clip sub-range) the body launchers currently work on; null = m->ws
     bool sticky_error = false;        // set by internal consistency checks inside the launch sequence; reported by artalk_infer
@@ -228,7 +239,7 @@ struct artalk_model {
     // recorded after its H2D copies, so artalk_infer never has to wait for its own copies (it blocks only if kStageSlots calls
     // are still in flight).  h_status receives the device status word at the end of every call (async), status_ev marks it.
     static constexpr int kStageSlots = 4;
-    struct Stage { long* src = nullptr; uint8_t* has = nullptr; float** slots = nullptr; hipEvent_t done = nullptr; bool used = false; };
+    struct Stage { long* src = nullptr; uint8_t* has = nullptr; float** slots = nullptr; int4* smooth = nullptr; hipEvent_t done = nullptr; bool used = false; };
     Stage stage[kStageSlots];
     int stage_cap_c = 0, stage_cap_b = 0, stage_next = 0;
     // one slot per call in flight (ring of kStatusSlots, indexed by the call's ticket): a caller that keeps several calls queued reads
@@ -1101,7 +1112,8 @@ void free_stage(artalk_model* m) {
         if (st.src) (void)hipHostFree(st.src);
         if (st.has) (void)hipHostFree(st.has);
         if (st.slots) (void)hipHostFree(st.slots);
-        st.src = nullptr; st.has = nullptr; st.slots = nullptr; st.used = false;
+        if (st.smooth) (void)hipHostFree(st.smooth);
+        st.src = nullptr; st.has = nullptr; st.slots = nullptr; st.smooth = nullptr; st.used = false;
     }
     m->stage_cap_c = m->stage_cap_b = 0;
 }
@@ -1118,6 +1130,7 @@ int ensure_stage(artalk_model* m, int maxB, int maxC) {
         HIPCHK(m, hipHostMalloc(reinterpret_cast<void**>(&st.src), (size_t)maxC * sizeof(long), hipHostMallocDefault));
         HIPCHK(m, hipHostMalloc(reinterpret_cast<void**>(&st.has), (size_t)maxB, hipHostMallocDefault));
         HIPCHK(m, hipHostMalloc(reinterpret_cast<void**>(&st.slots), (size_t)maxB * sizeof(float*), hipHostMallocDefault));
+        HIPCHK(m, hipHostMalloc(reinterpret_cast<void**>(&st.smooth), (size_t)maxB * sizeof(int4), hipHostMallocDefault));
         if (!st.done) HIPCHK(m, hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
     }
     m->stage_cap_b = maxB; m->stage_cap_c = maxC;
@@ -1242,7 +1255,7 @@ void build_site_table(artalk_model* m) {
 // A change of site scales closes every open session (the device is idle: the caller synchronised): their history was written under the
 // old exponents' arithmetic, and a session never mixes exponents.  The ids are remembered so that a later step can say why it fails.
 void end_sessions_by_scales(artalk_model* m) {
-    for (const auto& kv : m->sess.open) { m->sess.ended_by_scales.insert(kv.first); m->sess.owner[kv.second] = 0; }
+    for (const auto& kv : m->sess.open) { m->sess.ended_by_scales.insert(kv.first); m->sess.owner[kv.second.slot] = 0; }
     m->sess.open.clear();
 }
 // The one way new site exponents take effect (artalk_set_site_scales, artalk_calibrate): `next` is a complete SiteExps.  When anything
@@ -1345,7 +1358,68 @@ int grow_sessions(artalk_model* m, int64_t n_slots) {
         ss.blocks.push_back(static_cast<float*>(p));
         ss.owner.resize(ss.owner.size() + artalk_model::kSessBlock, 0);
     }
+    if (ss.smooth_cap < (int64_t)ss.owner.size()) {      // the table of artalk_session_smooth: one row per slot is always enough (hipFree waits for the device)
+        if (ss.smooth_tab) (void)hipFree(ss.smooth_tab);
+        ss.smooth_tab = nullptr; ss.smooth_cap = 0;
+        HIPCHK(m, hipMalloc(&ss.smooth_tab, ss.owner.size() * (sizeof(float*) + sizeof(int4))));
+        ss.smooth_cap = (int64_t)ss.owner.size();
+    }
     return ARTALK_OK;
+}
+
+// ---------------------------------------------------------------------------------- streaming smoother: the checks, on the host alone
+// Which stream frames a smoother call emits: [max(0, seen - 4), last ? seen + nf : seen + nf - 4)  (model.py: smooth_span)
+void smooth_span(int64_t seen, int nf, bool last, int* first, int* count) {
+    const int64_t f = seen > kSavgolLag ? seen - kSavgolLag : 0;
+    *first = (int)f;
+    *count = (int)((last ? seen + nf : seen + nf - kSavgolLag) - f);
+}
+// one row of a smoother call, in two parts (a finished smoother is refused between them); `who` names the row in the message
+int smooth_row_range(const std::string& who, int nf, bool last, std::string* err) {
+    if (nf < 0 || nf > 100) { *err = who + ": n_frames " + std::to_string(nf) + " is outside 0..100"; return ARTALK_EINVAL; }
+    if (nf < 100 && !last) { *err = who + ": fewer than 100 frames (" + std::to_string(nf) + ") without `last`"; return ARTALK_EINVAL; }
+    return ARTALK_OK;
+}
+int smooth_row_length(const std::string& who, int64_t seen, int nf, bool last, std::string* err) {
+    if (seen < 0 || seen > INT_MAX - 2 * kSavgolMaxOut) { *err = who + ": frame count out of range"; return ARTALK_EINVAL; }
+    if (last && seen + nf < kSavgolCarry) { *err = who + ": savgol (mode='interp') needs window_length <= T (T >= 9)"; return ARTALK_EINVAL; }
+    return ARTALK_OK;
+}
+int smooth_stride_check(const char* fn, bool have_raw, bool need_raw, int64_t raw_stride, int64_t out_stride, int D, std::string* err) {
+    if (need_raw && !have_raw) { *err = std::string(fn) + ": no raw frames given"; return ARTALK_EINVAL; }
+    if (need_raw && raw_stride < 100LL * D) { *err = std::string(fn) + ": raw_stride is below 100 x " + std::to_string(D); return ARTALK_EINVAL; }
+    if (out_stride < (int64_t)kSavgolMaxOut * D) { *err = std::string(fn) + ": out_stride is below 104 x " + std::to_string(D); return ARTALK_EINVAL; }
+    return ARTALK_OK;
+}
+// every check of artalk_session_smooth, in the order the header lists them; on success st[i] is the state of ids[i].  Nothing is changed.
+int smooth_check(artalk_model::Sessions& ss, const int64_t* ids, int n, bool have_raw, int64_t raw_stride, const int* n_frames,
+                 const uint8_t* last, int64_t out_stride, int D, std::vector<artalk_model::Sessions::Open*>* st, std::string* err) {
+    st->assign((size_t)n, nullptr);
+    std::set<int64_t> listed;
+    for (int i = 0; i < n; ++i) {
+        const auto it = ss.open.find(ids[i]);
+        if (it == ss.open.end()) {
+            if (ss.ended_by_scales.count(ids[i])) {
+                *err = "session " + std::to_string(ids[i]) + ": the site scales changed since artalk_session_open; open the session again";
+                return ARTALK_ESTATE;
+            }
+            *err = "artalk_session_smooth: " + std::to_string(ids[i]) + " is not an open session";
+            return ARTALK_EINVAL;
+        }
+        if (!listed.insert(ids[i]).second) { *err = "artalk_session_smooth: session " + std::to_string(ids[i]) + " is listed twice"; return ARTALK_EINVAL; }
+        (*st)[i] = &it->second;
+    }
+    bool need_raw = false;
+    for (int i = 0; i < n; ++i) {
+        const int nf = n_frames ? n_frames[i] : 100;
+        const bool lst = last && last[i];
+        const std::string who = "artalk_session_smooth: session " + std::to_string(ids[i]);
+        if (int rc = smooth_row_range(who, nf, lst, err)) return rc;
+        if ((*st)[i]->smooth_done) { *err = who + " has been smoothed to its end (a `last` call was made)"; return ARTALK_ESTATE; }
+        if (int rc = smooth_row_length(who, (*st)[i]->seen, nf, lst, err)) return rc;
+        need_raw |= nf > 0;
+    }
+    return smooth_stride_check("artalk_session_smooth", have_raw, need_raw, raw_stride, out_stride, D, err);
 }
 // the device table of this call's slots (row i = slot[i]) through the pinned slot `stg`; the caller records stg->done afterwards
 int stage_session_slots(artalk_model* m, hipStream_t s, artalk_model::Stage* stg, const int* slot, int n) {
@@ -1418,6 +1492,7 @@ void artalk_destroy(artalk_model* m) {
     for (void* p : m->allocs) if (p) (void)hipFree(p);
     for (void* p : m->ws_allocs) if (p) (void)hipFree(p);
     for (float* p : m->sess.blocks) if (p) (void)hipFree(p);
+    if (m->sess.smooth_tab) (void)hipFree(m->sess.smooth_tab);
     delete m;
 }
 
@@ -1930,7 +2005,7 @@ int artalk_session_open(artalk_model* m, int n, const float* style_motion_dev, c
     for (int i = 0; i < n; ++i) {
         ids_out[i] = ss.next_id++;
         ss.owner[slot[i]] = ids_out[i];
-        ss.open.emplace(ids_out[i], slot[i]);
+        ss.open.emplace(ids_out[i], artalk_model::Sessions::Open{slot[i]});
     }
     return ARTALK_OK;
 }
@@ -1950,7 +2025,7 @@ int artalk_session_step(artalk_model* m, const int64_t* ids, int n, const float*
             return fail(m, ARTALK_EINVAL, "artalk_session_step: " + std::to_string(ids[i]) + " is not an open session");
         }
         if (!seen.insert(ids[i]).second) return fail(m, ARTALK_EINVAL, "artalk_session_step: session " + std::to_string(ids[i]) + " is listed twice");
-        slot[i] = it->second;
+        slot[i] = it->second.slot;
     }
     hipStream_t s;
     if (int rc = call_stream(m, stream, &s)) return rc;
@@ -1988,8 +2063,48 @@ int artalk_session_close(artalk_model* m, const int64_t* ids, int n) {
             return fail(m, ARTALK_EINVAL, "artalk_session_close: " + std::to_string(ids[i]) + " is not an open session (or is listed twice)");
     for (int i = 0; i < n; ++i) {
         const auto it = ss.open.find(ids[i]);
-        if (it != ss.open.end()) { ss.owner[it->second] = 0; ss.open.erase(it); }
+        if (it != ss.open.end()) { ss.owner[it->second.slot] = 0; ss.open.erase(it); }
         ss.ended_by_scales.erase(ids[i]);      // a session the scale change closed: only the note is dropped
+    }
+    return ARTALK_OK;
+}
+
+// The Savitzky-Golay filter of artalk_savgol for live sessions (savgol_stream_kernel): row i of raw_dev holds the n_frames[i] codes the last
+// artalk_session_step produced for ids[i]; the frames that have become final - everything up to 4 frames behind the newest, or up to the
+// end with last[i] - land in row i of out_dev, and first_out / count_out say which they are.  Two small table copies (slot pointers,
+// frame counts) through the pinned ring and one launch; no synchronisation, no status word, no workspace row: a lockstep session lives on, and the precision mode plays no part.
+int artalk_session_smooth(artalk_model* m, const int64_t* ids, int n, const float* raw_dev, int64_t raw_stride, const int* n_frames,
+                          const uint8_t* last, float* out_dev, int64_t out_stride, int* first_out, int* count_out, void* stream) {
+    if (!m || !ids || n <= 0 || !out_dev || !first_out || !count_out) return ARTALK_EINVAL;
+    artalk_model::Sessions& ss = m->sess;
+    // everything is checked before anything is enqueued or any session changes
+    std::vector<artalk_model::Sessions::Open*> st;
+    std::string err;
+    if (int rc = smooth_check(ss, ids, n, raw_dev != nullptr, raw_stride, n_frames, last, out_stride, m->cfg.motion_dim, &st, &err)) return fail(m, rc, err);
+    hipStream_t s;
+    if (int rc = call_stream(m, stream, &s)) return rc;
+    if (n > m->stage_cap_b) { if (int rc = ensure_stage(m, n, m->stage_cap_c)) return rc; }      // pinned tables only: the workspace stays
+    artalk_model::Stage* stg = nullptr;
+    if (int rc = next_stage(m, &stg)) return rc;
+    for (int i = 0; i < n; ++i) {
+        stg->slots[i] = m->sess_slot(st[i]->slot);
+        stg->smooth[i] = make_int4((int)st[i]->seen, n_frames ? n_frames[i] : 100, last && last[i] ? 1 : 0, 0);
+    }
+    float** slots_dev = static_cast<float**>(ss.smooth_tab);
+    int4* meta_dev = reinterpret_cast<int4*>(slots_dev + ss.smooth_cap);
+    HIPCHK(m, hipMemcpyAsync(slots_dev, stg->slots, (size_t)n * sizeof(float*), hipMemcpyHostToDevice, s));
+    HIPCHK(m, hipMemcpyAsync(meta_dev, stg->smooth, (size_t)n * sizeof(int4), hipMemcpyHostToDevice, s));
+    HIPCHK(m, hipEventRecord(stg->done, s));
+    stg->used = true;
+    launch_savgol_stream(slots_dev, meta_dev, (long)m->sess_carry_off(), raw_dev, (long)raw_stride, out_dev, (long)out_stride, n,
+                         m->cfg.motion_dim, s);
+    HIPCHK(m, hipGetLastError());
+    for (int i = 0; i < n; ++i) {
+        const int nf = n_frames ? n_frames[i] : 100;
+        const bool lst = last && last[i];
+        smooth_span(st[i]->seen, nf, lst, &first_out[i], &count_out[i]);
+        st[i]->seen += nf;
+        st[i]->smooth_done = lst;
     }
     return ARTALK_OK;
 }
@@ -2773,6 +2888,51 @@ int artalk_op_session_gather(const float* const* slots_dev, float* style, float*
     if (!slots_dev || n <= 0 || !op_session_rows(style, prev_in, prev_fdec, s16, p16, f16, &w)) return ARTALK_EINVAL;
     launch_session_gather(slots_dev, w, n, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+int artalk_op_savgol_stream(float* const* slots_dev, const float* raw, int64_t raw_stride, const int* seen, const int* n_frames,
+                            const uint8_t* last, float* out, int64_t out_stride, int n, void* stream) {
+    if (!slots_dev || !seen || !n_frames || !last || !out || n <= 0) return ARTALK_EINVAL;
+    std::string err;
+    bool need_raw = false;
+    for (int i = 0; i < n; ++i) {
+        const std::string who = "artalk_op_savgol_stream: row " + std::to_string(i);
+        if (int rc = smooth_row_range(who, n_frames[i], last[i] != 0, &err)) return rc;
+        if (int rc = smooth_row_length(who, seen[i], n_frames[i], last[i] != 0, &err)) return rc;
+        need_raw |= n_frames[i] > 0;
+    }
+    if (int rc = smooth_stride_check("artalk_op_savgol_stream", raw != nullptr, need_raw, raw_stride, out_stride, kOpMotionDim, &err)) return rc;
+    if (g_rows_dry_run) return ARTALK_OK;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int4> meta((size_t)n);
+    for (int i = 0; i < n; ++i) meta[i] = make_int4(seen[i], n_frames[i], last[i] ? 1 : 0, 0);
+    int4* dmeta = nullptr;
+    if (hipMalloc(&dmeta, (size_t)n * sizeof(int4)) != hipSuccess) return ARTALK_EHIP;
+    if (hipMemcpy(dmeta, meta.data(), (size_t)n * sizeof(int4), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(dmeta); return ARTALK_EHIP; }
+    launch_savgol_stream(slots_dev, dmeta, (long)slot_carry_off(kOpCodeDim), raw, (long)raw_stride, out, (long)out_stride, n, kOpMotionDim, s);
+    const hipError_t e1 = hipStreamSynchronize(s);
+    (void)hipFree(dmeta);
+    return (e1 == hipSuccess && hipGetLastError() == hipSuccess) ? ARTALK_OK : ARTALK_EHIP;
+}
+int artalk_op_session_smooth_check(const int64_t* open_ids, const int64_t* open_seen, const uint8_t* open_done, int n_open,
+                                   const int64_t* ended_ids, int n_ended, const int64_t* ids, int n, int have_raw, int64_t raw_stride,
+                                   const int* n_frames, const uint8_t* last, int64_t out_stride, int* first_out, int* count_out, char* msg,
+                                   int msg_len) {
+    if (n_open < 0 || n_ended < 0 || (n_open && (!open_ids || !open_seen || !open_done)) || (n_ended && !ended_ids) || !ids || n <= 0)
+        return ARTALK_EINVAL;
+    artalk_model::Sessions ss;
+    for (int i = 0; i < n_open; ++i) {
+        artalk_model::Sessions::Open o;
+        o.slot = i; o.seen = open_seen[i]; o.smooth_done = open_done[i] != 0;
+        ss.open.emplace(open_ids[i], o);
+    }
+    for (int i = 0; i < n_ended; ++i) ss.ended_by_scales.insert(ended_ids[i]);
+    std::vector<artalk_model::Sessions::Open*> st;
+    std::string err;
+    const int rc = smooth_check(ss, ids, n, have_raw != 0, raw_stride, n_frames, last, out_stride, kOpMotionDim, &st, &err);
+    if (msg && msg_len > 0) { std::strncpy(msg, err.c_str(), (size_t)msg_len - 1); msg[msg_len - 1] = 0; }
+    for (int i = 0; rc == ARTALK_OK && first_out && count_out && i < n; ++i)
+        smooth_span(st[i]->seen, n_frames ? n_frames[i] : 100, last && last[i], &first_out[i], &count_out[i]);
+    return rc;
 }
 int artalk_op_session_scatter(float* const* slots_dev, const float* style, const float* prev_in, const float* prev_fdec, int s16, int p16,
                               int f16, int n, int with_style, void* stream) {

@@ -210,6 +210,15 @@ void launch_style_finish(const float* feat /*[B*50,128]*/, const float* Ws, cons
 void launch_add_row(float* X, const float* v, int M, int D, hipStream_t s);
 // Savitzky-Golay post filter of reference inference.py:89-95 on device: in [T,106] -> out [T,106]
 void launch_savgol(const float* in, float* out, int T, int D, hipStream_t s);
+// The same filter for live sessions, bit for bit what launch_savgol gives on the concatenated clip, at a lag of kSavgolLag frames: the
+// last kSavgolCarry raw frames of a session stay in its pool slot (carry_off floats behind the slot's start).  Workgroup i serves session
+// i: meta[i] = {seen (raw frames consumed before), nf (valid rows of raw row i, <= 100), last, -}; T' = seen + nf.  It emits the stream
+// frames [max(0, seen - 4), last ? T' : T' - 4) into out row i (rows at index count and beyond stay untouched; raw rows at index nf and
+// beyond are not read) and leaves the last min(9, T') raw frames in the carry.  The caller has checked: nf == 100 unless last, T' >= 9
+// if last, raw_stride >= 100 * D, out_stride >= kSavgolMaxOut * D.  D = 106.
+constexpr int kSavgolLag = 4, kSavgolCarry = 9, kSavgolMaxOut = 104;
+void launch_savgol_stream(float* const* slots, const int4* meta, long carry_off, const float* raw, long raw_stride, float* out,
+                          long out_stride, int n, int D, hipStream_t s);
 
 double launch_mfma_f32_peak(float* out, int blocks, int iters, int nacc, hipStream_t s);   // calibration kernel, returns FLOPs
 // sinc resampler + channel mean: x [nch][n] -> out [n_out], taps [new][2*width+orig]

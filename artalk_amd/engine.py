@@ -100,17 +100,76 @@ class ARTAvatarInferEngine:
             style_motion = self.style_motion[0]
         return self.ARTalk.open_session(style_motion)
 
-    def stream_step(self, streams, chunks, n_valid=None):
+    def stream_step(self, streams, chunks, n_valid=None, smooth=False):
         """Next 4 seconds of the listed streams: ``chunks`` (n, 64000) -> (n, 100, 106) (with ``n_valid`` also the valid frame counts,
-        ``BitwiseARModel.step_sessions``), with ``fix_pose`` applied and dims 104: zeroed as ``inference`` does.  The Savitzky-Golay
-        smoothing of ``inference`` is NOT applied: its window reaches 4 frames into the future, which a live block does not have yet
-        (a streaming smoother is a separate piece of work)."""
-        res = self.ARTalk.step_sessions(streams, chunks, n_valid=n_valid)
+        ``BitwiseARModel.step_sessions``), with ``fix_pose`` applied and dims 104: zeroed as ``inference`` does.  These are the raw codes:
+        the Savitzky-Golay window of ``inference`` reaches 4 frames into the future, which a live block does not have yet.
+
+        ``smooth=True`` returns what ``inference`` returns instead, 4 frames (160 ms) late: ``(frames (n, 104, 106), spans)``, where the
+        first ``count`` rows of ``frames[i]`` are stream i's frames ``first .. first + count - 1`` of ``_postprocess`` of its whole clip,
+        bit for bit, and ``spans[i] = (first, count)`` - 96 frames on a stream's first step, 100 afterwards, everything that is left on
+        its last (``BitwiseARModel.smooth_sessions``; the filter's state, 9 raw frames, lives with the session).  With ``n_valid`` a
+        stream whose chunk has fewer than 100 valid frames ends there; a row with ``n_valid <= 0`` flushes a stream that has not ended
+        yet and is skipped (count 0) for one that has.  A stream that ends on a chunk boundary never says so: ``stream_flush`` ends it.
+        A stream that would end shorter than 9 frames raises ``ValueError`` before anything runs, as ``inference`` does for such a clip -
+        also a stream that was never stepped and is listed with ``n_valid <= 0``: that row is a flush of nothing.  A stream is
+        smoothed from its first step on or not at all: one that was stepped with ``smooth=False`` before raises ``RuntimeError``
+        (the smoother would filter across the gap)."""
+        if not smooth:
+            res = self.ARTalk.step_sessions(streams, chunks, n_valid=n_valid)
+            pred = res[0] if n_valid is not None else res
+            if self.fix_pose:
+                pred[..., 100:103] *= 0.0
+            pred[..., 104:] *= 0.0
+            return (pred, res[1]) if n_valid is not None else pred
+        m = self.ARTalk
+        n = len(streams)
+        if n_valid is None:
+            plan = [(100, False)] * n
+        else:      # the frame counts step_sessions is going to report, known before it runs
+            plan = [(m.valid_frames(st.fed, int(nv)), True) if int(nv) <= 0 or m.valid_frames(st.fed, int(nv)) < 100 else (100, False)
+                    for st, nv in zip(streams, n_valid)]
+        rows = [i for i, (st, (nf, last)) in enumerate(zip(streams, plan)) if not (st.smooth_done and nf == 0)]
+        for i in rows:
+            self._check_smoothable(streams[i], *plan[i])
+        res = m.step_sessions(streams, chunks, n_valid=n_valid)
         pred = res[0] if n_valid is not None else res
+        frames = torch.zeros(n, 104, pred.shape[-1], dtype=pred.dtype, device=pred.device)
+        spans = [(st.frames_seen, 0) for st in streams]
+        if rows:
+            sub, sub_spans = m.smooth_sessions([streams[i] for i in rows], pred if len(rows) == n else pred[rows],
+                                               [plan[i][0] for i in rows], [plan[i][1] for i in rows])
+            if len(rows) == n:
+                frames = sub
+            else:
+                frames[rows] = sub
+            for i, sp in zip(rows, sub_spans):
+                spans[i] = sp
+        return self._zero_dims(frames), spans
+
+    def stream_flush(self, streams):
+        """End streams that stopped on a chunk boundary, where no short chunk told ``stream_step(smooth=True)`` so: the 4 frames the
+        smoother still holds back, ``(frames (n, 4, 106), spans)``.  A stream that has ended already raises ``RuntimeError``."""
+        for st in streams:
+            self._check_smoothable(st, 0, True)
+        frames, spans = self.ARTalk.smooth_sessions(streams, None, [0] * len(streams), [True] * len(streams))
+        return self._zero_dims(frames)[:, :4], spans
+
+    def _check_smoothable(self, st, nf, last):
+        if st.smooth_done:
+            raise RuntimeError(f"session {st.id} has been smoothed to its end; open a new stream")
+        if st.frames_seen != 100 * st.steps:
+            raise RuntimeError(f"session {st.id} was stepped without smooth=True before ({st.frames_seen} frames smoothed in "
+                               f"{st.steps} steps): a stream is smoothed from its first step on")
+        if last and st.frames_seen + nf < 9:      # scipy raises for mode='interp' when window_length exceeds the signal length
+            raise ValueError("If mode is 'interp', window_length must be less than or equal to the size of x.")
+
+    def _zero_dims(self, frames):
+        """The rest of ``_postprocess``, after smoothing."""
         if self.fix_pose:
-            pred[..., 100:103] *= 0.0
-        pred[..., 104:] *= 0.0
-        return (pred, res[1]) if n_valid is not None else pred
+            frames[..., 100:103] *= 0.0
+        frames[..., 104:] *= 0.0
+        return frames
 
     def smooth_motion_savgol(self, motion_codes):
         """``smooth_motion_savgol`` (inference.py:89-95) without the host round trip: Savitzky-Golay (5, 2) on all dims,

@@ -81,15 +81,33 @@ class _BasicVAE:
         raise ValueError("Invalid shape of shape_params: {}".format(shape_params.shape))
 
 
+SMOOTH_LAG = 4          # half width of the widest Savitzky-Golay window of smooth_motion_savgol: the lag of the streaming smoother
+SMOOTH_MIN_FRAMES = 9   # scipy's mode='interp' refuses a clip shorter than the window
+SMOOTH_MAX_OUT = 104    # frames one smoother call can emit: the last call of a stream, 100 new frames plus the 4 held back
+
+
+def smooth_span(seen: int, nf: int, last: bool):
+    """Which stream frames a smoother call emits, ``(first, count)``: ``seen`` raw frames consumed before, ``nf`` new ones, ``last`` =
+    the stream ends with them.  A frame is final once 4 later frames exist, or the stream has ended (artalk_session_smooth)."""
+    first = max(0, seen - SMOOTH_LAG)
+    end = seen + nf if last else seen + nf - SMOOTH_LAG
+    return first, end - first
+
+
 class StreamSession:
     """One independent stream of ``BitwiseARModel.open_session``: ``id`` (the library's session id, never reused), ``fed`` (real samples
     fed so far), ``style_motion`` (kept for a recalibration on a step that trips the range guard), ``closed`` and ``close()``.  A session
-    is closed by ``close()``, by a range trip in ``step_sessions`` and by any change of the site scales (``why`` says which)."""
+    is closed by ``close()``, by a range trip in ``step_sessions`` and by any change of the site scales (``why`` says which).
+    ``steps`` counts the session's steps; ``frames_seen`` (raw frames the streaming smoother has consumed) and ``smooth_done`` (its
+    last call was made) mirror the library's state for ``smooth_sessions``."""
 
     def __init__(self, model, sid: int, style_motion=None):
         self._model = model
         self.id = int(sid)
         self.fed = 0
+        self.steps = 0
+        self.frames_seen = 0
+        self.smooth_done = False
         self.style_motion = style_motion
         self.closed = False
         self.why = None
@@ -734,17 +752,15 @@ class BitwiseARModel:
             self._trip_to_f32("session step")
             raise RuntimeError("artalk_amd: an activation left fp16's range during a session step; the model is now in f32 mode - "
                                "open the sessions again")
+        for sess in sessions:
+            sess.steps += 1
         res = [out]
         if n_valid is not None:
             frames = []
-            spc = self.cfg.samples_per_chunk
             for b, sess in enumerate(sessions):
                 before = sess.fed
                 sess.fed = before + int(n_valid[b])
-                if int(n_valid[b]) <= 0:
-                    frames.append(0)
-                    continue
-                frames.append(max(0, min(100, self.seq_length(sess.fed) - 100 * (before // spc))))
+                frames.append(self.valid_frames(before, int(n_valid[b])))
             res.append(frames)
         else:
             for sess in sessions:
@@ -752,6 +768,65 @@ class BitwiseARModel:
         if return_aux:
             res += [bits, hist]
         return res[0] if len(res) == 1 else tuple(res)
+
+    @torch.no_grad()
+    def smooth_sessions(self, sessions: Sequence[StreamSession], raw: Optional[torch.Tensor], n_frames: Optional[Sequence[int]] = None,
+                        last: Optional[Sequence[bool]] = None):
+        """The Savitzky-Golay filter of ``inference`` (inference.py:89-95) on live sessions (artalk_session_smooth): ``raw`` (n, 100, 106)
+        holds the codes ``step_sessions`` just returned for ``sessions``, ``n_frames[i]`` (default 100) of row i are valid and ``last[i]``
+        says that the stream ends with them.  Returns ``(frames (n, 104, 106), spans)``: the first ``count`` rows of ``frames[i]`` are the
+        stream's smoothed frames ``first .. first + count - 1`` with ``spans[i] = (first, count)`` (``smooth_span``) - bit for bit what the
+        filter gives on the whole clip, 4 frames late; the other rows are zero.  ``n_frames[i] == 0`` with ``last[i]`` flushes the 4
+        pending frames of a stream that ended on a chunk boundary (``raw`` may then be None).  Nothing synchronises; the 9 raw frames
+        carried between calls live in the session's pool slot and die with the session."""
+        n = len(sessions)
+        assert n > 0, "smooth_sessions needs at least one session"
+        for sess in sessions:
+            if sess.closed:
+                raise RuntimeError(f"session {sess.id} is closed ({sess.why}); open it again")
+        nf = [100] * n if n_frames is None else [int(v) for v in n_frames]
+        lst = [False] * n if last is None else [bool(v) for v in last]
+        assert len(nf) == n and len(lst) == n, "n_frames and last need one entry per session"
+        if raw is not None:
+            assert raw.dim() == 3 and raw.shape[0] == n and raw.shape[1] >= 100 and raw.shape[2] == self.cfg.motion_dim, \
+                f"expected ({n}, 100, {self.cfg.motion_dim}) raw frames"
+        dev = self._device
+        ids = (C.c_int64 * n)(*[sess.id for sess in sessions])
+        c_nf, c_last = (C.c_int32 * n)(*nf), (C.c_uint8 * n)(*[int(v) for v in lst])
+        first, count = (C.c_int32 * n)(), (C.c_int32 * n)()
+        with torch.cuda.device(dev):
+            x = None
+            if raw is not None:
+                x = raw.to(device=dev, dtype=torch.float32)
+                if x.stride(2) != 1 or x.stride(1) != x.shape[2]:
+                    x = x.contiguous()
+            out = torch.zeros(n, SMOOTH_MAX_OUT, self.cfg.motion_dim, dtype=torch.float32, device=dev)
+            if self._stream is None:
+                self._stream = torch.cuda.Stream(device=dev)
+            caller = torch.cuda.current_stream()
+            self._stream.wait_stream(caller)
+            rc = capi.lib().artalk_session_smooth(self._h, ids, n, capi.ptr(x), x.stride(0) if x is not None else 0, c_nf, c_last,
+                                                  capi.ptr(out), out.stride(0), first, count, C.c_void_p(self._stream.cuda_stream))
+            caller.wait_stream(self._stream)
+            for t in (x, out):
+                if t is not None:
+                    t.record_stream(self._stream)
+        if rc != capi.OK:
+            msg = self._err()
+            self._sync_sessions()
+            if rc == capi.EINVAL and "window_length" in msg:
+                raise ValueError("If mode is 'interp', window_length must be less than or equal to the size of x.")
+            raise RuntimeError("artalk_session_smooth failed: " + msg)
+        for i, sess in enumerate(sessions):
+            sess.frames_seen += nf[i]
+            sess.smooth_done = lst[i]
+        return out, [(int(first[i]), int(count[i])) for i in range(n)]
+
+    def valid_frames(self, fed_before: int, n_valid: int) -> int:
+        """Valid frames of a chunk that brings ``n_valid`` real samples to a stream that had ``fed_before`` (step_sessions' count)."""
+        if n_valid <= 0:
+            return 0
+        return max(0, min(100, self.seq_length(fed_before + n_valid) - 100 * (fed_before // self.cfg.samples_per_chunk)))
 
     # ------------------------------------------------------------------ geometry of app/models.py:66,78-80
     def seq_length(self, n_samples: int) -> int:

@@ -108,7 +108,8 @@ int artalk_stream_chunk(artalk_model* m, const float* audio_dev, int64_t chunk_s
 
 /* Independent streaming sessions: the same chunk step for streams that join and leave between steps (a server with live users).
  * What a stream carries from chunk to chunk - style condition [768], history tokens [181][768], decoder features of the previous
- * chunk [100][32], fp32 in every precision mode: 571 904 bytes - lives in a session pool owned by the model, outside the workspace:
+ * chunk [100][32], fp32 in every precision mode: 571 904 bytes, and behind them the streaming smoother's carry, the last 9 raw frames
+ * [9][106] padded to 16 bytes: 3 824 bytes - lives in a session pool owned by the model, outside the workspace:
  * device blocks of 32 slots that are never moved or freed before artalk_destroy.  A step gathers the listed sessions into workspace
  * rows 0..n-1 (one copy kernel), runs there what artalk_stream_chunk runs for n streams - the same rows, hence the same captured
  * graphs and the same bits - and scatters the new history back (one copy kernel); nothing synchronises.  Between library calls the
@@ -138,13 +139,35 @@ int artalk_stream_chunk(artalk_model* m, const float* audio_dev, int64_t chunk_s
  * artalk_session_close     frees the slots of the n listed sessions (host bookkeeping only; ordered by the caller against the steps
  *                          that still use them).  ARTALK_EINVAL, with nothing changed, for an id that is not open or listed twice; an id
  *                          that a scale change closed is accepted.
- * artalk_session_count     number of open sessions. */
+ * artalk_session_count     number of open sessions.
+ * artalk_session_smooth    smooth_motion_savgol (inference.py:89-95: savgol_filter (5, 2) on every dim, (9, 3) on dims 100:103, mode='interp')
+ *                          for live sessions: bit for bit what artalk_savgol gives on the session's concatenated codes, 4 frames (160 ms)
+ *                          late - the filter's half width.  Row i of raw_dev [n][raw_stride] holds the n_frames[i] codes (0..100) the last
+ *                          artalk_session_step produced for ids[i]; last[i] says that the stream ends with them.  n_frames, last: host [n]
+ *                          (NULL: 100 / 0 everywhere).  With T' = frames consumed so far + n_frames[i], row i of out_dev [n][out_stride]
+ *                          (out_stride >= 104 x 106) receives the stream frames [max(0, T' - n_frames[i] - 4), T' - 4), or up to T' with
+ *                          last[i]; first_out / count_out (host [n], filled before the call returns) say which: 96 frames on a stream's
+ *                          first call, 100 afterwards, up to 104 at the end.  Rows of out_dev at index count_out[i] and beyond are left
+ *                          untouched, rows of raw_dev at index n_frames[i] and beyond are not read.  n_frames[i] == 0 with last[i] is the
+ *                          flush of a stream that ended on a chunk boundary: the pending 4 frames, raw_dev row i (or a NULL raw_dev) is not
+ *                          read.  Checked before anything is enqueued or any session changes: ARTALK_EINVAL for an id that is not open or
+ *                          listed twice (ARTALK_ESTATE, with artalk_session_step's message, for one a scale change closed), for n_frames
+ *                          outside 0..100 or below 100 without last, for a last call that leaves the stream shorter than 9 frames (scipy
+ *                          refuses such a clip, and so does artalk_savgol) and for strides that are too small; ARTALK_ESTATE for a session
+ *                          whose last call was made already.  Two small table copies and one launch on `stream`: nothing synchronises, no status
+ *                          word is published, the workspace is not touched (a lockstep session lives on) and the precision mode plays no
+ *                          part.  The state - 9 raw frames in the slot, a frame count on the host - is born with artalk_session_open and
+ *                          dropped by whatever closes the session.  Like every call for one model, smooth calls are ordered by the
+ *                          caller: the device table of a call is reused by the next one, so two calls on streams that are not ordered
+ *                          against each other must not be in flight together. */
 int artalk_sessions_reserve(artalk_model* m, int max_sessions);
 int artalk_session_open(artalk_model* m, int n, const float* style_motion_dev, const uint8_t* has_style, int64_t* ids_out, void* stream);
 int artalk_session_step(artalk_model* m, const int64_t* ids, int n, const float* audio_dev, int64_t chunk_stride, float* out_motion_dev,
                         int64_t out_stride, uint8_t* out_bits_dev, uint8_t* out_hist_bits_dev, void* stream);
 int artalk_session_close(artalk_model* m, const int64_t* ids, int n);
 int artalk_session_count(const artalk_model* m);
+int artalk_session_smooth(artalk_model* m, const int64_t* ids, int n, const float* raw_dev, int64_t raw_stride, const int* n_frames,
+                          const uint8_t* last, float* out_dev, int64_t out_stride, int* first_out, int* count_out, void* stream);
 
 /* FLAME linear blend skinning: the consumer behind BITWISE_VAE.get_flame_verts (bitwise_vae.py:43-57) ->
  * FLAMEModel.forward(no_lmks=True) (app/flame_model/FLAME.py:117-142) -> lbs (app/flame_model/lbs.py:142-233).  Host arrays in
@@ -406,6 +429,19 @@ int artalk_op_session_gather(const float* const* slots_dev, float* style, float*
                              void* stream);
 int artalk_op_session_scatter(float* const* slots_dev, const float* style, const float* prev_in, const float* prev_fdec, int s16, int p16,
                               int f16, int n, int with_style, void* stream);
+/* savgol_stream_kernel alone (artalk_session_smooth without a model): slots_dev is a device table of n pool slots in the library's layout
+ * (the carry 142 976 floats behind the slot's start); seen, n_frames, last are host arrays [n]; raw [n][raw_stride], out [n][out_stride].
+ * The per-row and stride checks of artalk_session_smooth run before the device is touched (ARTALK_EINVAL); artalk_op_rows_dry_run is
+ * honoured; the stream is synchronised. */
+int artalk_op_savgol_stream(float* const* slots_dev, const float* raw, int64_t raw_stride, const int* seen, const int* n_frames,
+                            const uint8_t* last, float* out, int64_t out_stride, int n, void* stream);
+/* every check of artalk_session_smooth on a session table made up by the caller - open ids with their frame counts and finished flags, ids a
+ * scale change closed - and no device: returns what artalk_session_smooth would return before it enqueues anything, its message in msg,
+ * and on ARTALK_OK the spans in first_out / count_out (optional) */
+int artalk_op_session_smooth_check(const int64_t* open_ids, const int64_t* open_seen, const uint8_t* open_done, int n_open,
+                                   const int64_t* ended_ids, int n_ended, const int64_t* ids, int n, int have_raw, int64_t raw_stride,
+                                   const int* n_frames, const uint8_t* last, int64_t out_stride, int* first_out, int* count_out, char* msg,
+                                   int msg_len);
 /* *slot_dev = max(*slot_dev, bit pattern of max |x|) over rows x cols of an fp32 buffer of row pitch ld floats, or (is_p8) of the hi halves
  * of a P8 buffer times 2^-p8_exp; a NaN counts as +inf; rows r with r % junk_period >= junk_from (junk_period > 0) are skipped; rows == 0
  * changes nothing.  cols % 8 != 0, ld < cols or p8_exp outside [-8, 4]: ARTALK_EINVAL.  What artalk_calibrate reads its maxima with. */
