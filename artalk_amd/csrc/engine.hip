@@ -538,58 +538,27 @@ bool gemm(artalk_model* m, const GemmArgs& g0, hipStream_t s, const LnArgs* fuse
     g.graph_tag = m->in_body ? 1 : 0;
     g.cus = m->n_cus;
     g.status = m->precision == 1 ? (m->view ? m->view->status : m->ws.status) : nullptr;     // P8 range guard at the producers
-    bool split = false;
-    if (m->precision == 1 && !g.exact) {
-        g.Wp = packed_of(m, g.W);
-        split = gemm_f16s_eligible(g);
-    }
-    const bool bf16 = m->precision == 2 && !g.exact;
-    if (bf16) {
+    if (m->precision == 1 && !g.exact) g.Wp = packed_of(m, g.W);
+    if (m->precision == 2 && !g.exact) {
         g.Wb = bf16_of(m, g.W);
         if (!g.Wb || ((unsigned long long)g.Wb & 15) || (g.ldw & 7)) {
             m->err = "internal: bf16 GEMM without an aligned bf16 weight copy"; m->sticky_error = true; return false;
         }
         if (g.a_packed) { m->err = "internal: P8 activation handed to a bf16 GEMM"; m->sticky_error = true; return false; }
     }
-    if (g.a_packed && !split) { m->err = "internal: P8 activation handed to an fp32 GEMM"; m->sticky_error = true; return false; }
     const Workspace& cw = m->view ? *m->view : m->ws;
-    const bool p8 = split && gemm_p8_sm_eligible(g);      // P8 activation: the f16x3 planner picks kernel, split-K and fetch policy
-    P8Plan plan;
-    if (p8) {
-        plan = plan_gemm_p8(g, cw.splitk ? cw.splitk_floats : 0);
-    } else if (g.batch == 1 && g.amode == 0 && cw.splitk && g.K >= 256) {
-        // split-K for grids that would leave most CUs idle (small-M scale steps): S workgroups per output tile
-        const int tiles = bf16 ? gemm_bf16_tile_count(g) : gemm_tile_count(g, split);
-        if (tiles < m->splitk_tiles) {
-            int S = std::min(std::min(g.K / 64, (m->splitk_target + tiles - 1) / tiles), 16);
-            while (S > 1 && (int64_t)S * g.M * g.N > cw.splitk_floats) --S;
-            if (S > 1) g.splitk = S;
-        }
-    }
-    if (g.splitk > 1) g.partial = cw.splitk;
-    const bool dominant = !m->in_body && g.M > 0 &&
-                          (bf16 ? gemm_bf16_config(g) == 1 : p8 ? plan.dominant : split ? !g.a_packed && gemm_f16s_config(g) == 0 : gemm_config(g) == 4);
+    const GemmPolicy pol{m->precision, false, cw.splitk, cw.splitk_floats, m->splitk_tiles, m->splitk_target};
+    const GemmPlan plan = plan_gemm(g, pol, fuse_ln);
+    if (g.a_packed && plan.path == GEMM_F32) { m->err = "internal: P8 activation handed to an fp32 GEMM"; m->sticky_error = true; return false; }
+    const bool timed = m->profiling && plan.dominant && !m->in_body;
     size_t i0 = 0, i1 = 0;
-    if (m->profiling && dominant) next_event(m, s, &i0);
-    // second copy of the result in P8 (GemmArgs::c2): written by the kernel's epilogue where the plan says so, otherwise by a split
-    // pass over the fp32 result
-    float* const c2 = g.c2;
-    if (!plan.c2_fused) g.c2 = nullptr;
-    if (bf16) launch_gemm_bf16(g, s);
-    else if (p8) launch_gemm_p8(g, s);
-    else if (split) launch_gemm_f16s(g, s);
-    else launch_gemm(g, s);
-    bool fused = false;
-    if (g.splitk > 1) {
-        if (fuse_ln && splitk_reduce_ln_eligible(g, *fuse_ln)) { launch_splitk_reduce_ln(g, *fuse_ln, s); fused = true; }
-        else launch_splitk_reduce(g, s);
-    }
-    if (c2 && !plan.c2_fused) launch_pack_split(g.C, reinterpret_cast<unsigned int*>(c2), (long)g.M * g.N, false, s, g.status, g.c_exp);
-    if (m->profiling && dominant) {
+    if (timed) next_event(m, s, &i0);
+    run_gemm(g, plan, fuse_ln, s);
+    if (timed) {
         next_event(m, s, &i1);
         m->dom_events.emplace_back(i0, gemm_flops(g));
     }
-    return fused;
+    return plan.fused_ln;
 }
 
 // ---- intermediate taps (include/artalk_hip.h: artalk_set_tap) ----
@@ -2246,7 +2215,7 @@ int artalk_op_gemm_f16s_ex(const float* A, int64_t lda, const float* W, const fl
         launch_pack_split(A, ap, (long)M * lda, false, s, status_dev, a_exp);
         g.A = reinterpret_cast<const float*>(ap); g.a_packed = 1;
     }
-    launch_gemm_f16s(g, s);
+    run_gemm(g, plan_gemm(g, GemmPolicy{1, true}, nullptr), nullptr, s);
     (void)hipStreamSynchronize(s);
     (void)hipFree(wp);
     if (ap) (void)hipFree(ap);
@@ -2283,8 +2252,7 @@ int artalk_op_gemm_bf16(const float* A, int64_t lda, const float* W, const float
         if (nb > 1 || am) { (void)hipFree(wb); (void)hipFree(part); return ARTALK_EINVAL; }     // (split-K is a batch-1 plain-window form)
         g.splitk = S; g.partial = part;
     }
-    launch_gemm_bf16(g, s);
-    if (S > 1) launch_splitk_reduce(g, s);
+    run_gemm(g, plan_gemm(g, GemmPolicy{2}, nullptr), nullptr, s);
     (void)hipStreamSynchronize(s);
     (void)hipFree(wb);
     if (part) (void)hipFree(part);
@@ -2338,10 +2306,10 @@ int artalk_op_gemm_f16s_packed_ex(const void* A, int a_packed, int64_t lda, cons
         if (cfg == 13) cfg = 99;
         else if (cfg == 29 || cfg == 33) cfg = 28;
         else if (cfg == 30) cfg = 31;
-        const bool small = cfg == 20 || cfg == 23 || cfg == 24 || cfg == 28 || cfg == 31;
-        if (!a_packed || !(small || cfg == 7 || cfg == 8 || cfg == 12 || cfg == 99)) return ARTALK_EINVAL;
+        const int cls = gemm_p8_class(cfg);
+        if (!a_packed || (cls == P8_NONE && cfg != 99)) return ARTALK_EINVAL;
         g.force_cfg = cfg == 99 ? -1 : cfg;      // 99: the planner's own choice (without split-K)
-        if (small) {     // bits 8-15: split-K factor (slabs in a temporary)
+        if (cls == P8_SMALL) {     // bits 8-15: split-K factor (slabs in a temporary)
             g.w_nt = (force_cfg >> 16) & 1;      // tuning: bit 16 = non-temporal weight pieces
             if (S > 1) {
                 const size_t need = (size_t)S * M * N * 4;
@@ -2358,16 +2326,10 @@ int artalk_op_gemm_f16s_packed_ex(const void* A, int a_packed, int64_t lda, cons
                 g.splitk = S; g.partial = g_op_scratch;
             }
         }
-        const P8Plan plan = plan_gemm_p8(g, 0);
-        // the second copy as the model's gemm() makes it: by the kernel's epilogue where the plan says so, otherwise by a split pass
-        if (!plan.c2_fused) g.c2 = nullptr;
-        launch_gemm_p8(g, (hipStream_t)stream);
-        if (g.splitk > 1) launch_splitk_reduce(g, (hipStream_t)stream);
-        if (c2_u32 && !plan.c2_fused)
-            launch_pack_split(g.C, (unsigned int*)c2_u32, (long)g.M * g.N, false, (hipStream_t)stream, g.status, g.c_exp);
-    } else {
-        launch_gemm_f16s(g, (hipStream_t)stream);
     }
+    const GemmPlan plan = plan_gemm(g, GemmPolicy{1, force_cfg < 2}, nullptr);
+    if (force_cfg >= 2 && plan.path != GEMM_P8) return ARTALK_EINVAL;      // (a P8 row pitch the LDS-DMA kernels cannot read)
+    run_gemm(g, plan, nullptr, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
 }
 
@@ -2388,7 +2350,7 @@ int artalk_op_gemm_p8_plan(int M, int N, int K, int residual) {
     g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldc = N; g.a_packed = 1;
     g.Wp = reinterpret_cast<const unsigned int*>(16);      // only its presence and alignment are looked at (so are R's)
     if (residual) { g.R = reinterpret_cast<const float*>(16); g.ldr = N; }
-    plan_gemm_p8(g, 0);
+    plan_gemm(g, GemmPolicy{1}, nullptr);
     return g.force_cfg;
 }
 
@@ -2496,18 +2458,15 @@ int artalk_op_gemm_rows(const artalk_op_gemm_rows_args* a, void* stream) {
         if ((a->R && a->ldr % 4 != 0) || (a->gate && a->ldg % 4 != 0)) return ARTALK_EINVAL;
     }
     // tile configuration and split
-    int cfg = (a->force_cfg == -1 || a->force_cfg == 99) ? -1 : a->force_cfg;
-    if (cfg != -1) {
-        const bool ok = a->mode == 0 ? (cfg >= 1 && cfg <= 4) : a->mode == 2 ? (cfg >= 0 && cfg <= 2)
-                        : (cfg == 7 || cfg == 8 || cfg == 12 || cfg == 20 || cfg == 23 || cfg == 24 || cfg == 28 || cfg == 31);
-        if (!ok) return ARTALK_EINVAL;
-    }
+    const int cfg = (a->force_cfg == -1 || a->force_cfg == 99) ? -1 : a->force_cfg;
+    if (cfg != -1 && !(a->mode == 0 ? (cfg >= 1 && cfg <= 4) : a->mode == 2 ? (cfg >= 0 && cfg <= 2) : gemm_p8_class(cfg) != P8_NONE))
+        return ARTALK_EINVAL;
     if (a->splitk < 0 || a->splitk > 16 || (a->splitk > 1 && 32 * a->splitk > K)) return ARTALK_EINVAL;
     // column groups
     const int G = a->ngrp ? N / a->ngrp : 1;
     if (a->ngrp) {
         if (!p8 || a->ngrp < 0 || a->ngrp % 128 != 0 || N % a->ngrp != 0 || a->grpW < 0 || a->grpB < 0 || a->grpC < 0 || a->grpW % 8 != 0 ||
-            a->grpB % 4 != 0 || a->grpC % 4 != 0 || a->gate || a->R || a->ln_Y || a->splitk > 1 || (cfg != -1 && cfg != 8))
+            a->grpB % 4 != 0 || a->grpC % 4 != 0 || a->gate || a->R || a->ln_Y || a->splitk > 1 || (cfg != -1 && gemm_p8_class(cfg) != P8_GROUPS))
             return ARTALK_EINVAL;
     }
     const int64_t gw = a->ngrp ? a->ngrp : N;      // columns one group (or the whole launch) touches from its base
@@ -2546,56 +2505,33 @@ int artalk_op_gemm_rows(const artalk_op_gemm_rows_args* a, void* stream) {
     g.gate = a->gate; g.ldg = a->ldg; g.gmap = RowMap{a->gmap[0], a->gmap[1], a->gmap[2]}; g.R = a->R; g.ldr = a->ldr;
     g.M = M; g.N = N; g.K = K; g.act = a->act; g.force_cfg = cfg; g.status = a->status_dev;
     g.ngrp = a->ngrp; g.grpW = a->grpW; g.grpB = a->grpB; g.grpC = a->grpC;
-    int S = a->splitk > 1 ? a->splitk : 1;
-    if (p8) {
-        g.Wp = reinterpret_cast<const unsigned int*>(16);      // the planner looks at its presence only; the copy is made below
-        if (a->ngrp && cfg == -1 && !gemm_p8_eligible(g)) return ARTALK_EINVAL;
-        const bool own_split = a->splitk == 0 && cfg == -1;
-        g.splitk = 1;
-        plan_gemm_p8(g, own_split ? (int64_t)8 * M * N : 0);
-        const bool small = g.force_cfg == 20 || g.force_cfg == 23 || g.force_cfg == 24 || g.force_cfg == 28 || g.force_cfg == 31;
-        if (a->ngrp && g.force_cfg != 8) return ARTALK_EINVAL;
-        if (S > 1 && !small) return ARTALK_EINVAL;
-        if (own_split) S = g.splitk;
-        g.splitk = S;
-    } else {
-        g.splitk = S;
-    }
-    bool fused = false;
-    if (a->ln_Y) {
-        g.partial = reinterpret_cast<float*>(16);      // (eligibility looks at its alignment; hipMalloc's is at least that)
-        fused = S > 1 && splitk_reduce_ln_eligible(g, ln);
-        if (!fused && !ident_c) return ARTALK_EINVAL;      // launch_layernorm reads x as dense rows
-    }
-    if (g_rows_dry_run) {
-        if (a->used_cfg) *a->used_cfg = a->mode == 0 ? gemm_config(g) : a->mode == 2 ? gemm_bf16_config(g) : g.force_cfg;
-        if (a->used_splitk) *a->used_splitk = S;
-        if (a->fused_ln) *a->fused_ln = fused ? 1 : 0;
-        return ARTALK_OK;
-    }
+    // a forced split is kept; with splitk 0 and no forced configuration the f16x3 planner may split on its own (the other families'
+    // small-grid rule stays off).  The planner looks at the presence of Wp and the alignment of the slabs only: both are made below.
+    g.splitk = a->splitk > 1 ? a->splitk : 1;
+    if (p8) g.Wp = reinterpret_cast<const unsigned int*>(16);
+    const GemmPolicy pol{a->mode, false, reinterpret_cast<float*>(16), p8 && a->splitk == 0 && cfg == -1 ? (int64_t)8 * M * N : 0};
+    const GemmPlan plan = plan_gemm(g, pol, a->ln_Y ? &ln : nullptr);
+    if (a->ngrp && gemm_p8_class(plan.cfg) != P8_GROUPS) return ARTALK_EINVAL;
+    if (p8 && a->splitk > 1 && gemm_p8_class(plan.cfg) != P8_SMALL) return ARTALK_EINVAL;
+    if (a->ln_Y && !plan.fused_ln && !ident_c) return ARTALK_EINVAL;      // launch_layernorm reads x as dense rows
+    if (a->used_cfg) *a->used_cfg = plan.cfg;
+    if (a->used_splitk) *a->used_splitk = g.splitk;
+    if (a->fused_ln) *a->fused_ln = plan.fused_ln ? 1 : 0;
+    if (g_rows_dry_run) return ARTALK_OK;
     // ---- the device from here on
     hipStream_t s = (hipStream_t)stream;
     void* wcopy = nullptr;
     float* part = nullptr;
     if (a->mode != 0 && hipMalloc(&wcopy, (size_t)w_last * (p8 ? 4 : 2)) != hipSuccess) return ARTALK_EHIP;
-    if (S > 1 && hipMalloc(&part, (size_t)S * M * N * 4) != hipSuccess) { if (wcopy) (void)hipFree(wcopy); return ARTALK_EHIP; }
+    if (g.splitk > 1 && hipMalloc(&part, (size_t)g.splitk * M * N * 4) != hipSuccess) { if (wcopy) (void)hipFree(wcopy); return ARTALK_EHIP; }
     g.partial = part;
     if (p8) { launch_pack_split(a->W, (unsigned int*)wcopy, w_last, true, s); g.Wp = (const unsigned int*)wcopy; }
     if (a->mode == 2) { launch_pack_bf16(a->W, wcopy, w_last, s); g.Wb = wcopy; }
-    if (a->mode == 0) launch_gemm(g, s);
-    else if (p8) launch_gemm_p8(g, s);
-    else launch_gemm_bf16(g, s);
-    if (S > 1) {
-        if (fused) launch_splitk_reduce_ln(g, ln, s);
-        else launch_splitk_reduce(g, s);
-    }
-    if (a->ln_Y && !fused) launch_layernorm(ln, s);
+    run_gemm(g, plan, &ln, s);
+    if (a->ln_Y && !plan.fused_ln) launch_layernorm(ln, s);
     const hipError_t e1 = hipStreamSynchronize(s);
     if (wcopy) (void)hipFree(wcopy);
     if (part) (void)hipFree(part);
-    if (a->used_cfg) *a->used_cfg = a->mode == 0 ? gemm_config(g) : a->mode == 2 ? gemm_bf16_config(g) : g.force_cfg;
-    if (a->used_splitk) *a->used_splitk = S;
-    if (a->fused_ln) *a->fused_ln = fused ? 1 : 0;
     return (e1 == hipSuccess && hipGetLastError() == hipSuccess) ? ARTALK_OK : ARTALK_EHIP;
 }
 
@@ -2794,8 +2730,8 @@ int artalk_op_posconv_rows(int mode, const float* X, int64_t x_elems, const floa
         g.amode = 1; g.pc_T = T; g.pc_tstride = Ts; g.pc_pad = taps / 2; g.pc_cin = cg;
         g.N = cg; g.force_cfg = force_cfg;
         g.batch = groups; g.sA = cg; g.sW = (long)cg * K; g.sBias = bias ? cg : 0; g.sC = cg; g.sR = R ? cg : 0;
-        if (mode == 2) { launch_pack_bf16(W, wcopy, H * K, s); g.Wb = wcopy; launch_gemm_bf16(g, s); }
-        else launch_gemm(g, s);
+        if (mode == 2) { launch_pack_bf16(W, wcopy, H * K, s); g.Wb = wcopy; }
+        run_gemm(g, plan_gemm(g, GemmPolicy{mode}, nullptr), nullptr, s);
     }
     const hipError_t e1 = hipStreamSynchronize(s);
     if (wcopy) (void)hipFree(wcopy);

@@ -17,6 +17,7 @@
 // hi halves + 16 bytes of lo halves), so a packed matrix has the same size, pitch and 16-byte loads as the fp32 one and a
 // 16-byte chunk is an MFMA fragment.  LDS rows (register-staged kernel) hold the hi plane (BK halves) followed by the lo
 // plane, padded to 144 bytes (conflict-free ds_read_b128 for the 32x32x16 operand map: lane (r,h) holds k = 8h..8h+7).
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
@@ -1627,7 +1628,7 @@ static void launch_p8_sm_cfg(const GemmArgs& g, hipStream_t s) {
     if (g.graph_tag) ARTALK_LAUNCH((gemm_p8_sm_kernel<BM, BN, STAGES, 1>), dim3(tiles, g.splitk), dim3(256), lds, s, g);
     else ARTALK_LAUNCH((gemm_p8_sm_kernel<BM, BN, STAGES, 0>), dim3(tiles, g.splitk), dim3(256), lds, s, g);
 }
-bool gemm_p8_sm_eligible(const GemmArgs& g) {
+static bool gemm_p8_sm_eligible(const GemmArgs& g) {      // both operands in P8, any grid
     return g.Wp != nullptr && g.a_packed && g.amode == 0 && g.batch == 1 && g.K % 32 == 0 && (g.lda % 8) == 0;
 }
 template <int STAGES>
@@ -1763,7 +1764,7 @@ bool gemm_p8_eligible(const GemmArgs& g) {
 // split in 3 vs 13.2.  A split 768-wide result also gets its LayerNorm for free (the engine's fused reduce + LayerNorm).
 static int plan_gemm_p8_small(GemmArgs& g, int64_t splitk_floats) {
     if (g.K < 256) return 20;
-    const int tiles = gemm_tile_count(g, true);
+    const int tiles = ((g.M + 63) / 64) * ((g.N + 63) / 64);      // 64x64 tiles
     int S = 1, cfg = -1;
     if (g.K >= 2048) {
         if (tiles <= 24) { S = 8; cfg = 23; }
@@ -1800,30 +1801,8 @@ static int plan_gemm_p8_small(GemmArgs& g, int64_t splitk_floats) {
     if (g.M <= 160) g.w_nt = 1;
     return cfg < 0 ? 20 : cfg;
 }
-P8Plan plan_gemm_p8(GemmArgs& g, int64_t splitk_floats) {
-    int cfg = g.force_cfg;
-    // a forced configuration the shape cannot take: the big tiles fall back to the persistent 128x128 kernel, that one (it needs the
-    // 16-byte epilogue path) to the plan, the ping-pong kernel to the mid-grid one
-    if ((cfg == 7 || cfg == 12) && !p8_big_ok(g)) cfg = 8;
-    if (cfg == 8 && !epi_vec_host(g)) cfg = -1;
-    if (cfg == 31 && !gemm_p8_pp_ok(g)) cfg = 28;
-    if (cfg < 0 && gemm_p8_eligible(g)) {
-        const int v = gemm_p8_variant(g);
-        cfg = v == 1 ? 7 : (v == 2 ? 12 : 8);
-    }
-    if (cfg < 0) { g.force_cfg = -1; cfg = plan_gemm_p8_small(g, splitk_floats); }
-    g.force_cfg = cfg;
-    P8Plan p;
-    p.dominant = cfg == 7 || cfg == 12;
-    // the second P8 copy of the result (GemmArgs::c2) comes from the small-grid kernel's epilogue when that kernel finishes the tiles
-    // itself, through the epilogue's 16-byte path (every pointer and row start aligned)
-    p.c2_fused = g.c2 && (cfg == 20 || cfg == 23 || cfg == 24) && g.splitk == 1 && !g.c_p8 && (g.N % 8) == 0 && (g.ldc % 8) == 0 &&
-                 !g.gate && (g.ldr % 4) == 0 &&
-                 (((unsigned long long)g.C | (unsigned long long)g.c2 | (unsigned long long)g.bias | (unsigned long long)g.R) & 15) == 0;
-    return p;
-}
 
-// Launches the planned configuration (g.force_cfg, plan_gemm_p8):
+// Launches the planned configuration (g.force_cfg, plan_gemm); gemm_p8_class below is the list of them:
 //   large grid: 7 / 12 = gemm_p8_big_kernel with 256 x 256 / 320 x 256 tiles (persistent, one workgroup per CU), 8 = gemm_p8_2wgp_kernel
 //     (persistent 128 x 128, two workgroups per CU, deferred epilogue);
 //   small grid: 20 = gemm_p8_sm_kernel, 64x64 x 4 stages; deep rings for the split-K launches of the small scale steps, where a
@@ -1836,7 +1815,7 @@ P8Plan plan_gemm_p8(GemmArgs& g, int64_t splitk_floats) {
 // kernel lost registers to it): their P8 results (q|k|v, FFN hidden) are consumed by the attention kernel and by the next GEMM +
 // LayerNorm, an out-of-range value turns into inf / NaN there, and those producers (attention output, LayerNorm) carry the
 // guard - one kernel later instead of in place.
-void launch_gemm_p8(const GemmArgs& g0, hipStream_t s) {
+static void launch_gemm_p8(const GemmArgs& g0, hipStream_t s) {
     if (g0.M <= 0 || g0.N <= 0) return;
     GemmArgs g = g0;
     switch (g.force_cfg) {
@@ -1848,6 +1827,14 @@ void launch_gemm_p8(const GemmArgs& g0, hipStream_t s) {
         case 23: launch_p8_sm_cfg<64, 64, 8>(g, s); break;
         case 24: launch_p8_sm_cfg<64, 64, 5>(g, s); break;
         default: launch_p8_sm_cfg<64, 64, 4>(g, s); break;
+    }
+}
+int gemm_p8_class(int cfg) {
+    switch (cfg) {
+        case 7: case 12: return P8_BIG;
+        case 8: return P8_GROUPS;
+        case 20: case 23: case 24: case 28: case 31: return P8_SMALL;
+        default: return P8_NONE;
     }
 }
 
@@ -1867,7 +1854,7 @@ static void launch_f16s_cfg(const GemmArgs& g, hipStream_t s) {
 }
 
 // 0: 128x128 (dominant kernel of the split mode), 1: 64x64
-int gemm_f16s_config(const GemmArgs& g) {
+static int gemm_f16s_config(const GemmArgs& g) {
     if (g.force_cfg >= 0) return g.force_cfg;
     if (g.amode == 1) return 1;   // N = 64 per group
     // 64x64 tiles (4-5 workgroups/CU) beat 128x128 (2/CU) until the grid is several waves deep: M=3200,N=3072,K=768 runs at
@@ -1875,16 +1862,79 @@ int gemm_f16s_config(const GemmArgs& g) {
     const long t128 = (long)((g.M + 127) / 128) * ((g.N + 127) / 128);
     return t128 >= 1024 ? 0 : 1;
 }
+static int gemm_f16s_tile_count(const GemmArgs& g) {
+    const int b = gemm_f16s_config(g) == 0 ? 128 : 64;
+    return ((g.M + b - 1) / b) * ((g.N + b - 1) / b);
+}
 
-bool gemm_f16s_eligible(const GemmArgs& g) {
+static bool gemm_f16s_eligible(const GemmArgs& g) {
     if (g.amode == 1) return g.Wp != nullptr && !g.a_packed && g.splitk == 1 && g.K % 32 == 0 && g.pc_cin % 32 == 0;
     return g.Wp != nullptr && g.batch == 1 && g.K % 32 == 0;
 }
 
-void launch_gemm_f16s(const GemmArgs& g, hipStream_t s) {
+static void launch_gemm_f16s(const GemmArgs& g, hipStream_t s) {
     if (g.M <= 0 || g.N <= 0) return;
     if (gemm_f16s_config(g) == 0) launch_f16s_cfg<128, 128, 2, 2>(g, s);
     else launch_f16s_cfg<64, 64, 2, 2>(g, s);
+}
+
+// ---- the GEMM dispatch of every family (kernels.h: plan_gemm / run_gemm)
+GemmPlan plan_gemm(GemmArgs& g, const GemmPolicy& p, const LnArgs* fuse_ln) {
+    GemmPlan plan;
+    const bool f16s = p.precision == 1 && !g.exact && gemm_f16s_eligible(g);
+    plan.path = p.precision == 2 && !g.exact ? GEMM_BF16 : !f16s ? GEMM_F32 : !p.reg_staged && gemm_p8_sm_eligible(g) ? GEMM_P8 : GEMM_F16S;
+    const int64_t budget = p.slabs ? p.slab_floats : 0;
+    if (plan.path == GEMM_P8) {
+        // P8 activation: kernel, split-K and fetch policy of the f16x3 plan; a forced split leaves it the kernel only
+        const int forced = g.splitk;
+        g.splitk = 1;
+        int cfg = g.force_cfg;
+        // a forced configuration the shape cannot take: the big tiles fall back to the persistent 128x128 kernel, that one (it needs the
+        // 16-byte epilogue path) to the plan, the ping-pong kernel to the mid-grid one
+        if ((cfg == 7 || cfg == 12) && !p8_big_ok(g)) cfg = 8;
+        if (cfg == 8 && !epi_vec_host(g)) cfg = -1;
+        if (cfg == 31 && !gemm_p8_pp_ok(g)) cfg = 28;
+        if (cfg < 0 && gemm_p8_eligible(g)) {
+            const int v = gemm_p8_variant(g);
+            cfg = v == 1 ? 7 : (v == 2 ? 12 : 8);
+        }
+        if (cfg < 0) cfg = plan_gemm_p8_small(g, forced > 1 ? 0 : budget);
+        g.force_cfg = cfg;
+        if (forced > 1) g.splitk = forced;
+    } else if (g.splitk == 1 && g.batch == 1 && g.amode == 0 && g.K >= 256) {
+        // split-K for grids that would leave most CUs idle (small-M scale steps): S workgroups per output tile
+        const int tiles = plan.path == GEMM_BF16 ? gemm_bf16_tile_count(g) : f16s ? gemm_f16s_tile_count(g) : gemm_tile_count(g);
+        if (tiles < p.splitk_tiles) {
+            int S = std::min(std::min(g.K / 64, (p.splitk_target + tiles - 1) / tiles), 16);
+            while (S > 1 && (int64_t)S * g.M * g.N > budget) --S;
+            if (S > 1) g.splitk = S;
+        }
+    }
+    if (g.splitk > 1 && !g.partial) g.partial = p.slabs;
+    plan.cfg = plan.path == GEMM_BF16 ? gemm_bf16_config(g) : plan.path == GEMM_P8 ? g.force_cfg : f16s ? gemm_f16s_config(g) : gemm_config(g);
+    plan.dominant = g.M > 0 && (plan.path == GEMM_BF16 ? plan.cfg == 1 : plan.path == GEMM_P8 ? gemm_p8_class(plan.cfg) == P8_BIG
+                                : f16s ? !g.a_packed && plan.cfg == 0 : plan.cfg == 4);
+    // the second P8 copy of the result (GemmArgs::c2) comes from the small-grid kernel's epilogue when that kernel finishes the tiles
+    // itself, through the epilogue's 16-byte path (every pointer and row start aligned)
+    plan.c2_fused = plan.path == GEMM_P8 && g.c2 && (plan.cfg == 20 || plan.cfg == 23 || plan.cfg == 24) && g.splitk == 1 && !g.c_p8 &&
+                    (g.N % 8) == 0 && (g.ldc % 8) == 0 && !g.gate && (g.ldr % 4) == 0 &&
+                    (((unsigned long long)g.C | (unsigned long long)g.c2 | (unsigned long long)g.bias | (unsigned long long)g.R) & 15) == 0;
+    plan.fused_ln = g.splitk > 1 && fuse_ln && splitk_reduce_ln_eligible(g, *fuse_ln);
+    return plan;
+}
+
+void run_gemm(const GemmArgs& g0, const GemmPlan& plan, const LnArgs* fuse_ln, hipStream_t s) {
+    GemmArgs g = g0;
+    if (!plan.c2_fused) g.c2 = nullptr;
+    switch (plan.path) {
+        case GEMM_BF16: launch_gemm_bf16(g, s); break;
+        case GEMM_P8: launch_gemm_p8(g, s); break;
+        case GEMM_F16S: launch_gemm_f16s(g, s); break;
+        default: launch_gemm(g, s); break;
+    }
+    if (plan.fused_ln) launch_splitk_reduce_ln(g, *fuse_ln, s);
+    else if (g.splitk > 1) launch_splitk_reduce(g, s);
+    if (g0.c2 && !plan.c2_fused) launch_pack_split(g.C, reinterpret_cast<unsigned int*>(g0.c2), (long)g.M * g.N, false, s, g.status, g.c_exp);
 }
 
 }  // namespace artalk

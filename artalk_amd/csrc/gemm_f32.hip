@@ -337,10 +337,9 @@ void launch_splitk_reduce_ln(const GemmArgs& g, const LnArgs& ln, hipStream_t s)
         default: ARTALK_LAUNCH(splitk_reduce_ln768_kernel<8>, grid, dim3(256), 0, s, g, ln); break;
     }
 }
-int gemm_tile_count(const GemmArgs& g, bool f16s) {
+int gemm_tile_count(const GemmArgs& g) {
     int bm, bn;
-    if (f16s) { if (gemm_f16s_config(g) == 0) { bm = 128; bn = 128; } else { bm = 64; bn = 64; } }
-    else switch (gemm_config(g)) {
+    switch (gemm_config(g)) {
         case 4: bm = 128; bn = 128; break;
         case 1: bm = 128; bn = 64; break;
         case 2: bm = 64; bn = 64; break;

@@ -62,7 +62,7 @@ struct GemmArgs {
     int exact = 0;                       // 1: decision-critical GEMM (logit / code heads), always on the fp32 MFMA path
     const float* bias = nullptr;
     float* C = nullptr; long ldc = 0; RowMap cmap = {INT_MAX, 0, 0};
-    float* c2 = nullptr;                 // optional: the (fp32) result once more in the P8 split format, same pitch (engine gemm(): the small-grid kernel writes both, otherwise a split pass follows; needs ldc == N and an identity cmap)
+    float* c2 = nullptr;                 // optional: the (fp32) result once more in the P8 split format, same pitch (run_gemm: the small-grid kernel writes both, otherwise a split pass follows; needs ldc == N and an identity cmap)
     const float* gate = nullptr; long ldg = 0; RowMap gmap = {INT_MAX, 0, 0};
     const float* R = nullptr; long ldr = 0;     // residual, addressed with cmap; may alias C
     int M = 0, N = 0, K = 0;
@@ -92,32 +92,45 @@ struct LnArgs;
 // split-K epilogue pass fused with the AdaLN-modulated LayerNorm that consumes the 768-wide result (AR residual stream)
 bool splitk_reduce_ln_eligible(const GemmArgs& g, const LnArgs& ln);
 void launch_splitk_reduce_ln(const GemmArgs& g, const LnArgs& ln, hipStream_t s);
-int gemm_tile_count(const GemmArgs& g, bool f16s);             // output tiles of the configuration launch_gemm[_f16s] would pick
+int gemm_config(const GemmArgs& g);   // 4: 128x128 BK16 (dominant kernel), 2: 64x64, 1: 128x64, 3: 32x128
+int gemm_tile_count(const GemmArgs& g);       // output tiles of that configuration
 // fp32-accurate GEMM on the fp16 matrix cores by operand splitting (gemm_f16s.hip)
 void launch_pack_split(const float* w, unsigned int* out, long n, bool is_weight, hipStream_t s, int* status = nullptr, int p8_exp = kActExp);
-bool gemm_f16s_eligible(const GemmArgs& g);
-int gemm_f16s_config(const GemmArgs& g);     // register-staged kernel: 0: 128x128, 1: 64x64
-void launch_gemm_f16s(const GemmArgs& g, hipStream_t s);
 bool gemm_p8_eligible(const GemmArgs& g);      // both operands in P8 and a large grid: the persistent LDS-DMA kernels (gemm_p8_big / _2wgp)
-bool gemm_p8_sm_eligible(const GemmArgs& g);   // both operands in P8, any grid: what plan_gemm_p8 / launch_gemm_p8 take
-// The f16x3 GEMM planner, the one place the kernel of a GEMM with a P8 activation is chosen: sets g.force_cfg (a forced configuration
-// the shape cannot take falls back), and for an unforced small grid g.splitk (its slabs, S x M x N floats, within splitk_floats; the
-// caller points g.partial at them) and g.w_nt.  launch_gemm_p8 launches the planned configuration.
-struct P8Plan {
-    bool c2_fused = false;      // the kernel's epilogue writes GemmArgs::c2 (otherwise a split pass over the fp32 result must)
-    bool dominant = false;      // a big-tile kernel (the step's dominant GEMMs, for profiling)
-};
-P8Plan plan_gemm_p8(GemmArgs& g, int64_t splitk_floats);
-void launch_gemm_p8(const GemmArgs& g, hipStream_t s);
 void gemm_p8_prepare();      // one-time kernel attributes (call once per process before the first captured launch)
 // bf16 GEMM (precision mode 2, gemm_bf16.hip): bf16(A) * bf16(W)^T with fp32 accumulation; A is fp32, W is read from g.Wb
 void launch_gemm_bf16(const GemmArgs& g, hipStream_t s);
 int gemm_bf16_config(const GemmArgs& g);      // 0: 64x64, 1: 128x128 (large grids), 2: 32x128 (M <= 32)
 int gemm_bf16_tile_count(const GemmArgs& g);  // output tiles of that configuration
 void launch_pack_bf16(const float* in, void* out, long n, hipStream_t s);   // fp32 -> bf16 copy, same indexing
+
+// The GEMM dispatch (gemm_f16s.hip, host code), the one place where a GEMM's kernel family, tile configuration, split-K factor, slabs,
+// reduce pass and second-copy pass are chosen: the model's gemm() and the artalk_op_gemm_* entry points differ only in their GemmPolicy.
+struct GemmPolicy {                 // what the caller's context contributes
+    int precision = 0;              // 0: fp32, 1: f16x3 (needs g.Wp), 2: bf16 (needs g.Wb); g.exact keeps a GEMM on the fp32 kernels
+    bool reg_staged = false;        // f16x3: stay on the register-staged kernel even with a P8 activation (tuning entry points)
+    float* slabs = nullptr; int64_t slab_floats = 0;      // split-K scratch the planner may use (null: it never splits on its own)
+    int splitk_tiles = 0, splitk_target = 0;      // fp32, register-staged, bf16: grids below splitk_tiles tiles split towards splitk_target workgroups (0: off)
+};
+enum GemmPath { GEMM_F32 = 0, GEMM_F16S = 1, GEMM_P8 = 2, GEMM_BF16 = 3 };      // fp32 MFMA, register-staged f16x3, P8 LDS-DMA, bf16
+// the configurations of the P8 path: big tiles, the persistent 128x128 kernel (it alone takes column groups), small grids (they alone split)
+enum P8Class { P8_NONE = 0, P8_BIG, P8_GROUPS, P8_SMALL };
+int gemm_p8_class(int cfg);
+struct GemmPlan {
+    int path = GEMM_F32;
+    int cfg = -1;               // tile configuration the path's launcher runs (P8: gemm_p8_class(cfg) != P8_NONE)
+    bool c2_fused = false;      // the kernel's epilogue writes GemmArgs::c2 (otherwise run_gemm adds a split pass over the fp32 result)
+    bool dominant = false;      // a big-tile kernel (the step's dominant GEMMs, for profiling)
+    bool fused_ln = false;      // the split-K reduce also writes fuse_ln's output (otherwise the caller launches that LayerNorm)
+};
+// Host only, touches no device.  Sets g.force_cfg (P8 path; a forced configuration the shape cannot take falls back), g.splitk, g.partial
+// (the policy's slabs unless the caller brought its own) and g.w_nt.  A g.force_cfg >= 0 and a g.splitk > 1 forced on entry are kept: the
+// kernel is then chosen as for an unsplit launch, and whether it can split is the caller's to check (P8_SMALL).
+GemmPlan plan_gemm(GemmArgs& g, const GemmPolicy& p, const LnArgs* fuse_ln);
+// the planned kernel, then the reduce or reduce + LayerNorm pass of a split, then the c2 split pass where the epilogue did not write it
+void run_gemm(const GemmArgs& g, const GemmPlan& plan, const LnArgs* fuse_ln, hipStream_t s);
 // wav2vec2 positional convolution (16 groups of 64 channels, 128 taps) with the chunk's input window resident in LDS (gemm_f16s.hip)
 void launch_posconv_p8(const GemmArgs& g, int n_chunks, int T, int Ts, hipStream_t s);
-int gemm_config(const GemmArgs& g);   // 4: 128x128 BK16 (dominant kernel), 2: 64x64, 1: 128x64, 3: 32x128
 // Average kernel time helper for benches: FLOPs of one launch
 static inline double gemm_flops(const GemmArgs& g) { return 2.0 * g.M * (double)g.N * g.K * g.batch; }
 
