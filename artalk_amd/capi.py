@@ -70,6 +70,7 @@ class GemmRowsArgs(C.Structure):
         ("ln_scale", C.c_void_p), ("ln_shift", C.c_void_p), ("ln_ldm", C.c_int64), ("ln_mod_elems", C.c_int64), ("ln_mmap", C.c_int32 * 3),
         ("ln_eps", C.c_float), ("ln_out_p8", C.c_int32), ("ln_p8_exp", C.c_int32),
         ("used_cfg", C.POINTER(C.c_int32)), ("used_splitk", C.POINTER(C.c_int32)), ("fused_ln", C.POINTER(C.c_int32)),
+        ("cus", C.c_int32),
     ]
 
     def __init__(self, **kw):

@@ -2291,6 +2291,7 @@ int artalk_op_gemm_f16s_packed_ex(const void* A, int a_packed, int64_t lda, cons
     if (!A || !Wp || !C || K % 32 != 0 || M <= 0 || N <= 0 || (M <= 32 && (force_cfg & 0xff) < 20)) return ARTALK_EINVAL;
     if (!op_exp_ok(a_exp) || !op_exp_ok(c_exp)) return ARTALK_EINVAL;
     if (c2_u32 && (force_cfg < 2 || ((act >> 8) & 1) || N % 8 != 0)) return ARTALK_EINVAL;      // the second copy: LDS-DMA kernels, fp32 C
+    if (force_cfg >= 2 && 32 * ((force_cfg >> 8) & 0xff) > K) return ARTALK_EINVAL;      // a split factor that leaves a workgroup no K step
     GemmArgs g;
     g.a_exp = a_exp; g.c_exp = c_exp; g.status = status_dev; g.c2 = (float*)c2_u32;
     g.A = (const float*)A; g.a_packed = a_packed; g.lda = lda; g.W = nullptr; g.Wp = (const unsigned int*)Wp; g.ldw = K; g.bias = bias;
@@ -2433,7 +2434,8 @@ int artalk_op_gemm_rows_layout(int64_t* out, int n) {
         ROWS_FIELD(R), ROWS_FIELD(ldr), ROWS_FIELD(r_elems), ROWS_FIELD(c_p8), ROWS_FIELD(c_exp), ROWS_FIELD(force_cfg), ROWS_FIELD(splitk),
         ROWS_FIELD(ngrp), ROWS_FIELD(grpW), ROWS_FIELD(grpB), ROWS_FIELD(grpC), ROWS_FIELD(status_dev), ROWS_FIELD(ln_Y), ROWS_FIELD(ln_ldy),
         ROWS_FIELD(ln_y_elems), ROWS_FIELD(ln_scale), ROWS_FIELD(ln_shift), ROWS_FIELD(ln_ldm), ROWS_FIELD(ln_mod_elems), ROWS_FIELD(ln_mmap),
-        ROWS_FIELD(ln_eps), ROWS_FIELD(ln_out_p8), ROWS_FIELD(ln_p8_exp), ROWS_FIELD(used_cfg), ROWS_FIELD(used_splitk), ROWS_FIELD(fused_ln)};
+        ROWS_FIELD(ln_eps), ROWS_FIELD(ln_out_p8), ROWS_FIELD(ln_p8_exp), ROWS_FIELD(used_cfg), ROWS_FIELD(used_splitk), ROWS_FIELD(fused_ln),
+        ROWS_FIELD(cus)};
     const int total = (int)(sizeof(lay) / sizeof(lay[0]));
     if (!out || n < total) return ARTALK_EINVAL;
     for (int i = 0; i < total; ++i) out[i] = lay[i];
@@ -2462,6 +2464,7 @@ int artalk_op_gemm_rows(const artalk_op_gemm_rows_args* a, void* stream) {
     if (cfg != -1 && !(a->mode == 0 ? (cfg >= 1 && cfg <= 4) : a->mode == 2 ? (cfg >= 0 && cfg <= 2) : gemm_p8_class(cfg) != P8_NONE))
         return ARTALK_EINVAL;
     if (a->splitk < 0 || a->splitk > 16 || (a->splitk > 1 && 32 * a->splitk > K)) return ARTALK_EINVAL;
+    if (a->cus < 0 || (a->cus != 0 && !p8)) return ARTALK_EINVAL;      // a CU partition sizes the grid of the persistent f16x3 kernels only
     // column groups
     const int G = a->ngrp ? N / a->ngrp : 1;
     if (a->ngrp) {
@@ -2504,7 +2507,7 @@ int artalk_op_gemm_rows(const artalk_op_gemm_rows_args* a, void* stream) {
     g.C = (float*)a->C; g.ldc = a->ldc; g.cmap = RowMap{a->cmap[0], a->cmap[1], a->cmap[2]}; g.c_p8 = a->c_p8 ? 1 : 0; g.c_exp = a->c_exp;
     g.gate = a->gate; g.ldg = a->ldg; g.gmap = RowMap{a->gmap[0], a->gmap[1], a->gmap[2]}; g.R = a->R; g.ldr = a->ldr;
     g.M = M; g.N = N; g.K = K; g.act = a->act; g.force_cfg = cfg; g.status = a->status_dev;
-    g.ngrp = a->ngrp; g.grpW = a->grpW; g.grpB = a->grpB; g.grpC = a->grpC;
+    g.ngrp = a->ngrp; g.grpW = a->grpW; g.grpB = a->grpB; g.grpC = a->grpC; g.cus = a->cus;
     // a forced split is kept; with splitk 0 and no forced configuration the f16x3 planner may split on its own (the other families'
     // small-grid rule stays off).  The planner looks at the presence of Wp and the alignment of the slabs only: both are made below.
     g.splitk = a->splitk > 1 ? a->splitk : 1;

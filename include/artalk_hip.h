@@ -318,7 +318,8 @@ int artalk_op_gemm_bf16(const float* A, int64_t lda, const float* W, const float
  * (256x256 / 320x256 tiles), 8 = gemm_p8_2wgp_kernel (a forced 7 / 12 / 8 the shape cannot take falls back: 7 / 12 to 8, 8 to the plan),
  * 20 / 23 / 24 = gemm_p8_sm_kernel (64x64, 4 / 8 / 5 stages), 28 = gemm_p8_mid_kernel, 31 = gemm_p8_pp_kernel; for 20 .. 31 bits 8-15
  * are a split-K factor and bit 16 fetches the weights non-temporally; 99 = the planner's own choice (no split-K).  Retired values run
- * what replaced them: 13 as 99, 29 and 33 as 28, 30 as 31.  Other values: EINVAL. */
+ * what replaced them: 13 as 99, 29 and 33 as 28, 30 as 31.  Other values, and a split factor above K / 32 (a workgroup would own no
+ * K step): EINVAL before anything is allocated. */
 int artalk_op_pack_split(const float* in, void* out_u32, int64_t n, int is_weight, void* stream);   /* operand scale: 0 activation, 1 weight */
 int artalk_op_gemm_f16s_packed(const void* A, int a_packed, int64_t lda, const void* Wp, const float* bias, float* C, int M, int N,
                                int K, int act, int force_cfg, void* stream);
@@ -475,7 +476,12 @@ int artalk_op_absmax(const float* buf, int rows, int cols, int64_t ld, int is_p8
  *              plain reduce (or no reduce) and launch_layernorm, which reads C as dense rows: a cmap other than the identity is then
  *              ARTALK_EINVAL.  Y must not overlap C.
  *   R          may be C with ldr == ldc (the residual in place); any other overlap of R and C is ARTALK_EINVAL.
- *   used_cfg, used_splitk, fused_ln   host, nullable: the configuration and split that ran, whether the fused reduce did (0 / 1). */
+ *   used_cfg, used_splitk, fused_ln   host, nullable: the configuration and split that ran, whether the fused reduce did (0 / 1).
+ *   cus        mode 1: the compute units of a CU partition (what a model under artalk_set_cu_mask passes to its GEMMs), 0 = the whole
+ *              device.  It sizes the grid of the persistent kernels only - 7 / 12 run one workgroup per unit, 8 two - after rounding
+ *              down to a multiple of 8 and clamping to [8, the device's count]; every other configuration ignores it.  The stream is
+ *              NOT restricted to those units: the field changes which workgroup computes a tile, never a tile's arithmetic.
+ *              cus < 0, or cus != 0 in modes 0 and 2: ARTALK_EINVAL. */
 typedef struct artalk_op_gemm_rows_args {
     int32_t mode, M, N, K, act;
     const void* A; int64_t lda, a_elems; int32_t a_exp;
@@ -492,9 +498,10 @@ typedef struct artalk_op_gemm_rows_args {
     const float* ln_scale; const float* ln_shift; int64_t ln_ldm, ln_mod_elems; int32_t ln_mmap[3];
     float ln_eps; int32_t ln_out_p8, ln_p8_exp;
     int32_t* used_cfg; int32_t* used_splitk; int32_t* fused_ln;
+    int32_t cus;
 } artalk_op_gemm_rows_args;
 int artalk_op_gemm_rows(const artalk_op_gemm_rows_args* a, void* stream);
-/* sizeof(artalk_op_gemm_rows_args) followed by the offset of every field in declaration order (49 values; returns the count, ARTALK_EINVAL
+/* sizeof(artalk_op_gemm_rows_args) followed by the offset of every field in declaration order (50 values; returns the count, ARTALK_EINVAL
  * for n below it): what a binding checks its mirror of the struct against */
 int artalk_op_gemm_rows_layout(int64_t* out, int n);
 /* enable != 0: on the calling thread the three *_rows entry points validate as usual and return ARTALK_OK where they would first touch the

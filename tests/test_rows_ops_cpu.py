@@ -114,10 +114,10 @@ def test_gemm_rows_struct_mirror_matches_the_c_layout():
     out = (C.c_int64 * 64)()
     n = capi.lib().artalk_op_gemm_rows_layout(out, 64)
     fields = [f[0] for f in GemmRowsArgs._fields_]
-    assert n == 1 + len(fields) == 49
+    assert n == 1 + len(fields) == 50 and fields[-1] == "cus"
     assert out[0] == C.sizeof(GemmRowsArgs)
     assert [out[1 + i] for i in range(len(fields))] == [getattr(GemmRowsArgs, f).offset for f in fields]
-    assert capi.lib().artalk_op_gemm_rows_layout(out, 48) == capi.EINVAL and capi.lib().artalk_op_gemm_rows_layout(None, 64) == capi.EINVAL
+    assert capi.lib().artalk_op_gemm_rows_layout(out, 49) == capi.EINVAL and capi.lib().artalk_op_gemm_rows_layout(None, 64) == capi.EINVAL
 
 
 def _used():
