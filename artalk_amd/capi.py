@@ -29,7 +29,18 @@ SYMBOLS = [
     "artalk_op_bsq_history_ex", "artalk_op_ar_bits_next", "artalk_op_vq_embed", "artalk_op_ar_begin", "artalk_op_dec_input", "artalk_op_dec_finish", "artalk_op_enc_input_zero", "artalk_op_style_input", "artalk_op_add_row", "artalk_op_style_finish", "artalk_op_broadcast16", "artalk_op_session_gather", "artalk_op_session_scatter", "artalk_op_absmax",
     "artalk_op_gemm_rows", "artalk_op_layernorm_rows", "artalk_op_attention_rows", "artalk_op_gemm_rows_layout", "artalk_op_rows_dry_run",
     "artalk_op_w2v_front_rows", "artalk_op_pool_silu_rows", "artalk_op_posconv_rows",
+    "artalk_op_attention_plan", "artalk_op_attention_rows_cus",
 ]
+
+# ARTALK_ATTN_* of include/artalk_hip.h: the kernels of attention.hip, as artalk_op_attention_plan names them
+(ATTN_F32_64, ATTN_F32_32, ATTN_SHORT, ATTN_F16, ATTN_F16_P8, ATTN_F16_WIDE, ATTN_F16_PP, ATTN_F16_WIDE_AR,
+ ATTN_F16_WIDE_AR_P8) = range(9)
+ATTN_KERNELS = {
+    ATTN_F32_64: "attention_kernel<64>", ATTN_F32_32: "attention_kernel<32>", ATTN_SHORT: "attention_short_kernel",
+    ATTN_F16: "attention_f16_kernel<1>", ATTN_F16_P8: "attention_f16_kernel<1,1>", ATTN_F16_WIDE: "attention_f16_wide_kernel",
+    ATTN_F16_PP: "attention_f16_pp_kernel", ATTN_F16_WIDE_AR: "attention_f16_wide_ar_kernel<1>",
+    ATTN_F16_WIDE_AR_P8: "attention_f16_wide_ar_kernel<1,1,7,128>",
+}
 
 
 class ArtalkConfigStruct(C.Structure):
@@ -310,6 +321,11 @@ def lib() -> C.CDLL:
         L.artalk_op_gemm_rows_layout.restype = i32
         L.artalk_op_rows_dry_run.argtypes = [i32]
         L.artalk_op_rows_dry_run.restype = i32
+    if hasattr(L, "artalk_op_attention_plan"):      # (an older build loaded through ARTALK_LIB lacks the attention planner's entry points)
+        L.artalk_op_attention_plan.argtypes = [i32] * 9
+        L.artalk_op_attention_plan.restype = i32
+        L.artalk_op_attention_rows_cus.argtypes = L.artalk_op_attention_rows.argtypes[:-1] + [i32, C.POINTER(C.c_int32), vp]
+        L.artalk_op_attention_rows_cus.restype = i32
     if hasattr(L, "artalk_op_w2v_front_rows"):      # (an older build loaded through ARTALK_LIB lacks the chunk-strided wav2vec2 entry points)
         L.artalk_op_w2v_front_rows.argtypes = [vp, i64, C.POINTER(i64), i32, i32, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, vp]
         L.artalk_op_w2v_front_rows.restype = i32

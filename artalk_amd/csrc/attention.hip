@@ -1312,49 +1312,74 @@ void attention_prepare() {      // more than the default 64 KB of dynamic LDS fo
                               4 * 128 * 160);
     done[dev] = true;
 }
-void launch_attention(const AttnArgs& a, hipStream_t s) {
-    if (a.B <= 0 || a.Lq <= 0) return;
-    if (a.HD == 64 && a.split_q == 0 && a.Lq <= 64 && a.Lk >= 64 && !a.qkv_p8) {      // AR scale steps 0-3: key-split kernel
-        const dim3 grid(((a.H * a.B + 7) / 8) * 8 * ((a.Lq + 15) / 16));
-        ARTALK_LAUNCH((attention_short_kernel<64>), grid, dim3(256), 0, s, a);
-        return;
-    }
-    dim3 grid((a.Lq + 63) / 64, a.H, a.B), block(256);
-    // the f16 kernels use the v_exp_f32-based exp (1.2e-6 relative at |x| = 20, where p = 2e-9): 154 -> 137 us per wav2vec2 layer; the fp32 kernels keep expf
+// Which kernel runs.  The thresholds, in the order they are tried:
+//   short     fp32 rows, 64-wide heads, no mask, Lq <= 64, Lk >= 64 (AR scale steps 0-3: key-split kernel; with or without split16)
+//   P8 rows   Lq in (128, 208], Lk <= 256 and ARTALK_ATTN_WIDE [1]: one workgroup (or two) per head -
+//               ping-pong   no mask, Lk in (128, 224], at least two heads per compute unit of the partition, ARTALK_ATTN_PP [1]
+//               wide-AR P8  fewer than 256 heads (the VAE stacks of one clip group: 128): two 7-wave workgroups per head, 128 keys per phase
+//                           (14.1 -> 11.9 us; 100 queries: 7.2 vs 6.4 us, the 64-query form wins)
+//               wide        256 heads and more (the encoder's 1536 run the same either way: 109 us, bound by the softmax arithmetic)
+//             otherwise the 64-query P8 kernel
+//   split16   fp32 rows, no mask, Lq in (32, 112], Lk > 64 and ARTALK_ATTN_WIDE: wide-AR (the 100-query scale step of the AR decoder:
+//             one workgroup per (clip, head), 192 keys per staging phase); otherwise the 64-query f16 kernel
+//   fp32      attention_kernel<64> / <32>
+// the f16 kernels use the v_exp_f32-based exp (1.2e-6 relative at |x| = 20, where p = 2e-9): 154 -> 137 us per wav2vec2 layer; the fp32 kernels keep expf
+static int attn_grid_cus(const AttnArgs& a, int n_cu) { return a.cus > 0 ? (a.cus < n_cu ? a.cus : n_cu) : n_cu; }
+AttnKernel plan_attention(const AttnArgs& a, int n_cu) {
+    if (n_cu <= 0) n_cu = 256;
+    if (a.HD == 64 && a.split_q == 0 && a.Lq <= 64 && a.Lk >= 64 && !a.qkv_p8) return ATTN_SHORT;
     static const int wide = getenv("ARTALK_ATTN_WIDE") ? atoi(getenv("ARTALK_ATTN_WIDE")) : 1;      // 0 = 64-query workgroups everywhere (tests: the wide kernels are bit-identical to it)
-    if (a.HD == 64 && a.split16 && a.qkv_p8 && !a.l2norm && wide && a.Lq > 128 && a.Lq <= kWideMaxWaves * 16 && a.Lk <= kWideMaxKeys) {      // (100 queries: 7.2 vs 6.4 us, the two-workgroup form wins)
-        const size_t lds = (size_t)4 * ((a.Lk + 31) & ~31) * 160;
-        attention_prepare();
-        // fewer (clip, head) pairs than CUs (the VAE stacks of one clip group: 128): two 7-wave workgroups per head, 128 keys per phase
-        // (14.1 -> 11.9 us); the encoder's 1536 pairs run the same either way (109 us: bound by the softmax arithmetic, not by staging)
-        // ARTALK_ATTN_PP [1]: the persistent ping-pong kernel where every CU gets several heads (the encoder); 0 = the one-head-per-workgroup kernel
-        static const int pp = getenv("ARTALK_ATTN_PP") ? atoi(getenv("ARTALK_ATTN_PP")) : 1;
-        static int n_cu_dev[64] = {};      // per device: the CURRENT one (a model may live on any GPU of the node)
+    if (a.HD == 64 && a.split16 && a.qkv_p8 && !a.l2norm && wide && a.Lq > 128 && a.Lq <= kWideMaxWaves * 16 && a.Lk <= kWideMaxKeys) {
+        static const int pp = getenv("ARTALK_ATTN_PP") ? atoi(getenv("ARTALK_ATTN_PP")) : 1;      // 0 = the one-head-per-workgroup kernel
+        if (pp && a.split_q <= 0 && a.Lk > kPPRowsA && a.Lk <= kPPRowsA + kPPRowsB && (long)a.B * a.H >= 2L * attn_grid_cus(a, n_cu)) return ATTN_F16_PP;
+        return (long)a.B * a.H < 256 ? ATTN_F16_WIDE_AR_P8 : ATTN_F16_WIDE;
+    }
+    if (a.HD == 64 && a.split16 && a.qkv_p8 && !a.l2norm) return ATTN_F16_P8;
+    if (a.HD == 64 && a.split16 && wide && !a.qkv_p8 && a.split_q == 0 && a.Lq > 32 && a.Lq <= kWideArWaves * 16 && a.Lk > 64) return ATTN_F16_WIDE_AR;
+    if (a.HD == 64 && a.split16) return ATTN_F16;
+    return a.HD == 64 ? ATTN_F32_64 : a.HD == 32 ? ATTN_F32_32 : ATTN_NONE;
+}
+AttnKernel launch_attention(const AttnArgs& a, hipStream_t s) {
+    if (a.B <= 0 || a.Lq <= 0) return ATTN_NONE;
+    int n_cu = 0;
+    if (a.qkv_p8 && a.Lq > 128) {      // only the ping-pong kernel's threshold and grid look at the count: of the CURRENT device (a model may live on any GPU of the node)
+        static int n_cu_dev[64] = {};
         int dev = 0;
         (void)hipGetDevice(&dev);
         if (dev < 0 || dev >= 64) dev = 0;
-        int& n_cu = n_cu_dev[dev];
-        if (!n_cu && (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)) n_cu = 256;
-        const int cus = a.cus > 0 ? (a.cus < n_cu ? a.cus : n_cu) : n_cu;
-        if (pp && a.split_q <= 0 && a.Lk > kPPRowsA && a.Lk <= kPPRowsA + kPPRowsB && (long)a.B * a.H >= 2L * cus) {
-            ARTALK_LAUNCH((attention_f16_pp_kernel<1>), dim3(cus), dim3(kPPWaves * 64), (size_t)4 * (kPPRowsA + kPPRowsB) * 160, s, a);
-            return;
-        }
-        if ((long)a.B * a.H < 256) ARTALK_LAUNCH((attention_f16_wide_ar_kernel<1, 1, 7, 128>), dim3((a.Lq + 111) / 112, a.H, a.B), dim3(7 * 64), (size_t)4 * 128 * 160, s, a);
-        else ARTALK_LAUNCH((attention_f16_wide_kernel<1>), dim3(1, a.H, a.B), dim3(kWideMaxWaves * 64), lds, s, a);
-    } else if (a.HD == 64 && a.split16 && a.qkv_p8 && !a.l2norm)
-        ARTALK_LAUNCH((attention_f16_kernel<1, 1>), grid, block, 0, s, a);
-    else if (a.HD == 64 && a.split16 && wide && !a.qkv_p8 && a.split_q == 0 && a.Lq > 32 && a.Lq <= kWideArWaves * 16 && a.Lk > 64) {
-        attention_prepare();      // the 100-query scale step of the AR decoder: one workgroup per (clip, head), 192 keys per staging phase
+        int& n = n_cu_dev[dev];
+        if (!n && (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)) n = 256;
+        n_cu = n;
+    }
+    const AttnKernel k = plan_attention(a, n_cu);
+    const dim3 grid((a.Lq + 63) / 64, a.H, a.B), block(256);
+    switch (k) {
+    case ATTN_SHORT:
+        ARTALK_LAUNCH((attention_short_kernel<64>), dim3(((a.H * a.B + 7) / 8) * 8 * ((a.Lq + 15) / 16)), dim3(256), 0, s, a);
+        break;
+    case ATTN_F16_PP:
+        attention_prepare();
+        ARTALK_LAUNCH((attention_f16_pp_kernel<1>), dim3(attn_grid_cus(a, n_cu)), dim3(kPPWaves * 64), (size_t)4 * (kPPRowsA + kPPRowsB) * 160, s, a);
+        break;
+    case ATTN_F16_WIDE_AR_P8:
+        attention_prepare();
+        ARTALK_LAUNCH((attention_f16_wide_ar_kernel<1, 1, 7, 128>), dim3((a.Lq + 111) / 112, a.H, a.B), dim3(7 * 64), (size_t)4 * 128 * 160, s, a);
+        break;
+    case ATTN_F16_WIDE:
+        attention_prepare();
+        ARTALK_LAUNCH((attention_f16_wide_kernel<1>), dim3(1, a.H, a.B), dim3(kWideMaxWaves * 64), (size_t)4 * ((a.Lk + 31) & ~31) * 160, s, a);
+        break;
+    case ATTN_F16_P8: ARTALK_LAUNCH((attention_f16_kernel<1, 1>), grid, block, 0, s, a); break;
+    case ATTN_F16_WIDE_AR:
+        attention_prepare();
         ARTALK_LAUNCH((attention_f16_wide_ar_kernel<1>), dim3(1, a.H, a.B), dim3(kWideArWaves * 64), (size_t)4 * kWideArKeys * 160, s, a);
-    } else if (a.HD == 64 && a.split16)
-        ARTALK_LAUNCH(attention_f16_kernel<1>, grid, block, 0, s, a);
-    else if (a.HD == 64)
-        ARTALK_LAUNCH(attention_kernel<64>, grid, block, 0, s, a);
-    else if (a.HD == 32)
-        ARTALK_LAUNCH(attention_kernel<32>, grid, block, 0, s, a);
-    else
-        abort();
+        break;
+    case ATTN_F16: ARTALK_LAUNCH(attention_f16_kernel<1>, grid, block, 0, s, a); break;
+    case ATTN_F32_64: ARTALK_LAUNCH(attention_kernel<64>, grid, block, 0, s, a); break;
+    case ATTN_F32_32: ARTALK_LAUNCH(attention_kernel<32>, grid, block, 0, s, a); break;
+    default: abort();
+    }
+    return k;
 }
 
 }  // namespace artalk

@@ -2570,17 +2570,41 @@ int artalk_op_layernorm_rows(const float* X, float* Y, const float* w, const flo
     return (e1 == hipSuccess && hipGetLastError() == hipSuccess) ? ARTALK_OK : ARTALK_EHIP;
 }
 
+static_assert(ATTN_F32_64 == ARTALK_ATTN_F32_64 && ATTN_F32_32 == ARTALK_ATTN_F32_32 && ATTN_SHORT == ARTALK_ATTN_SHORT && ATTN_F16 == ARTALK_ATTN_F16 &&
+              ATTN_F16_P8 == ARTALK_ATTN_F16_P8 && ATTN_F16_WIDE == ARTALK_ATTN_F16_WIDE && ATTN_F16_PP == ARTALK_ATTN_F16_PP &&
+              ATTN_F16_WIDE_AR == ARTALK_ATTN_F16_WIDE_AR && ATTN_F16_WIDE_AR_P8 == ARTALK_ATTN_F16_WIDE_AR_P8, "include/artalk_hip.h");
+// the shape, flag and partition checks artalk_op_attention_rows_cus and artalk_op_attention_plan share
+static bool op_attn_shape_ok(int B, int H, int HD, int Lq, int Lk, int l2norm, int split, int out_p8, int cus) {
+    if ((HD != 64 && HD != 32) || B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0 || split < 0 || l2norm < 0 || l2norm > 7 || cus < 0) return false;
+    const int split16 = (l2norm >> 1) & 1, qkv_p8 = (l2norm >> 2) & 1;
+    if ((split16 || qkv_p8 || out_p8) && HD != 64) return false;      // the f16 kernels and the P8 rows are 64-wide heads
+    return !(qkv_p8 && (!split16 || (l2norm & 1)));
+}
+int artalk_op_attention_plan(int B, int H, int HD, int Lq, int Lk, int l2norm, int split, int cus, int n_cu) {
+    if (!op_attn_shape_ok(B, H, HD, Lq, Lk, l2norm, split, 0, cus) || n_cu <= 0) return ARTALK_EINVAL;
+    AttnArgs a;
+    a.B = B; a.H = H; a.HD = HD; a.Lq = Lq; a.Lk = Lk; a.l2norm = l2norm & 1; a.split16 = (l2norm >> 1) & 1; a.qkv_p8 = (l2norm >> 2) & 1;
+    a.split_q = split; a.split_k = split; a.cus = cus;
+    return (int)plan_attention(a, n_cu);
+}
 int artalk_op_attention_rows(const float* Q, const float* K, const float* V, float* O, int B, int H, int HD, int Lq, int Lk,
                              float scale, int l2norm, const float* qscale, int split, int qkv_exp, int o_exp, int out_p8,
                              int* status_dev, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bstride, int64_t k_bstride,
                              int64_t v_bstride, int64_t o_bstride, int64_t q_elems, int64_t k_elems, int64_t v_elems, int64_t o_elems,
                              void* stream) {
+    return artalk_op_attention_rows_cus(Q, K, V, O, B, H, HD, Lq, Lk, scale, l2norm, qscale, split, qkv_exp, o_exp, out_p8, status_dev, ldq, ldk,
+                                        ldv, ldo, q_bstride, k_bstride, v_bstride, o_bstride, q_elems, k_elems, v_elems, o_elems, 0, nullptr,
+                                        stream);
+}
+int artalk_op_attention_rows_cus(const float* Q, const float* K, const float* V, float* O, int B, int H, int HD, int Lq, int Lk,
+                                 float scale, int l2norm, const float* qscale, int split, int qkv_exp, int o_exp, int out_p8,
+                                 int* status_dev, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bstride, int64_t k_bstride,
+                                 int64_t v_bstride, int64_t o_bstride, int64_t q_elems, int64_t k_elems, int64_t v_elems, int64_t o_elems,
+                                 int cus, int* used_kernel, void* stream) {
     if (!Q || !K || !V || !O || (HD != 64 && HD != 32) || ((l2norm & 1) && !qscale)) return ARTALK_EINVAL;
     if (!op_exp_ok(qkv_exp) || !op_exp_ok(o_exp)) return ARTALK_EINVAL;
-    if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0 || split < 0 || l2norm < 0 || l2norm > 7) return ARTALK_EINVAL;
+    if (!op_attn_shape_ok(B, H, HD, Lq, Lk, l2norm, split, out_p8, cus)) return ARTALK_EINVAL;
     const int split16 = (l2norm >> 1) & 1, qkv_p8 = (l2norm >> 2) & 1;
-    if ((split16 || qkv_p8 || out_p8) && HD != 64) return ARTALK_EINVAL;      // the f16 kernels and the P8 rows are 64-wide heads
-    if (qkv_p8 && (!split16 || (l2norm & 1))) return ARTALK_EINVAL;
     const int64_t D = (int64_t)H * HD;
     // rows are read and written as 16-byte vectors, P8 rows as 32-byte groups
     const int kin = qkv_p8 ? 8 : 4, kout = out_p8 ? 8 : 4;
@@ -2602,10 +2626,14 @@ int artalk_op_attention_rows(const float* Q, const float* K, const float* V, flo
     a.Q = Q; a.K = K; a.V = V; a.O = O; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
     a.q_bstride = q_bstride; a.k_bstride = k_bstride; a.v_bstride = v_bstride; a.o_bstride = o_bstride;
     a.B = B; a.H = H; a.HD = HD; a.Lq = Lq; a.Lk = Lk; a.scale = scale; a.l2norm = l2norm & 1; a.qscale = qscale;
-    a.split_q = split; a.split_k = split;
-    if (g_rows_dry_run) return ARTALK_OK;
+    a.split_q = split; a.split_k = split; a.cus = cus;
+    if (g_rows_dry_run) {
+        if (used_kernel) *used_kernel = (int)plan_attention(a, 0);
+        return ARTALK_OK;
+    }
     hipStream_t s = (hipStream_t)stream;
-    launch_attention(a, s);
+    const AttnKernel ran = launch_attention(a, s);
+    if (used_kernel) *used_kernel = (int)ran;
     const hipError_t e1 = hipStreamSynchronize(s);
     return (e1 == hipSuccess && hipGetLastError() == hipSuccess) ? ARTALK_OK : ARTALK_EHIP;
 }

@@ -169,8 +169,24 @@ struct AttnArgs {
     int* status = nullptr;                           // out_p8: range guard (see GemmArgs::status)
     int cus = 0;                                     // compute units of the model's partition (0 = the whole device): grid of the persistent kernel
 };
-void launch_attention(const AttnArgs& a, hipStream_t s);
-void attention_prepare();      // one-time kernel attributes (call once per process before the first captured launch)
+// the kernels of attention.hip, one value per instantiation (ARTALK_ATTN_* of include/artalk_hip.h)
+enum AttnKernel {
+    ATTN_NONE = -1,            // no kernel takes this head dim
+    ATTN_F32_64 = 0,           // attention_kernel<64>
+    ATTN_F32_32 = 1,           // attention_kernel<32>
+    ATTN_SHORT = 2,            // attention_short_kernel<64>
+    ATTN_F16 = 3,              // attention_f16_kernel<1>
+    ATTN_F16_P8 = 4,           // attention_f16_kernel<1, 1>
+    ATTN_F16_WIDE = 5,         // attention_f16_wide_kernel<1>
+    ATTN_F16_PP = 6,           // attention_f16_pp_kernel<1>
+    ATTN_F16_WIDE_AR = 7,      // attention_f16_wide_ar_kernel<1>
+    ATTN_F16_WIDE_AR_P8 = 8,   // attention_f16_wide_ar_kernel<1, 1, 7, 128>
+};
+// which kernel a launch runs: shapes, flags, split mask, a.cus and the device's compute-unit count n_cu (<= 0: 256) decide, and the
+// two environment switches ARTALK_ATTN_WIDE / ARTALK_ATTN_PP, each read once per process; no pointer is looked at, no device touched
+AttnKernel plan_attention(const AttnArgs& a, int n_cu);
+AttnKernel launch_attention(const AttnArgs& a, hipStream_t s);      // returns what it launched (ATTN_NONE: B or Lq <= 0, nothing launched)
+void attention_prepare();    // one-time kernel attributes (call once per process before the first captured launch)
 
 // ---- wav2vec2 front-end ----
 // per-chunk mean / unbiased std, writes (x-mean)/(std+1e-6); chunk c is read at audio + src_off[c]

@@ -521,6 +521,31 @@ int artalk_op_attention_rows(const float* Q, const float* K, const float* V, flo
                              int* status_dev, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bstride, int64_t k_bstride,
                              int64_t v_bstride, int64_t o_bstride, int64_t q_elems, int64_t k_elems, int64_t v_elems, int64_t o_elems,
                              void* stream);
+/* The kernels of attention.hip, one value per instantiation: what artalk_op_attention_plan returns and artalk_op_attention_rows_cus reports */
+#define ARTALK_ATTN_F32_64 0          /* attention_kernel<64>: fp32 MFMAs, 64-query workgroups */
+#define ARTALK_ATTN_F32_32 1          /* attention_kernel<32> (the style encoder's 32-wide heads) */
+#define ARTALK_ATTN_SHORT 2           /* attention_short_kernel: fp32, keys split over the waves (Lq <= 64, Lk >= 64, no mask) */
+#define ARTALK_ATTN_F16 3             /* attention_f16_kernel<1>: f16-split MFMAs, fp32 rows, 64-query workgroups */
+#define ARTALK_ATTN_F16_P8 4          /* attention_f16_kernel<1, 1>: the same on P8 rows */
+#define ARTALK_ATTN_F16_WIDE 5        /* attention_f16_wide_kernel: P8 rows, one workgroup per head, all keys staged once */
+#define ARTALK_ATTN_F16_PP 6          /* attention_f16_pp_kernel: P8 rows, persistent, two LDS buffers filled by LDS-DMA */
+#define ARTALK_ATTN_F16_WIDE_AR 7     /* attention_f16_wide_ar_kernel<1>: fp32 rows, one 7-wave workgroup per head, 192 keys per phase */
+#define ARTALK_ATTN_F16_WIDE_AR_P8 8  /* attention_f16_wide_ar_kernel<1, 1, 7, 128>: P8 rows, 7-wave workgroups of 112 queries, 128 keys per phase */
+/* Which kernel an attention launch of this shape runs on a device of n_cu compute units (> 0), for a model partition of cus units
+ * (0 = the whole device; >= 0): plan_attention, the function launch_attention switches on, asked without a device.  l2norm is the flag
+ * word of artalk_op_attention_ex (| 1 L2 norm, | 2 f16-split kernels, | 4 P8 rows), split its mask.  Returns ARTALK_ATTN_*, or
+ * ARTALK_EINVAL for what artalk_op_attention_rows refuses in these arguments.  The environment switches ARTALK_ATTN_WIDE and
+ * ARTALK_ATTN_PP (each read once per process) take part in the answer as they do in a launch. */
+int artalk_op_attention_plan(int B, int H, int HD, int Lq, int Lk, int l2norm, int split, int cus, int n_cu);
+/* artalk_op_attention_rows (which forwards here with cus = 0, used_kernel = NULL) for a model partition of cus compute units
+ * (AttnArgs::cus: the grid and the heads-per-unit threshold of the persistent kernel; the stream is NOT restricted to them; cus < 0:
+ * ARTALK_EINVAL).  used_kernel (host, nullable) receives the ARTALK_ATTN_* value that ran; under artalk_op_rows_dry_run, the plan for
+ * a device of 256 units. */
+int artalk_op_attention_rows_cus(const float* Q, const float* K, const float* V, float* O, int B, int H, int HD, int Lq, int Lk,
+                                 float scale, int l2norm, const float* qscale, int split, int qkv_exp, int o_exp, int out_p8,
+                                 int* status_dev, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t q_bstride, int64_t k_bstride,
+                                 int64_t v_bstride, int64_t o_bstride, int64_t q_elems, int64_t k_elems, int64_t v_elems, int64_t o_elems,
+                                 int cus, int* used_kernel, void* stream);
 /* ---- the wav2vec2 stage's kernels in the chunk-strided forms run_wav2vec launches them (tests/test_w2v_ops_gpu.py, tests/test_w2v_ops_cpu.py).
  * Conventions of the *_rows entry points above: every buffer reached through an offset, a pitch or a stride comes with its size in 4-byte
  * elements, the furthest element of the launch is worked out on the host, any bad argument is ARTALK_EINVAL before the device is touched,
