@@ -30,6 +30,7 @@ SYMBOLS = [
     "artalk_op_gemm_rows", "artalk_op_layernorm_rows", "artalk_op_attention_rows", "artalk_op_gemm_rows_layout", "artalk_op_rows_dry_run",
     "artalk_op_w2v_front_rows", "artalk_op_pool_silu_rows", "artalk_op_posconv_rows",
     "artalk_op_attention_plan", "artalk_op_attention_rows_cus",
+    "artalk_infer_samples", "artalk_set_tail_skip", "artalk_conv_tail_geometry", "artalk_conv_tail_class",
 ]
 
 # ARTALK_ATTN_* of include/artalk_hip.h: the kernels of attention.hip, as artalk_op_attention_plan names them
@@ -152,6 +153,16 @@ def lib() -> C.CDLL:
     L.artalk_weight_bytes.restype = i64
     L.artalk_infer.argtypes = [vp, vp, i64, C.POINTER(i64), i32, vp, vp, vp, i64, vp, vp, vp, vp]
     L.artalk_infer.restype = i32
+    if hasattr(L, "artalk_infer_samples"):      # (an older build loaded through ARTALK_LIB for an A/B run runs every chunk whole)
+        L.artalk_infer_samples.argtypes = [vp, vp, i64, C.POINTER(i64), C.POINTER(i64), i32, vp, vp, vp, i64, vp, vp, vp, vp]
+        L.artalk_infer_samples.restype = i32
+        L.artalk_set_tail_skip.argtypes = [vp, i32]
+        L.artalk_set_tail_skip.restype = i32
+        pi = C.POINTER(i32)
+        L.artalk_conv_tail_geometry.argtypes = [i64, i32, i32, pi, pi, pi, pi, pi, pi]
+        L.artalk_conv_tail_geometry.restype = i32
+        L.artalk_conv_tail_class.argtypes = [i64, i32]
+        L.artalk_conv_tail_class.restype = i64
     L.artalk_get_status.argtypes = [vp, C.POINTER(C.c_int), vp]
     L.artalk_get_status.restype = i32
     L.artalk_poll_status.argtypes = [vp, C.POINTER(C.c_int)]
@@ -345,3 +356,26 @@ def ptr(t):
 def current_stream_ptr():
     import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def conv_tail_geometry(valid: int, cfg: ARTalkConfig = None):
+    """``artalk_conv_tail_geometry`` for a chunk with ``valid`` real samples: (partial, t_const, Tp, Sp, samples_read), lists per conv
+    layer.  Host only: needs no GPU."""
+    cfg = cfg or ARTalkConfig.full()
+    kernel, stride = list(cfg.w2v["conv_kernel"]), list(cfg.w2v["conv_stride"])
+    n = len(kernel)
+    arr = C.c_int32 * n
+    k, st, tc, tp, sp = arr(*kernel), arr(*stride), arr(), arr(), arr()
+    read = C.c_int32(0)
+    rc = lib().artalk_conv_tail_geometry(int(valid), int(cfg.samples_per_chunk), n, k, st, tc, tp, sp, C.byref(read))
+    if rc < 0:
+        raise ValueError(f"artalk_conv_tail_geometry({valid}) failed ({rc})")
+    return bool(rc), list(tc), list(tp), list(sp), int(read.value)
+
+
+def conv_tail_class(valid: int, samples_per_chunk: int = 64000) -> int:
+    """Upper bound, in samples, of the length class a chunk with ``valid`` real samples runs at (``artalk_conv_tail_class``)."""
+    rc = int(lib().artalk_conv_tail_class(int(valid), int(samples_per_chunk)))
+    if rc < 0:
+        raise ValueError(f"artalk_conv_tail_class({valid}) failed ({rc})")
+    return rc

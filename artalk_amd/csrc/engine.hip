@@ -200,6 +200,12 @@ struct artalk_model {
     // derived sizes
     int n_conv = 0; int conv_T[8]{}; int conv_S[8]{};   // valid frames / padded row stride per conv layer output
     int Tw = 0, Ts = 0;                                 // 199, 200
+    // Conv stack over the frames that hear real audio (run_wav2vec): a chunk whose tail is zero padding runs the stack up to ONE frame
+    // of the padded region.  Chunks fall into length classes by quarter of a chunk and run at their class's upper bound: tail_geo[q - 1]
+    // for a chunk with valid samples in ((q - 1) / 4, q / 4] of a chunk (artalk_conv_tail_geometry of the bound; partial = false: the
+    // whole chunk, conv_T / conv_S).
+    struct TailGeo { bool partial = false; int tc = 0; int T[8]{}, S[8]{}; } tail_geo[4];
+    bool tail_skip = true;                              // artalk_set_tail_skip
     int ada_n = 0;                                      // 12*4608 + 1536
     int pn[kMaxLv]{}, off[kMaxLv + 1]{};
     // weights
@@ -533,8 +539,13 @@ void audit(artalk_model* m, const float* buf, int rows, int cols, long ld, bool 
     launch_absmax(buf, rows, cols & ~7, ld, is_p8 ? 1 : 0, m->audit_vals + idx, s, junk_period, junk_from, ex ? *ex : kActExp);
 }
 
-bool gemm(artalk_model* m, const GemmArgs& g0, hipStream_t s, const LnArgs* fuse_ln = nullptr) {
+// plan_M > 0: the launch has fewer rows than the launch of plan_M rows whose rows it computes (the conv stack of run_wav2vec without the
+// frames that hear zero padding alone): it is planned as that launch - kernel family, tile configuration, split-K factor - and the plan
+// is pinned on the rows it runs, so that every row sees the summation order it would have seen there.
+bool gemm(artalk_model* m, const GemmArgs& g0, hipStream_t s, const LnArgs* fuse_ln = nullptr, int plan_M = 0) {
     GemmArgs g = g0;
+    const int run_M = g.M;
+    if (plan_M > 0) g.M = plan_M;
     g.graph_tag = m->in_body ? 1 : 0;
     g.cus = m->n_cus;
     g.status = m->precision == 1 ? (m->view ? m->view->status : m->ws.status) : nullptr;     // P8 range guard at the producers
@@ -548,7 +559,19 @@ bool gemm(artalk_model* m, const GemmArgs& g0, hipStream_t s, const LnArgs* fuse
     }
     const Workspace& cw = m->view ? *m->view : m->ws;
     const GemmPolicy pol{m->precision, false, cw.splitk, cw.splitk_floats, m->splitk_tiles, m->splitk_target};
-    const GemmPlan plan = plan_gemm(g, pol, fuse_ln);
+    GemmPlan plan = plan_gemm(g, pol, fuse_ln);
+    if (plan_M > 0) {
+        g.M = run_M;
+        if (plan.path != GEMM_P8) g.force_cfg = plan.cfg;      // (the P8 plan has set it; the other launchers would choose again from M)
+        else if (gemm_p8_class(plan.cfg) == P8_BIG) {
+            // the big-tile kernel's two tile heights run the same K loop per row (bit-identical results: tests/test_p8_depth_gpu.py): the
+            // height is chosen for the rows this launch has, where the cost model still sees a big-tile launch
+            GemmArgs h = g;
+            h.force_cfg = g0.force_cfg; h.splitk = g0.splitk; h.partial = g0.partial;
+            const GemmPlan alt = plan_gemm(h, pol, fuse_ln);
+            if (alt.path == GEMM_P8 && gemm_p8_class(alt.cfg) == P8_BIG && h.splitk == g.splitk) { g.force_cfg = alt.cfg; plan.cfg = alt.cfg; }
+        }
+    }
     if (g.a_packed && plan.path == GEMM_F32) { m->err = "internal: P8 activation handed to an fp32 GEMM"; m->sticky_error = true; return false; }
     const bool timed = m->profiling && plan.dominant && !m->in_body;
     size_t i0 = 0, i1 = 0;
@@ -575,13 +598,14 @@ void tap_copy(artalk_model* m, int field, int row0, const float* src, int rows, 
 enum { LF_EXACT = 1, LF_A_P8 = 2, LF_C_P8 = 4 };   // linear() flags: decision-critical (fp32 path) / A is in P8 / write C in P8
 // plain y = act(x W^T + b) [+ R]
 void linear(artalk_model* m, const float* A, long lda, const float* W, const float* bias, float* C, long ldc, int M, int N, int K,
-            int act, const float* R, hipStream_t s, int flags = 0, float* c2 = nullptr, int a_exp = kActExp, int c_exp = kActExp) {
+            int act, const float* R, hipStream_t s, int flags = 0, float* c2 = nullptr, int a_exp = kActExp, int c_exp = kActExp,
+            int plan_M = 0) {
     GemmArgs g;
     g.c2 = c2; g.a_exp = a_exp; g.c_exp = c_exp;
     g.exact = flags & LF_EXACT; g.a_packed = (flags & LF_A_P8) ? 1 : 0; g.c_p8 = (flags & LF_C_P8) ? 1 : 0;
     g.A = A; g.lda = lda; g.W = W; g.ldw = K; g.bias = bias; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.act = act;
     g.R = R; g.ldr = ldc;
-    gemm(m, g, s);
+    gemm(m, g, s, nullptr, plan_M);
 }
 
 void layernorm(const float* X, float* Y, const float* w, const float* b, int M, int D, float eps, int act, hipStream_t s, int out_p8 = 0,
@@ -593,8 +617,13 @@ void layernorm(const float* X, float* Y, const float* w, const float* b, int M, 
 }
 
 // ------------------------------------------------------------------------------------------------ stages
+// The conv stack's passes over the chunks of one run_wav2vec call (tail skip): pass p holds n[p] chunks, `off[p]` chunks into the pass
+// order, at the geometry of tail_geo[cls[p]] (cls 3: whole chunks).  The chunk table of the pass order and the gather table that
+// brings the result back to the call's order (launch_conv_tail_gather) are rows `perm` and `tab` of the device chunk table.
+struct ConvPasses { int np = 0; int off[4]{}, n[4]{}, cls[4]{}; const long* perm = nullptr; const long* tab = nullptr; };
+
 // wav2vec2 on chunks [c0, c0+n) of the chunk list (app/modules/wav2vec.py:11-20); writes SiLU(pooled cond) rows c0*181..
-void run_wav2vec(artalk_model* m, const float* audio, int c0, int n, float* out_w2v, hipStream_t s) {
+void run_wav2vec(artalk_model* m, const float* audio, int c0, int n, float* out_w2v, hipStream_t s, const ConvPasses* tail = nullptr) {
     const artalk_config& c = m->cfg;
     Workspace& w = m->ws;
     const int CD = c.w2v_conv_dim, Hs = c.w2v_hidden;
@@ -605,22 +634,59 @@ void run_wav2vec(artalk_model* m, const float* audio, int c0, int n, float* out_
     Range r_w2v("artalk.wav2vec2");
     roctxRangePushA("artalk.wav2vec2.conv_stack");      // K1-K3: normalise, conv0+LN+GELU, conv1-6 as GEMMs + LN + GELU
     kbucket(m, KB_CONV);
-    launch_audio_normalize(audio, w.src_off + c0, w.xnorm, n, kSamplesPerChunk, s);
+    // The samples of every chunk are normalised, zeros included (the statistics are the reference's); with passes, in pass order.
+    launch_audio_normalize(audio, tail ? tail->perm : w.src_off + c0, w.xnorm, n, kSamplesPerChunk, s);
     SiteExps& ex = m->ex;
-    launch_conv0(w.xnorm, kSamplesPerChunk, m->conv0_w, m->conv_b[0], m->conv_lnw[0], m->conv_lnb[0], w.convA, n, m->conv_T[0],
-                 m->conv_S[0], s, p8, w.status, ex.conv[0]);
-    audit(m, w.convA, n * m->conv_S[0], CD, CD, p8, s, &ex.conv[0], m->conv_S[0], m->conv_T[0]);
+    // Pass p: its chunks compute T[i] frames of layer i at a row stride of S[i] per chunk, S[i-1] = 2 S[i] in every geometry.  The passes'
+    // rows of a layer follow one another (pass p starts at row0 = sum of n[q] S_q[i] over q < p), so a pass's start doubles from layer to
+    // layer as its stride does, and ONE GEMM per layer - output row r reads input rows 2r .. - covers all passes.  Without length
+    // classes (tail = null): one pass of n whole chunks.
+    ConvPasses one;
+    one.np = 1; one.n[0] = n; one.cls[0] = 3;
+    const ConvPasses& ps = tail ? *tail : one;
+    auto geo_T = [&](int p) { const artalk_model::TailGeo& tg = m->tail_geo[ps.cls[p]]; return ps.cls[p] != 3 && tg.partial ? tg.T : m->conv_T; };
+    auto geo_S = [&](int p) { const artalk_model::TailGeo& tg = m->tail_geo[ps.cls[p]]; return ps.cls[p] != 3 && tg.partial ? tg.S : m->conv_S; };
+    auto row0 = [&](int p, int i) { long r = 0; for (int q = 0; q < p; ++q) r += (long)ps.n[q] * geo_S(q)[i]; return r; };
     float* src = w.convA; float* dst = w.convB;
+    for (int p = 0; p < ps.np; ++p) {
+        const int *T = geo_T(p), *S = geo_S(p);
+        float* y = src + row0(p, 0) * CD;
+        launch_conv0(w.xnorm + (long)ps.off[p] * kSamplesPerChunk, kSamplesPerChunk, m->conv0_w, m->conv_b[0], m->conv_lnw[0], m->conv_lnb[0], y, ps.n[p],
+                     T[0], S[0], s, p8, w.status, ex.conv[0]);
+        audit(m, y, ps.n[p] * S[0], CD, CD, p8, s, &ex.conv[0], S[0], T[0]);
+    }
     for (int i = 1; i < c.w2v_n_conv; ++i) {
-        // stride-2 conv as a GEMM: output row r reads input rows 2r..2r+k-1 (contiguous K = k*512 floats)
-        const int M = n * m->conv_S[i];
+        // stride-2 conv as a GEMM: output row r reads input rows 2r..2r+k-1 (contiguous K = k*512 floats).  With passes it has fewer rows
+        // than the launch over n whole chunks, and is planned as that launch (gemm(): plan_M): kernel family, tile configuration and
+        // split over K decide a row's summation order, its place in the launch does not.
+        const int M = (int)row0(ps.np, i), plan_M = M == n * m->conv_S[i] ? 0 : n * m->conv_S[i];
         linear(m, src, (long)c.w2v_conv_stride[i] * CD, m->conv_w[i], m->conv_b[i], dst, CD, M, CD, c.w2v_conv_kernel[i] * CD,
-               ACT_NONE, nullptr, s, AP, nullptr, ex.conv[i - 1]);
+               ACT_NONE, nullptr, s, AP, nullptr, ex.conv[i - 1], kActExp, plan_M);
         // the last conv output feeds a LayerNorm (feature projection), not a GEMM: it stays fp32
-        // rows t >= conv_T[i] of every chunk are layout padding (computed from the padding rows below them): no range guard there
-        layernorm(dst, dst, m->conv_lnw[i], m->conv_lnb[i], M, CD, 1e-5f, ACT_GELU_ERF, s, (p8 && i + 1 < c.w2v_n_conv) ? 1 : 0, w.status,
-                  m->conv_S[i], m->conv_T[i], ex.conv[i]);
-        if (i + 1 < c.w2v_n_conv) audit(m, dst, M, CD, CD, p8, s, &ex.conv[i], m->conv_S[i], m->conv_T[i]);
+        // rows t >= T[i] of every chunk are layout padding (computed from the padding rows below them): no range guard there.  One
+        // launch takes two passes (LnArgs::junk_row2: each with its own padding rows).
+        for (int p = 0; p < ps.np; p += 2) {
+            const int *T = geo_T(p), *S = geo_S(p);
+            float* y = dst + row0(p, i) * CD;
+            const int Mp = ps.n[p] * S[i], Mq = p + 1 < ps.np ? ps.n[p + 1] * geo_S(p + 1)[i] : 0;
+            LnArgs a;
+            a.plan_M = plan_M;
+            a.out_p8 = (p8 && i + 1 < c.w2v_n_conv) ? 1 : 0; a.p8_exp = ex.conv[i]; a.status = a.out_p8 ? w.status : nullptr;
+            a.junk_period = S[i]; a.junk_from = T[i];
+            if (Mq) { a.junk_row2 = Mp; a.junk_period2 = geo_S(p + 1)[i]; a.junk_from2 = geo_T(p + 1)[i]; }
+            a.X = y; a.ldx = CD; a.Y = y; a.ldy = CD; a.w = m->conv_lnw[i]; a.b = m->conv_lnb[i]; a.M = Mp + Mq; a.D = CD; a.eps = 1e-5f; a.act = ACT_GELU_ERF;
+            launch_layernorm(a, s);
+            if (i + 1 < c.w2v_n_conv) {
+                audit(m, y, Mp, CD, CD, p8, s, &ex.conv[i], S[i], T[i]);
+                if (Mq) audit(m, y + (long)Mp * CD, Mq, CD, CD, p8, s, &ex.conv[i], a.junk_period2, a.junk_from2);
+            }
+        }
+        std::swap(src, dst);
+    }
+    if (tail) {
+        // the encoder's layout (Ts rows per chunk, the call's chunk order) into the other buffer: row t of a chunk is its computed row
+        // min(t, tc), the rows past tc being copies of row tc (same inputs, same instruction sequence: the same bits)
+        launch_conv_tail_gather(src, tail->tab, dst, n, m->Tw, m->Ts, CD, s);
         std::swap(src, dst);
     }
     stage_mark(m, s, PB_CONV);
@@ -1096,7 +1162,7 @@ int ensure_stage(artalk_model* m, int maxB, int maxC) {
     for (auto& st : m->stage) if (st.used) HIPCHK(m, hipEventSynchronize(st.done));
     free_stage(m);
     for (auto& st : m->stage) {
-        HIPCHK(m, hipHostMalloc(reinterpret_cast<void**>(&st.src), (size_t)maxC * sizeof(long), hipHostMallocDefault));
+        HIPCHK(m, hipHostMalloc(reinterpret_cast<void**>(&st.src), (size_t)3 * maxC * sizeof(long), hipHostMallocDefault));
         HIPCHK(m, hipHostMalloc(reinterpret_cast<void**>(&st.has), (size_t)maxB, hipHostMallocDefault));
         HIPCHK(m, hipHostMalloc(reinterpret_cast<void**>(&st.slots), (size_t)maxB * sizeof(float*), hipHostMallocDefault));
         HIPCHK(m, hipHostMalloc(reinterpret_cast<void**>(&st.smooth), (size_t)maxB * sizeof(int4), hipHostMallocDefault));
@@ -1143,7 +1209,7 @@ int reserve(artalk_model* m, int maxB, int maxC) {
     w.maxB = maxB; w.maxC = maxC; w.G = std::min(maxC, 96);
     auto F = [&](int64_t n) { w.bytes += n * 4; return dalloc_in<float>(m->ws_allocs, n); };
     const int G = w.G;
-    w.src_off = dalloc_in<long>(m->ws_allocs, maxC);
+    w.src_off = dalloc_in<long>(m->ws_allocs, (int64_t)3 * maxC);      // chunk table of a call [C] | in pass order [C] | gather table [C] (ConvPasses)
     w.xnorm = F((int64_t)G * kSamplesPerChunk);
     w.convA = F(((int64_t)G * m->conv_S[0] + 16) * CD);
     w.convB = F(((int64_t)G * m->conv_S[1] + 16) * CD);
@@ -1404,6 +1470,44 @@ extern "C" {
 
 const char* artalk_last_error(const artalk_model* m) { return m ? m->err.c_str() : g_create_error.c_str(); }
 
+// Conv stack geometry of a chunk with `valid` real samples in front of zero padding (host only).  Row t of layer i starts at sample
+// J_i t (J_i = product of the strides up to i): from t_const[i] = ceil(valid / J_i) on, a row sees the padding alone, and all such rows
+// of a layer are equal.  Rows to compute: the last layer's rows 0 .. t_c = t_const[last] (one representative of the constant rows),
+// counted back as Tp[i-1] = (Tp[i] - 1) stride + kernel; row strides Sp[last] = Tp[last] + 1, Sp[i-1] = 2 Sp[i] (the full chunk's
+// rule, artalk_create).  Returns 1 and that geometry, or 0 and the whole chunk's when t_c leaves no constant row to skip.
+int artalk_conv_tail_geometry(int64_t valid, int samples_per_chunk, int n_conv, const int* kernel, const int* stride, int* t_const, int* Tp,
+                              int* Sp, int* samples_read) {
+    if (!kernel || !stride || !t_const || !Tp || !Sp || !samples_read || n_conv < 2 || n_conv > 8 || samples_per_chunk <= 0 || valid < 1 ||
+        valid > samples_per_chunk)
+        return ARTALK_EINVAL;
+    int T[8], J = 1, t = samples_per_chunk;
+    for (int i = 0; i < n_conv; ++i) {
+        if (kernel[i] <= 0 || stride[i] <= 0 || (i > 0 && stride[i] != 2) || t < kernel[i]) return ARTALK_EINVAL;
+        t = (t - kernel[i]) / stride[i] + 1; T[i] = t;
+        J *= stride[i];
+        t_const[i] = (int)((valid + J - 1) / J);
+    }
+    const int L = n_conv - 1;
+    const bool partial = t_const[L] < T[L] - 1;
+    Tp[L] = partial ? t_const[L] + 1 : T[L];
+    Sp[L] = Tp[L] + 1;
+    for (int i = L; i > 0; --i) {
+        Tp[i - 1] = partial ? (Tp[i] - 1) * stride[i] + kernel[i] : T[i - 1];
+        Sp[i - 1] = 2 * Sp[i];
+        if (Tp[i - 1] > Sp[i - 1] || Tp[i - 1] > T[i - 1]) return ARTALK_EINVAL;
+    }
+    *samples_read = partial ? (Tp[0] - 1) * stride[0] + kernel[0] : samples_per_chunk;
+    return partial ? 1 : 0;
+}
+// The length class of such a chunk: classes are quarters of a chunk, and a chunk runs at its class's upper bound, which is returned
+// (samples_per_chunk: the whole chunk).
+int64_t artalk_conv_tail_class(int64_t valid, int samples_per_chunk) {
+    if (samples_per_chunk <= 0 || valid < 1 || valid > samples_per_chunk) return ARTALK_EINVAL;
+    if (samples_per_chunk % 4) return samples_per_chunk;
+    const int64_t q = samples_per_chunk / 4;
+    return (valid + q - 1) / q * q;
+}
+
 int artalk_create(int device_id, const artalk_config* cfg, artalk_model** out) {
     if (!cfg || !out) { g_create_error = "null argument"; return ARTALK_EINVAL; }
     const artalk_config& c = *cfg;
@@ -1429,6 +1533,14 @@ int artalk_create(int device_id, const artalk_config* cfg, artalk_model** out) {
             if (c.w2v_conv_stride[i] != 2 || m->conv_T[i - 1] > 2 * S) { g_create_error = "conv stack geometry unsupported"; delete m; return ARTALK_EINVAL; }
             S *= 2;
         }
+    }
+    for (int q = 1; q <= 4 && kSamplesPerChunk % 4 == 0; ++q) {
+        artalk_model::TailGeo& tg = m->tail_geo[q - 1];
+        int tconst[8], read = 0;
+        const int rc = artalk_conv_tail_geometry((int64_t)q * (kSamplesPerChunk / 4), kSamplesPerChunk, c.w2v_n_conv, c.w2v_conv_kernel, c.w2v_conv_stride,
+                                                 tconst, tg.T, tg.S, &read);
+        tg.partial = rc == 1;      // (a geometry the function rejects runs whole chunks)
+        tg.tc = tconst[c.w2v_n_conv - 1];
     }
     for (int i = 0; i < 5; ++i) { m->pn[i] = c.patch_nums[i]; m->off[i + 1] = m->off[i] + c.patch_nums[i]; }
     if (init_ms_tables() != 0) { g_create_error = "uploading the interpolation tables to the device failed"; delete m; return ARTALK_EHIP; }
@@ -1611,6 +1723,7 @@ int artalk_set_precision(artalk_model* m, int mode) {
     m->precision = mode;   // captured graphs are keyed by mode: switching costs nothing and keeps every set
     return ARTALK_OK;
 }
+int artalk_set_tail_skip(artalk_model* m, int on) { if (!m) return ARTALK_EINVAL; m->tail_skip = on != 0; return ARTALK_OK; }
 int artalk_set_graphs(artalk_model* m, int enable) {
     if (!m) return ARTALK_EINVAL;
     m->use_graphs = (enable & 0xff) != 0;
@@ -1791,8 +1904,20 @@ int artalk_set_cu_mask(artalk_model* m, const uint32_t* mask, int n_words) {
 int artalk_infer(artalk_model* m, const float* audio_dev, int64_t audio_clip_stride, const int64_t* n_chunks, int B,
                  const float* style_motion_dev, const uint8_t* has_style, float* out_motion_dev, int64_t out_clip_stride,
                  uint8_t* out_bits_dev, uint8_t* out_hist_bits_dev, float* out_w2v_dev, void* stream) {
+    return artalk_infer_samples(m, audio_dev, audio_clip_stride, n_chunks, nullptr, B, style_motion_dev, has_style, out_motion_dev, out_clip_stride,
+                                out_bits_dev, out_hist_bits_dev, out_w2v_dev, stream);
+}
+
+// artalk_infer for clips whose length is known: n_samples[b] real samples, zeros behind them up to n_chunks[b] whole chunks.  The conv
+// stack then skips the frames that hear the padding alone (run_wav2vec); n_samples = NULL: every chunk is full.
+int artalk_infer_samples(artalk_model* m, const float* audio_dev, int64_t audio_clip_stride, const int64_t* n_chunks, const int64_t* n_samples,
+                         int B, const float* style_motion_dev, const uint8_t* has_style, float* out_motion_dev, int64_t out_clip_stride,
+                         uint8_t* out_bits_dev, uint8_t* out_hist_bits_dev, float* out_w2v_dev, void* stream) {
     if (!m || !audio_dev || !n_chunks || !out_motion_dev || B <= 0) return ARTALK_EINVAL;
     if (!m->finalized) return fail(m, ARTALK_ESTATE, "artalk_infer before artalk_finalize_weights");
+    for (int b = 0; n_samples && b < B; ++b)
+        if (n_chunks[b] > 0 && (n_samples[b] < 1 || n_samples[b] > n_chunks[b] * kSamplesPerChunk))
+            return fail(m, ARTALK_EINVAL, "n_samples[" + std::to_string(b) + "] must be in 1 .. n_chunks * " + std::to_string(kSamplesPerChunk));
     hipStream_t s;
     if (int rc = call_stream(m, stream, &s)) return rc;
     const artalk_config& c = m->cfg;
@@ -1819,7 +1944,45 @@ int artalk_infer(artalk_model* m, const float* audio_dev, int64_t audio_clip_str
         }
         base[maxch] = idx;
     }
-    HIPCHK(m, hipMemcpyAsync(w.src_off, src, C * sizeof(long), hipMemcpyHostToDevice, s));
+    // Tail skip: the length class of every chunk (3: the whole chunk - also a chunk wholly behind the clip's end, which cannot arise from
+    // a count that matches its chunk count), and per run_wav2vec group with a partial chunk its passes, the chunk table in pass order
+    // (src[C ..]) and the gather table (src[2 C ..]): launch_conv_tail_gather.
+    std::vector<ConvPasses> passes;
+    bool any_tail = false;
+    if (n_samples && m->tail_skip) {
+        std::vector<int> cls((size_t)C, 3);
+        for (int64_t j = 0, idx = 0; j < maxch; ++j)
+            for (int b = 0; b < B && n_chunks[b] > j; ++b, ++idx) {
+                const int64_t v = std::min<int64_t>(n_samples[b] - j * kSamplesPerChunk, kSamplesPerChunk);
+                const int64_t bound = v >= 1 ? artalk_conv_tail_class(v, kSamplesPerChunk) : 0;
+                const int q = bound >= 1 && kSamplesPerChunk % 4 == 0 ? (int)(bound / (kSamplesPerChunk / 4)) : 4;
+                cls[idx] = m->tail_geo[q - 1].partial ? q - 1 : 3;
+            }
+        const int last = m->n_conv - 1;
+        for (int c0 = 0; c0 < C; c0 += w.G) {
+            const int n = (int)std::min<int64_t>(w.G, C - c0);
+            ConvPasses cp;
+            static const int order[4] = {3, 0, 1, 2};      // whole chunks first, then the classes
+            int pos = 0;
+            long row0 = 0;                                 // where the pass's rows of the last layer start (run_wav2vec)
+            for (int k = 0; k < 4; ++k) {
+                const int cl = order[k], off = pos;
+                const artalk_model::TailGeo& tg = m->tail_geo[cl];
+                const long rows = cl == 3 ? m->Ts : tg.S[last], tc = cl == 3 ? m->Tw - 1 : tg.tc;
+                for (int i = 0; i < n; ++i)
+                    if (cls[c0 + i] == cl) {
+                        src[C + c0 + pos] = src[c0 + i];
+                        src[2 * C + c0 + i] = (row0 + (pos - off) * rows) | (tc << 32);
+                        ++pos;
+                    }
+                if (pos > off) { cp.off[cp.np] = off; cp.n[cp.np] = pos - off; cp.cls[cp.np] = cl; ++cp.np; row0 += (pos - off) * rows; }
+            }
+            if (cp.np == 1 && cp.cls[0] == 3) cp.np = 0;      // whole chunks only: the launches of a call without counts, no gather
+            else { cp.perm = w.src_off + C + c0; cp.tab = w.src_off + 2 * C + c0; any_tail = true; }
+            passes.push_back(cp);
+        }
+    }
+    HIPCHK(m, hipMemcpyAsync(w.src_off, src, (any_tail ? 3 : 1) * C * sizeof(long), hipMemcpyHostToDevice, s));
     m->stream_B = 0; m->stream_scales_ended = false;   // the batch call reuses the workspace that holds the streaming history
     m->ev_used = 0; m->dom_events.clear(); m->marks.clear(); m->prof_stream = s;
     // level 3: every kernel of this call is launched with its own start / stop events (kernels.h ARTALK_LAUNCH) - on this thread, for the
@@ -1830,7 +1993,8 @@ int artalk_infer(artalk_model* m, const float* audio_dev, int64_t audio_clip_str
     // (wav2vec2 of chunk index j + 1 on a stream of its own beside the AR/VAE body of index j was an option until round 3: with the
     // persistent one-workgroup-per-CU GEMM kernels, whose workgroups hold a CU's LDS for a whole launch, the body's short kernels wait
     // behind them - 82 -> 128 ms per step; removed)
-    for (int c0 = 0; c0 < C; c0 += w.G) run_wav2vec(m, audio_dev, c0, (int)std::min<int64_t>(w.G, C - c0), out_w2v_dev, s);
+    for (int c0 = 0, gi = 0; c0 < C; c0 += w.G, ++gi)
+        run_wav2vec(m, audio_dev, c0, (int)std::min<int64_t>(w.G, C - c0), out_w2v_dev, s, !passes.empty() && passes[gi].np ? &passes[gi] : nullptr);
     // initial history: encode + quantise an all-zero motion (app/models.py:86-89) - the same for every clip: cached per model
     if (int rc = run_init_history(m, B, s)) return rc;
     const size_t bits_row = (size_t)kNTok * c.code_dim;

@@ -150,6 +150,10 @@ struct LnArgs {
     // valid frames; their input is whatever an earlier launch left there and no valid row ever reads them): they are stored as
     // zeros, which keeps everything computed from them finite and inside the P8 range, and are exempt from the range guard.
     int junk_period = 0, junk_from = 0;
+    // junk_row2 > 0: rows from junk_row2 on are a second run of chunks with a layout of its own - row r of it is padding where
+    // (r - junk_row2) % junk_period2 >= junk_from2 (the conv stack's chunks of two length classes in one launch)
+    int junk_row2 = 0, junk_period2 = 0, junk_from2 = 0;
+    int plan_M = 0;   // > 0: pick the kernel (rows per wave) as for a launch of plan_M rows (a pass over part of the rows keeps the whole launch's kernel)
 };
 void launch_layernorm(const LnArgs& a, hipStream_t s);
 // softmax(scale * Q K^T [+mask]) V, fp32 MFMA, online softmax over 64-key blocks staged in LDS.
@@ -194,6 +198,9 @@ void launch_audio_normalize(const float* audio, const long* src_off, float* xnor
 // conv0 (Cin=1,k=10,s=5) + bias + LN(512, affine) + GELU(erf): xnorm [C, n] -> Y rows c*row_stride + t, t < T
 void launch_conv0(const float* xnorm, int n, const float* w /*[512,10]*/, const float* bias, const float* lnw,
                   const float* lnb, float* Y, int n_chunks, int T, int row_stride, hipStream_t s, int out_p8 = 0, int* status = nullptr, int p8_exp = kActExp);
+// conv-stack tail broadcast (run_wav2vec): Y row c*Ts + t = X row base(c) + min(t, tc(c)) for t < Tw, zeros for Tw <= t < Ts; D floats per
+// row (D % 4 == 0); tab[c] = base(c) | tc(c) << 32 (device table, one word per chunk)
+void launch_conv_tail_gather(const float* X, const long* tab, float* Y, int n_chunks, int Tw, int Ts, int D, hipStream_t s);
 // multi-scale adaptive average pooling 199 -> {1,5,25,50,100} followed by SiLU: X rows c*x_tstride + t -> Y rows c*181 + tok
 void launch_pool_silu(const float* X, int x_tstride, int T, float* Y, int n_chunks, const int* patch_nums, int n_lvls,
                       int D, hipStream_t s, int out_p8 = 0, int* status = nullptr, int p8_exp = kActExp);

@@ -86,7 +86,9 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const LnArgs a) {
         for (int i = 0; i < NV; ++i) { const float d = v[rr][i] - mean; q += d * d; }
         const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / D) + a.eps);
         float* y = a.Y + (long)row * a.ldy;
-        const bool junk = a.junk_period && row % a.junk_period >= a.junk_from;      // layout padding row: stored as zeros (kernels.h)
+        const bool second = a.junk_row2 > 0 && row >= a.junk_row2;
+        const int jr = second ? row - a.junk_row2 : row, jp = second ? a.junk_period2 : a.junk_period, jf = second ? a.junk_from2 : a.junk_from;
+        const bool junk = jp && jr % jp >= jf;      // layout padding row: stored as zeros (kernels.h)
         int* const status = junk ? nullptr : a.status;
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
@@ -119,7 +121,7 @@ static void launch_ln(const LnArgs& a, hipStream_t s) {
 
 void launch_layernorm(const LnArgs& a, hipStream_t s) {
     if (a.M <= 0) return;
-    const bool big = a.M >= 8192;      // several rows per wave only when there are enough rows to fill the chip anyway
+    const bool big = (a.plan_M > 0 ? a.plan_M : a.M) >= 8192;      // several rows per wave only when there are enough rows to fill the chip anyway
     switch (a.D) {
         case 128: launch_ln<128, 1>(a, s); break;
         case 512: if (big) launch_ln<512, 4>(a, s); else launch_ln<512, 1>(a, s); break;

@@ -121,6 +121,31 @@ void launch_conv0(const float* xnorm, int n, const float* w, const float* bias, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Conv-stack output of the chunks of a call in the encoder's layout (Ts rows per chunk, the call's chunk order) from the passes that
+// computed them: a chunk whose tail is zero padding was computed up to ONE row of the padded region (row tc), which stands for every
+// later row.  Two rows per workgroup, 16 bytes per lane: a copy.
+__global__ __launch_bounds__(256) void conv_tail_gather_kernel(const float* __restrict__ X, const long* __restrict__ tab, float* __restrict__ Y,
+                                                               int Tw, int Ts, int D) {
+    const int c = blockIdx.y, t = blockIdx.x * 2 + (threadIdx.x >> 7);
+    if (t >= Ts) return;
+    const long e = tab[c];
+    const long base = e & 0xffffffffL;
+    const int tc = (int)(e >> 32);
+    const float* x = X + (base + min(t, tc)) * D;
+    float* y = Y + ((long)c * Ts + t) * D;
+    for (int d = (threadIdx.x & 127) * 4; d < D; d += 512) {
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (t < Tw) v = *reinterpret_cast<const f32x4*>(x + d);
+        *reinterpret_cast<f32x4*>(y + d) = v;
+    }
+}
+
+void launch_conv_tail_gather(const float* X, const long* tab, float* Y, int n_chunks, int Tw, int Ts, int D, hipStream_t s) {
+    if (n_chunks <= 0) return;
+    ARTALK_LAUNCH(conv_tail_gather_kernel, dim3((Ts + 1) / 2, n_chunks), dim3(256), 0, s, X, tab, Y, Tw, Ts, D);
+}
+
+// ------------------------------------------------------------------------------------------------
 struct PoolLevels { int n; int pn[8]; };
 
 __global__ __launch_bounds__(256) void pool_silu_kernel(const float* __restrict__ X, int x_tstride, int T, float* __restrict__ Y,

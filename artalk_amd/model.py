@@ -409,6 +409,12 @@ class BitwiseARModel:
         tuning knobs (multiples of 16, 0 = keep)."""
         capi.lib().artalk_set_graphs(self._h, int(bool(on)) | (int(branches) << 8) | ((splitk_tiles // 16) << 16) | ((splitk_target // 16) << 24))
 
+    def set_tail_skip(self, on: bool):
+        """Conv stack over the frames that hear real audio only (``artalk_set_tail_skip``, default on): the frames of a clip's last chunk
+        that see nothing but its zero padding are one row, computed once.  Same bits either way: the A/B and test switch."""
+        if capi.lib().artalk_set_tail_skip(self._h, int(bool(on))) != capi.OK:
+            raise RuntimeError("artalk_set_tail_skip failed")
+
     def graph_count(self):
         """(graphs held, captures so far): the body-graph cache is bounded (artalk_graph_count)."""
         n = C.c_longlong(0)
@@ -930,9 +936,14 @@ class BitwiseARModel:
                 if L.artalk_set_tap(self._h, capi.ptr(tap_t), B, maxch) != capi.OK:
                     raise RuntimeError("artalk_set_tap failed: " + self._err())
             nch_sorted = (C.c_int64 * B)(*[nch[i] for i in order])
-            rc = L.artalk_infer(self._h, capi.ptr(audio_pad), audio_pad.stride(0), nch_sorted, B, capi.ptr(style_t),
-                                C.cast(has, C.c_void_p) if has is not None else None, capi.ptr(out), out.stride(0),
-                                capi.ptr(bits), capi.ptr(hist), capi.ptr(w2v), C.c_void_p(self._stream.cuda_stream))
+            tail = (capi.ptr(out), out.stride(0), capi.ptr(bits), capi.ptr(hist), capi.ptr(w2v), C.c_void_p(self._stream.cuda_stream))
+            has_p = C.cast(has, C.c_void_p) if has is not None else None
+            if hasattr(L, "artalk_infer_samples"):
+                # the clips' lengths go with them: the conv stack skips the frames that hear the zero padding alone (set_tail_skip)
+                ns_sorted = (C.c_int64 * B)(*[n_samples[i] for i in order])
+                rc = L.artalk_infer_samples(self._h, capi.ptr(audio_pad), audio_pad.stride(0), nch_sorted, ns_sorted, B, capi.ptr(style_t), has_p, *tail)
+            else:      # (an older build loaded through ARTALK_LIB for an A/B run)
+                rc = L.artalk_infer(self._h, capi.ptr(audio_pad), audio_pad.stride(0), nch_sorted, B, capi.ptr(style_t), has_p, *tail)
             caller.wait_stream(self._stream)
             if tap_t is not None:
                 L.artalk_set_tap(self._h, None, 0, 0)        # (synchronises: the tap buffer is complete)

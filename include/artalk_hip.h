@@ -90,6 +90,27 @@ int artalk_infer(artalk_model* m, const float* audio_dev, int64_t audio_clip_str
                  const float* style_motion_dev, const uint8_t* has_style, float* out_motion_dev, int64_t out_clip_stride,
                  uint8_t* out_bits_dev, uint8_t* out_hist_bits_dev, float* out_w2v_dev, void* stream);
 
+/* artalk_infer for clips whose length the caller knows: n_samples host, [B], the real samples of clip b (1 .. n_chunks[b]*64000); what
+ * follows them up to n_chunks[b] whole chunks MUST be zeros.  The wav2vec2 conv stack has no padding and mixes no frames, so every
+ * frame of a chunk that hears the zero padding alone equals the first such frame bit for bit: the stack computes that one and copies
+ * it (chunks in length classes by quarter of a chunk, one pass per class).  Same results as artalk_infer, bit for bit, in every
+ * precision mode; n_samples = NULL is artalk_infer (every chunk runs whole).  artalk_set_tail_skip(m, 0) runs every chunk whole
+ * whatever the counts say (default 1): the A/B and test switch.  The streaming calls always run whole chunks. */
+int artalk_infer_samples(artalk_model* m, const float* audio_dev, int64_t audio_clip_stride, const int64_t* n_chunks,
+                         const int64_t* n_samples, int B, const float* style_motion_dev, const uint8_t* has_style, float* out_motion_dev,
+                         int64_t out_clip_stride, uint8_t* out_bits_dev, uint8_t* out_hist_bits_dev, float* out_w2v_dev, void* stream);
+int artalk_set_tail_skip(artalk_model* m, int on);
+/* The geometry behind it (host only, no device): for a chunk of samples_per_chunk samples with `valid` (1 .. samples_per_chunk) real ones
+ * and the conv table kernel[n_conv] / stride[n_conv] (stride 2 from layer 1 on), per layer i: t_const[i], the first output row whose
+ * receptive field starts at or after sample `valid`; Tp[i], the rows to compute - the last layer's rows up to and including
+ * t_const[last], counted back as Tp[i-1] = (Tp[i] - 1) stride[i] + kernel[i]; Sp[i], the per-chunk row stride (Sp[last] = Tp[last] + 1,
+ * Sp[i-1] = 2 Sp[i] >= Tp[i-1]); *samples_read, the samples layer 0 then reads.  Returns 1, or 0 when t_const[last] is the last row
+ * or beyond (nothing to skip: Tp / Sp are the whole chunk's), or ARTALK_EINVAL.  artalk_conv_tail_class: the upper bound, in
+ * samples, of the length class (quarters of a chunk) a chunk with `valid` real samples runs at. */
+int artalk_conv_tail_geometry(int64_t valid, int samples_per_chunk, int n_conv, const int* kernel, const int* stride, int* t_const,
+                              int* Tp, int* Sp, int* samples_read);
+int64_t artalk_conv_tail_class(int64_t valid, int samples_per_chunk);
+
 /* Style condition of n style clips (app/models.py:67-73: StyleEncoder -> style_cond_embed -> 1.1 c - 0.1 null), for callers that
  * keep one style across many calls as the reference's engine does (inference.py:41-45): style_motion_dev [n][50][106] ->
  * out_cond_dev [n][768].  Pass a condition back through artalk_infer / artalk_stream_begin with has_style[b] = 2. */
