@@ -31,6 +31,7 @@ SYMBOLS = [
     "artalk_op_w2v_front_rows", "artalk_op_pool_silu_rows", "artalk_op_posconv_rows",
     "artalk_op_attention_plan", "artalk_op_attention_rows_cus",
     "artalk_infer_samples", "artalk_set_tail_skip", "artalk_conv_tail_geometry", "artalk_conv_tail_class",
+    "artalk_render_create", "artalk_render_mesh", "artalk_render_set_slab", "artalk_render_destroy", "artalk_render_last_error",
 ]
 
 # ARTALK_ATTN_* of include/artalk_hip.h: the kernels of attention.hip, as artalk_op_attention_plan names them
@@ -207,6 +208,17 @@ def lib() -> C.CDLL:
     L.artalk_flame_destroy.restype = None
     L.artalk_flame_last_error.argtypes = [vp]
     L.artalk_flame_last_error.restype = C.c_char_p
+    if hasattr(L, "artalk_render_create"):      # (an older build loaded through ARTALK_LIB for an A/B run lacks the mesh renderer)
+        L.artalk_render_create.argtypes = [i32, i32, i32, vp, i32, f32, C.POINTER(vp)]
+        L.artalk_render_create.restype = i32
+        L.artalk_render_mesh.argtypes = [vp, vp, i32, vp, f32, vp, vp, vp, vp]
+        L.artalk_render_mesh.restype = i32
+        L.artalk_render_set_slab.argtypes = [vp, i32]
+        L.artalk_render_set_slab.restype = i32
+        L.artalk_render_destroy.argtypes = [vp]
+        L.artalk_render_destroy.restype = None
+        L.artalk_render_last_error.argtypes = [vp]
+        L.artalk_render_last_error.restype = C.c_char_p
     L.artalk_savgol.argtypes = [vp, vp, vp, i32, vp]
     L.artalk_savgol.restype = i32
     L.artalk_set_profiling.argtypes = [vp, i32]

@@ -3,7 +3,8 @@
 Same constructor arguments, attributes and methods as the reference class, so code written against it (the CLI
 at ``inference.py:225-237``, the Gradio handler at ``:99-125``) keeps working for everything up to the FLAME
 codes.  Rendering (``inference.py:59-87``: FLAME mesh / GAGAvatar, PyAV muxing) is downstream of the drop-in
-boundary and out of scope: ``rendering`` only forwards to a renderer the caller plugs in.
+boundary: ``rendering`` only forwards to the FLAME model and the mesh renderer the caller plugs in
+(``artalk_amd.flame.FLAMEModel``, ``artalk_amd.render.RenderMesh``); GAGAvatar and muxing are out of scope.
 """
 from __future__ import annotations
 
@@ -190,14 +191,22 @@ class ARTAvatarInferEngine:
 
     def rendering(self, audio, pred_motions, shape_id="mesh", shape_code=None, save_name="ARTAvatar.mp4"):
         """Downstream of the boundary (inference.py:59-87).  Produces the vertices the reference's mesh branch would
-        feed its renderer when a FLAME model has been plugged in; rasterising and muxing are not part of this package."""
+        feed its renderer when a FLAME model has been plugged in.  With a renderer plugged into ``engine.mesh_renderer`` as well
+        (``artalk_amd.render.RenderMesh``) it returns what the reference stacks into ``pred_images`` (inference.py:70-72, :83):
+        a ``(T, 3, S, S)`` tensor in [0, 1], on the device and from one batched call over all frames (the reference renders frame by
+        frame and moves each image to the host).  Writing the video (PyAV muxing) is not part of this package."""
         if shape_id != "mesh" or self.flame_model is None:
             raise NotImplementedError("rendering is outside the audio->motion path; plug a FLAME model into "
-                                      "engine.flame_model to get vertices, or pass pred_motions to the reference renderer")
+                                      "engine.flame_model to get vertices (and an artalk_amd.render.RenderMesh into "
+                                      "engine.mesh_renderer to get images), or pass pred_motions to the reference renderer")
         if shape_code is None:
             shape_code = audio.new_zeros(1, 300).to(self.device).expand(pred_motions.shape[0], -1)
         else:
             assert shape_code.dim() == 2, f"Invalid shape_code dim: {shape_code.dim()}."
             assert shape_code.shape[0] == 1, f"Invalid shape_code shape: {shape_code.shape}."
             shape_code = shape_code.to(self.device).expand(pred_motions.shape[0], -1)
-        return self.ARTalk.basic_vae.get_flame_verts(self.flame_model, shape_code, pred_motions, with_global=True)
+        verts = self.ARTalk.basic_vae.get_flame_verts(self.flame_model, shape_code, pred_motions, with_global=True)
+        renderer = getattr(self, "mesh_renderer", None)      # (engines assembled without __init__ have no such attribute)
+        if renderer is None:
+            return verts
+        return renderer(verts)[0] / 255.0

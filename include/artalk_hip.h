@@ -202,6 +202,28 @@ int artalk_flame_verts(artalk_flame* f, const float* betas_dev, const float* ful
 void artalk_flame_destroy(artalk_flame* f);
 const char* artalk_flame_last_error(const artalk_flame* f);
 
+/* FLAME mesh renderer: a stand-in for RenderMesh.forward (app/flame_model/renderer_utils.py:55-85), which wraps pytorch3d's
+ * rasteriser (blur_radius 0, one face per pixel, no back-face culling, perspective-correct barycentrics) and HardPhongShader.  What
+ * is computed is defined in DESIGN.md ("Mesh renderer"); parity with pytorch3d itself is unpinned (no pytorch3d build to compare with).
+ * artalk_render_create: faces_host [F][3] vertex indices in [0, V), image_size in 1..16384, scale as RenderMesh's (default camera at
+ * distance 2 * scale).  ARTALK_EINVAL with a message (artalk_render_last_error(NULL)) before the device is touched for V <= 0, F <= 0,
+ * a bad image_size, a NULL faces_host / out or a face index outside [0, V).
+ * artalk_render_mesh: verts_dev [T][V][3] fp32 world space -> rgb_dev [T][3][S][S] in 0..255 (255 where no face covers the pixel),
+ * alpha_dev [T][1][S][S] 0 or 1, pix_to_face_dev_or_null [T][S][S] (-1 for background; for tests and debugging).
+ * transform_3x4_host_or_null: row-major M with R = M[:, :3], T = M[:, 3] (p_view = p_world . R + T), NULL = diag(-1, 1, -1) and
+ * (0, 0, 2 * scale); focal_or_0: focal length in NDC units, 0 = 12.  Runs on the caller's stream and does not synchronise; bit-identical
+ * from run to run and for any split of the frames over calls.  ARTALK_EINVAL for a NULL handle, NULL verts / rgb / alpha or T < 0;
+ * T == 0 succeeds and does nothing.
+ * artalk_render_set_slab: frames per pass over the key buffer (8 bytes per pixel and frame); 0 = the default chosen at create time (32 MiB
+ * of keys, at most 64 frames), which is also the largest value accepted.  Returns the value in force. */
+typedef struct artalk_mesh_renderer artalk_mesh_renderer;
+int artalk_render_create(int device_id, int V, int F, const int32_t* faces_host, int image_size, float scale, artalk_mesh_renderer** out);
+int artalk_render_mesh(artalk_mesh_renderer* r, const float* verts_dev, int T, const float* transform_3x4_host_or_null, float focal_or_0,
+                       float* rgb_dev, float* alpha_dev, int32_t* pix_to_face_dev_or_null, void* stream);
+int artalk_render_set_slab(artalk_mesh_renderer* r, int frames);
+void artalk_render_destroy(artalk_mesh_renderer* r);
+const char* artalk_render_last_error(const artalk_mesh_renderer* r);
+
 /* Numerical health of the work enqueued since the last artalk_infer / artalk_stream_begin started.  Every call ends with an
  * asynchronous copy of the device status word to pinned host memory.  artalk_get_status WAITS for that copy (an event wait:
  * the one synchronisation on this boundary, paid only by callers that ask; `stream` is ignored); artalk_poll_status never
