@@ -112,6 +112,4 @@ class FLAMEModel:
             rc = capi.lib().artalk_flame_verts(self._h, capi.ptr(betas), capi.ptr(full_pose), n, capi.ptr(out), capi.current_stream_ptr())
         if rc != capi.OK:
             raise RuntimeError("artalk_flame_verts failed: " + capi.lib().artalk_flame_last_error(self._h).decode())
-        if verts_sclae is not None:
-            return out * (verts_sclae / self.scale)
-        return out
+        return out      # FLAME.py:148-149: with no_lmks=True the reference returns vertices * self.scale and never looks at verts_sclae
