@@ -378,8 +378,8 @@ class BitwiseARModel:
         return int(capi.lib().artalk_weight_bytes(self._h))
 
     def set_profiling(self, level: int):
-        """0 off, 1 light (graphs on, eager launches bracketed), 2 full (graphs off), 3 kernel timer (graphs off, one clip group,
-        every launch timed: ``get_kernel_sums``)."""
+        """0 off, 1 light (graphs on, eager launches bracketed), 2 full (graphs off), 3 kernel timer (graphs off, the production clip
+        groups one after the other on one stream, every launch timed: ``get_kernel_sums``)."""
         capi.lib().artalk_set_profiling(self._h, int(level))
 
     def set_precision(self, mode):

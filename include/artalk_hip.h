@@ -255,8 +255,8 @@ int artalk_savgol(artalk_model* m, const float* in_dev, float* out_dev, int T, v
  *   conv1-6 and the AdaLN tables; f32 mode: the 128x128-tile fp32 MFMA GEMM)  out[8] their summed ms  out[9] their summed FLOP */
 int artalk_set_profiling(artalk_model* m, int level);
 int artalk_get_profile(artalk_model* m, double* out, int n);
-/* Kernel-time budget without a profiler: after an artalk_infer at profiling level 3 (graphs off, one clip group, every launch carries its
- * own start / stop events), out[b] = summed kernel durations (ms) per bucket - 0 style, 1 conv stack, 2 encoder, 3 AdaLN tables,
+/* Kernel-time budget without a profiler: after an artalk_infer at profiling level 3 (graphs off, the production clip groups one after the
+ * other on one stream, every launch carries its own start / stop events), out[b] = summed kernel durations (ms) per bucket - 0 style, 1 conv stack, 2 encoder, 3 AdaLN tables,
  * 4 history K/V + glue, 5..9 scale steps 0..4, 10 VAE decode, 11 re-encode, 12 other - and out[13] = kernels timed (n >= 14).
  * bench.py reports it next to the stages' event times as `budget_ms`. */
 int artalk_get_kernel_sums(artalk_model* m, double* out, int n);
