@@ -32,6 +32,8 @@ SYMBOLS = [
     "artalk_op_attention_plan", "artalk_op_attention_rows_cus",
     "artalk_infer_samples", "artalk_set_tail_skip", "artalk_conv_tail_geometry", "artalk_conv_tail_class",
     "artalk_render_create", "artalk_render_mesh", "artalk_render_set_slab", "artalk_render_destroy", "artalk_render_last_error",
+    "artalk_splat_create", "artalk_splat_render", "artalk_splat_set_timing", "artalk_splat_get_timing", "artalk_splat_destroy",
+    "artalk_splat_last_error",
 ]
 
 # ARTALK_ATTN_* of include/artalk_hip.h: the kernels of attention.hip, as artalk_op_attention_plan names them
@@ -219,6 +221,20 @@ def lib() -> C.CDLL:
         L.artalk_render_destroy.restype = None
         L.artalk_render_last_error.argtypes = [vp]
         L.artalk_render_last_error.restype = C.c_char_p
+    if hasattr(L, "artalk_splat_create"):      # (an older build loaded through ARTALK_LIB for an A/B run lacks the splat rasteriser)
+        L.artalk_splat_create.argtypes = [i32, C.POINTER(vp)]
+        L.artalk_splat_create.restype = i32
+        L.artalk_splat_render.argtypes = [vp, i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i32, f32, f32, f32,
+                                          vp, vp, vp, vp]
+        L.artalk_splat_render.restype = i32
+        L.artalk_splat_set_timing.argtypes = [vp, i32]
+        L.artalk_splat_set_timing.restype = i32
+        L.artalk_splat_get_timing.argtypes = [vp, C.POINTER(C.c_double), i32, C.POINTER(C.c_longlong), C.POINTER(i32)]
+        L.artalk_splat_get_timing.restype = i32
+        L.artalk_splat_destroy.argtypes = [vp]
+        L.artalk_splat_destroy.restype = None
+        L.artalk_splat_last_error.argtypes = [vp]
+        L.artalk_splat_last_error.restype = C.c_char_p
     L.artalk_savgol.argtypes = [vp, vp, vp, i32, vp]
     L.artalk_savgol.restype = i32
     L.artalk_set_profiling.argtypes = [vp, i32]

@@ -224,6 +224,40 @@ int artalk_render_set_slab(artalk_mesh_renderer* r, int frames);
 void artalk_render_destroy(artalk_mesh_renderer* r);
 const char* artalk_render_last_error(const artalk_mesh_renderer* r);
 
+/* Gaussian splat rasteriser, forward only, 32 channels: a stand-in for the CUDA extension diff_gaussian_rasterization_32d that the
+ * reference's GAGAvatar head calls under torch.no_grad (app/GAGAvatar/utils_renderer.py:6, models.py:63).  What is computed is defined in
+ * DESIGN.md ("Gaussian splat rasteriser"): the 3D-Gaussian-splatting forward pass with precomputed colours and 16 x 16 tiles; parity with
+ * the CUDA extension itself is unpinned (neither its source nor a build of it to compare with).  No spherical harmonics, no backward.
+ * artalk_splat_render: T frames of N Gaussians onto H x W.  The five attribute arrays are device fp32: means [N][3], colors [N][32],
+ * opacities [N], scales [N][3], rotations [N][4] as (r, x, y, z), used as given; each comes with the number of ELEMENTS between two
+ * frames, 0 = one set shared by all frames.  view_host / proj_host: n_cams (1 or T) row-major 4 x 4 matrices in HOST memory, row-vector
+ * convention ((p, 1) . V), read before the call returns.  bg_dev_or_null: 32 device floats, NULL = zeros.  out_dev [T][32][H][W],
+ * radii_dev [T][N] int32 (0: culled).  Every pixel and every radius is written; nothing else is.
+ * Unlike the rest of this interface the call WAITS ONCE on `stream`: the number of (tile, Gaussian) pairs depends on the data, so after a
+ * counting pass the host reads the frames' pair counts and grows the sort buffers (the CUDA extension does the same); artalk_model's
+ * no-synchronisation rule does not bind this object.  Growing a buffer waits for the device too; a repeated shape allocates nothing.
+ * Bit-identical from run to run and for any split of the frames over calls.
+ * ARTALK_EINVAL with a message, before the device is touched: a NULL handle (artalk_splat_last_error(NULL)), N < 0, T < 0, H or W outside
+ * 1..4096, n_cams not 1 or T, a tanfov that is not positive, a negative stride, NULL out, and with N > 0 a NULL attribute, matrix or
+ * radii pointer.  T == 0 succeeds and does nothing; N == 0 writes the background.  ARTALK_EHIP: an allocation failed (the message names
+ * the size); ARTALK_ECAPACITY: one frame has more than 2^31 - 1 pairs.  artalk_splat_create only refuses a NULL out or a negative
+ * device_id; the device is first touched by a render call that passes its checks.  One handle serves any shape; it must not be used
+ * from two threads at once.
+ * artalk_splat_set_timing / artalk_splat_get_timing (tools/splat_bench.py): with timing on, a call records HIP events around its stages and
+ * waits for them at its end; get_timing copies up to n of the 6 per-stage sums in ms (count pass, preprocess, scan + emit, sort, ranges,
+ * blend) of the last call, its pairs and frames (each nullable), and returns 6. */
+typedef struct artalk_splat artalk_splat;
+int artalk_splat_create(int device_id, artalk_splat** out);
+int artalk_splat_render(artalk_splat* s, int N, int T, int H, int W, const float* means_dev, int64_t means_stride, const float* colors_dev,
+                        int64_t colors_stride, const float* opacities_dev, int64_t opacities_stride, const float* scales_dev,
+                        int64_t scales_stride, const float* rotations_dev, int64_t rotations_stride, const float* view_host,
+                        const float* proj_host, int n_cams, float tanfovx, float tanfovy, float scale_modifier, const float* bg_dev_or_null,
+                        float* out_dev, int32_t* radii_dev, void* stream);
+int artalk_splat_set_timing(artalk_splat* s, int enable);
+int artalk_splat_get_timing(const artalk_splat* s, double* stage_ms, int n, long long* pairs, int* frames);
+void artalk_splat_destroy(artalk_splat* s);
+const char* artalk_splat_last_error(const artalk_splat* s);
+
 /* Numerical health of the work enqueued since the last artalk_infer / artalk_stream_begin started.  Every call ends with an
  * asynchronous copy of the device status word to pinned host memory.  artalk_get_status WAITS for that copy (an event wait:
  * the one synchronisation on this boundary, paid only by callers that ask; `stream` is ignored); artalk_poll_status never
