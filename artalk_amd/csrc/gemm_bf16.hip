@@ -14,6 +14,7 @@
 // It covers every GemmArgs form of the f32 path: conv-window lda, amode 1 (grouped positional conv window), grid.z batching,
 // cmap / gmap row maps, gate, residual aliasing C, bias, the 4 activations and split-K partials.
 #include "common.h"
+#include "gemm_tile.h"
 
 namespace artalk {
 
@@ -34,21 +35,9 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const GemmArgs g) {
     __bf16* Bs = smem_bf16 + 2 * BM * LDS_LD;     // [2][BN][LDS_LD]
 
     const int tid = threadIdx.x;
-    // tile order: the f32 kernel's (XCD-contiguous runs, GM row-tiles per group); placement only affects speed
     const int tiles_n = (g.N + BN - 1) / BN, tiles_m = (g.M + BM - 1) / BM;
     int tm, tn;
-    {
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        const int idx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-        constexpr int GM = (BM >= 128) ? 4 : 8;
-        const int width = GM * tiles_n;
-        const int group = idx / width, first_m = group * GM;
-        const int gsz = min(tiles_m - first_m, GM);
-        const int in_g = idx - group * width;
-        tn = in_g / gsz;
-        tm = first_m + (in_g - tn * gsz);
-    }
+    tile_order(gridDim.x, blockIdx.x, tiles_m, tiles_n, (BM >= 128) ? 4 : 8, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
     const int z = blockIdx.z;
     const float* __restrict__ A = g.A + z * g.sA;
@@ -69,11 +58,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const GemmArgs g) {
                 if (AMODE == 0) {
                     v = *reinterpret_cast<const f32x4*>(A + (long)gm * g.lda + k);
                 } else {
-                    const int c = gm / g.pc_tstride, t = gm - c * g.pc_tstride;
-                    const int tap = k / g.pc_cin, ci = k - tap * g.pc_cin;
-                    const int ts = t + tap - g.pc_pad;
-                    if (ts >= 0 && ts < g.pc_T)
-                        v = *reinterpret_cast<const f32x4*>(A + ((long)c * g.pc_tstride + ts) * g.lda + ci);
+                    long off;
+                    if (window_src(g, gm, k, off)) v = *reinterpret_cast<const f32x4*>(A + off);
                 }
             }
             ra[i] = v;
@@ -105,16 +91,12 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const GemmArgs g) {
     const int r = lane & 31, h = lane >> 5;
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    zero_acc(acc);
 
     // K % 32 == 0 (callers); split-K: this workgroup owns K steps [kt0, nk)
-    const int nk_all = g.K / BK;
-    const int kt0 = (int)((long)nk_all * blockIdx.y / g.splitk), nk = (int)((long)nk_all * (blockIdx.y + 1) / g.splitk);
+    int kt0, nkt;
+    k_range(g.K / BK, blockIdx.y, g.splitk, kt0, nkt);
+    const int nk = kt0 + nkt;
     if (kt0 < nk) {
         gload(kt0);
         lstore(0);

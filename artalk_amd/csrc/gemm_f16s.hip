@@ -17,15 +17,23 @@
 // hi halves + 16 bytes of lo halves), so a packed matrix has the same size, pitch and 16-byte loads as the fp32 one and a
 // 16-byte chunk is an MFMA fragment.  LDS rows (register-staged kernel) hold the hi plane (BK halves) followed by the lo
 // plane, padded to 144 bytes (conflict-free ds_read_b128 for the 32x32x16 operand map: lane (r,h) holds k = 8h..8h+7).
+//
+// P8 LDS layout of the LDS-DMA kernels (gemm_p8_*: BOTH operands already in P8, A written in P8 by its producer kernel, so staging
+// is a pure byte copy global -> LDS, global_load_lds_dwordx4 / buffer_load ... lds: no staging registers, behind counted vmcnt
+// waits and raw s_barriers).  A stage of the ring holds one 32-deep K tile: BM A rows x 128 B, then BN W rows x 128 B, rows
+// unpadded (a DMA wave-instruction, a "piece", writes 1 KiB = 8 rows).  The 16-byte chunk c of tile row r lives at physical chunk
+// c ^ ((r >> 1) & 7): the XOR is applied to the per-lane SOURCE address of the DMA and again on the fragment read (same
+// involution), which makes the ds_read_b128 fragment reads conflict-free.  Lane (r, h)'s fragments of k block kb are the logical
+// chunks (kb * 2 + h) * 2 (hi) and + 1 (lo).  gemm_tile.h states this arithmetic once (p8_phys_chunk, p8_frag_offsets, p8_piece_*).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
 #include "common.h"
+#include "gemm_tile.h"
 
 namespace artalk {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -82,18 +90,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16s_kernel(const GemmArgs g) {
     const int tid = threadIdx.x;
     const int tiles_n = (g.N + BN - 1) / BN, tiles_m = (g.M + BM - 1) / BM;
     int tm, tn;
-    {   // XCD-contiguous, grouped column-major tile order (see gemm_f32.hip)
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        const int idx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-        constexpr int GM = (BM >= 128) ? 4 : 8;
-        const int width = GM * tiles_n;
-        const int group = idx / width, first_m = group * GM;
-        const int gsz = min(tiles_m - first_m, GM);
-        const int in_g = idx - group * width;
-        tn = in_g / gsz;
-        tm = first_m + (in_g - tn * gsz);
-    }
+    tile_order(gridDim.x, blockIdx.x, tiles_m, tiles_n, (BM >= 128) ? 4 : 8, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
     const int z = blockIdx.z;
     const float* __restrict__ A = g.A + z * g.sA;
@@ -113,10 +110,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f16s_kernel(const GemmArgs g) {
                 if (AMODE == 0) {
                     v = *reinterpret_cast<const u32x4*>(A + (long)gm * g.lda + k);
                 } else {
-                    const int c = gm / g.pc_tstride, t = gm - c * g.pc_tstride;
-                    const int tap = k / g.pc_cin, ci = k - tap * g.pc_cin;
-                    const int ts = t + tap - g.pc_pad;
-                    if (ts >= 0 && ts < g.pc_T) v = *reinterpret_cast<const u32x4*>(A + ((long)c * g.pc_tstride + ts) * g.lda + ci);
+                    long off;
+                    if (window_src(g, gm, k, off)) v = *reinterpret_cast<const u32x4*>(A + off);
                 }
             }
             ra[i] = v;
@@ -157,15 +152,11 @@ __global__ __launch_bounds__(256, 2) void gemm_f16s_kernel(const GemmArgs g) {
     const int r = lane & 31, h = lane >> 5;
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    zero_acc(acc);
 
-    const int nk_all = g.K / BK;   // split-K: this workgroup owns K steps [kt0, nk)
-    const int kt0 = (int)((long)nk_all * blockIdx.y / g.splitk), nk = (int)((long)nk_all * (blockIdx.y + 1) / g.splitk);
+    int kt0, nkt;   // split-K: this workgroup owns K steps [kt0, nk)
+    k_range(g.K / BK, blockIdx.y, g.splitk, kt0, nkt);
+    const int nk = kt0 + nkt;
     gload(kt0);
     lstore(0);
     __syncthreads();
@@ -202,15 +193,12 @@ __global__ __launch_bounds__(256, 2) void gemm_f16s_kernel(const GemmArgs g) {
     }
 
     if (g.splitk > 1) {   // raw partial sums; the epilogue runs in splitk_reduce_kernel
+        scale_acc(acc, p8_out_scale_of(g.a_exp));
         float* __restrict__ P = g.partial + (long)blockIdx.y * g.M * g.N;
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int j = 0; j < TN; ++j) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] *= p8_out_scale_of(g.a_exp);
-                partial_tile32(g, P, m0 + wm * (BM / WM) + i * 32 + r, n0 + wn * (BN / WN) + j * 32, h, acc[i][j]);
-            }
+            for (int j = 0; j < TN; ++j) partial_tile32(g, P, m0 + wm * (BM / WM) + i * 32 + r, n0 + wn * (BN / WN) + j * 32, h, acc[i][j]);
         return;
     }
     const EpiCtx epi = make_epi(g, g.bias ? g.bias + z * g.sBias : nullptr, g.C + z * g.sC, g.R ? g.R + z * g.sR : nullptr);
@@ -218,41 +206,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f16s_kernel(const GemmArgs g) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// LDS-DMA kernels: BOTH operands already in P8 (A written in P8 by its producer kernel), so staging is a pure byte copy and goes
-// global -> LDS directly (global_load_lds_dwordx4: no staging registers) behind counted vmcnt waits and ONE raw s_barrier per K step.
-//   LDS stage: A rows x 128 B, then W rows x 128 B (BK = 32), rows unpadded (a DMA wave-instruction writes 1 KiB = 8 rows);
-//   16-byte chunk c of row r lives at physical chunk c ^ ((r >> 1) & 7): the XOR is applied to the per-lane SOURCE address
-//   of the DMA and again on the fragment read (same involution), which makes the ds_read_b128 fragment reads conflict-free.
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-// Fragment reads and their waits are hand-placed: while an LDS-DMA is pending hipcc treats it as a FLAT access to both memories
-// and turns every wait it inserts for a ds_read result into lgkmcnt(0), which drains the reads issued for the NEXT half step in
-// front of MFMAs that do not need them.  The sched_barrier keeps register-only MFMAs from being hoisted above the wait.
-template <int N>
-__device__ __forceinline__ void wait_lgkmcnt() {
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-template <int OFF>
-__device__ __forceinline__ f16x8 lds_read128(unsigned addr) {
-    f16x8 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-    return v;
-}
-template <int UNIT>
-__device__ __forceinline__ void wait_vmcnt_units(int units) {   // at most `units` groups of UNIT DMA instructions stay in flight
-    static_assert(7 * UNIT <= 63, "vmcnt is a 6-bit counter");
-    if (units >= 7) wait_vmcnt<7 * UNIT>();
-    else if (units == 6) wait_vmcnt<6 * UNIT>();
-    else if (units == 5) wait_vmcnt<5 * UNIT>();
-    else if (units == 4) wait_vmcnt<4 * UNIT>();
-    else if (units == 3) wait_vmcnt<3 * UNIT>();
-    else if (units == 2) wait_vmcnt<2 * UNIT>();
-    else if (units == 1) wait_vmcnt<UNIT>();
-    else wait_vmcnt<0>();
-}
-
-// ------------------------------------------------------------------------------------------------------------------
+// LDS-DMA kernels (P8 LDS layout: file header; waits, fragment reads and addressing: gemm_tile.h).
+//
 // Persistent big-tile kernel: (64 TM) x 256 tiles, TM = 4 (256 x 256) or 5 (320 x 256), one workgroup of 8 waves (2 x 4, wave tile
 // 32 TM x 64 = TM x 2 MFMA tiles = 128 / 160 accumulator registers) per CU walking the tile list with stride gridDim.x.  A 128x128
 // tile is bound by what the LDS-DMA path of a CU delivers (~60 GB/s: 32 KiB per K step in 0.53 us with the MFMAs removed); a
@@ -306,32 +261,16 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_big_kernel(const GemmArgs g) {
     auto derive = [&]() __attribute__((always_inline)) {
         asm volatile("" : "+v"(lane));
         r = lane & 31; h = lane >> 5; prow = lane >> 3; pchunk = lane & 7;
-        const int arow = wm * (32 * TM) + r, wrow = wn * 64 + r;
-        const int akey = (arow >> 1) & 7, wkey = (wrow >> 1) & 7;
-#pragma unroll
-        for (int lo = 0; lo < 2; ++lo) {
-            const int c = h * 2 + lo;
-            a_off[lo] = lds0 + arow * 128 + ((c ^ akey) << 4);
-            w_off[lo] = lds0 + BM * 128 + wrow * 128 + ((c ^ wkey) << 4);
-        }
+        p8_frag_offsets(lds0, BM * 128, wm * (32 * TM) + r, wn * 64 + r, h, a_off, w_off);
     };
     derive();
 
-    // tile index -> origin: XCD-contiguous (workgroups b and b + 8 share an XCD and gridDim.x % 8 == 0, so tile t runs on XCD t & 7),
-    // grouped column-major inside groups of GM row tiles
+    // tile index -> origin (gridDim.x % 8 == 0, so tile t runs on the XCD of t & 7); groups of 8 row tiles - or ALL of them when
+    // there are few (tile_order: the AdaLN table)
     auto tile_origin = [&](int t, int& m0, int& n0) __attribute__((always_inline)) {
-        const int xcd = t & 7, q = ntiles >> 3, rr = ntiles & 7;
-        const int idx = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (t >> 3);
-        // row tiles per group: 8 (an XCD then works on ~8 x 4 tiles at a time) - or ALL of them when there are few (the AdaLN table:
-        // 23 row tiles x 222 column tiles; with groups of 8 every XCD walked all 222 column tiles and pulled the whole 233 MB weight
-        // matrix, 2.0 GB read per launch; column-major over all rows an XCD reads an eighth of it)
-        const int GM = tiles_m <= 32 ? tiles_m : 8;
-        const int width = GM * tiles_n;
-        const int group = idx / width, first_m = group * GM;
-        const int gsz = min(tiles_m - first_m, GM);
-        const int in_g = idx - group * width;
-        const int tn = in_g / gsz;
-        m0 = (first_m + (in_g - tn * gsz)) * BM;
+        int tm, tn;
+        tile_order(ntiles, t, tiles_m, tiles_n, tiles_m <= 32 ? tiles_m : 8, tm, tn);
+        m0 = tm * BM;
         n0 = tn * BN;
     };
 
@@ -347,11 +286,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_big_kernel(const GemmArgs g) {
     // the 320-row tile into spilling.  Swizzle: chunk ^ ((row >> 1) & 7) with row = 8 * piece + prow, i.e. (piece & 1) * 4 + (prow >> 1).
     unsigned a_row0 = 0, w_row0 = 0, swz = 0;        // byte offsets of the lane's row of piece 0; (pchunk ^ (prow >> 1)) << 4
     const unsigned a_step = (unsigned)(8 * g.lda * 4), w_step = (unsigned)(8 * g.ldw * 4);
-    // descriptors: base, stride 0 (raw), bytes up to the end of the last row's K run, 32-bit data format
-    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.A), 0,
-                                                                            (int)(((unsigned)(g.M - 1) * (unsigned)g.lda + (unsigned)g.K) * 4u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned int*>(g.Wp), 0,
-                                                                            (int)(((unsigned)(g.N - 1) * (unsigned)g.ldw + (unsigned)g.K) * 4u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t a_rsrc = p8_rsrc(g.A, g.M, g.lda, g.K), w_rsrc = p8_rsrc(g.Wp, g.N, g.ldw, g.K);
     const unsigned char* const Bbase = g.bias ? reinterpret_cast<const unsigned char*>(g.bias) : reinterpret_cast<const unsigned char*>(g.Wp);
     int bias_col0 = 0;                               // (wave-uniform) first bias column of this wave for the tile `src` points at
     auto set_src = [&](int m0, int n0) __attribute__((always_inline)) {
@@ -427,10 +362,8 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_big_kernel(const GemmArgs g) {
             for (int t = 0; t < 3; ++t)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    if (t == 0) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[kb][j], ah[sl], acc[i][j], 0, 0, 0);
-                    else if (t == 1) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[kb][j], ah[sl], acc[i][j], 0, 0, 0);
-                    else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[kb][j], al[sl], acc[i][j], 0, 0, 0);
-                    const int piece = u * 3 + t;     // one DMA piece per two MFMAs from the start of the step
+                    mfma3_term(t, bh[kb][j], bl[kb][j], ah[sl], al[sl], acc[i][j]);
+                    const int piece = u * 3 + t;    // one DMA piece per two MFMAs from the start of the step
                     if (j == 1 && piece < NDMA) {
                         __builtin_amdgcn_sched_barrier(0);
                         issue_piece(piece, kt_issue, buf ^ 1);
@@ -458,12 +391,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_big_kernel(const GemmArgs g) {
     int gs = 0, tile_no = 0;        // ring parity (K steps run so far), bias slot parity
     while (true) {
         if (tile_no > 0) { derive(); set_src(m0, n0); }      // (see derive(): the epilogue's registers end here)
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+        zero_acc(acc);
         const int t_next = t + gridDim.x;
         const bool has_next = t_next < ntiles;
         int nm0 = 0, nn0 = 0;
@@ -556,30 +484,13 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_big_kernel(const GemmArgs g) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// Two-workgroups-per-CU variant: 128x128 tile, 4 waves (2 x 2, wave tile 64 x 64 = 64 accumulator registers), 2 stages of
+// Persistent two-workgroups-per-CU kernel: 128x128 tile, 4 waves (2 x 2, wave tile 64 x 64 = 64 accumulator registers), 2 stages of
 // 32 KiB = 64 KiB of LDS per workgroup, so two workgroups are co-resident on a CU and run out of phase: while one sits in its
 // epilogue (a tile's 64 KiB of stores drain in ~3.6 us whatever their shape: the write path, not instruction issue, bounds
 // them), in its prologue, at its barrier or waiting for a DMA stage, the other one owns the matrix cores.  Same two-stage
 // K-step structure as the 256x256 kernel: vmcnt(0) + one barrier at the top of a step, the 8 DMA pieces of the next stage
-// issued in the MFMA gaps of this one, fragments rolling through registers behind counted lgkmcnt waits.
-// Tile order of the persistent 128x128 kernel: tile index t -> origin.
-// XCD-contiguous (workgroups b and b + 8 share an XCD, so consecutive tile indices of one XCD walk one tile group) and grouped
-// column-major inside groups of GM row tiles, so that an XCD's L2 sees few distinct weight / activation rows at a time.
-__device__ __forceinline__ void p8_tile_origin128(int t, int ntiles, int tiles_m, int tiles_n, int& m0, int& n0, int GM = 4) {
-    const int xcd = t & 7, q = ntiles >> 3, rr = ntiles & 7;
-    const int idx = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (t >> 3);
-    const int width = GM * tiles_n;
-    const int group = idx / width, first_m = group * GM;
-    const int gsz = min(tiles_m - first_m, GM);
-    const int in_g = idx - group * width;
-    const int tn = in_g / gsz;
-    m0 = (first_m + (in_g - tn * gsz)) * 128;
-    n0 = tn * 128;
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Persistent form of the two-workgroup kernel with a DEFERRED epilogue: 512 workgroups (two per CU) walk the tile list with
-// stride 512; a finished tile's 64 result registers (scaled, bias added) are kept and its four 32x32 sub-tiles are finished
+// issued in the MFMA gaps of this one, fragments rolling through registers behind counted lgkmcnt waits.  512 workgroups (two per
+// CU) walk the tile list with stride 512 and the epilogue is DEFERRED: a finished tile's 64 result registers (scaled, bias added) are kept and its four 32x32 sub-tiles are finished
 // (activation, P8 split) and stored one per K step during the first four K steps of the NEXT tile, so the stores trickle out
 // under matrix work instead of blocking the CU's memory pipeline in a burst (the store tail costs 13-20 % of a K = 1024 GEMM,
 // DESIGN.md).  Deferred only where it is free of loads and of partial lanes: full tiles, 16-byte aligned rows, no residual, no
@@ -603,18 +514,7 @@ __global__ __launch_bounds__(256, 2) void gemm_p8_2wgp_kernel(const GemmArgs g) 
 
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem_p8;
     unsigned a_off[2][2], w_off[2][2];
-    {
-        const int arow = wm * 64 + r, wrow = wn * 64 + r;
-        const int akey = (arow >> 1) & 7, wkey = (wrow >> 1) & 7;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int lo = 0; lo < 2; ++lo) {
-                const int c = (kb * 2 + h) * 2 + lo;
-                a_off[kb][lo] = lds0 + arow * 128 + ((c ^ akey) << 4);
-                w_off[kb][lo] = lds0 + BM * 128 + wrow * 128 + ((c ^ wkey) << 4);
-            }
-    }
+    p8_frag_offsets(lds0, BM * 128, wm * 64 + r, wn * 64 + r, h, a_off, w_off);
     EpiCtx epi = make_epi(g, g.bias, g.C, g.R);
     const bool can_defer = epi.vec && !g.R && !g.gate && nk >= 5;      // four K steps before the last one carry the stores
     // Residual tiles (out-projection, FFN-out) are deferred too when the launcher added 16 KiB of LDS (g.res_lds): the kept sub-tile's
@@ -664,9 +564,7 @@ __global__ __launch_bounds__(256, 2) void gemm_p8_2wgp_kernel(const GemmArgs g) 
         for (int t = 0; t < 3; ++t)
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                if (t == 0) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[kb][j], ah[i], acc[i][j], 0, 0, 0);
-                else if (t == 1) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[kb][j], ah[i], acc[i][j], 0, 0, 0);
-                else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[kb][j], al[i], acc[i][j], 0, 0, 0);
+                mfma3_term(t, bh[kb][j], bl[kb][j], ah[i], al[i], acc[i][j]);
                 const int piece = (kb * 2 + i) * 3 + t;
                 if (ISSUE && j == 1 && piece < NDMA) {
                     __builtin_amdgcn_sched_barrier(0);
@@ -718,19 +616,21 @@ __global__ __launch_bounds__(256, 2) void gemm_p8_2wgp_kernel(const GemmArgs g) 
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-    auto tile_origin = [&](int t, int& m0, int& n0) { p8_tile_origin128(t, ntiles, tiles_m, tiles_n, m0, n0); };
+    auto tile_origin = [&](int t, int& m0, int& n0) {
+        int tm, tn;
+        tile_order(ntiles, t, tiles_m, tiles_n, 4, tm, tn);
+        m0 = tm * BM;
+        n0 = tn * BN;
+    };
     const int t_end = ntiles;
     auto set_src = [&](int m0, int n0) {
         const int grp = g.ngrp ? n0 / g.ngrp : 0;          // column group (kernels.h): global column indices stay, the bases move
         const long wgrp_off = grp ? (long)grp * (g.grpW - (long)g.ngrp * g.ldw) : 0;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const int ra = wave * 32 + q * 8 + prow;
-            const int gm = min(m0 + ra, g.M - 1);
-            const int gn = min(n0 + ra, g.N - 1);
-            const int sw = (pchunk ^ ((ra >> 1) & 7)) << 4;
-            src[q] = reinterpret_cast<const unsigned char*>(g.A) + ((long)gm * g.lda) * 4 + sw;
-            src[4 + q] = reinterpret_cast<const unsigned char*>(g.Wp) + ((long)gn * g.ldw + wgrp_off) * 4 + sw;
+            const int ra = p8_piece_row(wave, 4, q, prow);
+            src[q] = p8_piece_src(g.A, m0, ra, g.M, g.lda, pchunk);
+            src[4 + q] = p8_piece_src(g.Wp, n0, ra, g.N, g.ldw, pchunk, wgrp_off);
         }
     };
     auto set_epi = [&](int n0) {     // result / bias bases of the tile whose accumulators are about to be finished
@@ -750,12 +650,7 @@ __global__ __launch_bounds__(256, 2) void gemm_p8_2wgp_kernel(const GemmArgs g) 
     for (int q = 0; q < NDMA; ++q) issue_piece(q, 0, 0);
     int gs = 0, behind = 0;          // running K-step count (ring parity), see kstep
     while (true) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+        zero_acc(acc);
         const int t_next = t + gridDim.x;
         const bool has_next = t_next < t_end;
         int nm0 = 0, nn0 = 0;
@@ -830,9 +725,8 @@ __global__ __launch_bounds__(256, 2) void gemm_p8_2wgp_kernel(const GemmArgs g) 
 template <int STAGES, int TAG>
 __global__ __launch_bounds__(512, 1) void gemm_p8_mid_kernel(const GemmArgs g) {
     constexpr int BM = 128, BN = 128, BK = 32;
-    constexpr int WN_WAVES = (BM == 128) ? 4 : 2;          // waves along N
-    constexpr int TN = BN / WN_WAVES / 32;                 // n-tiles per wave (1 or 2); m-tiles per wave = 2
-    constexpr int APIECES = BM / 64, WPIECES = 2;          // 1-KiB DMA pieces per wave per stage
+    constexpr int WN_WAVES = 4, TN = 1;                    // waves along N, n-tiles per wave (m-tiles per wave = 2)
+    constexpr int APIECES = 2, WPIECES = 2;                // 1-KiB DMA pieces per wave per stage
     constexpr int NDMA = APIECES + WPIECES;
     constexpr int STAGE_BYTES = (BM + BN) * 128;
     static_assert(STAGES * STAGE_BYTES <= 160 * 1024, "LDS");
@@ -842,37 +736,18 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_mid_kernel(const GemmArgs g) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int tiles_n = (g.N + BN - 1) / BN, tiles_m = (g.M + BM - 1) / BM;
     int tm, tn;
-    {
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        const int idx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-        constexpr int GM = (BM == 128) ? 4 : 2;
-        const int width = GM * tiles_n;
-        const int group = idx / width, first_m = group * GM;
-        const int gsz = min(tiles_m - first_m, GM);
-        const int in_g = idx - group * width;
-        tn = in_g / gsz;
-        tm = first_m + (in_g - tn * gsz);
-    }
+    tile_order(gridDim.x, blockIdx.x, tiles_m, tiles_n, 4, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
-    const int nk_all_ = g.K / BK, kt0 = (int)((long)nk_all_ * blockIdx.y / g.splitk);     // split-K: first K tile of this workgroup
+    int kt0, nk;      // split-K: K tiles [kt0, kt0 + nk)
+    k_range(g.K / BK, blockIdx.y, g.splitk, kt0, nk);
 
-    // ---- DMA addressing: 1-KiB pieces (8 rows x 128 B); lane = (row in piece, physical chunk) ----
     const int prow = lane >> 3, pchunk = lane & 7;
     const unsigned char* asrc[APIECES];
     const unsigned char* wsrc[WPIECES];
 #pragma unroll
-    for (int q = 0; q < APIECES; ++q) {
-        const int ra = (wave * APIECES + q) * 8 + prow;                 // tile row 0..BM-1
-        const int gm = min(m0 + ra, g.M - 1);                           // clamp: rows >= M are never stored
-        asrc[q] = reinterpret_cast<const unsigned char*>(g.A) + ((long)gm * g.lda) * 4 + ((pchunk ^ ((ra >> 1) & 7)) << 4);
-    }
+    for (int q = 0; q < APIECES; ++q) asrc[q] = p8_piece_src(g.A, m0, p8_piece_row(wave, APIECES, q, prow), g.M, g.lda, pchunk);
 #pragma unroll
-    for (int q = 0; q < WPIECES; ++q) {
-        const int rw = (wave * WPIECES + q) * 8 + prow;
-        const int gn = min(n0 + rw, g.N - 1);
-        wsrc[q] = reinterpret_cast<const unsigned char*>(g.Wp) + ((long)gn * g.ldw) * 4 + ((pchunk ^ ((rw >> 1) & 7)) << 4);
-    }
+    for (int q = 0; q < WPIECES; ++q) wsrc[q] = p8_piece_src(g.Wp, n0, p8_piece_row(wave, WPIECES, q, prow), g.N, g.ldw, pchunk);
     // piece q of this wave for K tile kt into ring buffer buf: q < APIECES -> A rows, else W rows
     auto issue_piece = [&](int q, int kt, int buf) {
         unsigned char* base = smem_p8 + buf * STAGE_BYTES;
@@ -891,9 +766,10 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_mid_kernel(const GemmArgs g) {
 
     const int wm = wave / WN_WAVES, wn = wave % WN_WAVES;
     const int r = lane & 31, h = lane >> 5;
-    // LDS byte addresses of this lane's fragments inside a stage, [kb][hi/lo]; the second m tile (and n tile) is 32 rows = 4096 B
-    // further on with the same swizzle key, which goes into the instruction's immediate offset
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem_p8;
+    // own copies of the fragment offsets and of the accumulator zero / scale loops: through p8_frag_offsets, zero_acc and scale_acc this kernel
+    // measured +0.1 .. +0.3 % per launch, and with bh / bl as scalars and acc[2][1] (TN folded away) +0.4 .. +0.8 % (same instruction count)
+    // (as it stands: +0.05 .. +0.4 % over three runs, where the parent's own instructions at this position in the object measure -0.03 .. +0.4 %)
     unsigned a_off[2][2], w_off[2][2];
     {
         const int arow = wm * 64 + r, wrow = wn * (32 * TN) + r;
@@ -916,18 +792,11 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_mid_kernel(const GemmArgs g) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
-    const int nk = (int)((long)nk_all_ * (blockIdx.y + 1) / g.splitk) - kt0;      // K tiles [kt0, kt0 + nk); split-K workgroups write raw partial slabs
 #pragma unroll
     for (int st = 0; st < STAGES - 1; ++st)
         if (st < nk) issue(st, st);
 
-    // Fragment registers are one half-step ahead of the MFMAs, so LDS-read latency and the stage hand-over (vmcnt wait +
-    // barrier) sit under matrix work instead of in front of it.  Steady-state iteration kt (branch-free, so that hipcc counts
-    // its lgkmcnt waits exactly instead of draining at a join):
-    //   read kb=1 frags of stage kt | 6 MFMA kb=0 | vmcnt: stage kt+1 landed | barrier |
-    //   read kb=0 frags of stage kt+1 | 6 MFMA kb=1 with the DMA pieces of stage kt+S-1 issued one per MFMA gap
-    // The DMA reuses the buffer of stage kt-1, whose fragment reads were all consumed by MFMAs issued before this barrier, so no
-    // lgkmcnt drain is needed in front of the barrier and the kb=1 reads of stage kt stay in flight across it.
+    // the ring loop and its schedule: p8_ring_steps (gemm_tile.h)
     constexpr int NRD = 4 + 2 * TN;    // ds_read_b128 per half step
     auto read_frags = [&](int buf, int kb, f16x8 (&ah)[2], f16x8 (&al)[2], f16x8 (&bh)[TN], f16x8 (&bl)[TN]) {
         const unsigned sb = buf * STAGE_BYTES;
@@ -938,18 +807,12 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_mid_kernel(const GemmArgs g) {
         al[0] = lds_read128<0>(alp);
         ah[1] = lds_read128<4096>(ahp);
         al[1] = lds_read128<4096>(alp);
-        if constexpr (TN == 2) {
-            bh[TN - 1] = lds_read128<4096>(whp);
-            bl[TN - 1] = lds_read128<4096>(wlp);
-        }
     };
     constexpr int NMF = 2 * TN * 3;    // MFMAs per half step
     auto mfma_slot = [&](int sidx, const f16x8 (&ah)[2], const f16x8 (&al)[2], const f16x8 (&bh)[TN], const f16x8 (&bl)[TN]) {
         // term-major order: consecutive MFMAs go to different accumulators.  Weight fragment = A operand: C^T, see epilogue_tile32
         const int t = sidx / (2 * TN), i = (sidx / TN) % 2, j = sidx % TN;
-        if (t == 0) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[j], ah[i], acc[i][j], 0, 0, 0);
-        else if (t == 1) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[j], ah[i], acc[i][j], 0, 0, 0);
-        else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[j], al[i], acc[i][j], 0, 0, 0);
+        mfma3_term(t, bh[j], bl[j], ah[i], al[i], acc[i][j]);
     };
     auto mfmas = [&](const f16x8 (&ah)[2], const f16x8 (&al)[2], const f16x8 (&bh)[TN], const f16x8 (&bl)[TN]) {
 #pragma unroll
@@ -957,53 +820,11 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_mid_kernel(const GemmArgs g) {
     };
 
     f16x8 ah0[2], al0[2], bh0[TN], bl0[TN], ah1[2], al1[2], bh1[TN], bl1[TN];
-    wait_vmcnt_units<NDMA>(min(STAGES - 2, nk - 1));   // stage 0 landed (the prologue left up to STAGES-2 younger stages in flight)
-    __builtin_amdgcn_s_barrier();
-    read_frags(0, 0, ah0, al0, bh0, bl0);
-    int kt = 0, buf = 0;                               // buf = kt % STAGES
-    for (; kt + STAGES - 1 < nk; ++kt) {               // steady state: stage kt+S-1 still to be fetched
-        const int nbuf = (buf + 1 == STAGES) ? 0 : buf + 1;
-        const int fbuf = (buf == 0) ? STAGES - 1 : buf - 1;     // (kt + S - 1) % S
-        read_frags(buf, 1, ah1, al1, bh1, bl1);
-        wait_lgkmcnt<NRD>();                           // the kb=0 fragments (issued half a step ago) are in; the kb=1 reads fly on
-        mfmas(ah0, al0, bh0, bl0);
-        __builtin_amdgcn_sched_barrier(0);
-        wait_vmcnt<(STAGES - 3) * NDMA>();             // stage kt+1 landed for this wave (stages kt+2 .. kt+S-2 may still fly)
-        __builtin_amdgcn_s_barrier();                  // ... and for every wave; every wave is done with stage kt-1
-        __builtin_amdgcn_sched_barrier(0);
-        read_frags(nbuf, 0, ah0, al0, bh0, bl0);
-        wait_lgkmcnt<NRD>();                           // kb=1 fragments of stage kt
-#pragma unroll
-        for (int sidx = 0; sidx < NMF; ++sidx) {
-            mfma_slot(sidx, ah1, al1, bh1, bl1);
-            if (sidx < NDMA) {
-                __builtin_amdgcn_sched_barrier(0);
-                issue_piece(sidx, kt + STAGES - 1, fbuf);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        buf = nbuf;
-    }
-    for (; kt < nk; ++kt) {                            // drain: the last S-1 stages are in flight or landed
-        const int nbuf = (buf + 1 == STAGES) ? 0 : buf + 1;
-        read_frags(buf, 1, ah1, al1, bh1, bl1);
-        wait_lgkmcnt<NRD>();
-        mfmas(ah0, al0, bh0, bl0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (kt + 1 < nk) {
-            wait_vmcnt_units<NDMA>(min(STAGES - 3, nk - 2 - kt));
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            read_frags(nbuf, 0, ah0, al0, bh0, bl0);
-            wait_lgkmcnt<NRD>();
-        } else {
-            wait_lgkmcnt<0>();
-        }
-        mfmas(ah1, al1, bh1, bl1);
-        __builtin_amdgcn_sched_barrier(0);
-        buf = nbuf;
-    }
+    p8_ring_steps<STAGES, NDMA, NRD, NMF>(
+        nk, [&](int buf) __attribute__((always_inline)) { read_frags(buf, 0, ah0, al0, bh0, bl0); },
+        [&](int buf) __attribute__((always_inline)) { read_frags(buf, 1, ah1, al1, bh1, bl1); },
+        [&]() __attribute__((always_inline)) { mfmas(ah0, al0, bh0, bl0); }, [&]() __attribute__((always_inline)) { mfmas(ah1, al1, bh1, bl1); },
+        [&](int sidx) __attribute__((always_inline)) { mfma_slot(sidx, ah1, al1, bh1, bl1); }, issue_piece);
 
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -1032,7 +853,6 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_mid_kernel(const GemmArgs g) {
             for (int j = 0; j < TN; ++j) epilogue_tile32<true, true>(g, epi, m0 + wm * 64 + i * 32 + r, n0 + wn * (32 * TN) + j * 32, h, acc[i][j]);
     }
 }
-
 
 // ------------------------------------------------------------------------------------------------------------------
 // Ping-pong kernel for the one- and two-round launches of the AR / VAE body (round 5): BM x BN tile, ONE workgroup of 8
@@ -1067,39 +887,19 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_pp_kernel(const GemmArgs g) {
     const bool grp_y = wave >= 4;      // (wave-uniform) the half of the workgroup that runs one phase behind
     const int tiles_n = (g.N + BN - 1) / BN, tiles_m = (g.M + BM - 1) / BM;
     int tm, tn;
-    {   // XCD-contiguous, grouped column-major tile order (as gemm_p8_mid_kernel)
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        const int idx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-        constexpr int GM = (BM >= 256) ? 2 : 4;
-        const int width = GM * tiles_n;
-        const int group = idx / width, first_m = group * GM;
-        const int gsz = min(tiles_m - first_m, GM);
-        const int in_g = idx - group * width;
-        tn = in_g / gsz;
-        tm = first_m + (in_g - tn * gsz);
-    }
+    tile_order(gridDim.x, blockIdx.x, tiles_m, tiles_n, (BM >= 256) ? 2 : 4, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
-    const int nk_all = g.K / BK, kt0 = (int)((long)nk_all * blockIdx.y / g.splitk);
-    const int nk = (int)((long)nk_all * (blockIdx.y + 1) / g.splitk) - kt0;      // K tiles [kt0, kt0 + nk)
+    int kt0, nk;      // K tiles [kt0, kt0 + nk)
+    k_range(g.K / BK, blockIdx.y, g.splitk, kt0, nk);
 
-    // ---- DMA: piece = 8 rows x 128 B; wave w owns A pieces w * APIECES .. and W pieces w * WPIECES ..; lane = (row in piece, chunk) ----
+    // ---- DMA: wave w owns A pieces w * APIECES .. and W pieces w * WPIECES .. ----
     const int prow = lane >> 3, pchunk = lane & 7;
-    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.A), 0,
-                                                                            (int)(((unsigned)(g.M - 1) * (unsigned)g.lda + (unsigned)g.K) * 4u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned int*>(g.Wp), 0,
-                                                                            (int)(((unsigned)(g.N - 1) * (unsigned)g.ldw + (unsigned)g.K) * 4u), 0x00020000);
-    unsigned poff[NP];      // byte offset of this lane's 16 bytes of piece q at K tile 0 (rows beyond the operand: dropped by the range check -> zeros)
+    const __amdgpu_buffer_rsrc_t a_rsrc = p8_rsrc(g.A, g.M, g.lda, g.K), w_rsrc = p8_rsrc(g.Wp, g.N, g.ldw, g.K);
+    unsigned poff[NP];      // byte offset of this lane's 16 bytes of piece q at K tile 0
 #pragma unroll
-    for (int q = 0; q < APIECES; ++q) {
-        const int ra = (wave * APIECES + q) * 8 + prow;
-        poff[q] = (unsigned)(m0 + ra) * (unsigned)(g.lda * 4) + (unsigned)((pchunk ^ ((ra >> 1) & 7)) << 4);
-    }
+    for (int q = 0; q < APIECES; ++q) poff[q] = p8_piece_off(m0, p8_piece_row(wave, APIECES, q, prow), g.lda, pchunk);
 #pragma unroll
-    for (int q = 0; q < WPIECES; ++q) {
-        const int rw = (wave * WPIECES + q) * 8 + prow;
-        poff[APIECES + q] = (unsigned)(n0 + rw) * (unsigned)(g.ldw * 4) + (unsigned)((pchunk ^ ((rw >> 1) & 7)) << 4);
-    }
+    for (int q = 0; q < WPIECES; ++q) poff[APIECES + q] = p8_piece_off(n0, p8_piece_row(wave, WPIECES, q, prow), g.ldw, pchunk);
     auto issue_stage = [&](int kt, int buf) __attribute__((always_inline)) {
         unsigned char* base = smem_p8 + buf * STAGE_BYTES;
         const int koff = (kt0 + kt) * (BK * 4);
@@ -1113,27 +913,11 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_pp_kernel(const GemmArgs g) {
     const int wm = wave / WNW, wn = wave % WNW;
     const int r = lane & 31, h = lane >> 5;
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem_p8;
-    unsigned a_off[2][2], w_off[2][2];      // [kb][hi / lo]; further 32-row tiles are + 4096 B (same swizzle key: an immediate)
-    {
-        const int arow = wm * (32 * TMW) + r, wrow = wn * (32 * TNW) + r;
-        const int akey = (arow >> 1) & 7, wkey = (wrow >> 1) & 7;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int lo = 0; lo < 2; ++lo) {
-                const int c = (kb * 2 + h) * 2 + lo;
-                a_off[kb][lo] = lds0 + arow * 128 + ((c ^ akey) << 4);
-                w_off[kb][lo] = lds0 + BM * 128 + wrow * 128 + ((c ^ wkey) << 4);
-            }
-    }
+    unsigned a_off[2][2], w_off[2][2];
+    p8_frag_offsets(lds0, BM * 128, wm * (32 * TMW) + r, wn * (32 * TNW) + r, h, a_off, w_off);
 
     f32x16 acc[TMW][TNW];
-#pragma unroll
-    for (int i = 0; i < TMW; ++i)
-#pragma unroll
-        for (int j = 0; j < TNW; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    zero_acc(acc);
 
     f16x8 ah[2][TMW], al[2][TMW], bh[2][TNW], bl[2][TNW];      // all fragments of one K step: [kb][tile]
     constexpr int NRD_KB = 2 * (TMW + TNW);                       // ds_read_b128 per k block (lgkmcnt is a 4-bit counter: with 16 reads of a phase in flight the 16th waits at issue)
@@ -1170,11 +954,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_pp_kernel(const GemmArgs g) {
 #pragma unroll
                 for (int i = 0; i < TMW; ++i)
 #pragma unroll
-                    for (int j = 0; j < TNW; ++j) {      // weight fragment = A operand: C^T, see epilogue_tile32
-                        if (t == 0) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[kb][j], ah[kb][i], acc[i][j], 0, 0, 0);
-                        else if (t == 1) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[kb][j], ah[kb][i], acc[i][j], 0, 0, 0);
-                        else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[kb][j], al[kb][i], acc[i][j], 0, 0, 0);
-                    }
+                    for (int j = 0; j < TNW; ++j) mfma3_term(t, bh[kb][j], bl[kb][j], ah[kb][i], al[kb][i], acc[i][j]);
         }
         __builtin_amdgcn_sched_barrier(0);
     };
@@ -1211,13 +991,8 @@ __global__ __launch_bounds__(512, 1) void gemm_p8_pp_kernel(const GemmArgs g) {
     }
     if (!grp_y) __builtin_amdgcn_s_barrier();
 
-#pragma unroll
-    for (int i = 0; i < TMW; ++i)
-#pragma unroll
-        for (int j = 0; j < TNW; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] *= p8_out_scale_of(g.a_exp);
-    if (g.splitk > 1) {      // raw sums; splitk_reduce[_ln768]_kernel finishes them
+    scale_acc(acc, p8_out_scale_of(g.a_exp));
+    if (g.splitk > 1) {
         float* __restrict__ P = g.partial + (long)blockIdx.y * g.M * g.N;
 #pragma unroll
         for (int i = 0; i < TMW; ++i)
@@ -1259,37 +1034,17 @@ __global__ __launch_bounds__(256, 2) void gemm_p8_sm_kernel(const GemmArgs g) { 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int tiles_n = (g.N + BN - 1) / BN, tiles_m = (g.M + BM - 1) / BM;
     int tm, tn;
-    {
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        const int idx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-        constexpr int GM = 8;
-        const int width = GM * tiles_n;
-        const int group = idx / width, first_m = group * GM;
-        const int gsz = min(tiles_m - first_m, GM);
-        const int in_g = idx - group * width;
-        tn = in_g / gsz;
-        tm = first_m + (in_g - tn * gsz);
-    }
+    tile_order(gridDim.x, blockIdx.x, tiles_m, tiles_n, 8, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
-    const int nk_all = g.K / BK;   // split-K: this workgroup owns K tiles [kt0, kt0 + nk)
-    const int kt0 = (int)((long)nk_all * blockIdx.y / g.splitk);
-    const int nk = (int)((long)nk_all * (blockIdx.y + 1) / g.splitk) - kt0;
+    int kt0, nk;   // split-K: this workgroup owns K tiles [kt0, kt0 + nk)
+    k_range(g.K / BK, blockIdx.y, g.splitk, kt0, nk);
 
     const int prow = lane >> 3, pchunk = lane & 7;
-    const unsigned char* src[NDMA];
+    const unsigned char* src[NDMA];      // the lane's 16 bytes of piece q at K tile kt0
 #pragma unroll
-    for (int q = 0; q < APIECES; ++q) {
-        const int ra = (wave * APIECES + q) * 8 + prow;
-        const int gm = min(m0 + ra, g.M - 1);
-        src[q] = reinterpret_cast<const unsigned char*>(g.A) + ((long)gm * g.lda + (long)kt0 * BK) * 4 + ((pchunk ^ ((ra >> 1) & 7)) << 4);
-    }
+    for (int q = 0; q < APIECES; ++q) src[q] = p8_piece_src(g.A, m0, p8_piece_row(wave, APIECES, q, prow), g.M, g.lda, pchunk, (long)kt0 * BK);
 #pragma unroll
-    for (int q = 0; q < WPIECES; ++q) {
-        const int rw = (wave * WPIECES + q) * 8 + prow;
-        const int gn = min(n0 + rw, g.N - 1);
-        src[APIECES + q] = reinterpret_cast<const unsigned char*>(g.Wp) + ((long)gn * g.ldw + (long)kt0 * BK) * 4 + ((pchunk ^ ((rw >> 1) & 7)) << 4);
-    }
+    for (int q = 0; q < WPIECES; ++q) src[APIECES + q] = p8_piece_src(g.Wp, n0, p8_piece_row(wave, WPIECES, q, prow), g.N, g.ldw, pchunk, (long)kt0 * BK);
     const bool w_nt = g.w_nt != 0;      // (tuning) weight pieces with the non-temporal cache policy: they are read once per launch
     auto issue_piece = [&](int q, int kt, int buf) {
         unsigned char* dst = smem_p8 + buf * STAGE_BYTES +
@@ -1306,25 +1061,9 @@ __global__ __launch_bounds__(256, 2) void gemm_p8_sm_kernel(const GemmArgs g) { 
     const int r = lane & 31, h = lane >> 5;
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem_p8;
     unsigned a_off[2][2], w_off[2][2];
-    {
-        const int arow = wm * (BM / 2) + r, wrow = wn * (BN / 2) + r;
-        const int akey = (arow >> 1) & 7, wkey = (wrow >> 1) & 7;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int lo = 0; lo < 2; ++lo) {
-                const int c = (kb * 2 + h) * 2 + lo;
-                a_off[kb][lo] = lds0 + arow * 128 + ((c ^ akey) << 4);
-                w_off[kb][lo] = lds0 + BM * 128 + wrow * 128 + ((c ^ wkey) << 4);
-            }
-    }
+    p8_frag_offsets(lds0, BM * 128, wm * (BM / 2) + r, wn * (BN / 2) + r, h, a_off, w_off);
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    zero_acc(acc);
 
 #pragma unroll
     for (int st = 0; st < STAGES - 1; ++st)
@@ -1333,7 +1072,8 @@ __global__ __launch_bounds__(256, 2) void gemm_p8_sm_kernel(const GemmArgs g) { 
             for (int q = 0; q < NDMA; ++q) issue_piece(q, st, st);
         }
 
-    auto read_frags = [&](int buf, int kb, f16x8 (&ah)[TM], f16x8 (&al)[TM], f16x8 (&bh)[TN], f16x8 (&bl)[TN]) {
+    // the ring loop and its schedule: p8_ring_steps (gemm_tile.h)
+    auto read_frags = [&](int buf, int kb, f16x8 (&ah)[TM], f16x8 (&al)[TM], f16x8 (&bh)[TN], f16x8 (&bl)[TN]) __attribute__((always_inline)) {
         const unsigned sb = buf * STAGE_BYTES;
         const unsigned ahp = a_off[kb][0] + sb, alp = a_off[kb][1] + sb, whp = w_off[kb][0] + sb, wlp = w_off[kb][1] + sb;
         bh[0] = lds_read128<0>(whp);
@@ -1343,79 +1083,28 @@ __global__ __launch_bounds__(256, 2) void gemm_p8_sm_kernel(const GemmArgs g) { 
         if constexpr (TM == 2) { ah[TM - 1] = lds_read128<4096>(ahp); al[TM - 1] = lds_read128<4096>(alp); }
         if constexpr (TN == 2) { bh[TN - 1] = lds_read128<4096>(whp); bl[TN - 1] = lds_read128<4096>(wlp); }
     };
-    auto mfma_slot = [&](int sidx, const f16x8 (&ah)[TM], const f16x8 (&al)[TM], const f16x8 (&bh)[TN], const f16x8 (&bl)[TN]) {
-        const int t = sidx / (TM * TN), i = (sidx / TN) % TM, j = sidx % TN;
-        if (t == 0) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[j], ah[i], acc[i][j], 0, 0, 0);
-        else if (t == 1) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[j], ah[i], acc[i][j], 0, 0, 0);
-        else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[j], al[i], acc[i][j], 0, 0, 0);
+    auto mfma_slot = [&](int sidx, const f16x8 (&ah)[TM], const f16x8 (&al)[TM], const f16x8 (&bh)[TN], const f16x8 (&bl)[TN]) __attribute__((always_inline)) {
+        const int i = (sidx / TN) % TM, j = sidx % TN;      // term-major
+        mfma3_term(sidx / (TM * TN), bh[j], bl[j], ah[i], al[i], acc[i][j]);
     };
-    auto mfmas = [&](const f16x8 (&ah)[TM], const f16x8 (&al)[TM], const f16x8 (&bh)[TN], const f16x8 (&bl)[TN]) {
+    auto mfmas = [&](const f16x8 (&ah)[TM], const f16x8 (&al)[TM], const f16x8 (&bh)[TN], const f16x8 (&bl)[TN]) __attribute__((always_inline)) {
 #pragma unroll
         for (int sidx = 0; sidx < NMF; ++sidx) mfma_slot(sidx, ah, al, bh, bl);
     };
-
     f16x8 ah0[TM], al0[TM], bh0[TN], bl0[TN], ah1[TM], al1[TM], bh1[TN], bl1[TN];
-    wait_vmcnt_units<NDMA>(min(STAGES - 2, nk - 1));
-    __builtin_amdgcn_s_barrier();
-    read_frags(0, 0, ah0, al0, bh0, bl0);
-    int kt = 0, buf = 0;
-    for (; kt + STAGES - 1 < nk; ++kt) {               // steady state
-        const int nbuf = (buf + 1 == STAGES) ? 0 : buf + 1;
-        const int fbuf = (buf == 0) ? STAGES - 1 : buf - 1;
-        read_frags(buf, 1, ah1, al1, bh1, bl1);
-        wait_lgkmcnt<NRD>();
-        mfmas(ah0, al0, bh0, bl0);
-        __builtin_amdgcn_sched_barrier(0);
-        wait_vmcnt<(STAGES - 3) * NDMA>();
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        read_frags(nbuf, 0, ah0, al0, bh0, bl0);
-        wait_lgkmcnt<NRD>();
-#pragma unroll
-        for (int sidx = 0; sidx < (NMF > NDMA ? NMF : NDMA); ++sidx) {
-            if (sidx < NMF) mfma_slot(sidx, ah1, al1, bh1, bl1);
-            if (sidx < NDMA) {
-                __builtin_amdgcn_sched_barrier(0);
-                issue_piece(sidx, kt + STAGES - 1, fbuf);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        buf = nbuf;
-    }
-    for (; kt < nk; ++kt) {                            // drain
-        const int nbuf = (buf + 1 == STAGES) ? 0 : buf + 1;
-        read_frags(buf, 1, ah1, al1, bh1, bl1);
-        wait_lgkmcnt<NRD>();
-        mfmas(ah0, al0, bh0, bl0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (kt + 1 < nk) {
-            wait_vmcnt_units<NDMA>(min(STAGES - 3, nk - 2 - kt));
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            read_frags(nbuf, 0, ah0, al0, bh0, bl0);
-            wait_lgkmcnt<NRD>();
-        } else {
-            wait_lgkmcnt<0>();
-        }
-        mfmas(ah1, al1, bh1, bl1);
-        __builtin_amdgcn_sched_barrier(0);
-        buf = nbuf;
-    }
+    p8_ring_steps<STAGES, NDMA, NRD, NMF>(
+        nk, [&](int buf) __attribute__((always_inline)) { read_frags(buf, 0, ah0, al0, bh0, bl0); },
+        [&](int buf) __attribute__((always_inline)) { read_frags(buf, 1, ah1, al1, bh1, bl1); },
+        [&]() __attribute__((always_inline)) { mfmas(ah0, al0, bh0, bl0); }, [&]() __attribute__((always_inline)) { mfmas(ah1, al1, bh1, bl1); },
+        [&](int sidx) __attribute__((always_inline)) { mfma_slot(sidx, ah1, al1, bh1, bl1); }, issue_piece);
 
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] *= p8_out_scale_of(g.a_exp);
+    scale_acc(acc, p8_out_scale_of(g.a_exp));
     if (g.splitk > 1) {
         float* __restrict__ P = g.partial + (long)blockIdx.y * g.M * g.N;
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int j = 0; j < TN; ++j)
-                partial_tile32(g, P, m0 + wm * (BM / 2) + i * 32 + r, n0 + wn * (BN / 2) + j * 32, h, acc[i][j]);
+            for (int j = 0; j < TN; ++j) partial_tile32(g, P, m0 + wm * (BM / 2) + i * 32 + r, n0 + wn * (BN / 2) + j * 32, h, acc[i][j]);
         return;
     }
     const EpiCtx epi = make_epi(g, g.bias, g.C, g.R);
@@ -1437,12 +1126,6 @@ __global__ __launch_bounds__(256, 2) void gemm_p8_sm_kernel(const GemmArgs g) { 
 //   tap) and every fragment is that register plus a compile-time offset (channel half, k block, hi / lo, second row tile);
 //   the address arithmetic of an XOR-swizzled window cost more vector issue slots than the MFMAs leave free
 constexpr int PC_WIN_ROWS = 384, PC_PITCH = 272, PC_WIN_BYTES = PC_WIN_ROWS * PC_PITCH, PC_STAGE = 64 * 128, PC_STAGES = 4;
-template <int OFF>
-__device__ __forceinline__ f16x8 lds_read128_big(unsigned addr) {      // offset up to 65535 (the DS instructions' 16-bit immediate)
-    f16x8 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-    return v;
-}
 __global__ __launch_bounds__(512) void posconv_p8_kernel(const GemmArgs g, int T, int Ts) {
     constexpr int CG = 64, KT = 128, PAD = 64, NSTEP = KT * 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_p8[];
@@ -1525,18 +1208,18 @@ __global__ __launch_bounds__(512) void posconv_p8_kernel(const GemmArgs g, int T
     f16x8 a1h[2], a1l[2];               // activations of tile 1 [kb]
     auto read_w = [&](auto buf_tag, auto set_tag) {
         constexpr int S = decltype(set_tag)::value, OFF = decltype(buf_tag)::value * PC_STAGE;
-        bh[S][0] = lds_read128_big<OFF>(w_addr[0][0]); bl[S][0] = lds_read128_big<OFF>(w_addr[0][1]);
-        bh[S][1] = lds_read128_big<OFF>(w_addr[1][0]); bl[S][1] = lds_read128_big<OFF>(w_addr[1][1]);
+        bh[S][0] = lds_read128<OFF>(w_addr[0][0]); bl[S][0] = lds_read128<OFF>(w_addr[0][1]);
+        bh[S][1] = lds_read128<OFF>(w_addr[1][0]); bl[S][1] = lds_read128<OFF>(w_addr[1][1]);
     };
     auto read_a0 = [&](unsigned abase, auto half_tag, auto set_tag) {
         constexpr int S = decltype(set_tag)::value, HO = decltype(half_tag)::value * 128;
-        a0h[S][0] = lds_read128_big<HO>(abase);      a0l[S][0] = lds_read128_big<HO + 16>(abase);
-        a0h[S][1] = lds_read128_big<HO + 64>(abase); a0l[S][1] = lds_read128_big<HO + 80>(abase);
+        a0h[S][0] = lds_read128<HO>(abase);      a0l[S][0] = lds_read128<HO + 16>(abase);
+        a0h[S][1] = lds_read128<HO + 64>(abase); a0l[S][1] = lds_read128<HO + 80>(abase);
     };
     auto read_a1 = [&](unsigned abase, auto half_tag) {
         constexpr int HO = decltype(half_tag)::value * 128 + 32 * PC_PITCH;
-        a1h[0] = lds_read128_big<HO>(abase);      a1l[0] = lds_read128_big<HO + 16>(abase);
-        a1h[1] = lds_read128_big<HO + 64>(abase); a1l[1] = lds_read128_big<HO + 80>(abase);
+        a1h[0] = lds_read128<HO>(abase);      a1l[0] = lds_read128<HO + 16>(abase);
+        a1h[1] = lds_read128<HO + 64>(abase); a1l[1] = lds_read128<HO + 80>(abase);
     };
     using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
     using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;

@@ -12,6 +12,7 @@
 // window of output t a contiguous K=k*512 run at row 2t: a plain GEMM with lda = 2*512) and, with
 // amode=1, the grouped positional convolution (window rows gathered with zero padding).
 #include "common.h"
+#include "gemm_tile.h"
 
 namespace artalk {
 
@@ -32,24 +33,9 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const GemmArgs g) {
     float* Bs = smem + 2 * BM * LDS_LD;   // [2][BN][LDS_LD]
 
     const int tid = threadIdx.x;
-    // Tile order.  Workgroups are dealt round-robin over the 8 XCDs (each with a private 4 MiB L2), so first give each
-    // XCD a contiguous run of the tile sequence (bijective remap), then walk the sequence in groups of GM row-tiles,
-    // column-major inside a group: the GM A-panels (GM*BM*K floats) stay L2-resident while the W panels stream past once
-    // per group instead of once per row-tile.  Placement only affects speed, never results.
     const int tiles_n = (g.N + BN - 1) / BN, tiles_m = (g.M + BM - 1) / BM;
     int tm, tn;
-    {
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        const int idx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-        constexpr int GM = (BM >= 128) ? 4 : 8;
-        const int width = GM * tiles_n;
-        const int group = idx / width, first_m = group * GM;
-        const int gsz = min(tiles_m - first_m, GM);
-        const int in_g = idx - group * width;
-        tn = in_g / gsz;
-        tm = first_m + (in_g - tn * gsz);
-    }
+    tile_order(gridDim.x, blockIdx.x, tiles_m, tiles_n, (BM >= 128) ? 4 : 8, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
     const int z = blockIdx.z;
     const float* __restrict__ A = g.A + z * g.sA;
@@ -68,11 +54,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const GemmArgs g) {
                 if (AMODE == 0) {
                     v = *reinterpret_cast<const f32x4*>(A + (long)gm * g.lda + k);
                 } else {
-                    const int c = gm / g.pc_tstride, t = gm - c * g.pc_tstride;
-                    const int tap = k / g.pc_cin, ci = k - tap * g.pc_cin;
-                    const int ts = t + tap - g.pc_pad;
-                    if (ts >= 0 && ts < g.pc_T)
-                        v = *reinterpret_cast<const f32x4*>(A + ((long)c * g.pc_tstride + ts) * g.lda + ci);
+                    long off;
+                    if (window_src(g, gm, k, off)) v = *reinterpret_cast<const f32x4*>(A + off);
                 }
             }
             ra[i] = v;
@@ -99,16 +82,12 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const GemmArgs g) {
     const int r = lane & 31, h = lane >> 5;
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    zero_acc(acc);
 
-    // K % 32 == 0 is required by the callers, so K / BK is exact for BK = 16 and 32; split-K: this workgroup owns K steps [kt0, kt1)
-    const int nk_all = g.K / BK;
-    const int kt0 = (int)((long)nk_all * blockIdx.y / g.splitk), nk = (int)((long)nk_all * (blockIdx.y + 1) / g.splitk);
+    // K % 32 == 0 is required by the callers, so K / BK is exact for BK = 16 and 32; split-K: this workgroup owns K steps [kt0, nk)
+    int kt0, nkt;
+    k_range(g.K / BK, blockIdx.y, g.splitk, kt0, nkt);
+    const int nk = kt0 + nkt;
     gload(kt0);
     lstore(0);
     __syncthreads();
