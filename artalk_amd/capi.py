@@ -34,6 +34,9 @@ SYMBOLS = [
     "artalk_render_create", "artalk_render_mesh", "artalk_render_set_slab", "artalk_render_destroy", "artalk_render_last_error",
     "artalk_splat_create", "artalk_splat_render", "artalk_splat_set_timing", "artalk_splat_get_timing", "artalk_splat_destroy",
     "artalk_splat_last_error",
+    "artalk_styleunet_create", "artalk_styleunet_set_tensor", "artalk_styleunet_finalize", "artalk_styleunet_forward",
+    "artalk_styleunet_set_slab", "artalk_styleunet_set_timing", "artalk_styleunet_get_timing", "artalk_styleunet_destroy",
+    "artalk_styleunet_last_error", "artalk_op_conv2d", "artalk_op_resample2",
 ]
 
 # ARTALK_ATTN_* of include/artalk_hip.h: the kernels of attention.hip, as artalk_op_attention_plan names them
@@ -235,6 +238,29 @@ def lib() -> C.CDLL:
         L.artalk_splat_destroy.restype = None
         L.artalk_splat_last_error.argtypes = [vp]
         L.artalk_splat_last_error.restype = C.c_char_p
+    if hasattr(L, "artalk_styleunet_create"):      # (an older build loaded through ARTALK_LIB for an A/B run lacks the StyleUNet upsampler)
+        L.artalk_styleunet_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
+        L.artalk_styleunet_create.restype = i32
+        L.artalk_styleunet_set_tensor.argtypes = [vp, C.c_char_p, vp, i32, C.POINTER(i64)]
+        L.artalk_styleunet_set_tensor.restype = i32
+        L.artalk_styleunet_finalize.argtypes = [vp]
+        L.artalk_styleunet_finalize.restype = i32
+        L.artalk_styleunet_forward.argtypes = [vp, vp, i32, C.POINTER(vp), C.POINTER(i64), i32, vp, vp]
+        L.artalk_styleunet_forward.restype = i32
+        L.artalk_styleunet_set_slab.argtypes = [vp, i32]
+        L.artalk_styleunet_set_slab.restype = i32
+        L.artalk_styleunet_set_timing.argtypes = [vp, i32]
+        L.artalk_styleunet_set_timing.restype = i32
+        L.artalk_styleunet_get_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.artalk_styleunet_get_timing.restype = i32
+        L.artalk_styleunet_destroy.argtypes = [vp]
+        L.artalk_styleunet_destroy.restype = None
+        L.artalk_styleunet_last_error.argtypes = [vp]
+        L.artalk_styleunet_last_error.restype = C.c_char_p
+        L.artalk_op_conv2d.argtypes = [vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, f32, vp, i64, vp, vp, i32, vp, vp, vp, vp]
+        L.artalk_op_conv2d.restype = i32
+        L.artalk_op_resample2.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
+        L.artalk_op_resample2.restype = i32
     L.artalk_savgol.argtypes = [vp, vp, vp, i32, vp]
     L.artalk_savgol.restype = i32
     L.artalk_set_profiling.argtypes = [vp, i32]

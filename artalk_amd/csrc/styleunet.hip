@@ -1,0 +1,860 @@
+// StyleUNet upsampler of the GAGAvatar head, forward only, exact fp32 ("StyleUNet upsampler"): a stand-in for
+// app/GAGAvatar/modules/style_unet.py.  Activations are channels-last ([B][H][W][C]) between the two layout kernels at the ends of a
+// call, so the K index (tap, ci) of a convolution's implicit GEMM is contiguous in memory; the public tensors are NCHW.
+//
+//   conv_mfma_kernel   k x k (1 or 3), stride 1, zero padding k / 2: M = B H W pixels, N = Cout, K = k k Cin on
+//                      v_mfma_f32_32x32x2f32, with the input scale (modulation) as prologue and, as epilogue in this order, output
+//                      scale (demodulation), gain, noise, bias, LeakyReLU 0.2, SFT and residual
+//   resample2_kernel   bilinear x2 (0.25 / 0.75, edges clamped) and x0.5 (2 x 2 mean), align_corners = False
+//   linear / normstyle / demod kernels: the GEMV-sized style path, one wave per output value, fixed summation order
+//
+// No atomics and no split of K anywhere: the K order of every output value is fixed by the layer alone, so results are bit-identical
+// from run to run and for any split of the frames over slabs and calls.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "artalk_hip.h"
+#include "common.h"
+
+namespace artalk {
+
+// ------------------------------------------------------------------ convolution ------------------------------------------------------
+struct ConvArgs {
+    const float* x; long x_bstride;      // [B][H][W][Cin]; elements between two samples (0: one image for every sample)
+    const float* w;                      // [k k][Cin][Cout]
+    float* out;                          // [B][H][W][Cout]
+    int B, H, W, Cin, Cout, k;
+    const float* in_scale; long in_scale_ld;      // [B][in_scale_ld >= Cin] or null
+    const float* out_scale;              // [B][Cout] or null
+    float gain;                          // 1: none
+    const float* noise; long noise_bstride; const float* noise_w;      // [B or 1][H][W], one device float; null: none
+    const float* bias;                   // [Cout] or null
+    int lrelu;
+    const float* sft_scale; const float* sft_shift;      // [B][H][W][Cout] or null (both or neither)
+    const float* res;                    // [B][H][W][Cout] or null
+};
+
+constexpr int CV_BM = 128, CV_BK = 16;
+constexpr int CV_LDA = CV_BM + 32;      // pitches = 32 mod 64 banks: the two half-waves of a fragment read (k, k + 1) hit disjoint banks
+constexpr int CV_LDB = 96;
+
+// One workgroup: 128 pixels x 32 NT output channels; wave w owns pixels 32 w .. 32 w + 31 and all NT column tiles.  K runs tap by tap
+// and, inside a tap, over Cin in chunks of 16, two LDS buffers deep with the next chunk's global loads in flight during the MFMAs.
+// VA: Cin % 8 == 0 and 16-byte aligned rows of x (vector loads); VB: Cout % 4 == 0 (vector loads of w).
+template <int NT, bool VA, bool VB>
+__global__ __launch_bounds__(256) void conv_mfma_kernel(ConvArgs a) {
+    __shared__ float As[2][CV_BK * CV_LDA];
+    __shared__ float Bs[2][CV_BK * CV_LDB];
+    constexpr int BN = 32 * NT;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
+    const long M = (long)a.B * a.H * a.W;
+    const int HW = a.H * a.W;
+    const long m0 = (long)blockIdx.x * CV_BM;
+    const int n0 = blockIdx.y * BN;
+    const int pad = a.k >> 1;
+    const int nchunk = (a.Cin + CV_BK - 1) / CV_BK;
+    const int nsteps = a.k * a.k * nchunk;
+
+    // this thread's share of the A tile: pixel ai, 8 consecutive ci starting at 8 aq
+    const int ai = t & (CV_BM - 1), aq = t >> 7;
+    const long am = m0 + ai;
+    const bool apix = am < M;
+    int ab = 0, ay = 0, ax = 0;
+    if (apix) { ab = (int)(am / HW); const int rem = (int)(am - (long)ab * HW); ay = rem / a.W; ax = rem - ay * a.W; }
+    const float* xb = a.x + (long)ab * a.x_bstride;
+    const float* sb = a.in_scale ? a.in_scale + (long)ab * a.in_scale_ld : nullptr;
+    // ... and of the B tile: k row bk, 4 consecutive co starting at bc
+    constexpr int BQ = BN / 4;
+    const int bk = t / BQ, bc = (t % BQ) * 4;
+    const bool bthread = t < CV_BK * BQ;
+
+    float ra[8], rb[4];
+    auto gload = [&](int step) {
+        const int tap = step / nchunk, c0 = (step - tap * nchunk) * CV_BK;
+        const int ky = tap / a.k, kx = tap - ky * a.k;
+        const int yy = ay + ky - pad, xx = ax + kx - pad;
+        const bool inb = apix && yy >= 0 && yy < a.H && xx >= 0 && xx < a.W;
+        const int ci = c0 + aq * 8;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) ra[e] = 0.f;
+        if (inb) {
+            const float* p = xb + ((long)yy * a.W + xx) * a.Cin + ci;
+            if (VA) {
+                if (ci < a.Cin) {
+                    const f32x4 v0 = *reinterpret_cast<const f32x4*>(p), v1 = *reinterpret_cast<const f32x4*>(p + 4);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { ra[e] = v0[e]; ra[4 + e] = v1[e]; }
+                    if (sb) {
+                        const f32x4 s0 = *reinterpret_cast<const f32x4*>(sb + ci), s1 = *reinterpret_cast<const f32x4*>(sb + ci + 4);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) { ra[e] *= s0[e]; ra[4 + e] *= s1[e]; }
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    if (ci + e < a.Cin) ra[e] = sb ? p[e] * sb[ci + e] : p[e];
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) rb[e] = 0.f;
+        const int wci = c0 + bk, co = n0 + bc;
+        if (bthread && wci < a.Cin) {
+            const float* p = a.w + ((long)tap * a.Cin + wci) * a.Cout + co;
+            if (VB) {
+                if (co < a.Cout) { const f32x4 v = *reinterpret_cast<const f32x4*>(p); rb[0] = v[0]; rb[1] = v[1]; rb[2] = v[2]; rb[3] = v[3]; }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (co + e < a.Cout) rb[e] = p[e];
+            }
+        }
+    };
+    auto lstore = [&](int buf) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) As[buf][(aq * 8 + e) * CV_LDA + ai] = ra[e];
+        if (bthread) { const f32x4 v = {rb[0], rb[1], rb[2], rb[3]}; *reinterpret_cast<f32x4*>(&Bs[buf][bk * CV_LDB + bc]) = v; }
+    };
+
+    // Three levels of partial sums, so that a long K does not pile its rounding onto one running sum (one accumulator over
+    // K = 4608 measured 13 x the error of a float32 CPU conv): each 16-wide chunk sums from zero, 16 chunks make a block, blocks add up.
+    f32x16 acc[NT], mid[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) { acc[j][e] = 0.f; mid[j][e] = 0.f; }
+
+    gload(0);
+    lstore(0);
+    __syncthreads();
+    for (int step = 0; step < nsteps; ++step) {
+        const int buf = step & 1;
+        if (step + 1 < nsteps) gload(step + 1);
+        const float* as = &As[buf][h * CV_LDA + wave * 32 + r];
+        const float* bs = &Bs[buf][h * CV_LDB + r];
+        f32x16 part[NT];
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) part[j][e] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < CV_BK / 2; ++ks) {
+            const float av = as[2 * ks * CV_LDA];
+#pragma unroll
+            for (int j = 0; j < NT; ++j) part[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bs[2 * ks * CV_LDB + j * 32], part[j], 0, 0, 0);
+        }
+        if (step + 1 < nsteps) lstore(buf ^ 1);
+#pragma unroll
+        for (int j = 0; j < NT; ++j) mid[j] += part[j];
+        if ((step & 15) == 15) {
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                acc[j] += mid[j];
+#pragma unroll
+                for (int e = 0; e < 16; ++e) mid[j][e] = 0.f;
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < NT; ++j) acc[j] += mid[j];
+
+    // ---- epilogue: lane (r, h) holds output channel n0 + 32 j + r of pixels 32 wave + 8 q + 4 h + e ----
+    const float nw = a.noise ? a.noise_w[0] : 0.f;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const int co = n0 + j * 32 + r;
+        if (co >= a.Cout) continue;
+        const float bv = a.bias ? a.bias[co] : 0.f;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+            const long m = m0 + wave * 32 + 8 * (v >> 2) + 4 * h + (v & 3);
+            if (m >= M) continue;
+            const int b = (int)(m / HW);
+            float o = acc[j][v];
+            if (a.out_scale) o *= a.out_scale[(long)b * a.Cout + co];
+            if (a.gain != 1.f) o *= a.gain;
+            if (a.noise) o += nw * a.noise[(long)b * a.noise_bstride + (m - (long)b * HW)];
+            o += bv;
+            if (a.lrelu) o = o >= 0.f ? o : o * 0.2f;
+            const long idx = m * a.Cout + co;
+            if (a.sft_scale) o = o * a.sft_scale[idx] + a.sft_shift[idx];
+            if (a.res) o += a.res[idx];
+            a.out[idx] = o;
+        }
+    }
+}
+
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// The tile choice depends on Cout alone (never on B), so the K order of an output value does not depend on how frames are batched.
+static void launch_conv(const ConvArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
+    const long M = (long)a.B * a.H * a.W;
+    if (M <= 0) return;
+    const bool va = a.Cin % 8 == 0 && aligned16(a.x) && a.x_bstride % 4 == 0 && (!a.in_scale || (aligned16(a.in_scale) && a.in_scale_ld % 4 == 0));
+    const bool vb = a.Cout % 4 == 0 && aligned16(a.w);
+    const int nt = a.Cout <= 32 ? 1 : 2;
+    const dim3 grid((unsigned)((M + CV_BM - 1) / CV_BM), (unsigned)((a.Cout + 32 * nt - 1) / (32 * nt))), block(256);
+#define CV_GO(NT, VA, VB)                                                                                              \
+    do {                                                                                                               \
+        if (e0) hipExtLaunchKernelGGL((conv_mfma_kernel<NT, VA, VB>), grid, block, 0, s, e0, e1, 0, a);                \
+        else ARTALK_LAUNCH((conv_mfma_kernel<NT, VA, VB>), grid, block, 0, s, a);                                      \
+    } while (0)
+    if (nt == 1) {
+        if (va && vb) CV_GO(1, true, true); else if (va) CV_GO(1, true, false); else if (vb) CV_GO(1, false, true); else CV_GO(1, false, false);
+    } else {
+        if (va && vb) CV_GO(2, true, true); else if (va) CV_GO(2, true, false); else if (vb) CV_GO(2, false, true); else CV_GO(2, false, false);
+    }
+#undef CV_GO
+}
+
+// ------------------------------------------------------------------ resampling and layout --------------------------------------------
+// x [B][H][W][C] -> out [B][2H][2W][C] (up) or [B][H/2][W/2][C]; one thread per output value, C fastest.
+__global__ __launch_bounds__(256) void resample2_kernel(const float* __restrict__ x, float* __restrict__ out, int B, int H, int W, int C, int up) {
+    const int OH = up ? 2 * H : H / 2, OW = up ? 2 * W : W / 2;
+    const long n = (long)B * OH * OW * C;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int c = (int)(i % C);
+    long p = i / C;
+    const int ox = (int)(p % OW); p /= OW;
+    const int oy = (int)(p % OH);
+    const int b = (int)(p / OH);
+    const float* xb = x + (long)b * H * W * C + c;
+    if (up) {
+        // source coordinate (o + 0.5) / 2 - 0.5, clamped at 0: lower neighbour, weight of the upper one
+        const int y0 = oy == 0 ? 0 : (oy - 1) >> 1, x0 = ox == 0 ? 0 : (ox - 1) >> 1;
+        const float ly = oy == 0 ? 0.f : (oy & 1) ? 0.25f : 0.75f, lx = ox == 0 ? 0.f : (ox & 1) ? 0.25f : 0.75f;
+        const int y1 = min(y0 + 1, H - 1), x1 = min(x0 + 1, W - 1);
+        const float p00 = xb[((long)y0 * W + x0) * C], p01 = xb[((long)y0 * W + x1) * C];
+        const float p10 = xb[((long)y1 * W + x0) * C], p11 = xb[((long)y1 * W + x1) * C];
+        out[i] = (1.f - ly) * ((1.f - lx) * p00 + lx * p01) + ly * ((1.f - lx) * p10 + lx * p11);
+    } else {
+        const float p00 = xb[((long)(2 * oy) * W + 2 * ox) * C], p01 = xb[((long)(2 * oy) * W + 2 * ox + 1) * C];
+        const float p10 = xb[((long)(2 * oy + 1) * W + 2 * ox) * C], p11 = xb[((long)(2 * oy + 1) * W + 2 * ox + 1) * C];
+        out[i] = 0.5f * (0.5f * p00 + 0.5f * p01) + 0.5f * (0.5f * p10 + 0.5f * p11);
+    }
+}
+
+__global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, long n) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = a[i] + b[i];
+}
+
+// [B][C][HW] -> [B][HW][C] (one thread per output value)
+__global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restrict__ x, float* __restrict__ out, int B, int C, long HW) {
+    const long n = (long)B * C * HW;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int c = (int)(i % C);
+    const long p = i / C;
+    const long b = p / HW, q = p - b * HW;
+    out[i] = x[(b * C + c) * HW + q];
+}
+
+// [B][HW][C] -> [B][C][HW], with the final sigmoid (one thread per output value)
+__global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float* __restrict__ x, float* __restrict__ out, int B, int C, long HW, int sigmoid) {
+    const long n = (long)B * C * HW;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const long q = i % HW;
+    const long p = i / HW;
+    const int c = (int)(p % C);
+    const long b = p / C;
+    float v = x[(b * HW + q) * C + c];
+    if (sigmoid) v = 1.f / (1.f + expf(-v));
+    out[i] = v;
+}
+
+// ------------------------------------------------------------------ style path -------------------------------------------------------
+// y[b][o] = act(sum_i x[b][i] W[o][i] + bias[o]); one wave per (b, o), lane l sums i = l, l + 64, ... in order, then a butterfly
+__global__ __launch_bounds__(256) void linear_kernel(const float* __restrict__ x, const float* __restrict__ W, const float* __restrict__ bias,
+                                                     float* __restrict__ y, int B, int In, int Out, int lrelu) {
+    const long wid = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (wid >= (long)B * Out) return;
+    const int lane = threadIdx.x & 63;
+    const int b = (int)(wid / Out), o = (int)(wid - (long)b * Out);
+    const float* xr = x + (long)b * In;
+    const float* wr = W + (long)o * In;
+    float s = 0.f;
+    for (int i = lane; i < In; i += 64) s += xr[i] * wr[i];
+    s = wave_sum(s);
+    if (lane == 0) {
+        s += bias ? bias[o] : 0.f;
+        if (lrelu) s = s >= 0.f ? s : s * 0.2f;
+        y[wid] = s;
+    }
+}
+
+// NormStyleCode: y = x rsqrt(mean(x^2) + 1e-8); one wave per sample
+__global__ __launch_bounds__(64) void normstyle_kernel(const float* __restrict__ x, float* __restrict__ y, int n) {
+    const float* xr = x + (long)blockIdx.x * n;
+    float s = 0.f;
+    for (int i = threadIdx.x; i < n; i += 64) s += xr[i] * xr[i];
+    s = wave_sum(s);
+    const float k = rsqrtf(s / (float)n + 1e-8f);
+    for (int i = threadIdx.x; i < n; i += 64) y[(long)blockIdx.x * n + i] = xr[i] * k;
+}
+
+// d[b][co] = rsqrt(sum_ci s[b][ci]^2 wsq[co][ci] + 1e-8), wsq = sum over the taps of W^2; s rows are ld apart; one wave per (b, co)
+__global__ __launch_bounds__(256) void demod_kernel(const float* __restrict__ s, long ld, const float* __restrict__ wsq, float* __restrict__ d,
+                                                    int B, int Cin, int Cout) {
+    const long wid = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (wid >= (long)B * Cout) return;
+    const int lane = threadIdx.x & 63;
+    const int b = (int)(wid / Cout), co = (int)(wid - (long)b * Cout);
+    const float* sr = s + (long)b * ld;
+    const float* wr = wsq + (long)co * Cin;
+    float acc = 0.f;
+    for (int i = lane; i < Cin; i += 64) acc += sr[i] * sr[i] * wr[i];
+    acc = wave_sum(acc);
+    if (lane == 0) d[wid] = rsqrtf(acc + 1e-8f);
+}
+
+static inline unsigned blocks256(long n) { return (unsigned)((n + 255) / 256); }
+
+}  // namespace artalk
+
+using namespace artalk;
+
+// ------------------------------------------------------------------ the module -------------------------------------------------------
+namespace {
+
+struct SuSlot { std::vector<int64_t> shape; std::vector<float> host; bool set = false; };
+
+struct SuConv { const float* w = nullptr; const float* b = nullptr; int cin = 0, cout = 0, k = 0; };
+struct SuMod { SuConv c; const float* wsq = nullptr; const float* nw = nullptr; int mod_off = 0; };      // nw, wsq: style convs only
+
+}  // namespace
+
+struct artalk_styleunet {
+    int device = 0, in_dim = 0, out_dim = 0, S = 0, L = 0, num_layers = 0;
+    bool finalized = false, timing = false;
+    int slab_max = 1, slab = 1;
+    int64_t frame_floats = 0;
+    std::map<std::string, SuSlot> slots;
+    std::vector<std::string> order;
+    std::vector<void*> allocs;
+    float* ws = nullptr;
+    // device weights
+    SuConv first, final_conv;
+    std::vector<SuConv> dn1, dn2, dnsk, up1, up2, upsk, cs0, cs2, ch0, ch2;
+    const float *lin_w = nullptr, *lin_b = nullptr, *mlp_w[8] = {}, *mlp_b[8] = {}, *mod_w = nullptr, *mod_b = nullptr, *const_in = nullptr;
+    int mod_total = 0;
+    SuMod sc1, rgb1;
+    std::vector<SuMod> sconv, rgb;
+    std::vector<const float*> noise_buf;
+    // timing of the conv kernel (tools/styleunet_bench.py)
+    std::vector<hipEvent_t> ev; size_t ev_used = 0; double conv_ms = 0, total_ms = 0;
+    std::string err;
+};
+
+static thread_local std::string g_su_error;
+
+namespace {
+
+int su_fail(artalk_styleunet* u, int rc, const std::string& msg) { u->err = msg; return rc; }
+
+int su_ch(int size) { return size <= 32 ? 256 : 8192 / size; }      // 64: 128, 128: 64, 256: 32, 512: 16, 1024: 8
+
+void su_add(artalk_styleunet* u, const std::string& name, std::vector<int64_t> shape) {
+    u->slots[name].shape = std::move(shape);
+    u->order.push_back(name);
+}
+
+void su_manifest(artalk_styleunet* u) {
+    const int L = u->L, S = u->S, F = 512;
+    auto conv = [&](const std::string& n, int cin, int cout, int k, bool bias = true) {
+        su_add(u, n + ".weight", {cout, cin, k, k});
+        if (bias) su_add(u, n + ".bias", {cout});
+    };
+    auto resblock = [&](const std::string& n, int cin, int cout) {
+        conv(n + ".conv1", cin, cin, 3); conv(n + ".conv2", cin, cout, 3); conv(n + ".skip", cin, cout, 1, false);
+    };
+    auto modconv = [&](const std::string& n, int cin, int cout, int k) {
+        su_add(u, n + ".weight", {1, cout, cin, k, k});
+        su_add(u, n + ".modulation.weight", {cin, F});
+        su_add(u, n + ".modulation.bias", {cin});
+    };
+    auto styleconv = [&](const std::string& n, int cin, int cout) {
+        su_add(u, n + ".weight", {1});
+        su_add(u, n + ".bias", {1, cout, 1, 1});
+        modconv(n + ".modulated_conv", cin, cout, 3);
+    };
+    auto torgb = [&](const std::string& n, int cin) {
+        su_add(u, n + ".bias", {1, u->out_dim, 1, 1});
+        modconv(n + ".modulated_conv", cin, u->out_dim, 1);
+    };
+    conv("conv_body_first", u->in_dim, su_ch(S), 1);
+    int c = su_ch(S);
+    for (int j = 0, i = L; i > 2; --i, ++j) { resblock("conv_body_down." + std::to_string(j), c, su_ch(1 << (i - 1))); c = su_ch(1 << (i - 1)); }
+    conv("final_conv", c, 256, 3);
+    c = 256;
+    for (int j = 0, i = 3; i <= L; ++i, ++j) { resblock("conv_body_up." + std::to_string(j), c, su_ch(1 << i)); c = su_ch(1 << i); }
+    for (int j = 0, i = 3; i <= L; ++i, ++j) conv("toRGB." + std::to_string(j), su_ch(1 << i), 3, 1);      // dead in the forward pass
+    su_add(u, "final_linear.weight", {F, 4096});
+    su_add(u, "final_linear.bias", {F});
+    const std::string d = "stylegan_decoder.";
+    for (int j = 0; j < 8; ++j) {
+        su_add(u, d + "style_mlp." + std::to_string(2 * j + 1) + ".weight", {F, F});
+        su_add(u, d + "style_mlp." + std::to_string(2 * j + 1) + ".bias", {F});
+    }
+    su_add(u, d + "constant_input.weight", {1, 512, 4, 4});
+    styleconv(d + "style_conv1", 512, 512);
+    torgb(d + "to_rgb1", 512);
+    c = 512;
+    for (int j = 0, i = 3; i <= L; ++i, ++j) {
+        const int co = 2 * su_ch(1 << i);
+        styleconv(d + "style_convs." + std::to_string(2 * j), c, co);
+        styleconv(d + "style_convs." + std::to_string(2 * j + 1), co, co);
+        c = co;
+    }
+    for (int j = 0, i = 3; i <= L; ++i, ++j) torgb(d + "to_rgbs." + std::to_string(j), 2 * su_ch(1 << i));
+    for (int l = 0; l < u->num_layers; ++l) { const int r = 1 << ((l + 5) / 2); su_add(u, d + "noises.noise" + std::to_string(l), {1, 1, r, r}); }
+    for (const char* which : {"condition_scale.", "condition_shift."})
+        for (int j = 0, i = 3; i <= L; ++i, ++j) {
+            const int cc = su_ch(1 << i);
+            conv(which + std::to_string(j) + ".0", cc, cc, 3);
+            conv(which + std::to_string(j) + ".2", cc, 2 * cc, 3);
+        }
+}
+
+// One pass over the module: with dry = true it only sizes the workspace (floats per frame); otherwise it enqueues the n frames at x.
+struct SuRun {
+    artalk_styleunet* u; int n; hipStream_t s; bool dry;
+    int64_t off = 0, peak = 0;      // a stack: what a block needs only inside itself is released at its end (one stream: reuse is ordered)
+    float* alloc(int64_t per_frame) {
+        per_frame = (per_frame + 3) & ~(int64_t)3;
+        float* p = dry ? nullptr : u->ws + off;      // off counts floats: of one frame (dry) or of the n frames of this slab
+        off += per_frame * (dry ? 1 : n);
+        if (off > peak) peak = off;
+        return p;
+    }
+    void conv(const SuConv& c, const float* x, long x_bstride, float* out, int H, int lrelu, const float* res = nullptr,
+              const SuMod* m = nullptr, const float* smod = nullptr, const float* dmod = nullptr, const float* noise = nullptr,
+              long noise_bstride = 0, const float* sft_scale = nullptr, const float* sft_shift = nullptr) {
+        if (dry) return;
+        ConvArgs a{};
+        a.x = x; a.x_bstride = x_bstride; a.w = c.w; a.out = out; a.B = n; a.H = H; a.W = H; a.Cin = c.cin; a.Cout = c.cout; a.k = c.k;
+        a.in_scale = smod; a.in_scale_ld = u->mod_total; a.out_scale = dmod; a.gain = (m && m->nw) ? 1.41421356237309504880f : 1.f;
+        a.noise = noise; a.noise_bstride = noise_bstride; a.noise_w = m ? m->nw : nullptr;
+        a.bias = c.b; a.lrelu = lrelu; a.sft_scale = sft_scale; a.sft_shift = sft_shift; a.res = res;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (u->timing) {
+            if (u->ev_used + 2 > u->ev.size()) {
+                hipEvent_t a0, a1;
+                if (hipEventCreate(&a0) == hipSuccess && hipEventCreate(&a1) == hipSuccess) { u->ev.push_back(a0); u->ev.push_back(a1); }
+            }
+            if (u->ev_used + 2 <= u->ev.size()) { e0 = u->ev[u->ev_used]; e1 = u->ev[u->ev_used + 1]; u->ev_used += 2; }
+        }
+        launch_conv(a, s, e0, e1);
+    }
+    void resample(const float* x, float* out, int H, int C, int up) {
+        if (dry) return;
+        const long total = (long)n * (up ? 4L * H * H : (long)(H / 2) * (H / 2)) * C;
+        ARTALK_LAUNCH(resample2_kernel, dim3(blocks256(total)), dim3(256), 0, s, x, out, n, H, H, C, up);
+    }
+    void linear(const float* x, const float* W, const float* b, float* y, int In, int Out, int lrelu) {
+        if (dry) return;
+        ARTALK_LAUNCH(linear_kernel, dim3((unsigned)(((long)n * Out + 3) / 4)), dim3(256), 0, s, x, W, b, y, n, In, Out, lrelu);
+    }
+
+    // noise: per layer the pointer of this slab's first frame and the frame stride
+    void run(const float* x, const float* const* noise, const int64_t* nstride, int activation, float* out_dev) {
+        const int S = u->S, L = u->L;
+        const long SS = (long)S * S;
+        float* xin = alloc(SS * u->in_dim);
+        if (!dry) ARTALK_LAUNCH(nchw_to_nhwc_kernel, dim3(blocks256((long)n * u->in_dim * SS)), dim3(256), 0, s, x, xin, n, u->in_dim, SS);
+        float* feat = alloc(SS * u->first.cout);
+        conv(u->first, xin, SS * u->in_dim, feat, S, 1);
+        auto resblock = [&](const SuConv& c1, const SuConv& c2, const SuConv& sk, const float* in, int H, int up) -> float* {
+            const int OH = up ? 2 * H : H / 2;
+            const long hw = (long)H * H, ohw = (long)OH * OH;
+            float* o = alloc(ohw * c2.cout);
+            const int64_t mark = off;
+            float* t1 = alloc(hw * c1.cout);
+            conv(c1, in, hw * c1.cin, t1, H, 1);
+            float* t2 = alloc(ohw * c1.cout);
+            resample(t1, t2, H, c1.cout, up);
+            float* xs = alloc(ohw * c1.cin);
+            resample(in, xs, H, c1.cin, up);
+            float* skp = alloc(ohw * sk.cout);
+            conv(sk, xs, ohw * sk.cin, skp, OH, 0);
+            conv(c2, t2, ohw * c2.cin, o, OH, 1, skp);
+            off = mark;
+            return o;
+        };
+        std::vector<float*> skips(L - 2);
+        int cur = S;
+        for (int i = 0; i < L - 2; ++i) {
+            feat = resblock(u->dn1[i], u->dn2[i], u->dnsk[i], feat, cur, 0);
+            cur /= 2;
+            skips[L - 3 - i] = feat;
+        }
+        float* f4 = alloc(16 * 256);
+        conv(u->final_conv, feat, 16L * u->final_conv.cin, f4, 4, 1);
+        float* code = alloc(512);
+        linear(f4, u->lin_w, u->lin_b, code, 4096, 512, 0);
+        std::vector<float*> conds(2 * (L - 2));
+        feat = f4;
+        for (int i = 0; i < L - 2; ++i) {
+            const long hw = (long)cur * cur;
+            const int c = u->up1[i].cin;
+            float* sum = alloc(hw * c);      // (stays: the block's output is stacked above it)
+            if (!dry) ARTALK_LAUNCH(add_kernel, dim3(blocks256((long)n * hw * c)), dim3(256), 0, s, feat, skips[i], sum, (long)n * hw * c);
+            feat = resblock(u->up1[i], u->up2[i], u->upsk[i], sum, cur, 1);
+            cur *= 2;
+            const long ohw = (long)cur * cur;
+            const int cc = u->up2[i].cout;
+            for (int w = 0; w < 2; ++w) {
+                const SuConv& c0 = w ? u->ch0[i] : u->cs0[i];
+                const SuConv& c2 = w ? u->ch2[i] : u->cs2[i];
+                float* o = alloc(ohw * 2 * cc);
+                const int64_t mark = off;
+                float* t = alloc(ohw * cc);
+                conv(c0, feat, ohw * cc, t, cur, 1);
+                conv(c2, t, ohw * cc, o, cur, 0);
+                off = mark;
+                conds[2 * i + w] = o;
+            }
+        }
+        // ---- style path ----
+        float* lat = alloc(512);
+        if (!dry) ARTALK_LAUNCH(normstyle_kernel, dim3(n), dim3(64), 0, s, code, lat, 512);
+        for (int j = 0; j < 8; ++j) {
+            float* nx = alloc(512);
+            linear(lat, u->mlp_w[j], u->mlp_b[j], nx, 512, 512, 1);
+            lat = nx;
+        }
+        float* smod = alloc(u->mod_total);
+        linear(lat, u->mod_w, u->mod_b, smod, 512, u->mod_total, 0);
+        auto styleconv = [&](const SuMod& m, const float* in, long in_bstride, float* out, int H, int layer, const float* sc, const float* sh) {
+            float* d = alloc(m.c.cout);
+            if (!dry) ARTALK_LAUNCH(demod_kernel, dim3((unsigned)(((long)n * m.c.cout + 3) / 4)), dim3(256), 0, s, smod + m.mod_off, (long)u->mod_total,
+                                    m.wsq, d, n, m.c.cin, m.c.cout);
+            conv(m.c, in, in_bstride, out, H, 1, nullptr, &m, dry ? nullptr : smod + m.mod_off, d, dry ? nullptr : noise[layer],
+                 dry ? 0 : (long)nstride[layer], sc, sh);
+        };
+        float* o = alloc(16 * 512);
+        styleconv(u->sc1, u->const_in, 0, o, 4, 0, nullptr, nullptr);
+        float* skip = alloc(16 * u->out_dim);
+        conv(u->rgb1.c, o, 16L * 512, skip, 4, 0, nullptr, &u->rgb1, dry ? nullptr : smod + u->rgb1.mod_off);
+        cur = 4;
+        for (int j = 0; j < L - 2; ++j) {
+            const SuMod &m1 = u->sconv[2 * j], &m2 = u->sconv[2 * j + 1], &mr = u->rgb[j];
+            const long ohw = 4L * cur * cur;
+            float* o2 = alloc(ohw * m2.c.cout);
+            float* sk2 = alloc(ohw * u->out_dim);
+            const int64_t mark = off;
+            float* up = alloc(ohw * m1.c.cin);
+            resample(o, up, cur, m1.c.cin, 1);
+            float* o1 = alloc(ohw * m1.c.cout);
+            styleconv(m1, up, ohw * m1.c.cin, o1, 2 * cur, 1 + 2 * j, conds[2 * j], conds[2 * j + 1]);
+            styleconv(m2, o1, ohw * m2.c.cin, o2, 2 * cur, 2 + 2 * j, nullptr, nullptr);
+            float* su = alloc(ohw * u->out_dim);
+            resample(skip, su, cur, u->out_dim, 1);
+            conv(mr.c, o2, ohw * mr.c.cin, sk2, 2 * cur, 0, su, &mr, dry ? nullptr : smod + mr.mod_off);
+            off = mark;
+            o = o2; skip = sk2; cur *= 2;
+        }
+        if (!dry) ARTALK_LAUNCH(nhwc_to_nchw_kernel, dim3(blocks256((long)n * u->out_dim * SS)), dim3(256), 0, s, skip, out_dev, n, u->out_dim, SS,
+                                activation);
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+const char* artalk_styleunet_last_error(const artalk_styleunet* u) { return u ? u->err.c_str() : g_su_error.c_str(); }
+
+void artalk_styleunet_destroy(artalk_styleunet* u) {
+    if (!u) return;
+    if (!u->allocs.empty() || !u->ev.empty()) {
+        (void)hipSetDevice(u->device);
+        (void)hipDeviceSynchronize();
+        for (void* p : u->allocs) if (p) (void)hipFree(p);
+        for (hipEvent_t e : u->ev) (void)hipEventDestroy(e);
+    }
+    delete u;
+}
+
+int artalk_styleunet_create(int device_id, int in_dim, int out_dim, int out_size, artalk_styleunet** out) {
+    if (!out) { g_su_error = "out is NULL"; return ARTALK_EINVAL; }
+    if (device_id < 0) { g_su_error = "device_id must not be negative"; return ARTALK_EINVAL; }
+    if (in_dim < 1 || in_dim > 4096) { g_su_error = "in_dim must be in 1..4096"; return ARTALK_EINVAL; }
+    if (out_dim < 1 || out_dim > 4096) { g_su_error = "out_dim must be in 1..4096"; return ARTALK_EINVAL; }
+    if (out_size < 8 || out_size > 1024 || (out_size & (out_size - 1))) { g_su_error = "out_size must be a power of two in 8..1024"; return ARTALK_EINVAL; }
+    artalk_styleunet* u = new artalk_styleunet();
+    u->device = device_id; u->in_dim = in_dim; u->out_dim = out_dim; u->S = out_size;
+    for (u->L = 0; (1 << u->L) < out_size; ++u->L) {}
+    u->num_layers = (u->L - 2) * 2 + 1;
+    su_manifest(u);
+    // modulation rows of every modulated conv, in launch order, are one Linear: the latent is the same for all of them
+    u->mod_total = 0;
+    SuRun dry{u, 1, nullptr, true};
+    // (the dry run reads channel counts only: fill them from the manifest)
+    auto shape_conv = [&](const std::string& n, SuConv& c) {
+        const auto& sh = u->slots[n + ".weight"].shape;
+        const size_t o = sh.size() == 5 ? 1 : 0;
+        c.cout = (int)sh[o]; c.cin = (int)sh[o + 1]; c.k = (int)sh[o + 2];
+    };
+    const int nb = u->L - 2;
+    u->dn1.resize(nb); u->dn2.resize(nb); u->dnsk.resize(nb); u->up1.resize(nb); u->up2.resize(nb); u->upsk.resize(nb);
+    u->cs0.resize(nb); u->cs2.resize(nb); u->ch0.resize(nb); u->ch2.resize(nb); u->sconv.resize(2 * nb); u->rgb.resize(nb);
+    shape_conv("conv_body_first", u->first);
+    shape_conv("final_conv", u->final_conv);
+    const std::string d = "stylegan_decoder.";
+    auto shape_mod = [&](const std::string& n, SuMod& m) {
+        shape_conv(n + ".modulated_conv", m.c);
+        m.mod_off = u->mod_total;
+        u->mod_total += (m.c.cin + 3) & ~3;      // 16-byte aligned rows for the conv's vector loads
+    };
+    shape_mod(d + "style_conv1", u->sc1);
+    shape_mod(d + "to_rgb1", u->rgb1);
+    for (int j = 0; j < nb; ++j) {
+        const std::string js = std::to_string(j);
+        shape_conv("conv_body_down." + js + ".conv1", u->dn1[j]); shape_conv("conv_body_down." + js + ".conv2", u->dn2[j]);
+        shape_conv("conv_body_down." + js + ".skip", u->dnsk[j]);
+        shape_conv("conv_body_up." + js + ".conv1", u->up1[j]); shape_conv("conv_body_up." + js + ".conv2", u->up2[j]);
+        shape_conv("conv_body_up." + js + ".skip", u->upsk[j]);
+        shape_conv("condition_scale." + js + ".0", u->cs0[j]); shape_conv("condition_scale." + js + ".2", u->cs2[j]);
+        shape_conv("condition_shift." + js + ".0", u->ch0[j]); shape_conv("condition_shift." + js + ".2", u->ch2[j]);
+        shape_mod(d + "style_convs." + std::to_string(2 * j), u->sconv[2 * j]);
+        shape_mod(d + "style_convs." + std::to_string(2 * j + 1), u->sconv[2 * j + 1]);
+        shape_mod(d + "to_rgbs." + js, u->rgb[j]);
+    }
+    dry.run(nullptr, nullptr, nullptr, 0, nullptr);
+    u->frame_floats = dry.peak;
+    const int64_t budget = 4ll << 30;      // 4 GiB of activations, skips and conditions
+    const int64_t slab = budget / (u->frame_floats * 4);
+    u->slab_max = (int)(slab < 1 ? 1 : slab > 64 ? 64 : slab);
+    u->slab = u->slab_max;
+    *out = u;
+    return ARTALK_OK;
+}
+
+int artalk_styleunet_set_tensor(artalk_styleunet* u, const char* key, const void* host_ptr, int ndim, const int64_t* shape) {
+    if (!u) { g_su_error = "handle is NULL"; return ARTALK_EINVAL; }
+    if (!key || !host_ptr || !shape) return su_fail(u, ARTALK_EINVAL, "key, host_ptr and shape must not be NULL");
+    if (u->finalized) return su_fail(u, ARTALK_ESTATE, "weights are final after artalk_styleunet_finalize (packed copies exist); create a new handle");
+    auto it = u->slots.find(key);
+    if (it == u->slots.end()) return su_fail(u, ARTALK_EKEY, std::string("Unexpected key in state_dict: ") + key);
+    SuSlot& sl = it->second;
+    bool same = (int)sl.shape.size() == ndim;
+    for (int i = 0; same && i < ndim; ++i) same = sl.shape[i] == shape[i];
+    if (!same) return su_fail(u, ARTALK_EINVAL, std::string("size mismatch for ") + key);
+    int64_t n = 1;
+    for (int64_t v : sl.shape) n *= v;
+    sl.host.assign((const float*)host_ptr, (const float*)host_ptr + n);
+    sl.set = true;
+    return ARTALK_OK;
+}
+
+int artalk_styleunet_finalize(artalk_styleunet* u) {
+    if (!u) { g_su_error = "handle is NULL"; return ARTALK_EINVAL; }
+    if (u->finalized) return su_fail(u, ARTALK_ESTATE, "artalk_styleunet_finalize was already called");
+    std::string missing;
+    int nmiss = 0;
+    for (const std::string& k : u->order)
+        if (!u->slots[k].set) { if (nmiss++ < 8) missing += (missing.empty() ? "" : ", ") + k; }
+    if (nmiss) return su_fail(u, ARTALK_EMISSING, "Missing key(s) in state_dict: " + missing + (nmiss > 8 ? ", ..." : ""));
+    if (hipSetDevice(u->device) != hipSuccess) return su_fail(u, ARTALK_EHIP, "hipSetDevice failed");
+    bool ok = true;
+    auto upload = [&](const std::vector<float>& v) -> const float* {
+        void* p = nullptr;
+        if (hipMalloc(&p, (v.empty() ? 1 : v.size()) * sizeof(float)) != hipSuccess) { ok = false; return nullptr; }
+        u->allocs.push_back(p);
+        if (!v.empty() && hipMemcpy(p, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) ok = false;
+        return (const float*)p;
+    };
+    auto host = [&](const std::string& k) -> const std::vector<float>& { return u->slots[k].host; };
+    // [Cout][Cin][k][k] -> [k k][Cin][Cout]
+    auto pack = [&](const std::string& n, SuConv& c, bool bias) {
+        const std::vector<float>& w = host(n + ".weight");
+        const int kk = c.k * c.k;
+        std::vector<float> t(w.size());
+        for (int o = 0; o < c.cout; ++o)
+            for (int i = 0; i < c.cin; ++i)
+                for (int q = 0; q < kk; ++q) t[((size_t)q * c.cin + i) * c.cout + o] = w[((size_t)o * c.cin + i) * kk + q];
+        c.w = upload(t);
+        c.b = bias ? upload(host(n + ".bias")) : nullptr;
+    };
+    std::vector<float> modw((size_t)u->mod_total * 512, 0.f), modb((size_t)u->mod_total, 0.f);
+    auto pack_mod = [&](const std::string& n, SuMod& m, bool style) {
+        pack(n + ".modulated_conv", m.c, false);
+        m.c.b = upload(host(n + ".bias"));
+        const std::vector<float>& mw = host(n + ".modulated_conv.modulation.weight");
+        const std::vector<float>& mb = host(n + ".modulated_conv.modulation.bias");
+        std::memcpy(&modw[(size_t)m.mod_off * 512], mw.data(), mw.size() * sizeof(float));
+        std::memcpy(&modb[m.mod_off], mb.data(), mb.size() * sizeof(float));
+        if (style) {
+            m.nw = upload(host(n + ".weight"));
+            const std::vector<float>& w = host(n + ".modulated_conv.weight");
+            const int kk = m.c.k * m.c.k;
+            std::vector<float> sq((size_t)m.c.cout * m.c.cin);
+            for (size_t e = 0; e < sq.size(); ++e) {
+                float acc = 0.f;
+                for (int q = 0; q < kk; ++q) acc += w[e * kk + q] * w[e * kk + q];
+                sq[e] = acc;
+            }
+            m.wsq = upload(sq);
+        }
+    };
+    const int nb = u->L - 2;
+    const std::string d = "stylegan_decoder.";
+    pack("conv_body_first", u->first, true);
+    pack("final_conv", u->final_conv, true);
+    for (int j = 0; j < nb; ++j) {
+        const std::string js = std::to_string(j);
+        pack("conv_body_down." + js + ".conv1", u->dn1[j], true); pack("conv_body_down." + js + ".conv2", u->dn2[j], true);
+        pack("conv_body_down." + js + ".skip", u->dnsk[j], false);
+        pack("conv_body_up." + js + ".conv1", u->up1[j], true); pack("conv_body_up." + js + ".conv2", u->up2[j], true);
+        pack("conv_body_up." + js + ".skip", u->upsk[j], false);
+        pack("condition_scale." + js + ".0", u->cs0[j], true); pack("condition_scale." + js + ".2", u->cs2[j], true);
+        pack("condition_shift." + js + ".0", u->ch0[j], true); pack("condition_shift." + js + ".2", u->ch2[j], true);
+        pack_mod(d + "style_convs." + std::to_string(2 * j), u->sconv[2 * j], true);
+        pack_mod(d + "style_convs." + std::to_string(2 * j + 1), u->sconv[2 * j + 1], true);
+        pack_mod(d + "to_rgbs." + js, u->rgb[j], false);
+    }
+    pack_mod(d + "style_conv1", u->sc1, true);
+    pack_mod(d + "to_rgb1", u->rgb1, false);
+    u->mod_w = upload(modw);
+    u->mod_b = upload(modb);
+    {   // final_linear reads the 4 x 4 x 256 feature channels-last: column c 16 + p of the reference becomes p 256 + c
+        const std::vector<float>& w = host("final_linear.weight");
+        std::vector<float> t(w.size());
+        for (int o = 0; o < 512; ++o)
+            for (int c = 0; c < 256; ++c)
+                for (int p = 0; p < 16; ++p) t[(size_t)o * 4096 + p * 256 + c] = w[(size_t)o * 4096 + c * 16 + p];
+        u->lin_w = upload(t);
+        u->lin_b = upload(host("final_linear.bias"));
+    }
+    for (int j = 0; j < 8; ++j) {
+        u->mlp_w[j] = upload(host(d + "style_mlp." + std::to_string(2 * j + 1) + ".weight"));
+        u->mlp_b[j] = upload(host(d + "style_mlp." + std::to_string(2 * j + 1) + ".bias"));
+    }
+    {   // constant input [1][512][4][4] -> [4][4][512]
+        const std::vector<float>& w = host(d + "constant_input.weight");
+        std::vector<float> t(w.size());
+        for (int c = 0; c < 512; ++c)
+            for (int p = 0; p < 16; ++p) t[(size_t)p * 512 + c] = w[(size_t)c * 16 + p];
+        u->const_in = upload(t);
+    }
+    u->noise_buf.resize(u->num_layers);
+    for (int l = 0; l < u->num_layers; ++l) u->noise_buf[l] = upload(host(d + "noises.noise" + std::to_string(l)));
+    void* ws = nullptr;
+    if (ok && hipMalloc(&ws, (size_t)u->frame_floats * u->slab_max * sizeof(float)) != hipSuccess) {
+        return su_fail(u, ARTALK_EHIP, "hipMalloc of the workspace failed (" + std::to_string(u->frame_floats * u->slab_max * 4) + " bytes)");
+    }
+    if (ws) u->allocs.push_back(ws);
+    u->ws = (float*)ws;
+    if (!ok || hipDeviceSynchronize() != hipSuccess) return su_fail(u, ARTALK_EHIP, "uploading the weights failed");
+    for (auto& kv : u->slots) { std::vector<float>().swap(kv.second.host); }
+    u->finalized = true;
+    return ARTALK_OK;
+}
+
+int artalk_styleunet_set_slab(artalk_styleunet* u, int frames) {
+    if (!u) { g_su_error = "handle is NULL"; return ARTALK_EINVAL; }
+    if (frames < 0 || frames > u->slab_max)
+        return su_fail(u, ARTALK_EINVAL, "slab must be in 0.." + std::to_string(u->slab_max) + " frames (0: the default)");
+    u->slab = frames == 0 ? u->slab_max : frames;
+    return u->slab;
+}
+
+int artalk_styleunet_set_timing(artalk_styleunet* u, int enable) {
+    if (!u) { g_su_error = "handle is NULL"; return ARTALK_EINVAL; }
+    u->timing = enable != 0;
+    return ARTALK_OK;
+}
+
+int artalk_styleunet_get_timing(const artalk_styleunet* u, double* conv_ms, double* total_ms) {
+    if (!u) { g_su_error = "handle is NULL"; return ARTALK_EINVAL; }
+    if (conv_ms) *conv_ms = u->conv_ms;
+    if (total_ms) *total_ms = u->total_ms;
+    return ARTALK_OK;
+}
+
+int artalk_styleunet_forward(artalk_styleunet* u, const float* x_dev, int B, const float* const* noise_ptrs_or_null,
+                             const int64_t* noise_batch_strides, int activation, float* out_dev, void* stream) {
+    if (!u) { g_su_error = "handle is NULL"; return ARTALK_EINVAL; }
+    if (!u->finalized) return su_fail(u, ARTALK_ESTATE, "artalk_styleunet_forward before artalk_styleunet_finalize");
+    if (B < 0) return su_fail(u, ARTALK_EINVAL, "B must not be negative");
+    if (!x_dev || !out_dev) return su_fail(u, ARTALK_EINVAL, "x and out must not be NULL");
+    if (noise_ptrs_or_null) {
+        if (!noise_batch_strides) return su_fail(u, ARTALK_EINVAL, "noise_batch_strides must not be NULL when noise_ptrs is given");
+        for (int l = 0; l < u->num_layers; ++l) {
+            const int64_t r = 1 << ((l + 5) / 2);
+            if (!noise_ptrs_or_null[l]) return su_fail(u, ARTALK_EINVAL, "noise_ptrs[" + std::to_string(l) + "] is NULL");
+            if (noise_batch_strides[l] != 0 && noise_batch_strides[l] < r * r)
+                return su_fail(u, ARTALK_EINVAL, "noise_batch_strides[" + std::to_string(l) + "] must be 0 or at least " + std::to_string(r * r));
+        }
+    }
+    if (B == 0) return ARTALK_OK;
+    (void)hipSetDevice(u->device);
+    hipStream_t s = (hipStream_t)stream;
+    const long SS = (long)u->S * u->S;
+    std::vector<const float*> np(u->num_layers);
+    std::vector<int64_t> ns(u->num_layers);
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (u->timing) {
+        u->ev_used = 0;
+        if (hipEventCreate(&t0) != hipSuccess || hipEventCreate(&t1) != hipSuccess) return su_fail(u, ARTALK_EHIP, "hipEventCreate failed");
+        (void)hipEventRecord(t0, s);
+    }
+    for (int b0 = 0; b0 < B; b0 += u->slab) {
+        const int n = B - b0 < u->slab ? B - b0 : u->slab;
+        for (int l = 0; l < u->num_layers; ++l) {
+            ns[l] = noise_ptrs_or_null ? noise_batch_strides[l] : 0;
+            np[l] = (noise_ptrs_or_null ? noise_ptrs_or_null[l] : u->noise_buf[l]) + (long)b0 * ns[l];
+        }
+        SuRun run{u, n, s, false};
+        run.run(x_dev + (long)b0 * u->in_dim * SS, np.data(), ns.data(), activation, out_dev + (long)b0 * u->out_dim * SS);
+    }
+    if (hipGetLastError() != hipSuccess) return su_fail(u, ARTALK_EHIP, "kernel launch failed");
+    if (u->timing) {
+        (void)hipEventRecord(t1, s);
+        if (hipEventSynchronize(t1) != hipSuccess) return su_fail(u, ARTALK_EHIP, "the call failed on the device");
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, t0, t1);
+        u->total_ms = ms;
+        u->conv_ms = 0;
+        for (size_t i = 0; i + 1 < u->ev_used; i += 2) { float k = 0.f; if (hipEventElapsedTime(&k, u->ev[i], u->ev[i + 1]) == hipSuccess) u->conv_ms += k; }
+        (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
+    }
+    return ARTALK_OK;
+}
+
+int artalk_op_conv2d(const float* x, int64_t x_bstride, const float* w, float* out, int B, int H, int W, int Cin, int Cout, int k,
+                     const float* in_scale, const float* out_scale, float gain, const float* noise, int64_t noise_bstride,
+                     const float* noise_weight, const float* bias, int lrelu, const float* sft_scale, const float* sft_shift,
+                     const float* residual, void* stream) {
+    if (!x || !w || !out) return ARTALK_EINVAL;
+    if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || (k != 1 && k != 3)) return ARTALK_EINVAL;
+    if ((int64_t)B * H * W > (int64_t)1 << 30 || (int64_t)H * W > INT_MAX) return ARTALK_EINVAL;
+    if (x_bstride != 0 && x_bstride < (int64_t)H * W * Cin) return ARTALK_EINVAL;
+    if (noise && (!noise_weight || (noise_bstride != 0 && noise_bstride < (int64_t)H * W))) return ARTALK_EINVAL;
+    if ((sft_scale == nullptr) != (sft_shift == nullptr)) return ARTALK_EINVAL;
+    ConvArgs a{};
+    a.x = x; a.x_bstride = x_bstride; a.w = w; a.out = out; a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.k = k;
+    a.in_scale = in_scale; a.in_scale_ld = Cin; a.out_scale = out_scale; a.gain = gain; a.noise = noise; a.noise_bstride = noise_bstride; a.noise_w = noise_weight;
+    a.bias = bias; a.lrelu = lrelu; a.sft_scale = sft_scale; a.sft_shift = sft_shift; a.res = residual;
+    launch_conv(a, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+
+int artalk_op_resample2(const float* x, float* out, int B, int H, int W, int C, int up, void* stream) {
+    if (!x || !out || B < 1 || H < 1 || W < 1 || C < 1) return ARTALK_EINVAL;
+    if (!up && ((H | W) & 1)) return ARTALK_EINVAL;
+    const long total = (long)B * (up ? 4L * H * W : (long)(H / 2) * (W / 2)) * C;
+    ARTALK_LAUNCH(resample2_kernel, dim3(blocks256(total)), dim3(256), 0, (hipStream_t)stream, x, out, B, H, W, C, up);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+
+}  // extern "C"

@@ -258,6 +258,48 @@ int artalk_splat_get_timing(const artalk_splat* s, double* stage_ms, int n, long
 void artalk_splat_destroy(artalk_splat* s);
 const char* artalk_splat_last_error(const artalk_splat* s);
 
+/* StyleUNet upsampler of the GAGAvatar head, forward only, exact fp32: a stand-in for StyleUNet(in_size = out_size)
+ * (app/GAGAvatar/modules/style_unet.py), the consumer of the splat image.  What is computed is defined in DESIGN.md ("StyleUNet
+ * upsampler").  Checked on synthetic weights only; parity on real GAGAvatar checkpoints is unpinned.
+ * artalk_styleunet_create: out_size a power of two in 8..1024, in_dim / out_dim in 1..4096; host work only (the device is first touched by
+ * finalize).  ARTALK_EINVAL with a message (artalk_styleunet_last_error(NULL)) otherwise.
+ * artalk_styleunet_set_tensor: one entry of the reference module's state_dict(), fp32 in host memory, with exactly its name and shape
+ * (the dead toRGB.* parameters and the stylegan_decoder.noises.noise{i} buffers included).  ARTALK_EKEY "Unexpected key in state_dict: K",
+ * ARTALK_EINVAL "size mismatch for K", ARTALK_ESTATE after finalize.
+ * artalk_styleunet_finalize: ARTALK_EMISSING "Missing key(s) in state_dict: ..." (the first 8); otherwise packs the weights, uploads them
+ * and allocates the workspace for the default slab.
+ * artalk_styleunet_forward: x_dev [B][in_dim][S][S] -> out_dev [B][out_dim][S][S], sigmoid applied when activation != 0.
+ * noise_ptrs_or_null: host array of num_layers = 2 log2(S) - 3 device pointers, layer l holding [B or 1][r][r] with r = 2^((l + 5) / 2);
+ * noise_batch_strides: elements between two samples per layer, 0 = one image for all samples.  NULL = the stored noise buffers.
+ * Runs on the caller's stream without synchronising, in slabs of frames; bit-identical from run to run and for any split of the frames
+ * over slabs and calls.  ARTALK_ESTATE before finalize; ARTALK_EINVAL before the device is touched for a NULL handle, x or out, B < 0, a
+ * NULL noise pointer or stride array, or a stride that is neither 0 nor at least r * r.  B == 0 succeeds and does nothing.
+ * artalk_styleunet_set_slab: frames per pass over the workspace; 0 = the default chosen at create time (4 GiB of workspace, at most 64
+ * frames), which is also the largest value accepted.  Returns the value in force.
+ * artalk_styleunet_set_timing / get_timing (tools/styleunet_bench.py): with timing on, a call times its conv launches with event pairs
+ * and WAITS at its end; get_timing returns the summed conv kernel time and the whole call's time of the last call, in ms.
+ * artalk_op_conv2d: one launch of the conv kernel on CHANNELS-LAST tensors.  x [B][H][W][Cin] (x_bstride elements between samples, 0 =
+ * one image for all), w [k k][Cin][Cout] (k = 1 or 3, stride 1, zero padding k / 2), out [B][H][W][Cout].  Prologue: in_scale [B][Cin].
+ * Epilogue, each part optional (NULL / gain 1 / lrelu 0), in this order: out_scale [B][Cout], gain, + noise_weight[0] *
+ * noise [B or 1][H][W] (noise_bstride 0 = shared), + bias [Cout], LeakyReLU 0.2, * sft_scale + sft_shift and + residual (all
+ * [B][H][W][Cout]).  artalk_op_resample2: channels-last bilinear x2 (up != 0) or x0.5 (H, W even), align_corners = False. */
+typedef struct artalk_styleunet artalk_styleunet;
+int artalk_styleunet_create(int device_id, int in_dim, int out_dim, int out_size, artalk_styleunet** out);
+int artalk_styleunet_set_tensor(artalk_styleunet* u, const char* key, const void* host_ptr, int ndim, const int64_t* shape);
+int artalk_styleunet_finalize(artalk_styleunet* u);
+int artalk_styleunet_forward(artalk_styleunet* u, const float* x_dev, int B, const float* const* noise_ptrs_or_null,
+                             const int64_t* noise_batch_strides, int activation, float* out_dev, void* stream);
+int artalk_styleunet_set_slab(artalk_styleunet* u, int frames);
+int artalk_styleunet_set_timing(artalk_styleunet* u, int enable);
+int artalk_styleunet_get_timing(const artalk_styleunet* u, double* conv_ms, double* total_ms);
+void artalk_styleunet_destroy(artalk_styleunet* u);
+const char* artalk_styleunet_last_error(const artalk_styleunet* u);
+int artalk_op_conv2d(const float* x, int64_t x_bstride, const float* w, float* out, int B, int H, int W, int Cin, int Cout, int k,
+                     const float* in_scale, const float* out_scale, float gain, const float* noise, int64_t noise_bstride,
+                     const float* noise_weight, const float* bias, int lrelu, const float* sft_scale, const float* sft_shift,
+                     const float* residual, void* stream);
+int artalk_op_resample2(const float* x, float* out, int B, int H, int W, int C, int up, void* stream);
+
 /* Numerical health of the work enqueued since the last artalk_infer / artalk_stream_begin started.  Every call ends with an
  * asynchronous copy of the device status word to pinned host memory.  artalk_get_status WAITS for that copy (an event wait:
  * the one synchronisation on this boundary, paid only by callers that ask; `stream` is ignored); artalk_poll_status never
