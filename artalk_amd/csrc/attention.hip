@@ -372,19 +372,264 @@ __global__ __launch_bounds__(256, 2) void attention_short_kernel(const AttnArgs 
 // The V^T operand needs 8 consecutive KEYS per lane at one d: read by ds_read_b64_tr_b16 (4 keys x 16 d block per 16 lanes,
 // delivered column-major), two reads per operand.  The k slots of the PV MFMA are assigned so that the S^T accumulator is the
 // P^T operand without any data movement: slot (g, e) = key 32T + 4g + e for e < 4 (tile 2T), key 32T + 16 + 4g + (e - 4) (tile 2T+1).
+//
+// Four kernels walk the keys this way (the 64-query kernel, wide, ping-pong, wide-AR): they differ in who stages which keys when, and
+// promise the same blocks in the same order with the same arithmetic per query - bit-identical results.  What a query does with one
+// 64-key block, its Q fragments, the four LDS images and the epilogue are therefore stated once, in the helpers below; a kernel
+// hands in the first LDS row of the block, the key limit, whether the block can hold masked keys and whether scores carry sfix.
+// Each kernel keeps its own staging ORDER (per pass, or every load before the first store) and the ping-pong kernel its own V reads.
 typedef _Float16 h8_t __attribute__((ext_vector_type(8)));
 typedef __fp16 fp16x4_raw __attribute__((__vector_size__(4 * sizeof(__fp16))));
+constexpr int HD = 64, KB = 64, PB = 160;      // head dim, keys per block, bytes per LDS row (64 halves + pad) of every f16-split kernel
+constexpr size_t f16_lds_bytes(int rows) { return (size_t)4 * rows * PB; }      // K and V, hi and lo images of `rows` keys
 __device__ __forceinline__ void split4(const f32x4 x, f16x4_t& hi, f16x4_t& lo) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) { const _Float16 a = (_Float16)x[e]; hi[e] = a; lo[e] = (_Float16)(x[e] - (float)a); }
 }
+__device__ __forceinline__ h8_t join8(const f16x4_t a, const f16x4_t b) { return h8_t{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}; }
+__device__ __forceinline__ void split8(const f32x4 x0, const f32x4 x1, h8_t& hi, h8_t& lo) {
+    f16x4_t h0, l0, h1, l1;
+    split4(x0, h0, l0);
+    split4(x1, h1, l1);
+    hi = join8(h0, h1);
+    lo = join8(l0, l1);
+}
+struct KVImages { unsigned char *Kh, *Kl, *Vh, *Vl; };      // row-major fp16 images, PB bytes per row
+__device__ __forceinline__ KVImages kv_images(unsigned char* base, int rows) {
+    return {base, base + rows * PB, base + 2 * rows * PB, base + 3 * rows * PB};
+}
+
+// ---- Q fragments (B operand of S^T): lane (r, g) holds Q[row][8g + 32kb .. +7], split; a lane whose query does not exist holds zeros.
+// P8 rows, hi | lo as stored: zeros where !valid (nothing is read there).  A kernel that wants the loads in flight without a use
+// behind them reads an existing row (clamped to Lq - 1) with valid = true and masks later, with f16_q_keep.
+__device__ __forceinline__ void f16_q_p8(const AttnArgs& a, int b, int h, int row, bool valid, int g, h8_t (&qh)[2], h8_t (&ql)[2]) {
+    const unsigned char* qp = reinterpret_cast<const unsigned char*>(a.Q + (long)b * a.q_bstride + (long)row * a.ldq + h * HD);
+    const h8_t z = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+        qh[kb] = valid ? *reinterpret_cast<const h8_t*>(qp + (g + 4 * kb) * 32) : z;          // 8-element group g + 4 kb: 16 B hi, 16 B lo
+        ql[kb] = valid ? *reinterpret_cast<const h8_t*>(qp + (g + 4 * kb) * 32 + 16) : z;
+    }
+}
+__device__ __forceinline__ void f16_q_keep(bool qvalid, const h8_t (&sh)[2], const h8_t (&sl)[2], h8_t (&qh)[2], h8_t (&ql)[2]) {
+    const h8_t z = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) { qh[kb] = qvalid ? sh[kb] : z; ql[kb] = qvalid ? sl[kb] : z; }
+}
+__device__ __forceinline__ void f16_q_f32(const AttnArgs& a, int b, int h, int row, bool qvalid, int g, h8_t (&qh)[2], h8_t (&ql)[2]) {      // fp32 rows (`row` exists: clamped): normalised, scaled, split
+    const float* qp = a.Q + (long)b * a.q_bstride + (long)row * a.ldq + h * HD;
+    f32x4 x[2][2];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            const f32x4 t = *reinterpret_cast<const f32x4*>(qp + 8 * g + 32 * kb + 4 * u);
+            x[kb][u] = qvalid ? t : z;
+        }
+    if (a.l2norm) {
+        float ss = 0.f;
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) ss += x[kb][u][e] * x[kb][u][e];
+        ss += lane_xor<16>(ss);
+        ss += lane_xor<32>(ss);
+        const float den = fmaxf(sqrtf(ss), 1e-12f);
+        const float mul = a.qscale[h];
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) x[kb][u][e] = (x[kb][u][e] / den) * mul;
+    }
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) split8(x[kb][0] * a.scale, x[kb][1] * a.scale, qh[kb], ql[kb]);
+}
+
+// ---- staging of one thread's piece of key row kr into row `row` of the images; a piece that is not `valid` is zeros.
+// P8 rows (plain copies; no conversion: the staging VALU work was ~40 % of the 64-query kernel's): 8-element group g8, 16 B hi + 16 B lo
+// of K and of V.  fp32 rows: columns c4 .. c4 + 3, 16 threads per row - k optionally L2-normalised (all 16 lanes of a row take part,
+// in range or not), both split on the way in.
+struct KV8 { h8_t kh, kl, vh, vl; };
+struct KV4 { f32x4 k, v; };
+__device__ __forceinline__ KV8 f16_load_kv_p8(const AttnArgs& a, const float* Kb, const float* Vb, int kr, int g8, bool valid) {
+    const h8_t z = {0, 0, 0, 0, 0, 0, 0, 0};
+    KV8 x = {z, z, z, z};
+    if (valid) {
+        const unsigned char* kp = reinterpret_cast<const unsigned char*>(Kb + (long)kr * a.ldk) + g8 * 32;
+        const unsigned char* vp = reinterpret_cast<const unsigned char*>(Vb + (long)kr * a.ldv) + g8 * 32;
+        x.kh = *reinterpret_cast<const h8_t*>(kp); x.kl = *reinterpret_cast<const h8_t*>(kp + 16);
+        x.vh = *reinterpret_cast<const h8_t*>(vp); x.vl = *reinterpret_cast<const h8_t*>(vp + 16);
+    }
+    return x;
+}
+__device__ __forceinline__ void f16_store_kv_p8(const KVImages& s, int row, int g8, const KV8& x) {
+    *reinterpret_cast<h8_t*>(s.Kh + row * PB + g8 * 16) = x.kh;
+    *reinterpret_cast<h8_t*>(s.Kl + row * PB + g8 * 16) = x.kl;
+    *reinterpret_cast<h8_t*>(s.Vh + row * PB + g8 * 16) = x.vh;
+    *reinterpret_cast<h8_t*>(s.Vl + row * PB + g8 * 16) = x.vl;
+}
+__device__ __forceinline__ KV4 f16_load_kv_f32(const AttnArgs& a, const float* Kb, const float* Vb, int kr, int c4, bool valid) {
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    KV4 x = {z, z};
+    if (valid) {
+        x.k = *reinterpret_cast<const f32x4*>(Kb + (long)kr * a.ldk + c4);
+        x.v = *reinterpret_cast<const f32x4*>(Vb + (long)kr * a.ldv + c4);
+    }
+    return x;
+}
+__device__ __forceinline__ void f16_store_kv_f32(const KVImages& s, int row, int c4, KV4 x, int l2norm, bool in_range) {
+    if (l2norm) {
+        float ss = x.k[0] * x.k[0] + x.k[1] * x.k[1] + x.k[2] * x.k[2] + x.k[3] * x.k[3];
+        ss = group_sum<16>(ss);
+        const float den = fmaxf(sqrtf(ss), 1e-12f);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x.k[e] = x.k[e] / den;
+    }
+    if (in_range) {
+        f16x4_t hh, ll;
+        split4(x.k, hh, ll);
+        *reinterpret_cast<f16x4_t*>(s.Kh + row * PB + c4 * 2) = hh;
+        *reinterpret_cast<f16x4_t*>(s.Kl + row * PB + c4 * 2) = ll;
+        split4(x.v, hh, ll);
+        *reinterpret_cast<f16x4_t*>(s.Vh + row * PB + c4 * 2) = hh;
+        *reinterpret_cast<f16x4_t*>(s.Vl + row * PB + c4 * 2) = ll;
+    }
+}
+
+// ---- one 64-key block of one wave's 16 queries, keys kb0 .. kb0 + 63 in LDS rows lb .. lb + 63.
+// S^T: st[t][j] = S[key kb0 + 16t + 4g + j][query]; 16-key tiles entirely past Lk are skipped (ntile, wave-uniform)
+__device__ __forceinline__ void f16_scores(const KVImages& s, int lb, int ntile, int r, int g, const h8_t (&qh)[2], const h8_t (&ql)[2],
+                                           f32x4 (&st)[4]) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        if (t < ntile) {
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) {
+                const int off = (lb + t * 16 + r) * PB + (8 * g + 32 * kb) * 2;
+                const h8_t kh = *reinterpret_cast<const h8_t*>(s.Kh + off), kl = *reinterpret_cast<const h8_t*>(s.Kl + off);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh, qh[kb], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kl, qh[kb], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh, ql[kb], acc, 0, 0, 0);
+            }
+        }
+        st[t] = acc;
+    }
+}
+// mask and online softmax: st becomes p, (m_run, l_part, ot) are brought to the new maximum.  SFIX: scores of P8 operands carry the
+// square of their site scale and no softmax scale yet.  `masked`: the block can hold keys >= klim (uniform over the wave; the values
+// are the same either way, an unmasked block only skips the compares)
+template <int FASTEXP, bool SFIX>
+__device__ __forceinline__ void f16_softmax(f32x4 (&st)[4], int kb0, int g, int klim, bool masked, float sfix, float& m_run, float& l_part,
+                                            f32x4 (&ot)[4]) {
+    float mx = -INFINITY;
+    if (!masked) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float sv = SFIX ? st[t][j] * sfix : st[t][j];
+                st[t][j] = sv;
+                mx = fmaxf(mx, sv);
+            }
+    } else {
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int kidx = kb0 + t * 16 + 4 * g + j;
+                const float sv = (kidx < klim) ? (SFIX ? st[t][j] * sfix : st[t][j]) : -INFINITY;
+                st[t][j] = sv;
+                mx = fmaxf(mx, sv);
+            }
+    }
+    mx = fmaxf(mx, lane_xor<16>(mx));
+    mx = fmaxf(mx, lane_xor<32>(mx));
+    const float m_new = fmaxf(m_run, mx);
+    const float m_safe = (m_new == -INFINITY) ? 0.f : m_new;
+    const float alpha = FASTEXP ? __expf(m_run - m_safe) : expf(m_run - m_safe);
+    m_run = m_new;
+    float ps = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float p = FASTEXP ? __expf(st[t][j] - m_safe) : expf(st[t][j] - m_safe);
+            st[t][j] = p;
+            ps += p;
+        }
+    l_part = l_part * alpha + ps;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) ot[d] *= alpha;
+}
+// O^T += V^T P^T, 32 keys at a time.  trq, trp: the transposed-read lane role inside its group of 16 (lane 4q + p supplies row q,
+// columns 4p .. 4p+3).  Tile 2T+1 may be past Lk: its p are exp(-inf) = 0 and its V rows were staged as zeros (or finite copies)
+__device__ __forceinline__ void f16_pv(const KVImages& s, int lb, int ntile, int g, int trq, int trp, const f32x4 (&st)[4], f32x4 (&ot)[4]) {
+#pragma unroll
+    for (int T = 0; T < 2; ++T) {
+        if (2 * T < ntile) {
+            h8_t ph, pl;
+            split8(st[2 * T], st[2 * T + 1], ph, pl);
+            const int row1 = lb + T * 32 + 4 * g + trq, row2 = row1 + 16;
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) {
+                const int col = (16 * dt + 4 * trp) * 2;
+                const f16x4_t a1 = __builtin_bit_cast(f16x4_t, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
+                    (__attribute__((address_space(3))) fp16x4_raw*)(s.Vh + row1 * PB + col)));
+                const f16x4_t a2 = __builtin_bit_cast(f16x4_t, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
+                    (__attribute__((address_space(3))) fp16x4_raw*)(s.Vh + row2 * PB + col)));
+                const f16x4_t b1 = __builtin_bit_cast(f16x4_t, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
+                    (__attribute__((address_space(3))) fp16x4_raw*)(s.Vl + row1 * PB + col)));
+                const f16x4_t b2 = __builtin_bit_cast(f16x4_t, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
+                    (__attribute__((address_space(3))) fp16x4_raw*)(s.Vl + row2 * PB + col)));
+                const h8_t vh = join8(a1, a2), vl = join8(b1, b2);
+                ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh, ph, ot[dt], 0, 0, 0);
+                ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vl, ph, ot[dt], 0, 0, 0);
+                ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh, pl, ot[dt], 0, 0, 0);
+            }
+        }
+    }
+}
+template <int FASTEXP, bool SFIX>
+__device__ __forceinline__ void f16_block(const KVImages& s, int lb, int kb0, int Lk, int klim, bool masked, float sfix, const h8_t (&qh)[2],
+                                          const h8_t (&ql)[2], int r, int g, int trq, int trp, float& m_run, float& l_part, f32x4 (&ot)[4]) {
+    const int ntile = min(4, (Lk - kb0 + 15) >> 4);
+    f32x4 st[4];
+    f16_scores(s, lb, ntile, r, g, qh, ql, st);
+    f16_softmax<FASTEXP, SFIX>(st, kb0, g, klim, masked, sfix, m_run, l_part, ot);
+    f16_pv(s, lb, ntile, g, trq, trp, st, ot);
+}
+// epilogue: ot[dt][reg] = O[query][d = 16 dt + 4 g + reg] (unnormalised).  P8IN: P8 values carry their site scale (x16 by default)
+template <bool P8IN>
+__device__ __forceinline__ void f16_finish(const AttnArgs& a, int b, int h, int qi, int g, bool qvalid, float l_part, const f32x4 (&ot)[4]) {
+    float l = l_part;
+    l += lane_xor<16>(l);
+    l += lane_xor<32>(l);
+    if (qvalid) {
+        const float inv = P8IN ? 1.0f / (l * p8_scale_of(a.qkv_exp)) : 1.0f / l;
+        float* op = a.O + (long)b * a.o_bstride + (long)qi * a.ldo + h * HD;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+            const int d0 = 16 * dt + 4 * g;
+            const float o0 = ot[dt][0] * inv, o1 = ot[dt][1] * inv, o2 = ot[dt][2] * inv, o3 = ot[dt][3] * inv;
+            if (a.out_p8) store_p8x4(op, d0, o0, o1, o2, o3, a.status, a.o_exp);
+            else { const f32x4 o = {o0, o1, o2, o3}; *reinterpret_cast<f32x4*>(op + d0) = o; }
+        }
+    }
+}
+
 // QKVP8: Q, K and V arrive already in the P8 split format (x16, hi | lo per 8 elements: common.h), written by the qkv GEMM's
-// epilogue: the fragments and the LDS images are then plain copies (no conversion: the staging VALU work was ~40 % of this kernel's);
-// the x16 of q and k is taken out of the scores together with the softmax scale, the x16 of v out of the final normalisation.
+// epilogue: the fragments and the LDS images are then plain copies; the x16 of q and k is taken out of the scores together with the
+// softmax scale, the x16 of v out of the final normalisation.
 template <int FASTEXP, int QKVP8 = 0>
 __global__ __launch_bounds__(256, 4) void attention_f16_kernel(const AttnArgs a) {
-    constexpr int HD = 64, KB = 64, PB = 160;      // keys per block, bytes per LDS row (64 halves + pad)
     __shared__ __attribute__((aligned(16))) unsigned char Kh[KB * PB], Kl[KB * PB], Vh[KB * PB], Vl[KB * PB];
+    const KVImages s = {Kh, Kl, Vh, Vl};
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int r = lane & 15, g = lane >> 4;
@@ -395,208 +640,51 @@ __global__ __launch_bounds__(256, 4) void attention_f16_kernel(const AttnArgs a)
     const bool qvalid = qi < a.Lq;
     const bool wave_active = q0 < a.Lq;
 
-    // ---- Q fragments (B operand of S^T): lane (r, g) holds Q[qi][8g + 32kb .. +7], split ----
     h8_t qh[2], ql[2];
     if constexpr (QKVP8) {
-        const unsigned char* qp = reinterpret_cast<const unsigned char*>(a.Q + (long)b * a.q_bstride + (long)qi * a.ldq + h * HD);
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            const h8_t z = {0, 0, 0, 0, 0, 0, 0, 0};
-            qh[kb] = qvalid ? *reinterpret_cast<const h8_t*>(qp + (g + 4 * kb) * 32) : z;          // 8-element group g + 4 kb: 16 B hi, 16 B lo
-            ql[kb] = qvalid ? *reinterpret_cast<const h8_t*>(qp + (g + 4 * kb) * 32 + 16) : z;
-        }
+        f16_q_p8(a, b, h, qi, qvalid, g, qh, ql);      // (not the clamped row + f16_q_keep: that put a vmcnt(0) in front of the first staging loads, +2.9 % at 100 x 100)
     } else {
-        const float* qp = a.Q + (long)b * a.q_bstride + (long)qi * a.ldq + h * HD;
-        f32x4 x[2][2];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                f32x4 z = {0.f, 0.f, 0.f, 0.f};
-                x[kb][u] = qvalid ? *reinterpret_cast<const f32x4*>(qp + 8 * g + 32 * kb + 4 * u) : z;
-            }
-        if (a.l2norm) {
-            float ss = 0.f;
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) ss += x[kb][u][e] * x[kb][u][e];
-            ss += lane_xor<16>(ss);
-            ss += lane_xor<32>(ss);
-            const float den = fmaxf(sqrtf(ss), 1e-12f);
-            const float mul = a.qscale[h];
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) x[kb][u][e] = (x[kb][u][e] / den) * mul;
-        }
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            f16x4_t h0, l0, h1, l1;
-            split4(x[kb][0] * a.scale, h0, l0);
-            split4(x[kb][1] * a.scale, h1, l1);
-            qh[kb] = h8_t{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-            ql[kb] = h8_t{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-        }
+        f16_q_f32(a, b, h, min(qi, a.Lq - 1), qvalid, g, qh, ql);
     }
-    const float sfix = QKVP8 ? a.scale * p8_scale_of(-2 * a.qkv_exp) : 1.0f;      // scores of P8 operands carry the square of their site scale (16 * 16 by default) and no softmax scale yet
+    const float sfix = QKVP8 ? a.scale * p8_scale_of(-2 * a.qkv_exp) : 1.0f;
     const int klim = (a.split_q > 0 && qi < a.split_q) ? a.split_k : a.Lk;
     const int qblk_last = min(qblk0 + 63, a.Lq - 1);
     const int lk_wg = (a.split_q > 0 && qblk_last < a.split_q) ? a.split_k : a.Lk;
 
     float m_run = -INFINITY, l_part = 0.f;
-    f32x4 ot[4];       // ot[dt][reg] = O[query r][d = 16 dt + 4 g + reg] (unnormalised)
+    f32x4 ot[4];
 #pragma unroll
     for (int d = 0; d < 4; ++d) { f32x4 z = {0.f, 0.f, 0.f, 0.f}; ot[d] = z; }
 
     const float* Kb = a.K + (long)b * a.k_bstride + h * HD;
     const float* Vb = a.V + (long)b * a.v_bstride + h * HD;
-    // transposed-read lane role inside its group of 16: lane 4q + p supplies row q, columns 4p .. 4p+3
     const int trq = r >> 2, trp = r & 3;
 
     for (int kb0 = 0; kb0 < lk_wg; kb0 += KB) {
         __syncthreads();
+        // ---- stage rows kb0 .. kb0 + 63, pass by pass; rows >= Lk are zero ----
         if constexpr (QKVP8) {
 #pragma unroll
-            for (int i = 0; i < KB * 8 / 256; ++i) {      // one 8-element group (16 B hi + 16 B lo) of K and of V per thread and pass
+            for (int i = 0; i < KB * 8 / 256; ++i) {
                 const int idx = tid + i * 256;
                 const int row = idx >> 3, g8 = idx & 7;
-                const int kr = kb0 + row;
-                h8_t kh = {0, 0, 0, 0, 0, 0, 0, 0}, kl = kh, vh = kh, vl = kh;
-                if (kr < a.Lk) {
-                    const unsigned char* kp = reinterpret_cast<const unsigned char*>(Kb + (long)kr * a.ldk) + g8 * 32;
-                    const unsigned char* vp = reinterpret_cast<const unsigned char*>(Vb + (long)kr * a.ldv) + g8 * 32;
-                    kh = *reinterpret_cast<const h8_t*>(kp); kl = *reinterpret_cast<const h8_t*>(kp + 16);
-                    vh = *reinterpret_cast<const h8_t*>(vp); vl = *reinterpret_cast<const h8_t*>(vp + 16);
-                }
-                *reinterpret_cast<h8_t*>(Kh + row * PB + g8 * 16) = kh;
-                *reinterpret_cast<h8_t*>(Kl + row * PB + g8 * 16) = kl;
-                *reinterpret_cast<h8_t*>(Vh + row * PB + g8 * 16) = vh;
-                *reinterpret_cast<h8_t*>(Vl + row * PB + g8 * 16) = vl;
+                f16_store_kv_p8(s, row, g8, f16_load_kv_p8(a, Kb, Vb, kb0 + row, g8, kb0 + row < a.Lk));
             }
         } else {
 #pragma unroll
-        for (int i = 0; i < KB * 16 / 256; ++i) {
-            const int idx = tid + i * 256;
-            const int row = idx >> 4, c4 = (idx & 15) * 4;
-            const int kr = kb0 + row;
-            f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-            if (kr < a.Lk) {
-                kv = *reinterpret_cast<const f32x4*>(Kb + (long)kr * a.ldk + c4);
-                vv = *reinterpret_cast<const f32x4*>(Vb + (long)kr * a.ldv + c4);
+            for (int i = 0; i < KB * 16 / 256; ++i) {
+                const int idx = tid + i * 256;
+                const int row = idx >> 4, c4 = (idx & 15) * 4;
+                f16_store_kv_f32(s, row, c4, f16_load_kv_f32(a, Kb, Vb, kb0 + row, c4, kb0 + row < a.Lk), a.l2norm, true);
             }
-            if (a.l2norm) {
-                float ss = kv[0] * kv[0] + kv[1] * kv[1] + kv[2] * kv[2] + kv[3] * kv[3];
-                ss = group_sum<16>(ss);
-                const float den = fmaxf(sqrtf(ss), 1e-12f);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) kv[e] = kv[e] / den;
-            }
-            f16x4_t hh, ll;
-            split4(kv, hh, ll);
-            *reinterpret_cast<f16x4_t*>(Kh + row * PB + c4 * 2) = hh;
-            *reinterpret_cast<f16x4_t*>(Kl + row * PB + c4 * 2) = ll;
-            split4(vv, hh, ll);
-            *reinterpret_cast<f16x4_t*>(Vh + row * PB + c4 * 2) = hh;
-            *reinterpret_cast<f16x4_t*>(Vl + row * PB + c4 * 2) = ll;
-        }
         }
         __syncthreads();
-        if (!wave_active) continue;      // wave-uniform: EXEC stays all ones for the transposed reads below
-
-        const int ntile = min(4, (a.Lk - kb0 + 15) >> 4);
-        f32x4 st[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            if (t < ntile) {
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb) {
-                    const int off = (t * 16 + r) * PB + (8 * g + 32 * kb) * 2;
-                    const h8_t kh = *reinterpret_cast<const h8_t*>(Kh + off), kl = *reinterpret_cast<const h8_t*>(Kl + off);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh, qh[kb], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kl, qh[kb], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh, ql[kb], acc, 0, 0, 0);
-                }
-            }
-            st[t] = acc;
-        }
-        float mx = -INFINITY;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int kidx = kb0 + t * 16 + 4 * g + j;
-                const float sv = (kidx < klim) ? (QKVP8 ? st[t][j] * sfix : st[t][j]) : -INFINITY;
-                st[t][j] = sv;
-                mx = fmaxf(mx, sv);
-            }
-        mx = fmaxf(mx, lane_xor<16>(mx));
-        mx = fmaxf(mx, lane_xor<32>(mx));
-        const float m_new = fmaxf(m_run, mx);
-        const float m_safe = (m_new == -INFINITY) ? 0.f : m_new;
-        const float alpha = FASTEXP ? __expf(m_run - m_safe) : expf(m_run - m_safe);
-        m_run = m_new;
-        float ps = 0.f;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float p = FASTEXP ? __expf(st[t][j] - m_safe) : expf(st[t][j] - m_safe);
-                st[t][j] = p;
-                ps += p;
-            }
-        l_part = l_part * alpha + ps;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) ot[d] *= alpha;
-#pragma unroll
-        for (int T = 0; T < 2; ++T) {
-            if (2 * T < ntile) {        // tile 2T+1 may be past Lk: its p are exp(-inf) = 0 and its V rows were staged as zeros
-                f16x4_t h0, l0, h1, l1;
-                split4(st[2 * T], h0, l0);
-                split4(st[2 * T + 1], h1, l1);
-                const h8_t ph = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-                const h8_t pl = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-                const int row1 = T * 32 + 4 * g + trq, row2 = row1 + 16;
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt) {
-                    const int col = (16 * dt + 4 * trp) * 2;
-                    const f16x4_t a1 = __builtin_bit_cast(f16x4_t, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                        (__attribute__((address_space(3))) fp16x4_raw*)(Vh + row1 * PB + col)));
-                    const f16x4_t a2 = __builtin_bit_cast(f16x4_t, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                        (__attribute__((address_space(3))) fp16x4_raw*)(Vh + row2 * PB + col)));
-                    const f16x4_t b1 = __builtin_bit_cast(f16x4_t, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                        (__attribute__((address_space(3))) fp16x4_raw*)(Vl + row1 * PB + col)));
-                    const f16x4_t b2 = __builtin_bit_cast(f16x4_t, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                        (__attribute__((address_space(3))) fp16x4_raw*)(Vl + row2 * PB + col)));
-                    const h8_t vh = {a1[0], a1[1], a1[2], a1[3], a2[0], a2[1], a2[2], a2[3]};
-                    const h8_t vl = {b1[0], b1[1], b1[2], b1[3], b2[0], b2[1], b2[2], b2[3]};
-                    ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh, ph, ot[dt], 0, 0, 0);
-                    ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vl, ph, ot[dt], 0, 0, 0);
-                    ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh, pl, ot[dt], 0, 0, 0);
-                }
-            }
-        }
+        if (!wave_active) continue;      // wave-uniform: EXEC stays all ones for the transposed reads
+        // (every block takes the masked form: this kernel has no "full block" fast path)
+        f16_block<FASTEXP, QKVP8 != 0>(s, 0, kb0, a.Lk, klim, true, sfix, qh, ql, r, g, trq, trp, m_run, l_part, ot);
     }
     if (!wave_active) return;
-    float l = l_part;
-    l += lane_xor<16>(l);
-    l += lane_xor<32>(l);
-    if (qvalid) {
-        const float inv = QKVP8 ? 1.0f / (l * p8_scale_of(a.qkv_exp)) : 1.0f / l;      // P8 values carry their site scale (x16 by default)
-        float* op = a.O + (long)b * a.o_bstride + (long)qi * a.ldo + h * HD;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-            const int d0 = 16 * dt + 4 * g;
-            const float o0 = ot[dt][0] * inv, o1 = ot[dt][1] * inv, o2 = ot[dt][2] * inv, o3 = ot[dt][3] * inv;
-            if (a.out_p8) store_p8x4(op, d0, o0, o1, o2, o3, a.status, a.o_exp);
-            else { const f32x4 o = {o0, o1, o2, o3}; *reinterpret_cast<f32x4*>(op + d0) = o; }
-        }
-    }
+    f16_finish<QKVP8 != 0>(a, b, h, qi, g, qvalid, l_part, ot);
 }
 
 // ---- One workgroup per (clip, head) for sequences of up to 208 queries x 256 keys with P8 operands (the wav2vec2 encoder: 199 x 199,
@@ -610,13 +698,10 @@ __global__ __launch_bounds__(256, 4) void attention_f16_kernel(const AttnArgs a)
 constexpr int kWideMaxWaves = 13, kWideMaxKeys = 256;
 template <int FASTEXP>
 __global__ __launch_bounds__(kWideMaxWaves * 64) void attention_f16_wide_kernel(const AttnArgs a) {
-    constexpr int HD = 64, KB = 64, PB = 160, NT = kWideMaxWaves * 64;
+    constexpr int NT = kWideMaxWaves * 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char wide_smem[];
     const int lkp = (a.Lk + 31) & ~31;             // rows staged: the P V step walks pairs of 16-key tiles
-    unsigned char* const Kh = wide_smem;
-    unsigned char* const Kl = Kh + lkp * PB;
-    unsigned char* const Vh = Kl + lkp * PB;
-    unsigned char* const Vl = Vh + lkp * PB;
+    const KVImages s = kv_images(wide_smem, lkp);
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int r = lane & 15, g = lane >> 4;
@@ -628,165 +713,45 @@ __global__ __launch_bounds__(kWideMaxWaves * 64) void attention_f16_wide_kernel(
 
     const float* Kb = a.K + (long)b * a.k_bstride + h * HD;
     const float* Vb = a.V + (long)b * a.v_bstride + h * HD;
-    // ---- stage: one 8-element group (16 B hi + 16 B lo) of K and of V per thread and pass, all passes' loads issued first ----
+    // ---- stage: one 8-element group of K and of V per thread and pass, all passes' loads (and the Q fragments') issued first ----
     constexpr int NPASS = (kWideMaxKeys * 8 + NT - 1) / NT;      // 3
-    {
-        h8_t kh[NPASS], kl[NPASS], vh[NPASS], vl[NPASS];
+    KV8 x[NPASS];
 #pragma unroll
-        for (int i = 0; i < NPASS; ++i) {
-            const int idx = tid + i * NT;
-            const int row = idx >> 3, g8 = idx & 7;
-            const h8_t z = {0, 0, 0, 0, 0, 0, 0, 0};
-            kh[i] = z; kl[i] = z; vh[i] = z; vl[i] = z;
-            if (row < a.Lk) {
-                const unsigned char* kp = reinterpret_cast<const unsigned char*>(Kb + (long)row * a.ldk) + g8 * 32;
-                const unsigned char* vp = reinterpret_cast<const unsigned char*>(Vb + (long)row * a.ldv) + g8 * 32;
-                kh[i] = *reinterpret_cast<const h8_t*>(kp); kl[i] = *reinterpret_cast<const h8_t*>(kp + 16);
-                vh[i] = *reinterpret_cast<const h8_t*>(vp); vl[i] = *reinterpret_cast<const h8_t*>(vp + 16);
-            }
-        }
-        // Q fragments (B operand of S^T): lane (r, g) holds Q[qi][8g + 32kb .. +7], hi | lo as stored
-        h8_t qh_[2], ql_[2];
-        {
-            const unsigned char* qp = reinterpret_cast<const unsigned char*>(a.Q + (long)b * a.q_bstride + (long)min(qi, a.Lq - 1) * a.ldq + h * HD);
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) {
-                qh_[kb] = *reinterpret_cast<const h8_t*>(qp + (g + 4 * kb) * 32);
-                ql_[kb] = *reinterpret_cast<const h8_t*>(qp + (g + 4 * kb) * 32 + 16);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < NPASS; ++i) {
-            const int idx = tid + i * NT;
-            const int row = idx >> 3, g8 = idx & 7;
-            if (row < lkp) {
-                *reinterpret_cast<h8_t*>(Kh + row * PB + g8 * 16) = kh[i];
-                *reinterpret_cast<h8_t*>(Kl + row * PB + g8 * 16) = kl[i];
-                *reinterpret_cast<h8_t*>(Vh + row * PB + g8 * 16) = vh[i];
-                *reinterpret_cast<h8_t*>(Vl + row * PB + g8 * 16) = vl[i];
-            }
-        }
-        __syncthreads();
-        if (!wave_active) return;
-        const h8_t z = {0, 0, 0, 0, 0, 0, 0, 0};
-        const h8_t qh[2] = {qvalid ? qh_[0] : z, qvalid ? qh_[1] : z}, ql[2] = {qvalid ? ql_[0] : z, qvalid ? ql_[1] : z};
-        const float sfix = a.scale * p8_scale_of(-2 * a.qkv_exp);      // scores of P8 operands carry the square of their site scale (16 * 16 by default) and no softmax scale yet
-        const int klim = (a.split_q > 0 && qi < a.split_q) ? a.split_k : a.Lk;
-        // attention_f16_kernel decides per 64-query workgroup how far the key loop runs; the same bound here keeps the block sequence
-        // (and with it every rounding) of a query identical to that kernel's
-        const int qblk_last = min((q0 & ~63) + 63, a.Lq - 1);
-        const int lk_wg = (a.split_q > 0 && qblk_last < a.split_q) ? a.split_k : a.Lk;
-
-        float m_run = -INFINITY, l_part = 0.f;
-        f32x4 ot[4];
-#pragma unroll
-        for (int d = 0; d < 4; ++d) { f32x4 zz = {0.f, 0.f, 0.f, 0.f}; ot[d] = zz; }
-        const int trq = r >> 2, trp = r & 3;
-
-        for (int kb0 = 0; kb0 < lk_wg; kb0 += KB) {
-            const int ntile = min(4, (a.Lk - kb0 + 15) >> 4);
-            f32x4 st[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-                if (t < ntile) {
-#pragma unroll
-                    for (int kb = 0; kb < 2; ++kb) {
-                        const int off = (kb0 + t * 16 + r) * PB + (8 * g + 32 * kb) * 2;
-                        const h8_t kh2 = *reinterpret_cast<const h8_t*>(Kh + off), kl2 = *reinterpret_cast<const h8_t*>(Kl + off);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh2, qh[kb], acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kl2, qh[kb], acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh2, ql[kb], acc, 0, 0, 0);
-                    }
-                }
-                st[t] = acc;
-            }
-            float mx = -INFINITY;
-            // the key mask only where a block can hold masked keys: the last block of the sequence, or any block under a split
-            // attention mask (the test is uniform over the workgroup; the values are the same either way)
-            if (kb0 + KB <= a.Lk && a.split_q <= 0) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float sv = st[t][j] * sfix;
-                        st[t][j] = sv;
-                        mx = fmaxf(mx, sv);
-                    }
-            } else {
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int kidx = kb0 + t * 16 + 4 * g + j;
-                        const float sv = (kidx < klim) ? st[t][j] * sfix : -INFINITY;
-                        st[t][j] = sv;
-                        mx = fmaxf(mx, sv);
-                    }
-            }
-            mx = fmaxf(mx, lane_xor<16>(mx));
-            mx = fmaxf(mx, lane_xor<32>(mx));
-            const float m_new = fmaxf(m_run, mx);
-            const float m_safe = (m_new == -INFINITY) ? 0.f : m_new;
-            const float alpha = FASTEXP ? __expf(m_run - m_safe) : expf(m_run - m_safe);
-            m_run = m_new;
-            float ps = 0.f;
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float p = FASTEXP ? __expf(st[t][j] - m_safe) : expf(st[t][j] - m_safe);
-                    st[t][j] = p;
-                    ps += p;
-                }
-            l_part = l_part * alpha + ps;
-#pragma unroll
-            for (int d = 0; d < 4; ++d) ot[d] *= alpha;
-#pragma unroll
-            for (int T = 0; T < 2; ++T) {
-                if (2 * T < ntile) {
-                    f16x4_t h0, l0, h1, l1;
-                    split4(st[2 * T], h0, l0);
-                    split4(st[2 * T + 1], h1, l1);
-                    const h8_t ph = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-                    const h8_t pl = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-                    const int row1 = kb0 + T * 32 + 4 * g + trq, row2 = row1 + 16;
-#pragma unroll
-                    for (int dt = 0; dt < 4; ++dt) {
-                        const int col = (16 * dt + 4 * trp) * 2;
-                        const f16x4_t a1 = __builtin_bit_cast(f16x4_t, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                            (__attribute__((address_space(3))) fp16x4_raw*)(Vh + row1 * PB + col)));
-                        const f16x4_t a2 = __builtin_bit_cast(f16x4_t, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                            (__attribute__((address_space(3))) fp16x4_raw*)(Vh + row2 * PB + col)));
-                        const f16x4_t b1 = __builtin_bit_cast(f16x4_t, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                            (__attribute__((address_space(3))) fp16x4_raw*)(Vl + row1 * PB + col)));
-                        const f16x4_t b2 = __builtin_bit_cast(f16x4_t, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                            (__attribute__((address_space(3))) fp16x4_raw*)(Vl + row2 * PB + col)));
-                        const h8_t vh2 = {a1[0], a1[1], a1[2], a1[3], a2[0], a2[1], a2[2], a2[3]};
-                        const h8_t vl2 = {b1[0], b1[1], b1[2], b1[3], b2[0], b2[1], b2[2], b2[3]};
-                        ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh2, ph, ot[dt], 0, 0, 0);
-                        ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vl2, ph, ot[dt], 0, 0, 0);
-                        ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh2, pl, ot[dt], 0, 0, 0);
-                    }
-                }
-            }
-        }
-        float l = l_part;
-        l += lane_xor<16>(l);
-        l += lane_xor<32>(l);
-        if (qvalid) {
-            const float inv = 1.0f / (l * p8_scale_of(a.qkv_exp));      // P8 values carry their site scale (x16 by default)
-            float* op = a.O + (long)b * a.o_bstride + (long)qi * a.ldo + h * HD;
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                const int d0 = 16 * dt + 4 * g;
-                const float o0 = ot[dt][0] * inv, o1 = ot[dt][1] * inv, o2 = ot[dt][2] * inv, o3 = ot[dt][3] * inv;
-                if (a.out_p8) store_p8x4(op, d0, o0, o1, o2, o3, a.status, a.o_exp);
-                else { const f32x4 o = {o0, o1, o2, o3}; *reinterpret_cast<f32x4*>(op + d0) = o; }
-            }
-        }
+    for (int i = 0; i < NPASS; ++i) {
+        const int idx = tid + i * NT;
+        const int row = idx >> 3, g8 = idx & 7;
+        x[i] = f16_load_kv_p8(a, Kb, Vb, row, g8, row < a.Lk);
     }
+    h8_t qrh[2], qrl[2];
+    f16_q_p8(a, b, h, min(qi, a.Lq - 1), true, g, qrh, qrl);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < NPASS; ++i) {
+        const int idx = tid + i * NT;
+        const int row = idx >> 3, g8 = idx & 7;
+        if (row < lkp) f16_store_kv_p8(s, row, g8, x[i]);
+    }
+    __syncthreads();
+    if (!wave_active) return;
+    h8_t qh[2], ql[2];
+    f16_q_keep(qvalid, qrh, qrl, qh, ql);
+    const float sfix = a.scale * p8_scale_of(-2 * a.qkv_exp);
+    const int klim = (a.split_q > 0 && qi < a.split_q) ? a.split_k : a.Lk;
+    // attention_f16_kernel decides per 64-query workgroup how far the key loop runs; the same bound here keeps the block sequence
+    // (and with it every rounding) of a query identical to that kernel's
+    const int qblk_last = min((q0 & ~63) + 63, a.Lq - 1);
+    const int lk_wg = (a.split_q > 0 && qblk_last < a.split_q) ? a.split_k : a.Lk;
+
+    float m_run = -INFINITY, l_part = 0.f;
+    f32x4 ot[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) { f32x4 z = {0.f, 0.f, 0.f, 0.f}; ot[d] = z; }
+    const int trq = r >> 2, trp = r & 3;
+
+    // the key mask only where a block can hold masked keys: the last block of the sequence, or any block under a split attention mask
+    for (int kb0 = 0; kb0 < lk_wg; kb0 += KB)
+        f16_block<FASTEXP, true>(s, kb0, kb0, a.Lk, klim, !(kb0 + KB <= a.Lk && a.split_q <= 0), sfix, qh, ql, r, g, trq, trp, m_run, l_part, ot);
+    f16_finish<true>(a, b, h, qi, g, qvalid, l_part, ot);
 }
 
 // ---- Persistent ping-pong form of the wide kernel for the wav2vec2 encoder (199 x 199 per head, 1536 heads per launch).  The wide
@@ -809,9 +774,9 @@ __device__ __forceinline__ f16x4_t pp_read_tr(unsigned addr) {
 template <int LOFF, int COL>
 __device__ __forceinline__ void pp_read_v(unsigned va, f16x4_t& a1, f16x4_t& a2, f16x4_t& b1, f16x4_t& b2) {
     a1 = pp_read_tr<COL>(va);
-    a2 = pp_read_tr<16 * 160 + COL>(va);
+    a2 = pp_read_tr<16 * PB + COL>(va);
     b1 = pp_read_tr<LOFF + COL>(va);
-    b2 = pp_read_tr<LOFF + 16 * 160 + COL>(va);
+    b2 = pp_read_tr<LOFF + 16 * PB + COL>(va);
 }
 template <int N>
 __device__ __forceinline__ void pp_wait_lgkm() {
@@ -820,10 +785,9 @@ __device__ __forceinline__ void pp_wait_lgkm() {
 }
 template <int FASTEXP>
 __global__ __launch_bounds__(kPPWaves * 64) void attention_f16_pp_kernel(const AttnArgs a) {
-    constexpr int HD = 64, KB = 64, PB = 160;
     extern __shared__ __attribute__((aligned(16))) unsigned char pp_smem[];
     unsigned char* const bufA = pp_smem;
-    unsigned char* const bufB = pp_smem + 4 * kPPRowsA * PB;
+    unsigned char* const bufB = pp_smem + f16_lds_bytes(kPPRowsA);
 
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int r = lane & 15, g = lane >> 4;
@@ -852,24 +816,15 @@ __global__ __launch_bounds__(kPPWaves * 64) void attention_f16_pp_kernel(const A
                                              (__attribute__((address_space(3))) void*)(buf + im * R * PB + n * 1024), 16, 0, 0);
         }
     };
-    auto load_q = [&](int item, h8_t (&qh)[2], h8_t (&ql)[2]) {
-        const int b = item / a.H, h = item - b * a.H;
-        const unsigned char* qp = reinterpret_cast<const unsigned char*>(a.Q + (long)b * a.q_bstride + (long)min(qi, a.Lq - 1) * a.ldq + h * HD);
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {      // (raw: nothing consumes these before the end of the current head, so no wait is placed behind the loads)
-            qh[kb] = *reinterpret_cast<const h8_t*>(qp + (g + 4 * kb) * 32);
-            ql[kb] = *reinterpret_cast<const h8_t*>(qp + (g + 4 * kb) * 32 + 16);
-        }
-    };
-    const h8_t z8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    // (raw fragments of the next head: nothing consumes them before the end of the current head, so no wait is placed behind the loads)
+    auto load_q = [&](int item, h8_t (&qh)[2], h8_t (&ql)[2]) { f16_q_p8(a, item / a.H, item % a.H, min(qi, a.Lq - 1), true, g, qh, ql); };
 
     int item = blockIdx.x;
     if (item >= n_items) return;
     h8_t qh[2], ql[2], qnh[2], qnl[2];
     issue_buffer(item, bufA, kPPRowsA, 0);
     load_q(item, qnh, qnl);
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) { qh[kb] = qvalid ? qnh[kb] : z8; ql[kb] = qvalid ? qnl[kb] : z8; }      // rows past Lq: zero fragments
+    f16_q_keep(qvalid, qnh, qnl, qh, ql);
     for (; item < n_items; item += gridDim.x) {
         const int next = item + (int)gridDim.x;
         float m_run = -INFINITY, l_part = 0.f;
@@ -878,84 +833,28 @@ __global__ __launch_bounds__(kPPWaves * 64) void attention_f16_pp_kernel(const A
         for (int d = 0; d < 4; ++d) { f32x4 zz = {0.f, 0.f, 0.f, 0.f}; ot[d] = zz; }
 
         // 64-key blocks [kfrom, kto) out of a buffer whose row 0 is key `key0`
-        auto phase = [&](const unsigned char* buf, auto r_tag, int key0, int kfrom, int kto) {
+        auto phase = [&](unsigned char* buf, auto r_tag, int key0, int kfrom, int kto) {
             constexpr int R = decltype(r_tag)::value;
-            const unsigned char* const Kh = buf;
-            const unsigned char* const Kl = buf + R * PB;
-            const unsigned vh_lds = (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)(buf + 2 * R * PB);
+            const KVImages s = kv_images(buf, R);
+            const unsigned vh_lds = (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)s.Vh;
             for (int kb0 = kfrom; kb0 < kto; kb0 += KB) {
                 const int ntile = min(4, (a.Lk - kb0 + 15) >> 4);
                 const int rb = kb0 - key0;
                 f32x4 st[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-                    if (t < ntile) {
-#pragma unroll
-                        for (int kb = 0; kb < 2; ++kb) {
-                            const int off = (rb + t * 16 + r) * PB + (8 * g + 32 * kb) * 2;
-                            const h8_t kh2 = *reinterpret_cast<const h8_t*>(Kh + off), kl2 = *reinterpret_cast<const h8_t*>(Kl + off);
-                            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh2, qh[kb], acc, 0, 0, 0);
-                            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kl2, qh[kb], acc, 0, 0, 0);
-                            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh2, ql[kb], acc, 0, 0, 0);
-                        }
-                    }
-                    st[t] = acc;
-                }
-                float mx = -INFINITY;
-                if (kb0 + KB <= a.Lk) {
-#pragma unroll
-                    for (int t = 0; t < 4; ++t)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const float sv = st[t][j] * sfix;
-                            st[t][j] = sv;
-                            mx = fmaxf(mx, sv);
-                        }
-                } else {
-#pragma unroll
-                    for (int t = 0; t < 4; ++t)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const int kidx = kb0 + t * 16 + 4 * g + j;
-                            const float sv = (kidx < a.Lk) ? st[t][j] * sfix : -INFINITY;
-                            st[t][j] = sv;
-                            mx = fmaxf(mx, sv);
-                        }
-                }
-                mx = fmaxf(mx, lane_xor<16>(mx));
-                mx = fmaxf(mx, lane_xor<32>(mx));
-                const float m_new = fmaxf(m_run, mx);
-                const float m_safe = (m_new == -INFINITY) ? 0.f : m_new;
-                const float alpha = FASTEXP ? __expf(m_run - m_safe) : expf(m_run - m_safe);
-                m_run = m_new;
-                float ps = 0.f;
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float p = FASTEXP ? __expf(st[t][j] - m_safe) : expf(st[t][j] - m_safe);
-                        st[t][j] = p;
-                        ps += p;
-                    }
-                l_part = l_part * alpha + ps;
-#pragma unroll
-                for (int d = 0; d < 4; ++d) ot[d] *= alpha;
+                f16_scores(s, rb, ntile, r, g, qh, ql, st);
+                f16_softmax<FASTEXP, true>(st, kb0, g, a.Lk, !(kb0 + KB <= a.Lk), sfix, m_run, l_part, ot);
+                // P V is this kernel's own (not f16_pv):
 #pragma unroll
                 for (int T = 0; T < 2; ++T) {
                     if (2 * T < ntile) {
-                        f16x4_t h0, l0, h1, l1;
-                        split4(st[2 * T], h0, l0);
-                        split4(st[2 * T + 1], h1, l1);
-                        const h8_t ph = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-                        const h8_t pl = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+                        h8_t ph, pl;
+                        split8(st[2 * T], st[2 * T + 1], ph, pl);
                         // The 16 transposed V reads of this pair of tiles go out as asm (the builtin makes hipcc wait for the LDS-DMA in
                         // flight - s_waitcnt vmcnt(0) in front of every read - which would serialise the fetch of the other buffer with
                         // this arithmetic); their results return in order and are waited for with counted lgkmcnt, four reads per d tile.
                         const unsigned va = vh_lds + (unsigned)((rb + T * 32 + 4 * g + trq) * PB + 8 * trp);
                         auto pv = [&](int dt, const f16x4_t& x1, const f16x4_t& x2, const f16x4_t& y1, const f16x4_t& y2) {
-                            const h8_t vh2 = {x1[0], x1[1], x1[2], x1[3], x2[0], x2[1], x2[2], x2[3]};
-                            const h8_t vl2 = {y1[0], y1[1], y1[2], y1[3], y2[0], y2[1], y2[2], y2[3]};
+                            const h8_t vh2 = join8(x1, x2), vl2 = join8(y1, y2);
                             ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh2, ph, ot[dt], 0, 0, 0);
                             ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vl2, ph, ot[dt], 0, 0, 0);
                             ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh2, pl, ot[dt], 0, 0, 0);
@@ -998,24 +897,9 @@ __global__ __launch_bounds__(kPPWaves * 64) void attention_f16_pp_kernel(const A
         }
         if (wave_active) {
             phase(bufB, std::integral_constant<int, kPPRowsB>{}, kPPRowsA, kPPRowsA, a.Lk);
-            float l = l_part;
-            l += lane_xor<16>(l);
-            l += lane_xor<32>(l);
-            if (qvalid) {
-                const int b = item / a.H, h = item - b * a.H;
-                const float inv = 1.0f / (l * p8_scale_of(a.qkv_exp));      // P8 values carry their site scale (x16 by default)
-                float* op = a.O + (long)b * a.o_bstride + (long)qi * a.ldo + h * HD;
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt) {
-                    const int d0 = 16 * dt + 4 * g;
-                    const float o0 = ot[dt][0] * inv, o1 = ot[dt][1] * inv, o2 = ot[dt][2] * inv, o3 = ot[dt][3] * inv;
-                    if (a.out_p8) store_p8x4(op, d0, o0, o1, o2, o3, a.status, a.o_exp);
-                    else { const f32x4 o = {o0, o1, o2, o3}; *reinterpret_cast<f32x4*>(op + d0) = o; }
-                }
-            }
+            f16_finish<true>(a, item / a.H, item % a.H, qi, g, qvalid, l_part, ot);
         }
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) { qh[kb] = qvalid ? qnh[kb] : z8; ql[kb] = qvalid ? qnl[kb] : z8; }
+        f16_q_keep(qvalid, qnh, qnl, qh, ql);      // rows past Lq: zero fragments
     }
 }
 
@@ -1025,15 +909,12 @@ __global__ __launch_bounds__(kPPWaves * 64) void attention_f16_pp_kernel(const A
 // Waves walk attention_f16_kernel<.., 0>'s 64-key blocks in the same order with the same arithmetic: bit-identical results.
 constexpr int kWideArWaves = 7, kWideArKeys = 192;
 // QKVP8 = 1: q, k, v rows in the P8 format (no normalisation; the encoder / VAE form), several workgroups of NW waves per head.
+constexpr int kWideArP8Waves = 7, kWideArP8Keys = 128;      // the instance that runs: two workgroups per head on the VAE stacks
 template <int FASTEXP, int QKVP8 = 0, int NW = kWideArWaves, int KPH = kWideArKeys>
 __global__ __launch_bounds__(NW * 64) void attention_f16_wide_ar_kernel(const AttnArgs a) {
-    constexpr int HD = 64, KB = 64, PB = 160, NT = NW * 64;
-    constexpr int NPASS = (KPH * 16 + NT - 1) / NT;      // 7
+    constexpr int NT = NW * 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char wide_smem[];
-    unsigned char* const Kh = wide_smem;
-    unsigned char* const Kl = Kh + KPH * PB;
-    unsigned char* const Vh = Kl + KPH * PB;
-    unsigned char* const Vl = Vh + KPH * PB;
+    const KVImages s = kv_images(wide_smem, KPH);
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int r = lane & 15, g = lane >> 4;
@@ -1054,57 +935,15 @@ __global__ __launch_bounds__(NW * 64) void attention_f16_wide_ar_kernel(const At
     const bool qvalid = qi < a.Lq;
     const bool wave_active = q0 < a.Lq;
 
-    // ---- Q fragments (B operand of S^T): lane (r, g) holds Q[qi][8g + 32kb .. +7], normalised, scaled, split ----
     h8_t qh[2], ql[2];
     if constexpr (QKVP8) {
-        const unsigned char* qp = reinterpret_cast<const unsigned char*>(a.Q + (long)b * a.q_bstride + (long)min(qi, a.Lq - 1) * a.ldq + h * HD);
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            const h8_t z = {0, 0, 0, 0, 0, 0, 0, 0};
-            const h8_t th = *reinterpret_cast<const h8_t*>(qp + (g + 4 * kb) * 32), tl = *reinterpret_cast<const h8_t*>(qp + (g + 4 * kb) * 32 + 16);
-            qh[kb] = qvalid ? th : z;
-            ql[kb] = qvalid ? tl : z;
-        }
+        h8_t qrh[2], qrl[2];
+        f16_q_p8(a, b, h, min(qi, a.Lq - 1), true, g, qrh, qrl);
+        f16_q_keep(qvalid, qrh, qrl, qh, ql);
     } else {
-        const float* qp = a.Q + (long)b * a.q_bstride + (long)min(qi, a.Lq - 1) * a.ldq + h * HD;
-        f32x4 x[2][2];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-                const f32x4 t = *reinterpret_cast<const f32x4*>(qp + 8 * g + 32 * kb + 4 * u);
-                x[kb][u] = qvalid ? t : z;
-            }
-        if (a.l2norm) {
-            float ss = 0.f;
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) ss += x[kb][u][e] * x[kb][u][e];
-            ss += lane_xor<16>(ss);
-            ss += lane_xor<32>(ss);
-            const float den = fmaxf(sqrtf(ss), 1e-12f);
-            const float mul = a.qscale[h];
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) x[kb][u][e] = (x[kb][u][e] / den) * mul;
-        }
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            f16x4_t h0, l0, h1, l1;
-            split4(x[kb][0] * a.scale, h0, l0);
-            split4(x[kb][1] * a.scale, h1, l1);
-            qh[kb] = h8_t{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-            ql[kb] = h8_t{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-        }
+        f16_q_f32(a, b, h, min(qi, a.Lq - 1), qvalid, g, qh, ql);
     }
-    const float sfix = QKVP8 ? a.scale * p8_scale_of(-2 * a.qkv_exp) : 1.0f;      // scores of P8 operands carry the square of their site scale (16 * 16 by default) and no softmax scale yet
+    const float sfix = QKVP8 ? a.scale * p8_scale_of(-2 * a.qkv_exp) : 1.0f;
     const int klim = (a.split_q > 0 && qi < a.split_q) ? a.split_k : a.Lk;
     // the 64-query workgroup of attention_f16_kernel this wave's queries belong to decides how far its key loop runs there: the same
     // bound here keeps the block sequence of a query identical; the phase loop runs to the furthest bound of the workgroup's waves
@@ -1121,180 +960,49 @@ __global__ __launch_bounds__(NW * 64) void attention_f16_wide_ar_kernel(const At
 
     for (int k0 = 0; k0 < lk_loop; k0 += KPH) {
         __syncthreads();                         // every wave is done with the previous phase's rows
-        if constexpr (QKVP8) {      // one 8-element group (16 B hi + 16 B lo) of K and of V per thread and pass: plain copies
-            constexpr int NP8 = (KPH * 8 + NT - 1) / NT;
-            h8_t kh[NP8], kl[NP8], vh[NP8], vl[NP8];
+        // ---- stage keys k0 .. k0 + KPH - 1, all loads first; rows >= Lk are zero ----
+        if constexpr (QKVP8) {
+            constexpr int NPASS = (KPH * 8 + NT - 1) / NT;
+            KV8 x[NPASS];
 #pragma unroll
-            for (int i = 0; i < NP8; ++i) {
+            for (int i = 0; i < NPASS; ++i) {
                 const int idx = tid + i * NT;
                 const int row = idx >> 3, g8 = idx & 7;
-                const int kr = k0 + row;
-                const h8_t z = {0, 0, 0, 0, 0, 0, 0, 0};
-                kh[i] = z; kl[i] = z; vh[i] = z; vl[i] = z;
-                if (row < KPH && kr < a.Lk) {
-                    const unsigned char* kp = reinterpret_cast<const unsigned char*>(Kb + (long)kr * a.ldk) + g8 * 32;
-                    const unsigned char* vp = reinterpret_cast<const unsigned char*>(Vb + (long)kr * a.ldv) + g8 * 32;
-                    kh[i] = *reinterpret_cast<const h8_t*>(kp); kl[i] = *reinterpret_cast<const h8_t*>(kp + 16);
-                    vh[i] = *reinterpret_cast<const h8_t*>(vp); vl[i] = *reinterpret_cast<const h8_t*>(vp + 16);
-                }
+                x[i] = f16_load_kv_p8(a, Kb, Vb, k0 + row, g8, row < KPH && k0 + row < a.Lk);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int i = 0; i < NP8; ++i) {
+            for (int i = 0; i < NPASS; ++i) {
                 const int idx = tid + i * NT;
                 const int row = idx >> 3, g8 = idx & 7;
-                if (row < KPH) {
-                    *reinterpret_cast<h8_t*>(Kh + row * PB + g8 * 16) = kh[i];
-                    *reinterpret_cast<h8_t*>(Kl + row * PB + g8 * 16) = kl[i];
-                    *reinterpret_cast<h8_t*>(Vh + row * PB + g8 * 16) = vh[i];
-                    *reinterpret_cast<h8_t*>(Vl + row * PB + g8 * 16) = vl[i];
-                }
+                if (row < KPH) f16_store_kv_p8(s, row, g8, x[i]);
             }
-        } else
-        {   // stage keys k0 .. k0 + KPH - 1: 16 threads per key row, all loads first
-            f32x4 kv[NPASS], vv[NPASS];
+        } else {
+            constexpr int NPASS = (KPH * 16 + NT - 1) / NT;      // 7
+            KV4 x[NPASS];
 #pragma unroll
             for (int i = 0; i < NPASS; ++i) {
                 const int idx = tid + i * NT;
                 const int row = idx >> 4, c4 = (idx & 15) * 4;
-                const int kr = k0 + row;
-                const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-                kv[i] = z; vv[i] = z;
-                if (row < KPH && kr < a.Lk) {
-                    kv[i] = *reinterpret_cast<const f32x4*>(Kb + (long)kr * a.ldk + c4);
-                    vv[i] = *reinterpret_cast<const f32x4*>(Vb + (long)kr * a.ldv + c4);
-                }
+                x[i] = f16_load_kv_f32(a, Kb, Vb, k0 + row, c4, row < KPH && k0 + row < a.Lk);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int i = 0; i < NPASS; ++i) {
                 const int idx = tid + i * NT;
                 const int row = idx >> 4, c4 = (idx & 15) * 4;
-                f32x4 kx = kv[i];
-                if (a.l2norm) {
-                    float ss = kx[0] * kx[0] + kx[1] * kx[1] + kx[2] * kx[2] + kx[3] * kx[3];
-                    ss = group_sum<16>(ss);
-                    const float den = fmaxf(sqrtf(ss), 1e-12f);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) kx[e] = kx[e] / den;
-                }
-                if (row < KPH) {
-                    f16x4_t hh, ll;
-                    split4(kx, hh, ll);
-                    *reinterpret_cast<f16x4_t*>(Kh + row * PB + c4 * 2) = hh;
-                    *reinterpret_cast<f16x4_t*>(Kl + row * PB + c4 * 2) = ll;
-                    split4(vv[i], hh, ll);
-                    *reinterpret_cast<f16x4_t*>(Vh + row * PB + c4 * 2) = hh;
-                    *reinterpret_cast<f16x4_t*>(Vl + row * PB + c4 * 2) = ll;
-                }
+                f16_store_kv_f32(s, row, c4, x[i], a.l2norm, row < KPH);
             }
         }
         __syncthreads();
         if (!wave_active) continue;              // wave-uniform
         const int kend = min(k0 + KPH, lk_wave);
-        for (int kb0 = k0; kb0 < kend; kb0 += KB) {
-            const int lb = kb0 - k0;             // first LDS row of this block
-            const int ntile = min(4, (a.Lk - kb0 + 15) >> 4);
-            f32x4 st[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-                if (t < ntile) {
-#pragma unroll
-                    for (int kb = 0; kb < 2; ++kb) {
-                        const int off = (lb + t * 16 + r) * PB + (8 * g + 32 * kb) * 2;
-                        const h8_t kh2 = *reinterpret_cast<const h8_t*>(Kh + off), kl2 = *reinterpret_cast<const h8_t*>(Kl + off);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh2, qh[kb], acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kl2, qh[kb], acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh2, ql[kb], acc, 0, 0, 0);
-                    }
-                }
-                st[t] = acc;
-            }
-            float mx = -INFINITY;
-            if (kb0 + KB <= a.Lk && a.split_q <= 0) {      // a full block without a split mask: no key to hide (uniform test, same values)
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float sv = QKVP8 ? st[t][j] * sfix : st[t][j];
-                        st[t][j] = sv;
-                        mx = fmaxf(mx, sv);
-                    }
-            } else {
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int kidx = kb0 + t * 16 + 4 * g + j;
-                        const float sv = (kidx < klim) ? (QKVP8 ? st[t][j] * sfix : st[t][j]) : -INFINITY;
-                        st[t][j] = sv;
-                        mx = fmaxf(mx, sv);
-                    }
-            }
-            mx = fmaxf(mx, lane_xor<16>(mx));
-            mx = fmaxf(mx, lane_xor<32>(mx));
-            const float m_new = fmaxf(m_run, mx);
-            const float m_safe = (m_new == -INFINITY) ? 0.f : m_new;
-            const float alpha = FASTEXP ? __expf(m_run - m_safe) : expf(m_run - m_safe);
-            m_run = m_new;
-            float ps = 0.f;
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float p = FASTEXP ? __expf(st[t][j] - m_safe) : expf(st[t][j] - m_safe);
-                    st[t][j] = p;
-                    ps += p;
-                }
-            l_part = l_part * alpha + ps;
-#pragma unroll
-            for (int d = 0; d < 4; ++d) ot[d] *= alpha;
-#pragma unroll
-            for (int T = 0; T < 2; ++T) {
-                if (2 * T < ntile) {
-                    f16x4_t h0, l0, h1, l1;
-                    split4(st[2 * T], h0, l0);
-                    split4(st[2 * T + 1], h1, l1);
-                    const h8_t ph = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-                    const h8_t pl = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-                    const int row1 = lb + T * 32 + 4 * g + trq, row2 = row1 + 16;
-#pragma unroll
-                    for (int dt = 0; dt < 4; ++dt) {
-                        const int col = (16 * dt + 4 * trp) * 2;
-                        const f16x4_t a1 = __builtin_bit_cast(f16x4_t, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                            (__attribute__((address_space(3))) fp16x4_raw*)(Vh + row1 * PB + col)));
-                        const f16x4_t a2 = __builtin_bit_cast(f16x4_t, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                            (__attribute__((address_space(3))) fp16x4_raw*)(Vh + row2 * PB + col)));
-                        const f16x4_t b1 = __builtin_bit_cast(f16x4_t, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                            (__attribute__((address_space(3))) fp16x4_raw*)(Vl + row1 * PB + col)));
-                        const f16x4_t b2 = __builtin_bit_cast(f16x4_t, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-                            (__attribute__((address_space(3))) fp16x4_raw*)(Vl + row2 * PB + col)));
-                        const h8_t vh2 = {a1[0], a1[1], a1[2], a1[3], a2[0], a2[1], a2[2], a2[3]};
-                        const h8_t vl2 = {b1[0], b1[1], b1[2], b1[3], b2[0], b2[1], b2[2], b2[3]};
-                        ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh2, ph, ot[dt], 0, 0, 0);
-                        ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vl2, ph, ot[dt], 0, 0, 0);
-                        ot[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh2, pl, ot[dt], 0, 0, 0);
-                    }
-                }
-            }
-        }
+        // a full block without a split mask has no key to hide
+        for (int kb0 = k0; kb0 < kend; kb0 += KB)
+            f16_block<FASTEXP, QKVP8 != 0>(s, kb0 - k0, kb0, a.Lk, klim, !(kb0 + KB <= a.Lk && a.split_q <= 0), sfix, qh, ql, r, g, trq, trp, m_run, l_part, ot);
     }
     if (!wave_active) return;
-    float l = l_part;
-    l += lane_xor<16>(l);
-    l += lane_xor<32>(l);
-    if (qvalid) {
-        const float inv = QKVP8 ? 1.0f / (l * p8_scale_of(a.qkv_exp)) : 1.0f / l;      // P8 values carry their site scale (x16 by default)
-        float* op = a.O + (long)b * a.o_bstride + (long)qi * a.ldo + h * HD;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-            const int d0 = 16 * dt + 4 * g;
-            const float o0 = ot[dt][0] * inv, o1 = ot[dt][1] * inv, o2 = ot[dt][2] * inv, o3 = ot[dt][3] * inv;
-            if (a.out_p8) store_p8x4(op, d0, o0, o1, o2, o3, a.status, a.o_exp);
-            else { const f32x4 o = {o0, o1, o2, o3}; *reinterpret_cast<f32x4*>(op + d0) = o; }
-        }
-    }
+    f16_finish<QKVP8 != 0>(a, b, h, qi, g, qvalid, l_part, ot);
 }
 
 void attention_prepare() {      // more than the default 64 KB of dynamic LDS for the wide kernel; called at model creation (outside any capture)
@@ -1303,13 +1011,13 @@ void attention_prepare() {      // more than the default 64 KB of dynamic LDS fo
     (void)hipGetDevice(&dev);
     if (dev < 0 || dev >= 64 || done[dev]) return;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f16_wide_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              4 * kWideMaxKeys * 160);
+                              (int)f16_lds_bytes(kWideMaxKeys));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f16_pp_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              4 * (kPPRowsA + kPPRowsB) * 160);
+                              (int)f16_lds_bytes(kPPRowsA + kPPRowsB));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f16_wide_ar_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              4 * kWideArKeys * 160);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f16_wide_ar_kernel<1, 1, 7, 128>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              4 * 128 * 160);
+                              (int)f16_lds_bytes(kWideArKeys));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f16_wide_ar_kernel<1, 1, kWideArP8Waves, kWideArP8Keys>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)f16_lds_bytes(kWideArP8Keys));
     done[dev] = true;
 }
 // Which kernel runs.  The thresholds, in the order they are tried:
@@ -1359,20 +1067,21 @@ AttnKernel launch_attention(const AttnArgs& a, hipStream_t s) {
         break;
     case ATTN_F16_PP:
         attention_prepare();
-        ARTALK_LAUNCH((attention_f16_pp_kernel<1>), dim3(attn_grid_cus(a, n_cu)), dim3(kPPWaves * 64), (size_t)4 * (kPPRowsA + kPPRowsB) * 160, s, a);
+        ARTALK_LAUNCH((attention_f16_pp_kernel<1>), dim3(attn_grid_cus(a, n_cu)), dim3(kPPWaves * 64), f16_lds_bytes(kPPRowsA + kPPRowsB), s, a);
         break;
     case ATTN_F16_WIDE_AR_P8:
         attention_prepare();
-        ARTALK_LAUNCH((attention_f16_wide_ar_kernel<1, 1, 7, 128>), dim3((a.Lq + 111) / 112, a.H, a.B), dim3(7 * 64), (size_t)4 * 128 * 160, s, a);
+        ARTALK_LAUNCH((attention_f16_wide_ar_kernel<1, 1, kWideArP8Waves, kWideArP8Keys>), dim3((a.Lq + kWideArP8Waves * 16 - 1) / (kWideArP8Waves * 16), a.H, a.B),
+                      dim3(kWideArP8Waves * 64), f16_lds_bytes(kWideArP8Keys), s, a);
         break;
     case ATTN_F16_WIDE:
         attention_prepare();
-        ARTALK_LAUNCH((attention_f16_wide_kernel<1>), dim3(1, a.H, a.B), dim3(kWideMaxWaves * 64), (size_t)4 * ((a.Lk + 31) & ~31) * 160, s, a);
+        ARTALK_LAUNCH((attention_f16_wide_kernel<1>), dim3(1, a.H, a.B), dim3(kWideMaxWaves * 64), f16_lds_bytes((a.Lk + 31) & ~31), s, a);
         break;
     case ATTN_F16_P8: ARTALK_LAUNCH((attention_f16_kernel<1, 1>), grid, block, 0, s, a); break;
     case ATTN_F16_WIDE_AR:
         attention_prepare();
-        ARTALK_LAUNCH((attention_f16_wide_ar_kernel<1>), dim3(1, a.H, a.B), dim3(kWideArWaves * 64), (size_t)4 * kWideArKeys * 160, s, a);
+        ARTALK_LAUNCH((attention_f16_wide_ar_kernel<1>), dim3(1, a.H, a.B), dim3(kWideArWaves * 64), f16_lds_bytes(kWideArKeys), s, a);
         break;
     case ATTN_F16: ARTALK_LAUNCH(attention_f16_kernel<1>, grid, block, 0, s, a); break;
     case ATTN_F32_64: ARTALK_LAUNCH(attention_kernel<64>, grid, block, 0, s, a); break;
