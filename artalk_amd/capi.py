@@ -37,6 +37,11 @@ SYMBOLS = [
     "artalk_styleunet_create", "artalk_styleunet_set_tensor", "artalk_styleunet_finalize", "artalk_styleunet_forward",
     "artalk_styleunet_set_slab", "artalk_styleunet_set_timing", "artalk_styleunet_get_timing", "artalk_styleunet_destroy",
     "artalk_styleunet_last_error", "artalk_op_conv2d", "artalk_op_resample2",
+    "artalk_flame_dims", "artalk_styleunet_dims",
+    "artalk_gaga_create", "artalk_gaga_set_avatar", "artalk_gaga_set_forehead", "artalk_gaga_set_watermark", "artalk_gaga_reset_state",
+    "artalk_gaga_set_slab", "artalk_gaga_render", "artalk_gaga_set_timing", "artalk_gaga_get_timing", "artalk_gaga_destroy",
+    "artalk_gaga_last_error", "artalk_gaga_cameras", "artalk_op_gaga_flame_inputs", "artalk_op_gaga_forehead", "artalk_op_gaga_means",
+    "artalk_op_gaga_finish", "artalk_op_gaga_check",
 ]
 
 # ARTALK_ATTN_* of include/artalk_hip.h: the kernels of attention.hip, as artalk_op_attention_plan names them
@@ -261,6 +266,46 @@ def lib() -> C.CDLL:
         L.artalk_op_conv2d.restype = i32
         L.artalk_op_resample2.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
         L.artalk_op_resample2.restype = i32
+    if hasattr(L, "artalk_gaga_create"):      # (an older build loaded through ARTALK_LIB for an A/B run lacks the GAGAvatar head)
+        pi = C.POINTER(i32)
+        L.artalk_flame_dims.argtypes = [vp, pi, pi, C.POINTER(f32)]
+        L.artalk_flame_dims.restype = i32
+        L.artalk_styleunet_dims.argtypes = [vp, pi, pi, pi, pi, pi]
+        L.artalk_styleunet_dims.restype = i32
+        L.artalk_gaga_create.argtypes = [i32, vp, vp, vp, i32, i32, i32, C.POINTER(vp)]
+        L.artalk_gaga_create.restype = i32
+        L.artalk_gaga_set_avatar.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.artalk_gaga_set_avatar.restype = i32
+        L.artalk_gaga_set_forehead.argtypes = [vp, vp, i32]
+        L.artalk_gaga_set_forehead.restype = i32
+        L.artalk_gaga_set_watermark.argtypes = [vp, vp, i32, i32]
+        L.artalk_gaga_set_watermark.restype = i32
+        L.artalk_gaga_reset_state.argtypes = [vp]
+        L.artalk_gaga_reset_state.restype = i32
+        L.artalk_gaga_set_slab.argtypes = [vp, i32]
+        L.artalk_gaga_set_slab.restype = i32
+        L.artalk_gaga_render.argtypes = [vp, vp, i64, i32, C.POINTER(vp), C.POINTER(i64), i32, vp, vp]
+        L.artalk_gaga_render.restype = i32
+        L.artalk_gaga_set_timing.argtypes = [vp, i32]
+        L.artalk_gaga_set_timing.restype = i32
+        L.artalk_gaga_get_timing.argtypes = [vp, C.POINTER(C.c_double), i32]
+        L.artalk_gaga_get_timing.restype = i32
+        L.artalk_gaga_destroy.argtypes = [vp]
+        L.artalk_gaga_destroy.restype = None
+        L.artalk_gaga_last_error.argtypes = [vp]
+        L.artalk_gaga_last_error.restype = C.c_char_p
+        L.artalk_gaga_cameras.argtypes = [vp, i64, i32, vp, vp, vp, vp]
+        L.artalk_gaga_cameras.restype = i32
+        L.artalk_op_gaga_flame_inputs.argtypes = [vp, i64, vp, i32, i32, vp, vp, vp]
+        L.artalk_op_gaga_flame_inputs.restype = i32
+        L.artalk_op_gaga_forehead.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
+        L.artalk_op_gaga_forehead.restype = i32
+        L.artalk_op_gaga_means.argtypes = [vp, vp, vp, i32, i32, i32, vp]
+        L.artalk_op_gaga_means.restype = i32
+        L.artalk_op_gaga_finish.argtypes = [vp, i32, i32, vp, i32, i32, vp]
+        L.artalk_op_gaga_finish.restype = i32
+        L.artalk_op_gaga_check.argtypes = [i32, i32, i32, vp, i32, i32, i32, i32, i64, i32, i32, C.c_char_p, i32]
+        L.artalk_op_gaga_check.restype = i32
     L.artalk_savgol.argtypes = [vp, vp, vp, i32, vp]
     L.artalk_savgol.restype = i32
     L.artalk_set_profiling.argtypes = [vp, i32]

@@ -200,6 +200,14 @@ int artalk_flame_create(int device_id, int V, int NB, int P, const float* v_temp
     return ARTALK_OK;
 }
 
+int artalk_flame_dims(const artalk_flame* f, int* V, int* NB, float* scale) {
+    if (!f) { g_flame_error = "handle is NULL"; return ARTALK_EINVAL; }
+    if (V) *V = f->V;
+    if (NB) *NB = f->NB;
+    if (scale) *scale = f->scale;
+    return f->device;
+}
+
 // betas_dev [T][NB] (shape ++ expression), full_pose_dev [T][15] (global, neck, jaw, eye_l, eye_r axis-angles: FLAME.py:131-136)
 // -> out_dev [T][V][3] = vertices * scale
 int artalk_flame_verts(artalk_flame* f, const float* betas_dev, const float* full_pose_dev, int T, float* out_dev, void* stream) {

@@ -1,0 +1,559 @@
+// The per-frame path of the GAGAvatar head ("GAGAvatar head"): motion codes -> RGB frames.  A stand-in for
+// GAGAvatar.build_forward_batch + forward_expression (reference app/GAGAvatar/models.py:63-138) on top of the three pieces that exist
+// already: FLAME skinning (flame.hip), the 32-channel splat rasteriser (splat.hip) and the StyleUNet upsampler (styleunet.hip).
+//
+//   gaga_flame_inputs_kernel   motion rows -> the betas and full_pose arrays artalk_flame_verts takes           (models.py:114-119)
+//   gaga_forehead_kernel       EMA over frames of K listed vertices; its state outlives the call               (models.py:120-125)
+//   gaga_means_kernel          per-frame Gaussian centres: V skinned vertices, then the avatar's static points (models.py:90)
+//   gaga_finish_kernel         clamp(0, 1) and the watermark blend, in place                                   (models.py:95, 131-138)
+//   artalk_gaga_cameras        host only: head-rotation codes -> the view / projection matrices the rasteriser reads (models.py:127)
+//
+// All fp32 and element-wise (no reductions, no atomics): bit-identical from run to run.  The EMA and the blend use torch's rounding
+// order - every product and sum rounded on its own, never contracted to an FMA - so they equal the torch statements bit for bit.
+// hipcc contracts a * b + c by default and HIP's __fmul_rn / __fadd_rn are plain operators that contract like any other, so the two
+// kernels switch contraction off for their bodies (#pragma clang fp contract(off)).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "artalk_hip.h"
+#include "common.h"
+
+namespace artalk {
+
+constexpr int kGagaMotion = 106;      // a motion row: 100 expression, 3 head rotation, 3 jaw
+constexpr int kGagaCh = 32;           // channels of the splat image
+constexpr int kForeheadDefault = 68;
+// the vertices the reference smooths (models.py:326-331): 68 distinct FLAME vertex ids, the largest 3913
+static const int32_t kForeheadIdx[kForeheadDefault] = {
+    2168, 2165, 3068, 2199, 2196, 3720, 2091, 2088, 3524, 625,  628,  3871, 705,  708,  2030, 667,  670,
+    3708, 3706, 3729, 3721, 3773, 3789, 3735, 3732, 3786, 3876, 3878, 3913, 3899, 3872, 3874, 3864, 3865,
+    3158, 3157, 336,  335,  3153, 3705, 2177, 2176, 3540, 671,  672,  3863, 2134, 16,   17,   2138, 2139,
+    2567, 2566, 337,  338,  3154, 3712, 2178, 2179, 3495, 674,  673,  3868, 2135, 27,   18,   1429, 1430};
+
+// one thread per (frame, column) of betas ++ full_pose: betas = shapecode ++ m[0:100]; full_pose = (0 x 6 | m[103:106] | 0 x 6)
+__global__ void gaga_flame_inputs_kernel(const float* __restrict__ motion, long stride, const float* __restrict__ shapecode, int NS,
+                                         float* __restrict__ betas, float* __restrict__ pose, int T) {
+    const int NB = NS + 100, W = NB + 15;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)T * W) return;
+    const int t = (int)(idx / W), c = (int)(idx - (long)t * W);
+    const float* m = motion + (long)t * stride;
+    if (c < NB) {
+        betas[(long)t * NB + c] = c < NS ? shapecode[c] : m[c - NS];
+    } else {
+        const int p = c - NB;
+        pose[(long)t * 15 + p] = (p >= 6 && p < 9) ? m[103 + (p - 6)] : 0.f;
+    }
+}
+
+// One workgroup; thread i owns coordinate i % 3 of listed vertex i / 3 and walks the T frames of the call in order:
+// unset state: state = cur (that frame is left as it is); otherwise state = 0.98 state + 0.02 cur, written back into the vertex.
+// state [K][3], *flag != 0: the state is set.  Both are read at the start and written at the end.
+__global__ __launch_bounds__(256) void gaga_forehead_kernel(float* __restrict__ verts /*[T][V][3]*/, const int32_t* __restrict__ index,
+                                                            int K, int T, int V, float* __restrict__ state, int* __restrict__ flag) {
+#pragma clang fp contract(off)
+    const bool was_set = *flag != 0;
+    __syncthreads();      // every thread has read the flag before thread 0 writes it
+    for (int i = threadIdx.x; i < K * 3; i += blockDim.x) {
+        const int k = i / 3, c = i - k * 3;
+        float* p = verts + (long)index[k] * 3 + c;
+        float s = state[i];
+        bool set = was_set;
+        for (int t = 0; t < T; ++t, p += (long)V * 3) {
+            const float cur = *p;
+            if (!set) { s = cur; set = true; }
+            else { s = 0.98f * s + 0.02f * cur; *p = s; }
+        }
+        state[i] = s;
+    }
+    if (threadIdx.x == 0 && T > 0 && K > 0) *flag = 1;
+}
+
+// means [F][N][3]: rows 0 .. V-1 from the frame's vertices, rows V .. N-1 from the avatar's xyz [N][3]
+__global__ void gaga_means_kernel(const float* __restrict__ verts, const float* __restrict__ xyz, float* __restrict__ means, int F, int V, int N) {
+    const long per = (long)N * 3, idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)F * per) return;
+    const int f = (int)(idx / per);
+    const long e = idx - (long)f * per;
+    means[idx] = e < (long)V * 3 ? verts[(long)f * V * 3 + e] : xyz[e];
+}
+
+// in place on img [F][3][S][S]: clamp(0, 1); on the bottom-right h x w patch a = alpha * 0.8, p = p * (1 - a) + rgb * a.
+// wm [4][h][w] (r, g, b, alpha) or null
+__global__ void gaga_finish_kernel(float* __restrict__ img, const float* __restrict__ wm, int h, int w, int S, int F) {
+#pragma clang fp contract(off)
+    const long SS = (long)S * S, idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)F * 3 * SS) return;
+    float v = fminf(fmaxf(img[idx], 0.f), 1.f);
+    if (wm) {
+        const long pix = idx % SS;
+        const int c = (int)((idx / SS) % 3);
+        const int y = (int)(pix / S) - (S - h), x = (int)(pix % S) - (S - w);
+        if (y >= 0 && x >= 0) {
+            const float a = wm[(3L * h + y) * w + x] * 0.8f;
+            v = v * (1.f - a) + wm[((long)c * h + y) * w + x] * a;
+        }
+    }
+    img[idx] = v;
+}
+
+static inline unsigned gaga_blocks(long n) { return (unsigned)((n + 255) / 256); }
+
+static void launch_gaga_flame_inputs(const float* motion, long stride, const float* shapecode, int NS, float* betas, float* pose, int T,
+                                     hipStream_t s) {
+    ARTALK_LAUNCH(gaga_flame_inputs_kernel, dim3(gaga_blocks((long)T * (NS + 115))), dim3(256), 0, s, motion, stride, shapecode, NS, betas, pose, T);
+}
+static void launch_gaga_forehead(float* verts, const int32_t* index, int K, int T, int V, float* state, int* flag, hipStream_t s) {
+    ARTALK_LAUNCH(gaga_forehead_kernel, dim3(1), dim3(256), 0, s, verts, index, K, T, V, state, flag);
+}
+static void launch_gaga_means(const float* verts, const float* xyz, float* means, int F, int V, int N, hipStream_t s) {
+    ARTALK_LAUNCH(gaga_means_kernel, dim3(gaga_blocks((long)F * N * 3)), dim3(256), 0, s, verts, xyz, means, F, V, N);
+}
+static void launch_gaga_finish(float* img, const float* wm, int h, int w, int S, int F, hipStream_t s) {
+    ARTALK_LAUNCH(gaga_finish_kernel, dim3(gaga_blocks((long)F * 3 * S * S)), dim3(256), 0, s, img, wm, h, w, S, F);
+}
+
+// ---- the host checks every entry point applies before the device is touched (artalk_op_gaga_check exposes them to the CPU tests)
+static int check_avatar(int V, int N, std::string* err) {
+    if (N < V) { *err = "N (" + std::to_string(N) + ") must be at least V (" + std::to_string(V) + "): the first V Gaussians ride on the vertices"; return ARTALK_EINVAL; }
+    return ARTALK_OK;
+}
+static int check_forehead(int V, const int32_t* index, int K, std::string* err) {
+    if (K < 0) { *err = "K must not be negative"; return ARTALK_EINVAL; }
+    if (K > 0 && !index) { *err = "idx is NULL"; return ARTALK_EINVAL; }
+    std::vector<char> seen((size_t)(V > 0 ? V : 0), 0);
+    for (int k = 0; k < K; ++k) {
+        if (index[k] < 0 || index[k] >= V) { *err = "forehead index " + std::to_string(index[k]) + " is outside [0, V = " + std::to_string(V) + ")"; return ARTALK_EINVAL; }
+        if (seen[index[k]]) { *err = "forehead index " + std::to_string(index[k]) + " is listed twice"; return ARTALK_EINVAL; }
+        seen[index[k]] = 1;
+    }
+    return ARTALK_OK;
+}
+static int check_watermark(int S, int h, int w, std::string* err) {
+    if (h < 1 || w < 1 || h > S || w > S) {
+        *err = "a watermark of " + std::to_string(h) + " x " + std::to_string(w) + " does not fit the " + std::to_string(S) + " x " + std::to_string(S) + " image";
+        return ARTALK_EINVAL;
+    }
+    return ARTALK_OK;
+}
+static int check_render(int T, int64_t motion_stride, bool have_avatar, bool finalized, std::string* err) {
+    if (T < 0) { *err = "T must not be negative"; return ARTALK_EINVAL; }
+    if (motion_stride < kGagaMotion) { *err = "motion_stride must be at least 106"; return ARTALK_EINVAL; }
+    if (!have_avatar) { *err = "no avatar set: call artalk_gaga_set_avatar first"; return ARTALK_EINVAL; }
+    if (!finalized) { *err = "the upsampler is not finalized (artalk_styleunet_finalize)"; return ARTALK_ESTATE; }
+    return ARTALK_OK;
+}
+
+}  // namespace artalk
+
+using namespace artalk;
+
+namespace {
+enum { kGagaInputsFlame, kGagaForeheadMeans, kGagaSplat, kGagaUpsampler, kGagaFinish, kGagaStages };
+}
+
+struct artalk_gaga {
+    int device = 0, V = 0, NB = 0, S = 0, num_layers = 0;
+    artalk_flame* flame = nullptr;
+    artalk_splat* splat = nullptr;
+    artalk_styleunet* unet = nullptr;
+    // avatar (device copies, uploaded once by set_avatar)
+    int N = 0;
+    bool have_avatar = false;
+    float *xyz = nullptr, *colors = nullptr, *opac = nullptr, *scales = nullptr, *rots = nullptr, *shapecode = nullptr;
+    float transform[12] = {};
+    // forehead EMA
+    int K = 0;
+    int32_t* index = nullptr;
+    float* state = nullptr;      // [K][3]
+    int* flag = nullptr;
+    // watermark
+    float* wm = nullptr;
+    int wm_h = 0, wm_w = 0;
+    // scratch of one slab
+    int slab_req = 0, cap_frames = 0, cap_N = 0;
+    float *betas = nullptr, *pose = nullptr, *verts = nullptr, *means = nullptr, *img = nullptr;
+    int32_t* radii = nullptr;
+    float* codes_host = nullptr;      // pinned [cap_codes][3]
+    int cap_codes = 0;
+    bool timing = false;
+    double stage_ms[kGagaStages] = {0, 0, 0, 0, 0};
+    std::string err;
+};
+
+static thread_local std::string g_gaga_error;
+
+namespace {
+
+int gaga_fail(artalk_gaga* g, int rc, const std::string& msg) { g->err = msg; return rc; }
+
+void gaga_free(float*& p) { if (p) (void)hipFree(p); p = nullptr; }
+
+bool gaga_upload(float*& dst, const float* host, size_t n) {
+    gaga_free(dst);
+    void* p = nullptr;
+    if (hipMalloc(&p, (n ? n : 1) * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return false; }
+    dst = (float*)p;
+    return n == 0 || hipMemcpy(p, host, n * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+}
+
+// frames whose means, radii, splat image and vertices fit 512 MiB, at most 64 and at most the upsampler's slab in force
+int gaga_default_slab(const artalk_gaga* g, int N) {
+    const int64_t per = (int64_t)N * 16 + (int64_t)kGagaCh * g->S * g->S * 4 + (int64_t)g->V * 12 + (int64_t)g->NB * 4 + 60;
+    int64_t n = (512ll << 20) / per;
+    return (int)(n < 1 ? 1 : n > 64 ? 64 : n);
+}
+
+int gaga_slab(const artalk_gaga* g) {
+    int unet_slab = 1;
+    (void)artalk_styleunet_dims(g->unet, nullptr, nullptr, nullptr, nullptr, &unet_slab);
+    const int want = g->slab_req > 0 ? g->slab_req : gaga_default_slab(g, g->have_avatar ? g->N : g->V);
+    return want < unet_slab ? want : unet_slab;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* artalk_gaga_last_error(const artalk_gaga* g) { return g ? g->err.c_str() : g_gaga_error.c_str(); }
+
+void artalk_gaga_destroy(artalk_gaga* g) {
+    if (!g) return;
+    (void)hipSetDevice(g->device);
+    (void)hipDeviceSynchronize();
+    for (float** p : {&g->xyz, &g->colors, &g->opac, &g->scales, &g->rots, &g->shapecode, &g->state, &g->wm, &g->betas, &g->pose, &g->verts,
+                      &g->means, &g->img})
+        gaga_free(*p);
+    if (g->index) (void)hipFree(g->index);
+    if (g->flag) (void)hipFree(g->flag);
+    if (g->radii) (void)hipFree(g->radii);
+    if (g->codes_host) (void)hipHostFree(g->codes_host);
+    delete g;
+}
+
+int artalk_gaga_cameras(const float* rot_host, int64_t rot_stride, int T, const float* transform_3x4_host, float* view_out, float* proj_out,
+                        float* cam_out_or_null) {
+    if (!rot_host || !transform_3x4_host || !view_out || !proj_out) { g_gaga_error = "rot, transform, view and proj must not be NULL"; return ARTALK_EINVAL; }
+    if (T < 0) { g_gaga_error = "T must not be negative"; return ARTALK_EINVAL; }
+    if (rot_stride < 3) { g_gaga_error = "rot_stride must be at least 3"; return ARTALK_EINVAL; }
+    // the projection of artalk_amd.splat.build_camera_matrices with focal 12, z_near 0.01, z_far 100, transposed for row vectors
+    const double focal = 12.0, zn = 0.01, zf = 100.0;
+    const double p00 = 1.0 / std::tan(std::atan(1.0 / focal)), p22 = zf / (zf - zn), p32 = -(zf * zn) / (zf - zn);
+    for (int t = 0; t < T; ++t) {
+        const float* r = rot_host + (size_t)t * rot_stride;
+        const double w[3] = {-(double)r[0], (double)r[1], -(double)r[2]};
+        const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], th = std::sqrt(th2);
+        // R = I + A [w]x + B [w]x^2, A = sin(th) / th, B = (1 - cos(th)) / th^2 = 2 sin^2(th / 2) / th^2 (no cancellation near 0)
+        const double sh = std::sin(0.5 * th);
+        const double A = th > 0.0 ? std::sin(th) / th : 1.0, B = th > 0.0 ? 2.0 * sh * sh / th2 : 0.5;
+        const double Kx[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
+        double R[9];
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b) {
+                const double kk = Kx[a * 3] * Kx[b] + Kx[a * 3 + 1] * Kx[3 + b] + Kx[a * 3 + 2] * Kx[6 + b];
+                R[a * 3 + b] = (a == b ? 1.0 : 0.0) + A * Kx[a * 3 + b] + B * kk;
+            }
+        // the frame's [M | t]: M = diag(-1, 1, -1) . R^T; the translation stays the avatar's own
+        double cam[12];
+        for (int a = 0; a < 3; ++a) {
+            for (int b = 0; b < 3; ++b) cam[a * 4 + b] = (a == 1 ? 1.0 : -1.0) * R[b * 3 + a];
+            cam[a * 4 + 3] = (double)transform_3x4_host[a * 4 + 3];
+        }
+        if (cam_out_or_null) for (int e = 0; e < 12; ++e) cam_out_or_null[(size_t)t * 12 + e] = (float)cam[e];
+        double view[16];
+        for (int a = 0; a < 3; ++a) {
+            for (int b = 0; b < 3; ++b) view[a * 4 + b] = cam[a * 4 + b];
+            view[a * 4 + 3] = 0.0;
+            view[12 + a] = cam[a * 4 + 3];
+        }
+        view[15] = 1.0;
+        for (int a = 0; a < 4; ++a) { view[a * 4] = -view[a * 4]; view[a * 4 + 1] = -view[a * 4 + 1]; }
+        float* vo = view_out + (size_t)t * 16;
+        float* po = proj_out + (size_t)t * 16;
+        for (int a = 0; a < 4; ++a) {
+            for (int b = 0; b < 4; ++b) vo[a * 4 + b] = (float)view[a * 4 + b];
+            po[a * 4] = (float)(view[a * 4] * p00);
+            po[a * 4 + 1] = (float)(view[a * 4 + 1] * p00);
+            po[a * 4 + 2] = (float)(view[a * 4 + 2] * p22 + view[a * 4 + 3] * p32);
+            po[a * 4 + 3] = (float)view[a * 4 + 2];
+        }
+    }
+    return ARTALK_OK;
+}
+
+int artalk_gaga_create(int device_id, artalk_flame* flame, artalk_splat* splat, artalk_styleunet* unet, int V, int NB, int S, artalk_gaga** out) {
+    if (!out) { g_gaga_error = "out is NULL"; return ARTALK_EINVAL; }
+    *out = nullptr;
+    if (device_id < 0) { g_gaga_error = "device_id must not be negative"; return ARTALK_EINVAL; }
+    if (!flame || !splat || !unet) { g_gaga_error = "flame, splat and unet must not be NULL"; return ARTALK_EINVAL; }
+    if (V < 1 || NB < 100 || S < 1) { g_gaga_error = "V and S must be positive and NB at least 100"; return ARTALK_EINVAL; }
+    int fV = 0, fNB = 0, in_dim = 0, out_dim = 0, uS = 0;
+    const int fdev = artalk_flame_dims(flame, &fV, &fNB, nullptr);
+    const int udev = artalk_styleunet_dims(unet, &in_dim, &out_dim, &uS, nullptr, nullptr);
+    if (fV != V || fNB != NB) {
+        g_gaga_error = "the FLAME model has V = " + std::to_string(fV) + ", NB = " + std::to_string(fNB) + ", not " + std::to_string(V) + ", " + std::to_string(NB);
+        return ARTALK_EINVAL;
+    }
+    if (uS != S || in_dim != kGagaCh || out_dim != 3) {
+        g_gaga_error = "the upsampler must map 32 channels to 3 at " + std::to_string(S) + " x " + std::to_string(S) + " (it maps " +
+                       std::to_string(in_dim) + " to " + std::to_string(out_dim) + " at " + std::to_string(uS) + ")";
+        return ARTALK_EINVAL;
+    }
+    if (fdev != device_id || udev != device_id) { g_gaga_error = "the FLAME model and the upsampler must live on device " + std::to_string(device_id); return ARTALK_EINVAL; }
+    artalk_gaga* g = new artalk_gaga();
+    g->device = device_id; g->V = V; g->NB = NB; g->S = S;
+    g->flame = flame; g->splat = splat; g->unet = unet;
+    for (g->num_layers = 0; (1 << g->num_layers) < S; ++g->num_layers) {}
+    g->num_layers = (g->num_layers - 2) * 2 + 1;
+    *out = g;
+    if (V > 3913) {
+        const int rc = artalk_gaga_set_forehead(g, kForeheadIdx, kForeheadDefault);
+        if (rc != ARTALK_OK) { g_gaga_error = g->err; artalk_gaga_destroy(g); *out = nullptr; return rc; }
+    }
+    return ARTALK_OK;
+}
+
+int artalk_gaga_set_avatar(artalk_gaga* g, int N, const float* xyz, const float* colors, const float* opacities, const float* scales,
+                           const float* rotations, const float* shapecode, const float* transform_3x4) {
+    if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
+    if (!xyz || !colors || !opacities || !scales || !rotations || !transform_3x4 || (g->NB > 100 && !shapecode))
+        return gaga_fail(g, ARTALK_EINVAL, "xyz, colors, opacities, scales, rotations, shapecode and transform must not be NULL");
+    const int rc = check_avatar(g->V, N, &g->err);
+    if (rc != ARTALK_OK) return rc;
+    if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
+    (void)hipDeviceSynchronize();      // an earlier call may still read the avatar that is replaced
+    g->have_avatar = false;
+    const size_t n = (size_t)N;
+    if (!gaga_upload(g->xyz, xyz, n * 3) || !gaga_upload(g->colors, colors, n * kGagaCh) || !gaga_upload(g->opac, opacities, n) ||
+        !gaga_upload(g->scales, scales, n * 3) || !gaga_upload(g->rots, rotations, n * 4) ||
+        !gaga_upload(g->shapecode, shapecode, (size_t)(g->NB - 100)))
+        return gaga_fail(g, ARTALK_EHIP, "uploading the avatar failed");
+    std::memcpy(g->transform, transform_3x4, sizeof(g->transform));
+    g->N = N;
+    g->have_avatar = true;
+    return ARTALK_OK;
+}
+
+int artalk_gaga_reset_state(artalk_gaga* g) {
+    if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
+    if (!g->flag) return ARTALK_OK;      // no indices: there is no state
+    if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
+    (void)hipDeviceSynchronize();
+    if (hipMemset(g->flag, 0, sizeof(int)) != hipSuccess || hipMemset(g->state, 0, (size_t)(g->K ? g->K : 1) * 3 * sizeof(float)) != hipSuccess)
+        return gaga_fail(g, ARTALK_EHIP, "hipMemset failed");
+    return ARTALK_OK;
+}
+
+int artalk_gaga_set_forehead(artalk_gaga* g, const int32_t* idx, int K) {
+    if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
+    const int rc = check_forehead(g->V, idx, K, &g->err);
+    if (rc != ARTALK_OK) return rc;
+    if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
+    (void)hipDeviceSynchronize();
+    if (g->index) (void)hipFree(g->index);
+    if (g->flag) (void)hipFree(g->flag);
+    gaga_free(g->state);
+    g->index = nullptr; g->flag = nullptr; g->K = 0;
+    if (K == 0) return ARTALK_OK;
+    void *pi = nullptr, *pf = nullptr, *ps = nullptr;
+    if (hipMalloc(&pi, (size_t)K * sizeof(int32_t)) != hipSuccess || hipMalloc(&pf, sizeof(int)) != hipSuccess ||
+        hipMalloc(&ps, (size_t)K * 3 * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        if (pi) (void)hipFree(pi);
+        if (pf) (void)hipFree(pf);
+        return gaga_fail(g, ARTALK_EHIP, "hipMalloc failed");
+    }
+    g->index = (int32_t*)pi; g->flag = (int*)pf; g->state = (float*)ps; g->K = K;
+    if (hipMemcpy(g->index, idx, (size_t)K * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
+        return gaga_fail(g, ARTALK_EHIP, "uploading the indices failed");
+    return artalk_gaga_reset_state(g);
+}
+
+int artalk_gaga_set_watermark(artalk_gaga* g, const float* rgba_host, int h, int w) {
+    if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
+    if (rgba_host) {
+        const int rc = check_watermark(g->S, h, w, &g->err);
+        if (rc != ARTALK_OK) return rc;
+    }
+    if (!rgba_host && !g->wm) return ARTALK_OK;
+    if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
+    (void)hipDeviceSynchronize();
+    gaga_free(g->wm);
+    g->wm_h = g->wm_w = 0;
+    if (!rgba_host) return ARTALK_OK;
+    if (!gaga_upload(g->wm, rgba_host, (size_t)4 * h * w)) return gaga_fail(g, ARTALK_EHIP, "uploading the watermark failed");
+    g->wm_h = h; g->wm_w = w;
+    return ARTALK_OK;
+}
+
+int artalk_gaga_set_slab(artalk_gaga* g, int frames) {
+    if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
+    if (frames < 0 || frames > 64) return gaga_fail(g, ARTALK_EINVAL, "slab must be in 0..64 frames (0: the default)");
+    g->slab_req = frames;
+    return gaga_slab(g);
+}
+
+int artalk_gaga_set_timing(artalk_gaga* g, int enable) {
+    if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
+    g->timing = enable != 0;
+    return ARTALK_OK;
+}
+
+int artalk_gaga_get_timing(const artalk_gaga* g, double* stage_ms, int n) {
+    if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
+    if (stage_ms) for (int i = 0; i < n && i < kGagaStages; ++i) stage_ms[i] = g->stage_ms[i];
+    return kGagaStages;
+}
+
+int artalk_gaga_render(artalk_gaga* g, const float* motion_dev, int64_t motion_stride, int T, const float* const* noise_ptrs_or_null,
+                       const int64_t* noise_batch_strides, int activation, float* out_dev, void* stream) {
+    if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
+    if (!motion_dev || !out_dev) return gaga_fail(g, ARTALK_EINVAL, "motion and out must not be NULL");
+    int finalized = 0;
+    (void)artalk_styleunet_dims(g->unet, nullptr, nullptr, nullptr, &finalized, nullptr);
+    const int rc = check_render(T, motion_stride, g->have_avatar, finalized != 0, &g->err);
+    if (rc != ARTALK_OK) return rc;
+    if (noise_ptrs_or_null) {
+        if (!noise_batch_strides) return gaga_fail(g, ARTALK_EINVAL, "noise_batch_strides must not be NULL when noise_ptrs is given");
+        for (int l = 0; l < g->num_layers; ++l) {
+            const int64_t r = 1 << ((l + 5) / 2);
+            if (!noise_ptrs_or_null[l]) return gaga_fail(g, ARTALK_EINVAL, "noise_ptrs[" + std::to_string(l) + "] is NULL");
+            if (noise_batch_strides[l] != 0 && noise_batch_strides[l] < r * r)
+                return gaga_fail(g, ARTALK_EINVAL, "noise_batch_strides[" + std::to_string(l) + "] must be 0 or at least " + std::to_string(r * r));
+        }
+    }
+    if (T == 0) return ARTALK_OK;
+    if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
+    hipStream_t s = (hipStream_t)stream;
+    const int V = g->V, N = g->N, S = g->S, NB = g->NB;
+    const long SS = (long)S * S;
+    const int slab = gaga_slab(g);
+    const int frames = T < slab ? T : slab;
+    if (frames > g->cap_frames || N > g->cap_N) {
+        (void)hipDeviceSynchronize();
+        for (float** p : {&g->betas, &g->pose, &g->verts, &g->means, &g->img}) gaga_free(*p);
+        if (g->radii) (void)hipFree(g->radii);
+        g->radii = nullptr; g->cap_frames = g->cap_N = 0;
+        const size_t f = (size_t)frames;
+        void* pr = nullptr;
+        bool ok = true;
+        auto grab = [&](float*& p, size_t n) {
+            void* q = nullptr;
+            if (hipMalloc(&q, n * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); ok = false; q = nullptr; }
+            p = (float*)q;
+        };
+        grab(g->betas, f * NB); grab(g->pose, f * 15); grab(g->verts, f * V * 3); grab(g->means, f * N * 3); grab(g->img, f * kGagaCh * SS);
+        if (hipMalloc(&pr, f * N * sizeof(int32_t)) != hipSuccess) { (void)hipGetLastError(); ok = false; pr = nullptr; }
+        g->radii = (int32_t*)pr;
+        if (!ok) return gaga_fail(g, ARTALK_EHIP, "hipMalloc of the scratch for " + std::to_string(frames) + " frames failed");
+        g->cap_frames = frames; g->cap_N = N;
+    }
+    if (T > g->cap_codes) {
+        (void)hipStreamSynchronize(s);
+        if (g->codes_host) (void)hipHostFree(g->codes_host);
+        g->codes_host = nullptr; g->cap_codes = 0;
+        void* p = nullptr;
+        if (hipHostMalloc(&p, (size_t)T * 3 * sizeof(float), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return gaga_fail(g, ARTALK_EHIP, "hipHostMalloc failed"); }
+        g->codes_host = (float*)p; g->cap_codes = T;
+    }
+    // the first wait of the call: the head-rotation codes become the cameras, which the rasteriser reads on the host
+    if (hipMemcpy2DAsync(g->codes_host, 3 * sizeof(float), motion_dev + 100, (size_t)motion_stride * sizeof(float), 3 * sizeof(float), (size_t)T,
+                         hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        (void)hipGetLastError();
+        return gaga_fail(g, ARTALK_EHIP, "reading the rotation codes failed");
+    }
+    std::vector<float> view((size_t)T * 16), proj((size_t)T * 16);
+    (void)artalk_gaga_cameras(g->codes_host, 3, T, g->transform, view.data(), proj.data(), nullptr);
+
+    std::vector<hipEvent_t> ev;
+    auto mark = [&]() {
+        if (!g->timing) return;
+        hipEvent_t e = nullptr;
+        if (hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, s); ev.push_back(e); }
+    };
+    auto drop_events = [&]() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); ev.clear(); };
+    for (double& m : g->stage_ms) m = 0;
+    std::vector<const float*> np(g->num_layers);
+    const float tanfov = (float)(1.0 / 12.0);
+    for (int f0 = 0; f0 < T; f0 += slab) {
+        const int n = T - f0 < slab ? T - f0 : slab;
+        mark();
+        launch_gaga_flame_inputs(motion_dev + (long)f0 * motion_stride, (long)motion_stride, g->shapecode, NB - 100, g->betas, g->pose, n, s);
+        if (artalk_flame_verts(g->flame, g->betas, g->pose, n, g->verts, s) != ARTALK_OK) {
+            drop_events();
+            return gaga_fail(g, ARTALK_EHIP, std::string("artalk_flame_verts failed: ") + artalk_flame_last_error(g->flame));
+        }
+        mark();
+        if (g->K > 0) launch_gaga_forehead(g->verts, g->index, g->K, n, V, g->state, g->flag, s);
+        launch_gaga_means(g->verts, g->xyz, g->means, n, V, N, s);
+        mark();
+        int rc2 = artalk_splat_render(g->splat, N, n, S, S, g->means, (int64_t)N * 3, g->colors, 0, g->opac, 0, g->scales, 0, g->rots, 0,
+                                      view.data() + (size_t)f0 * 16, proj.data() + (size_t)f0 * 16, n, tanfov, tanfov, 1.0f, nullptr, g->img,
+                                      g->radii, s);
+        if (rc2 != ARTALK_OK) { drop_events(); return gaga_fail(g, rc2, std::string("artalk_splat_render failed: ") + artalk_splat_last_error(g->splat)); }
+        mark();
+        if (noise_ptrs_or_null) for (int l = 0; l < g->num_layers; ++l) np[l] = noise_ptrs_or_null[l] + (long)f0 * noise_batch_strides[l];
+        float* out = out_dev + (long)f0 * 3 * SS;
+        rc2 = artalk_styleunet_forward(g->unet, g->img, n, noise_ptrs_or_null ? np.data() : nullptr, noise_batch_strides, activation, out, s);
+        if (rc2 != ARTALK_OK) { drop_events(); return gaga_fail(g, rc2, std::string("artalk_styleunet_forward failed: ") + artalk_styleunet_last_error(g->unet)); }
+        mark();
+        launch_gaga_finish(out, g->wm, g->wm_h, g->wm_w, S, n, s);
+        mark();
+    }
+    if (g->timing && !ev.empty()) {
+        (void)hipEventSynchronize(ev.back());
+        for (size_t k = 0; k + 1 < ev.size(); ++k) {
+            float ms = 0.f;
+            const int stage = (int)(k % (kGagaStages + 1));
+            if (stage < kGagaStages && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) g->stage_ms[stage] += ms;
+        }
+        drop_events();
+    }
+    if (hipGetLastError() != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "a launch failed");
+    return ARTALK_OK;
+}
+
+// ---- single launches and the host checks, for the tests
+int artalk_op_gaga_flame_inputs(const float* motion_dev, int64_t motion_stride, const float* shapecode_dev, int NB, int T, float* betas_dev,
+                                float* pose_dev, void* stream) {
+    if (!motion_dev || !betas_dev || !pose_dev || T < 1 || NB < 100 || motion_stride < kGagaMotion || (NB > 100 && !shapecode_dev)) return ARTALK_EINVAL;
+    launch_gaga_flame_inputs(motion_dev, (long)motion_stride, shapecode_dev, NB - 100, betas_dev, pose_dev, T, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+
+int artalk_op_gaga_forehead(float* verts_dev, const int32_t* idx_dev, int K, int T, int V, float* state_dev, int* flag_dev, void* stream) {
+    if (!verts_dev || !state_dev || !flag_dev || K < 0 || T < 0 || V < 1 || K > V || (K > 0 && !idx_dev)) return ARTALK_EINVAL;
+    if (K == 0 || T == 0) return ARTALK_OK;
+    launch_gaga_forehead(verts_dev, idx_dev, K, T, V, state_dev, flag_dev, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+
+int artalk_op_gaga_means(const float* verts_dev, const float* xyz_dev, float* means_dev, int F, int V, int N, void* stream) {
+    if (!verts_dev || !xyz_dev || !means_dev || F < 1 || V < 1 || N < V) return ARTALK_EINVAL;
+    launch_gaga_means(verts_dev, xyz_dev, means_dev, F, V, N, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+
+int artalk_op_gaga_finish(float* img_dev, int F, int S, const float* rgba_dev_or_null, int h, int w, void* stream) {
+    if (!img_dev || F < 1 || S < 1 || S > 4096) return ARTALK_EINVAL;
+    if (rgba_dev_or_null && (h < 1 || w < 1 || h > S || w > S)) return ARTALK_EINVAL;
+    launch_gaga_finish(img_dev, rgba_dev_or_null, rgba_dev_or_null ? h : 0, rgba_dev_or_null ? w : 0, S, F, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+
+int artalk_op_gaga_check(int V, int S, int N, const int32_t* idx_host, int K, int wm_h, int wm_w, int T, int64_t motion_stride, int have_avatar,
+                         int unet_finalized, char* msg, int msg_cap) {
+    std::string err;
+    int rc = check_avatar(V, N, &err);
+    if (rc == ARTALK_OK) rc = check_forehead(V, idx_host, K, &err);
+    if (rc == ARTALK_OK && (wm_h != 0 || wm_w != 0)) rc = check_watermark(S, wm_h, wm_w, &err);
+    if (rc == ARTALK_OK) rc = check_render(T, motion_stride, have_avatar != 0, unet_finalized != 0, &err);
+    if (msg && msg_cap > 0) { std::strncpy(msg, err.c_str(), (size_t)msg_cap - 1); msg[msg_cap - 1] = 0; }
+    return rc;
+}
+
+}  // extern "C"

@@ -768,6 +768,16 @@ int artalk_styleunet_set_slab(artalk_styleunet* u, int frames) {
     return u->slab;
 }
 
+int artalk_styleunet_dims(const artalk_styleunet* u, int* in_dim, int* out_dim, int* out_size, int* finalized, int* slab) {
+    if (!u) { g_su_error = "handle is NULL"; return ARTALK_EINVAL; }
+    if (in_dim) *in_dim = u->in_dim;
+    if (out_dim) *out_dim = u->out_dim;
+    if (out_size) *out_size = u->S;
+    if (finalized) *finalized = u->finalized ? 1 : 0;
+    if (slab) *slab = u->slab;
+    return u->device;
+}
+
 int artalk_styleunet_set_timing(artalk_styleunet* u, int enable) {
     if (!u) { g_su_error = "handle is NULL"; return ARTALK_EINVAL; }
     u->timing = enable != 0;

@@ -3,8 +3,9 @@
 Same constructor arguments, attributes and methods as the reference class, so code written against it (the CLI
 at ``inference.py:225-237``, the Gradio handler at ``:99-125``) keeps working for everything up to the FLAME
 codes.  Rendering (``inference.py:59-87``: FLAME mesh / GAGAvatar, PyAV muxing) is downstream of the drop-in
-boundary: ``rendering`` only forwards to the FLAME model and the mesh renderer the caller plugs in
-(``artalk_amd.flame.FLAMEModel``, ``artalk_amd.render.RenderMesh``); GAGAvatar and muxing are out of scope.
+boundary: ``rendering`` only forwards to what the caller plugs in - the FLAME model and the mesh renderer
+(``artalk_amd.flame.FLAMEModel``, ``artalk_amd.render.RenderMesh``) or the GAGAvatar head with its scale-5 FLAME model
+(``artalk_amd.gaga.GAGAvatar``); the identity side of GAGAvatar and muxing are out of scope.
 """
 from __future__ import annotations
 
@@ -23,12 +24,19 @@ from .model import BitwiseARModel
 class ARTAvatarInferEngine:
     def __init__(self, load_gaga=False, fix_pose=False, clip_length=750, device="cuda",
                  ckpt_path="./assets/ARTalk_wav2vec.pt", config_path=None, state_dict=None, config=None, model=None,
-                 calibration=None, precision=None):
+                 calibration=None, precision=None, gaga=None, gaga_flame=None):
         """Arguments of the reference class, plus (all optional): ``state_dict`` / ``config`` instead of a checkpoint file, ``model``
         (an already loaded BitwiseARModel), and ``calibration`` - the f16x3 site scales to start from: a ``save_scales`` file or a
         ``{site: exponent}`` dict (``load_scales``), or a sequence of 16 kHz audio tensors to calibrate on once here (``calibrate``).
         None keeps the model's scales (a checkpoint with outlier activations then recalibrates on its first outlier batch).
-        ``precision``: the GEMM arithmetic (``BitwiseARModel.set_precision``: 'f16x3', 'f32' or 'bf16'); None keeps the model's."""
+        ``precision``: the GEMM arithmetic (``BitwiseARModel.set_precision``: 'f16x3', 'f32' or 'bf16'); None keeps the model's.
+        ``gaga``: an ``artalk_amd.gaga.GAGAvatar`` or the path of an avatar pack (``GAGAvatar.load``), with ``gaga_flame``, an
+        ``artalk_amd.flame.FLAMEModel`` built with ``scale=5.0``: the photoreal head behind ``rendering(shape_id=<avatar id>)``.
+        Both can also be plugged into ``engine.GAGAvatar`` / ``engine.GAGAvatar_flame`` later, like ``flame_model``."""
+        if load_gaga and gaga is None:
+            raise NotImplementedError("load_gaga=True needs gaga=: an artalk_amd.gaga.GAGAvatar or the path of an avatar pack.  The "
+                                      "reference builds its avatars with DINOv2 from torch.hub, which is not part of this package: "
+                                      "export a pack on a machine that runs the reference (INTEGRATION.md section 1d)")
         self.device = device
         self.fix_pose = fix_pose
         self.clip_length = clip_length
@@ -62,8 +70,11 @@ class ARTAvatarInferEngine:
         self.mesh_renderer = None
         self.output_dir = "render_results/ARTAvatar_{}".format(audio_encoder)
         self.style_motion = None
-        if load_gaga:
-            raise NotImplementedError("GAGAvatar rendering is outside the audio->motion path (SURVEY.md section 2, #14)")
+        self.GAGAvatar = None
+        self.GAGAvatar_flame = gaga_flame
+        if gaga is not None:
+            from .gaga import GAGAvatar
+            self.GAGAvatar = gaga if isinstance(gaga, GAGAvatar) else GAGAvatar.load(gaga, device=device)
 
     def set_style_motion(self, style_motion):
         if isinstance(style_motion, str):
@@ -195,6 +206,14 @@ class ARTAvatarInferEngine:
         (``artalk_amd.render.RenderMesh``) it returns what the reference stacks into ``pred_images`` (inference.py:70-72, :83):
         a ``(T, 3, S, S)`` tensor in [0, 1], on the device and from one batched call over all frames (the reference renders frame by
         frame and moves each image to the host).  Writing the video (PyAV muxing) is not part of this package."""
+        head = getattr(self, "GAGAvatar", None)      # (engines assembled without __init__ have no such attribute)
+        if shape_id != "mesh" and head is not None:
+            # inference.py:73-79 in one library call: (T, 3, S, S) in [0, 1] on the device
+            flame = getattr(self, "GAGAvatar_flame", None)
+            if flame is None:
+                raise RuntimeError("plug an artalk_amd.flame.FLAMEModel built with scale=5.0 into engine.GAGAvatar_flame")
+            head.set_avatar_id(shape_id)
+            return head.render_clip(pred_motions, flame)
         if shape_id != "mesh" or self.flame_model is None:
             raise NotImplementedError("rendering is outside the audio->motion path; plug a FLAME model into "
                                       "engine.flame_model to get vertices (and an artalk_amd.render.RenderMesh into "

@@ -1,0 +1,316 @@
+"""Device stand-in for the per-frame half of the reference's ``GAGAvatar`` (``app/GAGAvatar/models.py:63-138``): motion codes in,
+photoreal RGB frames out, from one library call per clip on top of ``artalk_gaga_*`` (``include/artalk_hip.h``, ``csrc/gaga.hip``).
+What is computed is written out in DESIGN.md section 5 ("GAGAvatar head").
+
+The identity half (DINOv2 through ``torch.hub``, the DPT head, the three ``*GSGenerator``s) runs once per avatar and is not built here: its
+result, the avatar's Gaussians, comes in as data - a *pack* exported from a machine that runs the reference.
+There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import capi
+from . import splat as _splat
+from .styleunet import StyleUNet, noise_resolution
+
+FORMAT = "artalk-gaga-avatars/1"
+AVATAR_FIELDS = {"xyz": 3, "colors": 32, "opacities": 1, "scales": 3, "rotations": 4}      # per-Gaussian widths
+PACK_FIELDS = ("format", "upsampler", "water_mark", "n_dynamic", "avatars")
+FOCAL = 12.0
+MOTION_DIM = 106
+
+
+def camera_matrices(rot_codes, transform_matrix):
+    """``artalk_gaga_cameras`` (host only): head-rotation codes (T, 3) and the avatar's (3, 4) ``transform_matrix`` -> (view (T, 4, 4),
+    projection (T, 4, 4), cam (T, 3, 4)).  cam is the frame's ``t_transform``: ``transform_emoca_to_p3d(codes)[:, :3, :3]`` beside the
+    avatar's own translation; view and projection are what ``artalk_amd.splat.build_camera_matrices(cam, 12, 12)`` makes of it.
+    Evaluated in double and rounded once; ``rot_codes`` is not modified."""
+    r = torch.as_tensor(rot_codes).detach().to(dtype=torch.float32, device="cpu").reshape(-1, 3).contiguous()
+    tm = torch.as_tensor(transform_matrix).detach().to(dtype=torch.float32, device="cpu").contiguous()
+    if tuple(tm.shape) != (3, 4):
+        raise ValueError(f"transform_matrix must be (3, 4), got {tuple(tm.shape)}")
+    T = int(r.shape[0])
+    view, proj, cam = torch.empty(T, 4, 4), torch.empty(T, 4, 4), torch.empty(T, 3, 4)
+    L = capi.lib()
+    rc = L.artalk_gaga_cameras(capi.ptr(r), 3, T, capi.ptr(tm), capi.ptr(view), capi.ptr(proj), capi.ptr(cam))
+    if rc != capi.OK:
+        raise ValueError("artalk_gaga_cameras refused: " + L.artalk_gaga_last_error(None).decode())
+    return view, proj, cam
+
+
+def _check_avatar(name, av, n_dynamic):
+    if not isinstance(av, dict):
+        raise ValueError(f"avatar {name!r} must be a dict")
+    for k in tuple(AVATAR_FIELDS) + ("shapecode", "transform_matrix"):
+        if k not in av:
+            raise ValueError(f"avatar {name!r} lacks {k!r}")
+    N = None
+    out = {}
+    for k, width in AVATAR_FIELDS.items():
+        t = torch.as_tensor(av[k]).detach().to(dtype=torch.float32, device="cpu")
+        if t.dim() == 3 and t.shape[0] == 1:      # the reference keeps a batch axis of 1 on _gs_params
+            t = t[0]
+        t = t.reshape(t.shape[0], -1)
+        if t.shape[1] != width:
+            raise ValueError(f"avatar {name!r}: {k} must be (N, {width}), got {tuple(t.shape)}")
+        if N is None:
+            N = int(t.shape[0])
+        if t.shape[0] != N:
+            raise ValueError(f"avatar {name!r}: {k} holds {t.shape[0]} Gaussians, xyz {N}")
+        out[k] = t.contiguous()
+    if N < n_dynamic:
+        raise ValueError(f"avatar {name!r} holds {N} Gaussians, fewer than the {n_dynamic} that ride on the vertices")
+    out["shapecode"] = torch.as_tensor(av["shapecode"]).detach().to(dtype=torch.float32, device="cpu").reshape(-1).contiguous()
+    tm = torch.as_tensor(av["transform_matrix"]).detach().to(dtype=torch.float32, device="cpu")
+    if tuple(tm.shape[-2:]) not in ((3, 4), (4, 4)):
+        raise ValueError(f"avatar {name!r}: transform_matrix must be (3, 4), got {tuple(tm.shape)}")
+    out["transform_matrix"] = tm.reshape(-1, tm.shape[-2], 4)[0][:3].contiguous()
+    return out
+
+
+class GAGAvatar:
+    """``GAGAvatar(avatars, upsampler, water_mark=None, image_size=512, n_dynamic=5023, forehead_indices=None, device="cuda")``.
+
+    ``avatars``: ``{id: {"xyz", "colors", "opacities", "scales", "rotations", "shapecode", "transform_matrix"}}`` - an identity's
+    ``_gs_params`` after the reference's first ``forward_expression`` and its tracked ``shapecode`` / ``transform_matrix``.
+    ``upsampler``: an ``artalk_amd.styleunet.StyleUNet`` or its state dict.  ``water_mark``: a ``(4, h, w)`` RGBA tensor in [0, 1]
+    already at its final size (the reference resizes its logo to 82 x 256 with torchvision's antialiased resize: the exporter's job).
+    ``forehead_indices``: None = the reference's 68 vertices when the FLAME model has more than 3913, else none.
+
+    The device is first touched by ``render_clip``.  The forehead EMA state lives in the library object and survives clips and
+    ``set_avatar_id``, as ``upper_points`` does in the reference; ``reset_motion_state`` (ours) unsets it."""
+
+    def __init__(self, avatars, upsampler, water_mark=None, image_size=512, n_dynamic=5023, forehead_indices=None, device="cuda"):
+        self.image_size, self.n_dynamic = int(image_size), int(n_dynamic)
+        self.device = torch.device(device)
+        if not isinstance(avatars, dict) or not avatars:
+            raise ValueError("avatars must be a non-empty dict")
+        self.all_gagavatar_id = {k: _check_avatar(k, v, self.n_dynamic) for k, v in avatars.items()}
+        if isinstance(upsampler, StyleUNet):
+            if upsampler.out_size != self.image_size or upsampler.in_dim != 32 or upsampler.out_dim != 3:
+                raise ValueError(f"the upsampler must map 32 channels to 3 at {self.image_size} x {self.image_size}")
+            self.upsampler, self._upsampler_sd = upsampler, None
+        else:
+            self._upsampler_sd = dict(upsampler)
+            self.upsampler = StyleUNet(self.image_size, self.image_size, 32, 3)
+            self.upsampler.load_state_dict(self._upsampler_sd)      # names and shapes are checked here; the upload waits for the device
+        if water_mark is not None:
+            water_mark = torch.as_tensor(water_mark).detach().to(dtype=torch.float32, device="cpu").contiguous()
+            if water_mark.dim() != 3 or water_mark.shape[0] != 4:
+                raise ValueError(f"water_mark must be (4, h, w), got {tuple(water_mark.shape)}")
+            if water_mark.shape[1] > self.image_size or water_mark.shape[2] > self.image_size:
+                raise ValueError(f"a water_mark of {tuple(water_mark.shape[1:])} does not fit the {self.image_size} x {self.image_size} image")
+        self._water_mark = water_mark
+        if forehead_indices is not None:
+            forehead_indices = [int(i) for i in forehead_indices]
+            if len(set(forehead_indices)) != len(forehead_indices):
+                raise ValueError("forehead_indices lists a vertex twice")
+            if any(i < 0 or i >= self.n_dynamic for i in forehead_indices):
+                raise ValueError(f"forehead_indices must lie in [0, {self.n_dynamic})")
+        self.forehead_indices = forehead_indices
+        self.cam_params = {"focal_x": FOCAL, "focal_y": FOCAL, "size": [self.image_size, self.image_size]}
+        self._h = None
+        self._flame = None          # the FLAMEModel the library object borrows
+        self._tracked_name = None
+        self._uploaded = None       # id of the avatar the library object holds
+        self._index, self._borrowed = None, None
+        self._slab = 0
+
+    # ---- packs ----
+    @classmethod
+    def load(cls, path, device="cuda", forehead_indices=None):
+        pack = torch.load(path, map_location="cpu", weights_only=True)
+        if not isinstance(pack, dict) or pack.get("format") != FORMAT:
+            got = pack.get("format") if isinstance(pack, dict) else type(pack).__name__
+            raise ValueError(f"{path}: not an avatar pack of format {FORMAT!r} (found {got!r})")
+        missing = [k for k in PACK_FIELDS if k not in pack]
+        if missing:
+            raise ValueError(f"{path}: the pack lacks {', '.join(missing)}")
+        wm = pack["water_mark"]
+        size = int(pack.get("image_size", 512))
+        return cls(pack["avatars"], pack["upsampler"], water_mark=wm, image_size=size, n_dynamic=int(pack["n_dynamic"]),
+                   forehead_indices=forehead_indices, device=device)
+
+    def save(self, path):
+        if self._upsampler_sd is None:
+            raise RuntimeError("this head was built around a loaded StyleUNet: construct it from the state dict to save a pack")
+        torch.save({"format": FORMAT, "upsampler": self._upsampler_sd, "water_mark": self._water_mark, "n_dynamic": self.n_dynamic,
+                    "image_size": self.image_size, "avatars": self.all_gagavatar_id}, path)
+
+    # ---- torch.nn.Module look-alikes ----
+    def eval(self):
+        return self
+
+    def to(self, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("GAGAvatar runs on the GPU only (there is no CPU fallback)")
+        if self._h is not None and (device.index or 0) != (self.device.index or 0):
+            raise RuntimeError(f"the head lives on {self.device}: build a new one for {device}")
+        self.device = device
+        return self
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+    def _release(self):
+        if self._h is not None:
+            capi.lib().artalk_gaga_destroy(self._h)
+            self._h = None
+
+    def _err(self):
+        return capi.lib().artalk_gaga_last_error(self._h).decode()
+
+    # ---- the reference's methods ----
+    def set_avatar_id(self, avatar_id):
+        self.all_gagavatar_id[avatar_id]      # KeyError for an unknown id, like the reference's dict lookup
+        self._tracked_name = avatar_id
+
+    def reset_motion_state(self):
+        """Unset the forehead EMA: the next frame is taken as it is, like the reference's very first frame."""
+        if self._h is not None:
+            rc = capi.lib().artalk_gaga_reset_state(self._h)
+            if rc != capi.OK:
+                raise RuntimeError("artalk_gaga_reset_state failed: " + self._err())
+
+    def set_slab(self, frames):
+        """Frames per pass over the head's scratch (0: the default, what fits 512 MiB); never more than the upsampler's slab in force.
+        Returns the request before the device is touched, the value in force afterwards."""
+        frames = int(frames)
+        if frames < 0 or frames > 64:
+            raise ValueError("slab must be in 0..64 frames (0: the default)")
+        self._slab = frames
+        if self._h is None:
+            return frames
+        return int(capi.lib().artalk_gaga_set_slab(self._h, frames))
+
+    def build_forward_batch(self, motion_code, flame_model):
+        """The reference's two-step form.  The batch here is a handle for ``forward_expression``: the motion rows (a copy: unlike the
+        reference, ``motion_code`` is not modified), the FLAME model and ``t_transform`` (T, 3, 4), the per-frame cameras.  The vertices
+        and the forehead EMA are produced inside the library call that ``forward_expression`` makes, so the EMA advances there."""
+        if self._tracked_name is None:
+            self.set_avatar_id("11.jpg" if "11.jpg" in self.all_gagavatar_id else next(iter(self.all_gagavatar_id)))
+        motion_code = self._check_motion(motion_code)
+        tm = self.all_gagavatar_id[self._tracked_name]["transform_matrix"]
+        return {"motion_code": motion_code.clone(), "flame_model": flame_model,
+                "t_transform": camera_matrices(motion_code[:, 100:103].cpu(), tm)[2].to(motion_code.device)}
+
+    def forward_expression(self, batch, randomize_noise=True, noise=None):
+        return self.render_clip(batch["motion_code"], batch["flame_model"], randomize_noise=randomize_noise, noise=noise)
+
+    # ---- the fast path ----
+    @staticmethod
+    def _check_motion(motion_codes):
+        if not isinstance(motion_codes, torch.Tensor) or motion_codes.dim() != 2 or motion_codes.shape[1] < MOTION_DIM:
+            raise ValueError(f"motion_codes must be a (T, {MOTION_DIM}) tensor")
+        if not motion_codes.is_cuda:
+            raise RuntimeError("GAGAvatar runs on the GPU: motion_codes must be a CUDA tensor (there is no CPU fallback)")
+        return motion_codes
+
+    def _ensure(self, flame_model):
+        L = capi.lib()
+        if self._h is not None:
+            # the library object borrows three handles: another FLAME model, reloaded upsampler weights or released splat buffers
+            # mean a new object (and a new EMA state)
+            borrowed = (getattr(flame_model, "_h", None), self.upsampler._h, _splat._handles.get(self._index))
+            if self._flame is not flame_model or [b.value if b is not None else None for b in borrowed] != self._borrowed:
+                self._release()
+        if self._h is None:
+            if getattr(flame_model, "_h", None) is None:
+                raise ValueError("flame_model must be an artalk_amd.flame.FLAMEModel")
+            if abs(float(flame_model.scale) - 5.0) > 0:
+                raise ValueError(f"the GAGAvatar head skins at scale 5 (models.py: FLAMEModel(scale=5.0)); this FLAME model has scale {flame_model.scale}")
+            if flame_model.n_verts != self.n_dynamic:
+                raise ValueError(f"the FLAME model has {flame_model.n_verts} vertices, the pack's avatars {self.n_dynamic} dynamic Gaussians")
+            dev = self.device
+            idx = dev.index if dev.index is not None else torch.cuda.current_device()
+            with torch.cuda.device(idx):
+                self.upsampler.to(torch.device("cuda", idx))
+                if not self.upsampler._loaded:
+                    raise RuntimeError("the upsampler has no weights: load_state_dict first")
+                h = C.c_void_p()
+                rc = L.artalk_gaga_create(int(idx), flame_model._h, _splat._handle(torch.device("cuda", idx)), self.upsampler._h,
+                                          int(flame_model.n_verts), int(flame_model.n_betas), self.image_size, C.byref(h))
+                if rc != capi.OK:
+                    raise ValueError("artalk_gaga_create refused: " + L.artalk_gaga_last_error(None).decode())
+                self._h, self._flame, self._uploaded, self._index = h, flame_model, None, int(idx)
+                self._borrowed = [flame_model._h.value, self.upsampler._h.value, _splat._handles[int(idx)].value]
+                if self.forehead_indices is not None:
+                    arr = (C.c_int32 * max(len(self.forehead_indices), 1))(*self.forehead_indices)
+                    if L.artalk_gaga_set_forehead(h, arr, len(self.forehead_indices)) != capi.OK:
+                        raise ValueError("artalk_gaga_set_forehead refused: " + self._err())
+                if self._water_mark is not None:
+                    wm = self._water_mark
+                    if L.artalk_gaga_set_watermark(h, capi.ptr(wm), int(wm.shape[1]), int(wm.shape[2])) != capi.OK:
+                        raise ValueError("artalk_gaga_set_watermark refused: " + self._err())
+                if L.artalk_gaga_set_slab(h, self._slab) < 0:
+                    raise ValueError("artalk_gaga_set_slab refused: " + self._err())
+        if self._tracked_name is None:
+            self.set_avatar_id("11.jpg" if "11.jpg" in self.all_gagavatar_id else next(iter(self.all_gagavatar_id)))
+        if self._uploaded != self._tracked_name:
+            av = self.all_gagavatar_id[self._tracked_name]
+            if av["shapecode"].numel() != flame_model.n_betas - 100:
+                raise ValueError(f"avatar {self._tracked_name!r}: shapecode holds {av['shapecode'].numel()} values, the FLAME model "
+                                 f"takes {flame_model.n_betas - 100}")
+            rc = L.artalk_gaga_set_avatar(self._h, int(av["xyz"].shape[0]), capi.ptr(av["xyz"]), capi.ptr(av["colors"]), capi.ptr(av["opacities"]),
+                                          capi.ptr(av["scales"]), capi.ptr(av["rotations"]), capi.ptr(av["shapecode"]),
+                                          capi.ptr(av["transform_matrix"]))
+            if rc != capi.OK:
+                raise ValueError("artalk_gaga_set_avatar refused: " + self._err())
+            self._uploaded = self._tracked_name
+
+    def slab_in_force(self):
+        return None if self._h is None else int(capi.lib().artalk_gaga_set_slab(self._h, self._slab))
+
+    @torch.no_grad()
+    def render_clip(self, motion_codes, flame_model, randomize_noise=True, noise=None):
+        """motion_codes (T, 106) on the device -> (T, 3, S, S) in [0, 1] on the device, from one library call.  ``flame_model``: an
+        ``artalk_amd.flame.FLAMEModel`` built with ``scale=5.0``.  Unlike the reference, ``motion_codes`` is NOT modified (there
+        ``transform_emoca_to_p3d`` flips the sign of columns 100 and 102 in place through a view).  ``randomize_noise=True`` draws the
+        StyleGAN noise with torch's generator once per slab (the reference: once per frame); ``False`` uses the stored buffers;
+        ``noise`` - per layer a device tensor (T or 1, 1, r, r) - overrides both."""
+        m = self._check_motion(motion_codes)
+        if (m.device.index or 0) != (self.device.index if self.device.index is not None else torch.cuda.current_device()):
+            raise RuntimeError(f"motion_codes lives on {m.device}, the head on {self.device}")
+        m = m.detach()
+        if m.dtype != torch.float32 or m.stride(1) != 1 or (m.shape[0] > 1 and m.stride(0) < m.shape[1]):
+            m = m.float().contiguous()
+        T = int(m.shape[0])
+        stride = int(m.stride(0)) if T > 1 else int(m.shape[1])
+        S, nl = self.image_size, self.upsampler.num_layers
+        out = torch.empty(T, 3, S, S, dtype=torch.float32, device=m.device)
+        L = capi.lib()
+        with torch.cuda.device(m.device):
+            self._ensure(flame_model)
+            if T == 0:
+                return out
+            if noise is None and randomize_noise:
+                slab = self.slab_in_force()
+                parts = [[torch.empty(min(slab, T - f0), 1, noise_resolution(i), noise_resolution(i), device=m.device).normal_()
+                          for i in range(nl)] for f0 in range(0, T, slab)]
+                noise = [torch.cat([p[i] for p in parts]) for i in range(nl)]
+            ptrs = strides = None
+            if noise is not None:
+                if len(noise) != nl:
+                    raise ValueError(f"noise must hold {nl} tensors")
+                keep = []
+                for i, n in enumerate(noise):
+                    r = noise_resolution(i)
+                    if not n.is_cuda or tuple(n.shape[1:]) != (1, r, r) or n.shape[0] not in (1, T):
+                        raise ValueError(f"noise[{i}] must be a CUDA tensor of shape (1 or {T}, 1, {r}, {r})")
+                    keep.append(n.detach().float().contiguous())
+                ptrs = (C.c_void_p * nl)(*[t.data_ptr() for t in keep])
+                strides = (C.c_int64 * nl)(*[0 if t.shape[0] == 1 else t.shape[2] * t.shape[3] for t in keep])
+            rc = L.artalk_gaga_render(self._h, capi.ptr(m), stride, T, ptrs, strides, int(self.upsampler.activation), capi.ptr(out),
+                                      capi.current_stream_ptr())
+        if rc == capi.EINVAL:
+            raise ValueError("artalk_gaga_render refused: " + self._err())
+        if rc != capi.OK:
+            raise RuntimeError("artalk_gaga_render failed: " + self._err())
+        return out

@@ -300,6 +300,68 @@ int artalk_op_conv2d(const float* x, int64_t x_bstride, const float* w, float* o
                      const float* residual, void* stream);
 int artalk_op_resample2(const float* x, float* out, int B, int H, int W, int C, int up, void* stream);
 
+/* Read-only views of a handle, for objects that borrow it (artalk_gaga below).  Both return the handle's device index, or ARTALK_EINVAL for
+ * a NULL handle; every out pointer may be NULL.  artalk_styleunet_dims: *finalized is 1 after artalk_styleunet_finalize, *slab is the
+ * slab in force. */
+int artalk_flame_dims(const artalk_flame* f, int* V, int* NB, float* scale);
+int artalk_styleunet_dims(const artalk_styleunet* u, int* in_dim, int* out_dim, int* out_size, int* finalized, int* slab);
+
+/* The per-frame path of the GAGAvatar head: motion codes -> RGB frames, a stand-in for GAGAvatar.build_forward_batch + forward_expression
+ * (app/GAGAvatar/models.py:63-138).  What is computed is defined in DESIGN.md section 5 ("GAGAvatar head").  The identity side (DINOv2, the
+ * Gaussian generators) runs once per avatar elsewhere; its result, the avatar's Gaussians, comes in as data.
+ * artalk_gaga_create: borrows a FLAME handle (V vertices, NB betas, built with scale 5), a splat rasteriser and a StyleUNet (32 -> 3 channels
+ * at S x S), all on `device_id` and all outliving this object.  ARTALK_EINVAL with a message (artalk_gaga_last_error(NULL)) for a NULL handle
+ * or out, NB < 100, or V / NB / S that are not the borrowed handles'.  With V > 3913 the forehead indices are the reference's 68.
+ * artalk_gaga_set_avatar: host fp32 arrays xyz [N][3] (its first V rows are ignored: those Gaussians ride on the vertices), colors [N][32],
+ * opacities [N], scales [N][3], rotations [N][4], shapecode [NB - 100], transform [3][4] = [R | t]; uploaded once.  N >= V.  The EMA state
+ * is NOT touched (the reference's set_avatar_id does not touch it either).
+ * artalk_gaga_set_forehead: K distinct vertex indices in [0, V) whose positions are smoothed over frames (state = 0.98 state + 0.02
+ * current, the first frame ever taken as it is); K = 0 switches the smoothing off.  Resets the state.  artalk_gaga_reset_state unsets it.
+ * artalk_gaga_set_watermark: host rgba [4][h][w] with h, w <= S, blended into the bottom-right corner (p = p (1 - 0.8 alpha) + rgb 0.8 alpha);
+ * NULL removes it.
+ * artalk_gaga_set_slab: frames per pass over the head's own scratch (means, radii, splat image, vertices); 0 = the default, what fits
+ * 512 MiB, at most 64.  The value in force, which is returned, is never larger than the StyleUNet's slab in force.
+ * artalk_gaga_render: motion_dev [T][>= 106] device fp32 with motion_stride elements between rows (not modified) -> out_dev [T][3][S][S]
+ * in [0, 1].  Per slab: FLAME inputs -> artalk_flame_verts -> forehead EMA -> means -> artalk_splat_render (per-frame cameras from
+ * artalk_gaga_cameras, the avatar's attributes shared by all frames, zero background, tanfov 1 / 12) -> artalk_styleunet_forward
+ * (activation and noise arguments as there; the slab's slice of a per-frame noise) -> clamp and watermark.  WAITS on `stream` once for the
+ * T head-rotation codes (the cameras are built on the host), and the splat call waits once more in every slab; the scratch grows
+ * (and waits) on the first call of a size.  Bit-identical from run to run and for any split of the frames over slabs and calls (the EMA
+ * state carries over).  T == 0 succeeds and does nothing.  ARTALK_EINVAL with a message before the device is touched: a NULL handle, motion
+ * or out, T < 0, motion_stride < 106, no avatar set, a bad noise argument; ARTALK_ESTATE: the upsampler is not finalized.
+ * artalk_gaga_set_timing / get_timing (tools/gaga_bench.py): with timing on a call records HIP events around its stages and waits at its
+ * end; get_timing copies up to n of the 5 per-stage sums in ms (inputs + FLAME, forehead + means, splat, upsampler, finish), returns 5.
+ * artalk_gaga_cameras (host only): T rotation codes (rot_stride >= 3 floats apart) and the avatar's transform -> view_out / proj_out
+ * [T][16] as artalk_splat_render reads them, and cam_out_or_null [T][12] = the frame's [M | t] with M = diag(-1, 1, -1) . exp([w]x)^T,
+ * w = (-r0, r1, -r2), t the avatar's own; evaluated in double, rounded once.
+ * artalk_op_gaga_*: one launch of one kernel on device arrays.  flame_inputs: -> betas [T][NB], pose [T][15].  forehead: verts [T][V][3] in
+ * place, idx [K], state [K][3] and *flag in / out.  means: verts [F][V][3], xyz [N][3] -> means [F][N][3].  finish: img [F][3][S][S] in
+ * place, rgba [4][h][w] or NULL.  artalk_op_gaga_check (host only): the checks of set_avatar, set_forehead, set_watermark (skipped when
+ * wm_h = wm_w = 0) and render, in this order, on plain numbers; returns the first failing code and copies its message. */
+typedef struct artalk_gaga artalk_gaga;
+int artalk_gaga_create(int device_id, artalk_flame* flame, artalk_splat* splat, artalk_styleunet* unet, int V, int NB, int S, artalk_gaga** out);
+int artalk_gaga_set_avatar(artalk_gaga* g, int N, const float* xyz, const float* colors, const float* opacities, const float* scales,
+                           const float* rotations, const float* shapecode, const float* transform_3x4);
+int artalk_gaga_set_forehead(artalk_gaga* g, const int32_t* idx, int K);
+int artalk_gaga_set_watermark(artalk_gaga* g, const float* rgba_host, int h, int w);
+int artalk_gaga_reset_state(artalk_gaga* g);
+int artalk_gaga_set_slab(artalk_gaga* g, int frames);
+int artalk_gaga_render(artalk_gaga* g, const float* motion_dev, int64_t motion_stride, int T, const float* const* noise_ptrs_or_null,
+                       const int64_t* noise_batch_strides, int activation, float* out_dev, void* stream);
+int artalk_gaga_set_timing(artalk_gaga* g, int enable);
+int artalk_gaga_get_timing(const artalk_gaga* g, double* stage_ms, int n);
+void artalk_gaga_destroy(artalk_gaga* g);
+const char* artalk_gaga_last_error(const artalk_gaga* g);
+int artalk_gaga_cameras(const float* rot_host, int64_t rot_stride, int T, const float* transform_3x4_host, float* view_out, float* proj_out,
+                        float* cam_out_or_null);
+int artalk_op_gaga_flame_inputs(const float* motion_dev, int64_t motion_stride, const float* shapecode_dev, int NB, int T, float* betas_dev,
+                                float* pose_dev, void* stream);
+int artalk_op_gaga_forehead(float* verts_dev, const int32_t* idx_dev, int K, int T, int V, float* state_dev, int* flag_dev, void* stream);
+int artalk_op_gaga_means(const float* verts_dev, const float* xyz_dev, float* means_dev, int F, int V, int N, void* stream);
+int artalk_op_gaga_finish(float* img_dev, int F, int S, const float* rgba_dev_or_null, int h, int w, void* stream);
+int artalk_op_gaga_check(int V, int S, int N, const int32_t* idx_host, int K, int wm_h, int wm_w, int T, int64_t motion_stride, int have_avatar,
+                         int unet_finalized, char* msg, int msg_cap);
+
 /* Numerical health of the work enqueued since the last artalk_infer / artalk_stream_begin started.  Every call ends with an
  * asynchronous copy of the device status word to pinned host memory.  artalk_get_status WAITS for that copy (an event wait:
  * the one synchronisation on this boundary, paid only by callers that ask; `stream` is ignored); artalk_poll_status never
