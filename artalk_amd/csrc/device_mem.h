@@ -1,0 +1,120 @@
+// Owners of what the host side takes from the HIP runtime: device blocks, pinned host blocks, events, the events of a stage timer.
+// Host code only.  Every type is move-only, takes nothing in its constructor and gives back what it holds in its destructor, so an
+// object made of them is destroyed by `delete` and an early return leaks nothing.  A call that fails leaves its object empty
+// (capacity 0), clears the runtime's last error - the caller reports the failure once, and it does not come back from a later
+// hipGetLastError() as a failed launch - and returns false.  Private to csrc/.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <memory>
+#include <type_traits>
+#include <utility>
+#include <vector>
+
+namespace artalk {
+
+// One block of T, in device memory or (kPinned) in pinned host memory.  A request for 0 elements takes 1.
+template <typename T, bool kPinned>
+class Block {
+public:
+    T* get() const { return p_.get(); }
+    size_t capacity() const { return p_ ? cap_ : 0; }      // elements
+    void reset() { p_.reset(); }
+    bool alloc(size_t n) { return take((n ? n : 1) * sizeof(T)); }
+    // bytes that grow(n, slack_num, slack_den, ..) asks for: n elements and slack_num / slack_den of them on top
+    static size_t grown_bytes(size_t n, size_t slack_num, size_t slack_den) { return (n ? n : 1) * sizeof(T) * (slack_den + slack_num) / slack_den; }
+    // Nothing when n fits.  Else: wait for `wait`, the stream whose earlier work may still read the block, free it, and take n
+    // elements plus the slack (the contents are not kept).
+    bool grow(size_t n, size_t slack_num, size_t slack_den, hipStream_t wait) {
+        if (p_ && n <= cap_) return true;
+        if (p_) (void)hipStreamSynchronize(wait);
+        return take(grown_bytes(n, slack_num, slack_den));
+    }
+
+private:
+    bool take(size_t bytes) {
+        reset();
+        void* p = nullptr;
+        if ((kPinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes)) != hipSuccess) { (void)hipGetLastError(); return false; }
+        p_.reset(static_cast<T*>(p)); cap_ = bytes / sizeof(T);
+        return true;
+    }
+    struct Free { void operator()(T* p) const { if (kPinned) (void)hipHostFree(p); else (void)hipFree(p); } };
+    std::unique_ptr<T, Free> p_;
+    size_t cap_ = 0;
+};
+
+template <typename T>
+using PinnedBuf = Block<T, true>;
+
+template <typename T>
+class DevBuf : public Block<T, false> {
+public:
+    bool alloc_zero(size_t n) {      // the fill runs on the null stream
+        if (!this->alloc(n)) return false;
+        (void)hipMemset(this->get(), 0, (n ? n : 1) * sizeof(T));
+        return true;
+    }
+    bool upload(const T* host, size_t n) {
+        return this->alloc(n) && (n == 0 || hipMemcpy(this->get(), host, n * sizeof(T), hipMemcpyHostToDevice) == hipSuccess);
+    }
+};
+
+class Event {
+public:
+    hipEvent_t get() const { return e_.get(); }
+    void reset() { e_.reset(); }
+    bool create() {
+        if (e_) return true;
+        hipEvent_t e = nullptr;
+        if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); return false; }
+        e_.reset(e);
+        return true;
+    }
+
+private:
+    struct Destroy { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
+    std::unique_ptr<std::remove_pointer_t<hipEvent_t>, Destroy> e_;
+};
+
+// Time per stage of one call, from events on the call's stream: the interval that ENDS at a mark belongs to the mark's stage
+// (stage < 0: to none).  A mark whose event cannot be made is skipped.  Disabled, no method makes a HIP call.
+class StageTimer {
+public:
+    void start(hipStream_t s, bool enabled) { s_ = s; on_ = enabled; ev_.clear(); stage_.clear(); }
+    void mark(int stage) {
+        Event e;
+        if (!on_ || !e.create()) return;
+        (void)hipEventRecord(e.get(), s_);
+        ev_.push_back(std::move(e)); stage_.push_back(stage);
+    }
+    // waits for the last mark, then adds every interval to stage_ms[its stage] (n stages)
+    void finish(double* stage_ms, int n) {
+        if (!ev_.empty()) (void)hipEventSynchronize(ev_.back().get());
+        for (size_t k = 1; k < ev_.size(); ++k) {
+            float ms = 0.f;
+            if (stage_[k] >= 0 && stage_[k] < n && hipEventElapsedTime(&ms, ev_[k - 1].get(), ev_[k].get()) == hipSuccess) stage_ms[stage_[k]] += ms;
+        }
+        ev_.clear(); stage_.clear();
+    }
+
+private:
+    hipStream_t s_ = nullptr;
+    bool on_ = false;
+    std::vector<Event> ev_;      // ev_[k] closes an interval of stage stage_[k]
+    std::vector<int> stage_;
+};
+
+// zero-filled device block whose pointer goes into `pool` (a null entry records a failure): the engine's weight and workspace pools
+template <typename T>
+T* dalloc_in(std::vector<void*>& pool, int64_t n) {
+    void* p = nullptr;
+    if (n <= 0) n = 1;
+    if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) { pool.push_back(nullptr); return nullptr; }
+    (void)hipMemset(p, 0, n * sizeof(T));
+    pool.push_back(p);
+    return reinterpret_cast<T*>(p);
+}
+
+}  // namespace artalk

@@ -8,7 +8,8 @@
 //   verts    = (sum_j w_vj A_j) [v_posed, 1]                   (lbs.py:216-231)                  -> flame_skin_kernel
 // The C ABI of the vertex path (artalk_flame_*) follows the kernels.
 #include "common.h"
-#include "model.h"
+#include "device_mem.h"
+#include "../../include/artalk_hip.h"
 
 namespace artalk {
 
@@ -143,10 +144,9 @@ using namespace artalk;
 struct artalk_flame {
     int device = 0, V = 0, NB = 0, NBp = 0, P = 0, Pp = 0, cap = 0;
     float scale = 1.f;
-    float *v_template = nullptr, *shapedirs = nullptr, *posedirs = nullptr, *jreg = nullptr, *weights = nullptr;
-    int* parents = nullptr;
-    float *betas = nullptr, *feat = nullptr, *rot = nullptr, *J = nullptr, *vshaped = nullptr, *vposed = nullptr;
-    std::vector<void*> allocs, ws;
+    DevBuf<float> v_template, shapedirs, posedirs, jreg, weights;
+    DevBuf<int> parents;
+    DevBuf<float> betas, feat, rot, J, vshaped, vposed;      // scratch of `cap` frames
     std::string err;
 };
 
@@ -160,8 +160,6 @@ void artalk_flame_destroy(artalk_flame* f) {
     if (!f) return;
     (void)hipSetDevice(f->device);
     (void)hipDeviceSynchronize();
-    for (void* p : f->allocs) if (p) (void)hipFree(p);
-    for (void* p : f->ws) if (p) (void)hipFree(p);
     delete f;
 }
 
@@ -180,21 +178,19 @@ int artalk_flame_create(int device_id, int V, int NB, int P, const float* v_temp
     artalk_flame* f = new artalk_flame();
     f->device = device_id; f->V = V; f->NB = NB; f->P = P; f->scale = scale;
     f->NBp = (NB + 31) / 32 * 32; f->Pp = 64;
-    auto up = [&](const float* h, int64_t rows, int64_t cols, int64_t cols_pad) -> float* {
-        float* d = dalloc_in<float>(f->allocs, rows * cols_pad);
-        if (!d) return nullptr;
-        if (cols == cols_pad) { (void)hipMemcpy(d, h, rows * cols * 4, hipMemcpyHostToDevice); }
-        else (void)hipMemcpy2D(d, cols_pad * 4, h, cols * 4, cols * 4, rows, hipMemcpyHostToDevice);
-        return d;
+    auto up = [&](DevBuf<float>& d, const float* h, int64_t rows, int64_t cols, int64_t cols_pad) {      // pad columns stay zero
+        if (!d.alloc_zero(rows * cols_pad)) return false;
+        if (cols == cols_pad) { (void)hipMemcpy(d.get(), h, rows * cols * 4, hipMemcpyHostToDevice); }
+        else (void)hipMemcpy2D(d.get(), cols_pad * 4, h, cols * 4, cols * 4, rows, hipMemcpyHostToDevice);
+        return true;
     };
-    f->v_template = up(v_template, 1, (int64_t)V * 3, (int64_t)V * 3);
-    f->shapedirs = up(shapedirs, (int64_t)V * 3, NB, f->NBp);       // GEMM weight [N = 3V][K = NB padded]
-    f->posedirs = up(posedirs_t, (int64_t)V * 3, P, f->Pp);
-    f->jreg = up(J_regressor, 5, V, V);
-    f->weights = up(lbs_weights, V, 5, 5);
-    f->parents = dalloc_in<int>(f->allocs, 5);
-    for (void* p : f->allocs) if (!p) { g_flame_error = "hipMalloc failed"; artalk_flame_destroy(f); return ARTALK_EHIP; }
-    (void)hipMemcpy(f->parents, parents, 5 * sizeof(int), hipMemcpyHostToDevice);
+    if (!up(f->v_template, v_template, 1, (int64_t)V * 3, (int64_t)V * 3) ||
+        !up(f->shapedirs, shapedirs, (int64_t)V * 3, NB, f->NBp) ||       // GEMM weight [N = 3V][K = NB padded]
+        !up(f->posedirs, posedirs_t, (int64_t)V * 3, P, f->Pp) || !up(f->jreg, J_regressor, 5, V, V) || !up(f->weights, lbs_weights, V, 5, 5) ||
+        !f->parents.alloc_zero(5)) {
+        g_flame_error = "hipMalloc failed"; artalk_flame_destroy(f); return ARTALK_EHIP;
+    }
+    (void)hipMemcpy(f->parents.get(), parents, 5 * sizeof(int), hipMemcpyHostToDevice);
     if (hipDeviceSynchronize() != hipSuccess) { g_flame_error = "upload failed"; artalk_flame_destroy(f); return ARTALK_EHIP; }
     *out = f;
     return ARTALK_OK;
@@ -216,35 +212,33 @@ int artalk_flame_verts(artalk_flame* f, const float* betas_dev, const float* ful
     hipStream_t s = (hipStream_t)stream;
     if (T > f->cap) {
         (void)hipDeviceSynchronize();
-        for (void* p : f->ws) if (p) (void)hipFree(p);
-        f->ws.clear();
+        f->cap = 0;
+        for (DevBuf<float>* b : {&f->betas, &f->feat, &f->rot, &f->J, &f->vshaped, &f->vposed}) b->reset();
         const int64_t N = (int64_t)f->V * 3;
-        f->betas = dalloc_in<float>(f->ws, (int64_t)T * f->NBp);
-        f->feat = dalloc_in<float>(f->ws, (int64_t)T * f->Pp);
-        f->rot = dalloc_in<float>(f->ws, (int64_t)T * 45);
-        f->J = dalloc_in<float>(f->ws, (int64_t)T * 15);
-        f->vshaped = dalloc_in<float>(f->ws, T * N);
-        f->vposed = dalloc_in<float>(f->ws, T * N);
-        for (void* p : f->ws) if (!p) { f->err = "hipMalloc failed"; f->cap = 0; return ARTALK_EHIP; }
+        if (!f->betas.alloc_zero((int64_t)T * f->NBp) || !f->feat.alloc_zero((int64_t)T * f->Pp) || !f->rot.alloc_zero((int64_t)T * 45) ||
+            !f->J.alloc_zero((int64_t)T * 15) || !f->vshaped.alloc_zero(T * N) || !f->vposed.alloc_zero(T * N)) {
+            f->err = "hipMalloc failed"; return ARTALK_EHIP;
+        }
         (void)hipDeviceSynchronize();   // zero fills run on the null stream
         f->cap = T;
     }
     const int N = f->V * 3;
+    float *betas = f->betas.get(), *feat = f->feat.get(), *rot = f->rot.get(), *J = f->J.get(), *vshaped = f->vshaped.get(), *vposed = f->vposed.get();
     // betas into the K-padded GEMM operand (pad columns stay zero from allocation)
-    if (hipMemcpy2DAsync(f->betas, (size_t)f->NBp * 4, betas_dev, (size_t)f->NB * 4, (size_t)f->NB * 4, T, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+    if (hipMemcpy2DAsync(betas, (size_t)f->NBp * 4, betas_dev, (size_t)f->NB * 4, (size_t)f->NB * 4, T, hipMemcpyDeviceToDevice, s) != hipSuccess) {
         f->err = "copy failed"; return ARTALK_EHIP;
     }
     GemmArgs g;     // v_shaped = v_template + betas . shapedirs^T      (exact fp32 MFMA)
-    g.A = f->betas; g.lda = f->NBp; g.W = f->shapedirs; g.ldw = f->NBp; g.C = f->vshaped; g.ldc = N; g.R = f->v_template; g.ldr = 0;
+    g.A = betas; g.lda = f->NBp; g.W = f->shapedirs.get(); g.ldw = f->NBp; g.C = vshaped; g.ldc = N; g.R = f->v_template.get(); g.ldr = 0;
     g.M = T; g.N = N; g.K = f->NBp;
     launch_gemm(g, s);
-    launch_flame_joints(f->vshaped, f->jreg, f->J, T, f->V, s);
-    launch_flame_pose(full_pose_dev, f->rot, f->feat, T, f->Pp, s);
+    launch_flame_joints(vshaped, f->jreg.get(), J, T, f->V, s);
+    launch_flame_pose(full_pose_dev, rot, feat, T, f->Pp, s);
     GemmArgs p;     // v_posed = v_shaped + pose_feature . posedirs
-    p.A = f->feat; p.lda = f->Pp; p.W = f->posedirs; p.ldw = f->Pp; p.C = f->vposed; p.ldc = N; p.R = f->vshaped; p.ldr = N;
+    p.A = feat; p.lda = f->Pp; p.W = f->posedirs.get(); p.ldw = f->Pp; p.C = vposed; p.ldc = N; p.R = vshaped; p.ldr = N;
     p.M = T; p.N = N; p.K = f->Pp;
     launch_gemm(p, s);
-    launch_flame_skin(f->vposed, f->rot, f->J, f->parents, f->weights, out_dev, T, f->V, f->scale, s);
+    launch_flame_skin(vposed, rot, J, f->parents.get(), f->weights.get(), out_dev, T, f->V, f->scale, s);
     if (hipGetLastError() != hipSuccess) { f->err = "kernel launch failed"; return ARTALK_EHIP; }
     return ARTALK_OK;
 }

@@ -21,6 +21,7 @@
 
 #include "artalk_hip.h"
 #include "common.h"
+#include "device_mem.h"
 
 namespace artalk {
 
@@ -164,22 +165,21 @@ struct artalk_gaga {
     // avatar (device copies, uploaded once by set_avatar)
     int N = 0;
     bool have_avatar = false;
-    float *xyz = nullptr, *colors = nullptr, *opac = nullptr, *scales = nullptr, *rots = nullptr, *shapecode = nullptr;
+    DevBuf<float> xyz, colors, opac, scales, rots, shapecode;
     float transform[12] = {};
     // forehead EMA
     int K = 0;
-    int32_t* index = nullptr;
-    float* state = nullptr;      // [K][3]
-    int* flag = nullptr;
+    DevBuf<int32_t> index;
+    DevBuf<float> state;         // [K][3]
+    DevBuf<int> flag;
     // watermark
-    float* wm = nullptr;
+    DevBuf<float> wm;
     int wm_h = 0, wm_w = 0;
     // scratch of one slab
     int slab_req = 0, cap_frames = 0, cap_N = 0;
-    float *betas = nullptr, *pose = nullptr, *verts = nullptr, *means = nullptr, *img = nullptr;
-    int32_t* radii = nullptr;
-    float* codes_host = nullptr;      // pinned [cap_codes][3]
-    int cap_codes = 0;
+    DevBuf<float> betas, pose, verts, means, img;
+    DevBuf<int32_t> radii;
+    PinnedBuf<float> codes_host;      // [frames][3]
     bool timing = false;
     double stage_ms[kGagaStages] = {0, 0, 0, 0, 0};
     std::string err;
@@ -190,16 +190,6 @@ static thread_local std::string g_gaga_error;
 namespace {
 
 int gaga_fail(artalk_gaga* g, int rc, const std::string& msg) { g->err = msg; return rc; }
-
-void gaga_free(float*& p) { if (p) (void)hipFree(p); p = nullptr; }
-
-bool gaga_upload(float*& dst, const float* host, size_t n) {
-    gaga_free(dst);
-    void* p = nullptr;
-    if (hipMalloc(&p, (n ? n : 1) * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return false; }
-    dst = (float*)p;
-    return n == 0 || hipMemcpy(p, host, n * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
-}
 
 // frames whose means, radii, splat image and vertices fit 512 MiB, at most 64 and at most the upsampler's slab in force
 int gaga_default_slab(const artalk_gaga* g, int N) {
@@ -225,13 +215,6 @@ void artalk_gaga_destroy(artalk_gaga* g) {
     if (!g) return;
     (void)hipSetDevice(g->device);
     (void)hipDeviceSynchronize();
-    for (float** p : {&g->xyz, &g->colors, &g->opac, &g->scales, &g->rots, &g->shapecode, &g->state, &g->wm, &g->betas, &g->pose, &g->verts,
-                      &g->means, &g->img})
-        gaga_free(*p);
-    if (g->index) (void)hipFree(g->index);
-    if (g->flag) (void)hipFree(g->flag);
-    if (g->radii) (void)hipFree(g->radii);
-    if (g->codes_host) (void)hipHostFree(g->codes_host);
     delete g;
 }
 
@@ -328,9 +311,8 @@ int artalk_gaga_set_avatar(artalk_gaga* g, int N, const float* xyz, const float*
     (void)hipDeviceSynchronize();      // an earlier call may still read the avatar that is replaced
     g->have_avatar = false;
     const size_t n = (size_t)N;
-    if (!gaga_upload(g->xyz, xyz, n * 3) || !gaga_upload(g->colors, colors, n * kGagaCh) || !gaga_upload(g->opac, opacities, n) ||
-        !gaga_upload(g->scales, scales, n * 3) || !gaga_upload(g->rots, rotations, n * 4) ||
-        !gaga_upload(g->shapecode, shapecode, (size_t)(g->NB - 100)))
+    if (!g->xyz.upload(xyz, n * 3) || !g->colors.upload(colors, n * kGagaCh) || !g->opac.upload(opacities, n) ||
+        !g->scales.upload(scales, n * 3) || !g->rots.upload(rotations, n * 4) || !g->shapecode.upload(shapecode, (size_t)(g->NB - 100)))
         return gaga_fail(g, ARTALK_EHIP, "uploading the avatar failed");
     std::memcpy(g->transform, transform_3x4, sizeof(g->transform));
     g->N = N;
@@ -340,10 +322,11 @@ int artalk_gaga_set_avatar(artalk_gaga* g, int N, const float* xyz, const float*
 
 int artalk_gaga_reset_state(artalk_gaga* g) {
     if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
-    if (!g->flag) return ARTALK_OK;      // no indices: there is no state
+    if (!g->flag.get()) return ARTALK_OK;      // no indices: there is no state
     if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
     (void)hipDeviceSynchronize();
-    if (hipMemset(g->flag, 0, sizeof(int)) != hipSuccess || hipMemset(g->state, 0, (size_t)(g->K ? g->K : 1) * 3 * sizeof(float)) != hipSuccess)
+    if (hipMemset(g->flag.get(), 0, sizeof(int)) != hipSuccess ||
+        hipMemset(g->state.get(), 0, (size_t)(g->K ? g->K : 1) * 3 * sizeof(float)) != hipSuccess)
         return gaga_fail(g, ARTALK_EHIP, "hipMemset failed");
     return ARTALK_OK;
 }
@@ -354,21 +337,14 @@ int artalk_gaga_set_forehead(artalk_gaga* g, const int32_t* idx, int K) {
     if (rc != ARTALK_OK) return rc;
     if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
     (void)hipDeviceSynchronize();
-    if (g->index) (void)hipFree(g->index);
-    if (g->flag) (void)hipFree(g->flag);
-    gaga_free(g->state);
-    g->index = nullptr; g->flag = nullptr; g->K = 0;
+    g->index.reset(); g->flag.reset(); g->state.reset(); g->K = 0;
     if (K == 0) return ARTALK_OK;
-    void *pi = nullptr, *pf = nullptr, *ps = nullptr;
-    if (hipMalloc(&pi, (size_t)K * sizeof(int32_t)) != hipSuccess || hipMalloc(&pf, sizeof(int)) != hipSuccess ||
-        hipMalloc(&ps, (size_t)K * 3 * sizeof(float)) != hipSuccess) {
-        (void)hipGetLastError();
-        if (pi) (void)hipFree(pi);
-        if (pf) (void)hipFree(pf);
+    if (!g->index.alloc((size_t)K) || !g->flag.alloc(1) || !g->state.alloc((size_t)K * 3)) {
+        g->index.reset(); g->flag.reset();
         return gaga_fail(g, ARTALK_EHIP, "hipMalloc failed");
     }
-    g->index = (int32_t*)pi; g->flag = (int*)pf; g->state = (float*)ps; g->K = K;
-    if (hipMemcpy(g->index, idx, (size_t)K * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
+    g->K = K;
+    if (hipMemcpy(g->index.get(), idx, (size_t)K * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
         return gaga_fail(g, ARTALK_EHIP, "uploading the indices failed");
     return artalk_gaga_reset_state(g);
 }
@@ -379,13 +355,13 @@ int artalk_gaga_set_watermark(artalk_gaga* g, const float* rgba_host, int h, int
         const int rc = check_watermark(g->S, h, w, &g->err);
         if (rc != ARTALK_OK) return rc;
     }
-    if (!rgba_host && !g->wm) return ARTALK_OK;
+    if (!rgba_host && !g->wm.get()) return ARTALK_OK;
     if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
     (void)hipDeviceSynchronize();
-    gaga_free(g->wm);
+    g->wm.reset();
     g->wm_h = g->wm_w = 0;
     if (!rgba_host) return ARTALK_OK;
-    if (!gaga_upload(g->wm, rgba_host, (size_t)4 * h * w)) return gaga_fail(g, ARTALK_EHIP, "uploading the watermark failed");
+    if (!g->wm.upload(rgba_host, (size_t)4 * h * w)) return gaga_fail(g, ARTALK_EHIP, "uploading the watermark failed");
     g->wm_h = h; g->wm_w = w;
     return ARTALK_OK;
 }
@@ -417,15 +393,8 @@ int artalk_gaga_render(artalk_gaga* g, const float* motion_dev, int64_t motion_s
     (void)artalk_styleunet_dims(g->unet, nullptr, nullptr, nullptr, &finalized, nullptr);
     const int rc = check_render(T, motion_stride, g->have_avatar, finalized != 0, &g->err);
     if (rc != ARTALK_OK) return rc;
-    if (noise_ptrs_or_null) {
-        if (!noise_batch_strides) return gaga_fail(g, ARTALK_EINVAL, "noise_batch_strides must not be NULL when noise_ptrs is given");
-        for (int l = 0; l < g->num_layers; ++l) {
-            const int64_t r = 1 << ((l + 5) / 2);
-            if (!noise_ptrs_or_null[l]) return gaga_fail(g, ARTALK_EINVAL, "noise_ptrs[" + std::to_string(l) + "] is NULL");
-            if (noise_batch_strides[l] != 0 && noise_batch_strides[l] < r * r)
-                return gaga_fail(g, ARTALK_EINVAL, "noise_batch_strides[" + std::to_string(l) + "] must be 0 or at least " + std::to_string(r * r));
-        }
-    }
+    const int rcn = su_check_noise(g->num_layers, noise_ptrs_or_null, noise_batch_strides, &g->err);
+    if (rcn != ARTALK_OK) return rcn;
     if (T == 0) return ARTALK_OK;
     if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
     hipStream_t s = (hipStream_t)stream;
@@ -435,84 +404,54 @@ int artalk_gaga_render(artalk_gaga* g, const float* motion_dev, int64_t motion_s
     const int frames = T < slab ? T : slab;
     if (frames > g->cap_frames || N > g->cap_N) {
         (void)hipDeviceSynchronize();
-        for (float** p : {&g->betas, &g->pose, &g->verts, &g->means, &g->img}) gaga_free(*p);
-        if (g->radii) (void)hipFree(g->radii);
-        g->radii = nullptr; g->cap_frames = g->cap_N = 0;
-        const size_t f = (size_t)frames;
-        void* pr = nullptr;
-        bool ok = true;
-        auto grab = [&](float*& p, size_t n) {
-            void* q = nullptr;
-            if (hipMalloc(&q, n * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); ok = false; q = nullptr; }
-            p = (float*)q;
-        };
-        grab(g->betas, f * NB); grab(g->pose, f * 15); grab(g->verts, f * V * 3); grab(g->means, f * N * 3); grab(g->img, f * kGagaCh * SS);
-        if (hipMalloc(&pr, f * N * sizeof(int32_t)) != hipSuccess) { (void)hipGetLastError(); ok = false; pr = nullptr; }
-        g->radii = (int32_t*)pr;
-        if (!ok) return gaga_fail(g, ARTALK_EHIP, "hipMalloc of the scratch for " + std::to_string(frames) + " frames failed");
+        g->cap_frames = g->cap_N = 0; g->radii.reset();
+        for (DevBuf<float>* b : {&g->betas, &g->pose, &g->verts, &g->means, &g->img}) b->reset();
+        const size_t f = (size_t)frames;      // exact sizes: a slab is as large as it gets
+        if (!g->betas.alloc(f * NB) || !g->pose.alloc(f * 15) || !g->verts.alloc(f * V * 3) || !g->means.alloc(f * N * 3) ||
+            !g->img.alloc(f * kGagaCh * SS) || !g->radii.alloc(f * N))
+            return gaga_fail(g, ARTALK_EHIP, "hipMalloc of the scratch for " + std::to_string(frames) + " frames failed");
         g->cap_frames = frames; g->cap_N = N;
     }
-    if (T > g->cap_codes) {
-        (void)hipStreamSynchronize(s);
-        if (g->codes_host) (void)hipHostFree(g->codes_host);
-        g->codes_host = nullptr; g->cap_codes = 0;
-        void* p = nullptr;
-        if (hipHostMalloc(&p, (size_t)T * 3 * sizeof(float), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return gaga_fail(g, ARTALK_EHIP, "hipHostMalloc failed"); }
-        g->codes_host = (float*)p; g->cap_codes = T;
-    }
+    if (!g->codes_host.grow((size_t)T * 3, 0, 1, s)) return gaga_fail(g, ARTALK_EHIP, "hipHostMalloc failed");
     // the first wait of the call: the head-rotation codes become the cameras, which the rasteriser reads on the host
-    if (hipMemcpy2DAsync(g->codes_host, 3 * sizeof(float), motion_dev + 100, (size_t)motion_stride * sizeof(float), 3 * sizeof(float), (size_t)T,
+    if (hipMemcpy2DAsync(g->codes_host.get(), 3 * sizeof(float), motion_dev + 100, (size_t)motion_stride * sizeof(float), 3 * sizeof(float), (size_t)T,
                          hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
         (void)hipGetLastError();
         return gaga_fail(g, ARTALK_EHIP, "reading the rotation codes failed");
     }
     std::vector<float> view((size_t)T * 16), proj((size_t)T * 16);
-    (void)artalk_gaga_cameras(g->codes_host, 3, T, g->transform, view.data(), proj.data(), nullptr);
+    (void)artalk_gaga_cameras(g->codes_host.get(), 3, T, g->transform, view.data(), proj.data(), nullptr);
 
-    std::vector<hipEvent_t> ev;
-    auto mark = [&]() {
-        if (!g->timing) return;
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, s); ev.push_back(e); }
-    };
-    auto drop_events = [&]() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); ev.clear(); };
+    StageTimer timer;
+    timer.start(s, g->timing);
     for (double& m : g->stage_ms) m = 0;
     std::vector<const float*> np(g->num_layers);
     const float tanfov = (float)(1.0 / 12.0);
     for (int f0 = 0; f0 < T; f0 += slab) {
         const int n = T - f0 < slab ? T - f0 : slab;
-        mark();
-        launch_gaga_flame_inputs(motion_dev + (long)f0 * motion_stride, (long)motion_stride, g->shapecode, NB - 100, g->betas, g->pose, n, s);
-        if (artalk_flame_verts(g->flame, g->betas, g->pose, n, g->verts, s) != ARTALK_OK) {
-            drop_events();
+        timer.mark(-1);      // (what lies between two slabs counts to no stage)
+        launch_gaga_flame_inputs(motion_dev + (long)f0 * motion_stride, (long)motion_stride, g->shapecode.get(), NB - 100, g->betas.get(),
+                                 g->pose.get(), n, s);
+        if (artalk_flame_verts(g->flame, g->betas.get(), g->pose.get(), n, g->verts.get(), s) != ARTALK_OK)
             return gaga_fail(g, ARTALK_EHIP, std::string("artalk_flame_verts failed: ") + artalk_flame_last_error(g->flame));
-        }
-        mark();
-        if (g->K > 0) launch_gaga_forehead(g->verts, g->index, g->K, n, V, g->state, g->flag, s);
-        launch_gaga_means(g->verts, g->xyz, g->means, n, V, N, s);
-        mark();
-        int rc2 = artalk_splat_render(g->splat, N, n, S, S, g->means, (int64_t)N * 3, g->colors, 0, g->opac, 0, g->scales, 0, g->rots, 0,
-                                      view.data() + (size_t)f0 * 16, proj.data() + (size_t)f0 * 16, n, tanfov, tanfov, 1.0f, nullptr, g->img,
-                                      g->radii, s);
-        if (rc2 != ARTALK_OK) { drop_events(); return gaga_fail(g, rc2, std::string("artalk_splat_render failed: ") + artalk_splat_last_error(g->splat)); }
-        mark();
+        timer.mark(kGagaInputsFlame);
+        if (g->K > 0) launch_gaga_forehead(g->verts.get(), g->index.get(), g->K, n, V, g->state.get(), g->flag.get(), s);
+        launch_gaga_means(g->verts.get(), g->xyz.get(), g->means.get(), n, V, N, s);
+        timer.mark(kGagaForeheadMeans);
+        int rc2 = artalk_splat_render(g->splat, N, n, S, S, g->means.get(), (int64_t)N * 3, g->colors.get(), 0, g->opac.get(), 0, g->scales.get(), 0,
+                                      g->rots.get(), 0, view.data() + (size_t)f0 * 16, proj.data() + (size_t)f0 * 16, n, tanfov, tanfov, 1.0f,
+                                      nullptr, g->img.get(), g->radii.get(), s);
+        if (rc2 != ARTALK_OK) return gaga_fail(g, rc2, std::string("artalk_splat_render failed: ") + artalk_splat_last_error(g->splat));
+        timer.mark(kGagaSplat);
         if (noise_ptrs_or_null) for (int l = 0; l < g->num_layers; ++l) np[l] = noise_ptrs_or_null[l] + (long)f0 * noise_batch_strides[l];
         float* out = out_dev + (long)f0 * 3 * SS;
-        rc2 = artalk_styleunet_forward(g->unet, g->img, n, noise_ptrs_or_null ? np.data() : nullptr, noise_batch_strides, activation, out, s);
-        if (rc2 != ARTALK_OK) { drop_events(); return gaga_fail(g, rc2, std::string("artalk_styleunet_forward failed: ") + artalk_styleunet_last_error(g->unet)); }
-        mark();
-        launch_gaga_finish(out, g->wm, g->wm_h, g->wm_w, S, n, s);
-        mark();
+        rc2 = artalk_styleunet_forward(g->unet, g->img.get(), n, noise_ptrs_or_null ? np.data() : nullptr, noise_batch_strides, activation, out, s);
+        if (rc2 != ARTALK_OK) return gaga_fail(g, rc2, std::string("artalk_styleunet_forward failed: ") + artalk_styleunet_last_error(g->unet));
+        timer.mark(kGagaUpsampler);
+        launch_gaga_finish(out, g->wm.get(), g->wm_h, g->wm_w, S, n, s);
+        timer.mark(kGagaFinish);
     }
-    if (g->timing && !ev.empty()) {
-        (void)hipEventSynchronize(ev.back());
-        for (size_t k = 0; k + 1 < ev.size(); ++k) {
-            float ms = 0.f;
-            const int stage = (int)(k % (kGagaStages + 1));
-            if (stage < kGagaStages && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) g->stage_ms[stage] += ms;
-        }
-        drop_events();
-    }
+    timer.finish(g->stage_ms, kGagaStages);
     if (hipGetLastError() != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "a launch failed");
     return ARTALK_OK;
 }

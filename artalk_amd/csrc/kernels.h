@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include <hip/hip_ext.h>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -265,6 +266,9 @@ void launch_flame_pose(const float* pose, float* rot, float* feat, int T, int ld
 void launch_flame_joints(const float* vs, const float* jreg, float* J, int T, int V, hipStream_t s);
 void launch_flame_skin(const float* vposed, const float* rot, const float* J, const int* parents, const float* weights, float* out,
                        int T, int V, float scale, hipStream_t s);
+// StyleUNet (styleunet.hip), host only: the per-layer noise arguments of a forward call (ptrs == NULL: none given).  ARTALK_OK, or
+// ARTALK_EINVAL with the message in *err
+int su_check_noise(int num_layers, const float* const* ptrs, const int64_t* strides, std::string* err);
 // headroom audit: *slot = max(*slot, bits of max |x|) over rows x cols (cols % 8 == 0) of a P8 (is_p8: written with scale 2^p8_exp) or fp32 buffer
 void launch_absmax(const float* buf, int rows, int cols, long ld, int is_p8, unsigned int* slot, hipStream_t s, int junk_period = 0,
                    int junk_from = 0, int p8_exp = kActExp);

@@ -6,6 +6,7 @@
 //   ops.hip      the single-kernel entry points of tests and tuning tools (no artalk_model)
 // Private to csrc/: what one file alone uses stays in that file's anonymous namespace.
 #pragma once
+#include "device_mem.h"
 #include "kernels.h"
 #include "../../include/artalk_hip.h"
 
@@ -266,17 +267,7 @@ struct ProfilingOff {
 };
 
 template <typename T>
-T* dalloc_in(std::vector<void*>& pool, int64_t n) {
-    void* p = nullptr;
-    if (n <= 0) n = 1;
-    if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) { pool.push_back(nullptr); return nullptr; }
-    (void)hipMemset(p, 0, n * sizeof(T));
-    pool.push_back(p);
-    return reinterpret_cast<T*>(p);
-}
-template <typename T>
 T* dalloc(artalk_model* m, int64_t n) { return dalloc_in<T>(m->allocs, n); }
-
 
 // ---- the functions that cross a file boundary, by the file that defines them
 // engine.hip: the stages of the path and the chunk step (calls.hip runs them)

@@ -11,6 +11,7 @@
 //   render_shade_kernel    one thread per pixel: reads the winner, recomputes its barycentrics and shades
 // Frames are processed in slabs so that the per-pixel key buffer (8 bytes per pixel and frame) stays bounded.
 #include "common.h"
+#include "device_mem.h"
 #include "../../include/artalk_hip.h"
 
 #include <cmath>
@@ -183,11 +184,10 @@ using namespace artalk;
 struct artalk_mesh_renderer {
     int device = 0, V = 0, F = 0, S = 0, slab_max = 0, slab = 0;
     float scale = 1.f;
-    int *faces = nullptr, *adj_off = nullptr, *adj = nullptr;
-    float4* proj = nullptr;
-    float* nrm = nullptr;
-    unsigned long long* keys = nullptr;
-    std::vector<void*> allocs;
+    DevBuf<int> faces, adj_off, adj;
+    DevBuf<float4> proj;                   // the three below: scratch of slab_max frames
+    DevBuf<float> nrm;
+    DevBuf<unsigned long long> keys;
     std::string err;
 };
 
@@ -201,7 +201,6 @@ void artalk_render_destroy(artalk_mesh_renderer* r) {
     if (!r) return;
     (void)hipSetDevice(r->device);
     (void)hipDeviceSynchronize();
-    for (void* p : r->allocs) if (p) (void)hipFree(p);
     delete r;
 }
 
@@ -239,22 +238,14 @@ int artalk_render_create(int device_id, int V, int F, const int32_t* faces_host,
     int64_t slab = (32ll << 20) / key_bytes;      // 32 MiB of keys: 16 frames at 512 x 512
     r->slab_max = (int)(slab < 1 ? 1 : slab > 64 ? 64 : slab);
     r->slab = r->slab_max;
-    auto alloc = [&](size_t bytes) -> void* {
-        void* p = nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) p = nullptr;
-        r->allocs.push_back(p);
-        return p;
-    };
-    r->faces = (int*)alloc((size_t)F * 3 * sizeof(int));
-    r->adj_off = (int*)alloc((size_t)(V + 1) * sizeof(int));
-    r->adj = (int*)alloc(adj.size() * sizeof(int));
-    r->proj = (float4*)alloc((size_t)r->slab_max * V * sizeof(float4));
-    r->nrm = (float*)alloc((size_t)r->slab_max * V * 3 * sizeof(float));
-    r->keys = (unsigned long long*)alloc((size_t)r->slab_max * key_bytes);
-    for (void* p : r->allocs) if (!p) { g_render_error = "hipMalloc failed"; artalk_render_destroy(r); return ARTALK_EHIP; }
-    (void)hipMemcpy(r->faces, faces_host, (size_t)F * 3 * sizeof(int), hipMemcpyHostToDevice);
-    (void)hipMemcpy(r->adj_off, off.data(), (size_t)(V + 1) * sizeof(int), hipMemcpyHostToDevice);
-    (void)hipMemcpy(r->adj, adj.data(), adj.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (!r->faces.alloc((size_t)F * 3) || !r->adj_off.alloc((size_t)V + 1) || !r->adj.alloc(adj.size()) ||
+        !r->proj.alloc((size_t)r->slab_max * V) || !r->nrm.alloc((size_t)r->slab_max * V * 3) ||
+        !r->keys.alloc((size_t)r->slab_max * image_size * image_size)) {
+        g_render_error = "hipMalloc failed"; artalk_render_destroy(r); return ARTALK_EHIP;
+    }
+    (void)hipMemcpy(r->faces.get(), faces_host, (size_t)F * 3 * sizeof(int), hipMemcpyHostToDevice);
+    (void)hipMemcpy(r->adj_off.get(), off.data(), (size_t)(V + 1) * sizeof(int), hipMemcpyHostToDevice);
+    (void)hipMemcpy(r->adj.get(), adj.data(), adj.size() * sizeof(int), hipMemcpyHostToDevice);
     if (hipDeviceSynchronize() != hipSuccess) { g_render_error = "upload failed"; artalk_render_destroy(r); return ARTALK_EHIP; }
     *out = r;
     return ARTALK_OK;
@@ -294,13 +285,15 @@ int artalk_render_mesh(artalk_mesh_renderer* r, const float* verts_dev, int T, c
     for (int j = 0; j < 3; ++j) cam.C[j] = -(cam.T[0] * cam.R[j * 3] + cam.T[1] * cam.R[j * 3 + 1] + cam.T[2] * cam.R[j * 3 + 2]);
     const int V = r->V, F = r->F, S = r->S;
     const long SS = (long)S * S;
+    int *const faces = r->faces.get(), *const adj_off = r->adj_off.get(), *const adj = r->adj.get();
+    float4* const proj = r->proj.get(); float* const nrm = r->nrm.get(); unsigned long long* const keys = r->keys.get();
     for (int t0 = 0; t0 < T; t0 += r->slab) {
         const int n = T - t0 < r->slab ? T - t0 : r->slab;
         const float* verts = verts_dev + (long)t0 * V * 3;
-        if (hipMemsetAsync(r->keys, 0xFF, (size_t)n * SS * 8, s) != hipSuccess) { r->err = "memset failed"; return ARTALK_EHIP; }
-        ARTALK_LAUNCH(render_project_kernel, dim3((V + 255) / 256, n), dim3(256), 0, s, verts, r->faces, r->adj_off, r->adj, r->proj, r->nrm, V, cam);
-        ARTALK_LAUNCH(render_raster_kernel, dim3((F + 3) / 4, n), dim3(256), 0, s, r->proj, r->faces, r->keys, V, F, S);
-        ARTALK_LAUNCH(render_shade_kernel, dim3((unsigned)((SS + 255) / 256), n), dim3(256), 0, s, verts, r->proj, r->nrm, r->faces, r->keys,
+        if (hipMemsetAsync(keys, 0xFF, (size_t)n * SS * 8, s) != hipSuccess) { r->err = "memset failed"; return ARTALK_EHIP; }
+        ARTALK_LAUNCH(render_project_kernel, dim3((V + 255) / 256, n), dim3(256), 0, s, verts, faces, adj_off, adj, proj, nrm, V, cam);
+        ARTALK_LAUNCH(render_raster_kernel, dim3((F + 3) / 4, n), dim3(256), 0, s, proj, faces, keys, V, F, S);
+        ARTALK_LAUNCH(render_shade_kernel, dim3((unsigned)((SS + 255) / 256), n), dim3(256), 0, s, verts, proj, nrm, faces, keys,
                       rgb_dev + (long)t0 * 3 * SS, alpha_dev + (long)t0 * SS,
                       pix_to_face_dev_or_null ? pix_to_face_dev_or_null + (long)t0 * SS : (int32_t*)nullptr, V, S, cam);
     }

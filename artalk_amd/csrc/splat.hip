@@ -18,6 +18,7 @@
 // artalk_model's no-synchronisation rule.  Growing a buffer frees the old one, which waits for the device as well; a second call of the
 // same shape allocates nothing.
 #include "common.h"
+#include "device_mem.h"
 #include "../../include/artalk_hip.h"
 
 #include <hipcub/hipcub.hpp>
@@ -280,20 +281,19 @@ using namespace artalk;
 
 namespace {
 
-struct SplatBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-};
-
 enum { kStageCount, kStagePreprocess, kStageScanEmit, kStageSort, kStageRanges, kStageBlend, kSplatStages };
 
 }  // namespace
 
 struct artalk_splat {
     int device = 0;
-    SplatBuf cams, counts, xy, conic, depth, rect, touched, offsets, scan_tmp, ranges, keys_in, keys_out, vals_in, vals_out, sort_tmp;
-    void* host = nullptr;      // pinned: cameras going up, pair counts coming down
-    size_t host_cap = 0;
+    DevBuf<SplatCam> cams;
+    DevBuf<unsigned long long> counts, keys_in, keys_out;
+    DevBuf<float2> xy; DevBuf<float4> conic; DevBuf<float> depth; DevBuf<uint4> rect;      // per Gaussian of the frame in work
+    DevBuf<unsigned int> touched, offsets, vals_in, vals_out;
+    DevBuf<uint2> ranges;
+    DevBuf<char> scan_tmp, sort_tmp;
+    PinnedBuf<char> host;      // cameras going up, pair counts coming down
     bool timing = false, used = false;
     double stage_ms[kSplatStages] = {0, 0, 0, 0, 0, 0};
     long long last_pairs = 0;
@@ -303,22 +303,12 @@ struct artalk_splat {
 
 static thread_local std::string g_splat_error;
 
-static bool splat_grow(artalk_splat* s, SplatBuf& b, size_t bytes, hipStream_t st) {
-    if (bytes <= b.cap) return true;
-    if (b.p) {
-        (void)hipStreamSynchronize(st);      // earlier calls may still read it
-        (void)hipFree(b.p);
-        b.p = nullptr; b.cap = 0;
-    }
-    bytes += bytes / 4;                      // room to grow: pair counts change from call to call
-    if (hipMalloc(&b.p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        b.p = nullptr;
-        s->err = "hipMalloc of " + std::to_string(bytes) + " bytes failed";
-        return false;
-    }
-    b.cap = bytes;
-    return true;
+// room for n elements and a quarter more (pair counts change from call to call); earlier calls on the stream may still read the old block
+template <typename T>
+static bool splat_grow(artalk_splat* s, DevBuf<T>& b, size_t n, hipStream_t st) {
+    if (b.grow(n, 1, 4, st)) return true;
+    s->err = "hipMalloc of " + std::to_string(DevBuf<T>::grown_bytes(n, 1, 4)) + " bytes failed";
+    return false;
 }
 
 static int splat_bits(unsigned int tiles) {      // bits that hold every tile index below `tiles`
@@ -333,14 +323,10 @@ const char* artalk_splat_last_error(const artalk_splat* s) { return s ? s->err.c
 
 void artalk_splat_destroy(artalk_splat* s) {
     if (!s) return;
-    if (s->used) {
+    if (s->used) {      // (never used: the buffers are empty and the device stays untouched)
         (void)hipSetDevice(s->device);
         (void)hipDeviceSynchronize();
     }
-    for (SplatBuf* b : {&s->cams, &s->counts, &s->xy, &s->conic, &s->depth, &s->rect, &s->touched, &s->offsets, &s->scan_tmp, &s->ranges,
-                        &s->keys_in, &s->keys_out, &s->vals_in, &s->vals_out, &s->sort_tmp})
-        if (b->p) (void)hipFree(b->p);
-    if (s->host) (void)hipHostFree(s->host);
     delete s;
 }
 
@@ -408,67 +394,48 @@ int artalk_splat_render(artalk_splat* s, int N, int T, int H, int W, const float
     SplatAttrs a{means_dev, colors_dev, opacities_dev, scales_dev, rotations_dev,
                  (long)means_stride, (long)colors_stride, (long)opacities_stride, (long)scales_stride, (long)rotations_stride};
 
-    std::vector<hipEvent_t> ev;      // timing only: ev[k] closes an interval that belongs to stage ev_stage[k] (-1: to none)
-    std::vector<int> ev_stage;
-    auto mark = [&](int stage) {
-        if (!s->timing) return;
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, st); ev.push_back(e); ev_stage.push_back(stage); }
-    };
+    StageTimer timer;
+    timer.start(st, s->timing);
     for (double& m : s->stage_ms) m = 0;
     s->last_pairs = 0; s->last_frames = T;
 
-    if (!splat_grow(s, s->ranges, (size_t)tiles * sizeof(uint2), st)) return ARTALK_EHIP;
+    if (!splat_grow(s, s->ranges, tiles, st)) return ARTALK_EHIP;
     const unsigned long long* counts_host = nullptr;
     if (N > 0) {
         const size_t cam_bytes = (size_t)n_cams * sizeof(SplatCam), cnt_bytes = (size_t)T * sizeof(unsigned long long);
-        if (cam_bytes + cnt_bytes > s->host_cap) {
-            (void)hipStreamSynchronize(st);
-            if (s->host) (void)hipHostFree(s->host);
-            s->host = nullptr; s->host_cap = 0;
-            if (hipHostMalloc(&s->host, cam_bytes + cnt_bytes, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                s->host = nullptr;
-                s->err = "hipHostMalloc failed";
-                return ARTALK_EHIP;
-            }
-            s->host_cap = cam_bytes + cnt_bytes;
-        }
+        if (!s->host.grow(cam_bytes + cnt_bytes, 0, 1, st)) { s->err = "hipHostMalloc failed"; return ARTALK_EHIP; }
         size_t scan_bytes = 0;
         (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const unsigned int*)nullptr, (unsigned int*)nullptr, N, st);
-        if (!splat_grow(s, s->cams, cam_bytes, st) || !splat_grow(s, s->counts, cnt_bytes, st) ||
-            !splat_grow(s, s->xy, (size_t)N * sizeof(float2), st) || !splat_grow(s, s->conic, (size_t)N * sizeof(float4), st) ||
-            !splat_grow(s, s->depth, (size_t)N * sizeof(float), st) || !splat_grow(s, s->rect, (size_t)N * sizeof(uint4), st) ||
-            !splat_grow(s, s->touched, (size_t)N * sizeof(unsigned int), st) || !splat_grow(s, s->offsets, (size_t)N * sizeof(unsigned int), st) ||
-            !splat_grow(s, s->scan_tmp, scan_bytes ? scan_bytes : 16, st))
+        if (!splat_grow(s, s->cams, n_cams, st) || !splat_grow(s, s->counts, T, st) || !splat_grow(s, s->xy, N, st) ||
+            !splat_grow(s, s->conic, N, st) || !splat_grow(s, s->depth, N, st) || !splat_grow(s, s->rect, N, st) ||
+            !splat_grow(s, s->touched, N, st) || !splat_grow(s, s->offsets, N, st) || !splat_grow(s, s->scan_tmp, scan_bytes ? scan_bytes : 16, st))
             return ARTALK_EHIP;
         // the pinned block is free here: every earlier call waited on its stream after its upload, and its download ended that wait
-        SplatCam* hc = (SplatCam*)((char*)s->host + cnt_bytes);
+        SplatCam* hc = (SplatCam*)(s->host.get() + cnt_bytes);
         for (int c = 0; c < n_cams; ++c) {
             std::memcpy(hc[c].V, view_host + (size_t)c * 16, sizeof(float) * 16);
             std::memcpy(hc[c].P, proj_host + (size_t)c * 16, sizeof(float) * 16);
         }
-        if (hipMemcpyAsync(s->cams.p, hc, cam_bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
-            hipMemsetAsync(s->counts.p, 0, cnt_bytes, st) != hipSuccess) {
+        if (hipMemcpyAsync(s->cams.get(), hc, cam_bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+            hipMemsetAsync(s->counts.get(), 0, cnt_bytes, st) != hipSuccess) {
             (void)hipGetLastError();
             s->err = "camera upload failed";
             return ARTALK_EHIP;
         }
-        mark(-1);
+        timer.mark(-1);
         for (int t0 = 0; t0 < T; t0 += 32768) {      // (grid.y is a 16-bit quantity)
             const int n = T - t0 < 32768 ? T - t0 : 32768;
-            ARTALK_LAUNCH(splat_preprocess_kernel<true>, dim3(nblk, n), dim3(256), 0, st, a, v, (const SplatCam*)s->cams.p, n_cams == 1 ? 0 : 1,
-                          t0, radii_dev, (unsigned long long*)s->counts.p, (float2*)nullptr, (float4*)nullptr, (float*)nullptr, (uint4*)nullptr,
+            ARTALK_LAUNCH(splat_preprocess_kernel<true>, dim3(nblk, n), dim3(256), 0, st, a, v, (const SplatCam*)s->cams.get(), n_cams == 1 ? 0 : 1,
+                          t0, radii_dev, s->counts.get(), (float2*)nullptr, (float4*)nullptr, (float*)nullptr, (uint4*)nullptr,
                           (unsigned int*)nullptr);
         }
-        mark(kStageCount);
+        timer.mark(kStageCount);
         // the one wait of the call: the pair counts size the key buffers
-        if (hipMemcpyAsync(s->host, s->counts.p, cnt_bytes, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        if (hipMemcpyAsync(s->host.get(), s->counts.get(), cnt_bytes, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
             s->err = std::string("counting pass failed: ") + hipGetErrorString(hipGetLastError());
-            for (hipEvent_t e : ev) (void)hipEventDestroy(e);
             return ARTALK_EHIP;
         }
-        counts_host = (const unsigned long long*)s->host;
+        counts_host = (const unsigned long long*)s->host.get();
         unsigned long long maxp = 0;
         for (int t = 0; t < T; ++t) {
             if (counts_host[t] > maxp) maxp = counts_host[t];
@@ -476,7 +443,6 @@ int artalk_splat_render(artalk_splat* s, int N, int T, int H, int W, const float
         }
         if (maxp > (unsigned long long)INT_MAX) {
             s->err = "a frame has " + std::to_string(maxp) + " (tile, Gaussian) pairs; at most 2^31 - 1 are supported";
-            for (hipEvent_t e : ev) (void)hipEventDestroy(e);
             return ARTALK_ECAPACITY;
         }
         if (maxp > 0) {
@@ -484,56 +450,42 @@ int artalk_splat_render(artalk_splat* s, int N, int T, int H, int W, const float
             (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
                                                      (const unsigned int*)nullptr, (unsigned int*)nullptr, (int)maxp, 0,
                                                      32 + splat_bits(tiles), st);
-            if (!splat_grow(s, s->keys_in, maxp * 8, st) || !splat_grow(s, s->keys_out, maxp * 8, st) ||
-                !splat_grow(s, s->vals_in, maxp * 4, st) || !splat_grow(s, s->vals_out, maxp * 4, st) ||
-                !splat_grow(s, s->sort_tmp, sort_bytes ? sort_bytes : 16, st)) {
-                for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+            if (!splat_grow(s, s->keys_in, maxp, st) || !splat_grow(s, s->keys_out, maxp, st) || !splat_grow(s, s->vals_in, maxp, st) ||
+                !splat_grow(s, s->vals_out, maxp, st) || !splat_grow(s, s->sort_tmp, sort_bytes ? sort_bytes : 16, st))
                 return ARTALK_EHIP;
-            }
         }
     }
 
     bool ok = true;
     for (int t = 0; t < T && ok; ++t) {
         const unsigned int P = counts_host ? (unsigned int)counts_host[t] : 0u;
-        mark(-1);
+        timer.mark(-1);
         if (N > 0) {
-            ARTALK_LAUNCH(splat_preprocess_kernel<false>, dim3(nblk), dim3(256), 0, st, a, v, (const SplatCam*)s->cams.p, n_cams == 1 ? 0 : 1, t,
-                          (int*)nullptr, (unsigned long long*)nullptr, (float2*)s->xy.p, (float4*)s->conic.p, (float*)s->depth.p,
-                          (uint4*)s->rect.p, (unsigned int*)s->touched.p);
-            mark(kStagePreprocess);
+            ARTALK_LAUNCH(splat_preprocess_kernel<false>, dim3(nblk), dim3(256), 0, st, a, v, (const SplatCam*)s->cams.get(), n_cams == 1 ? 0 : 1, t,
+                          (int*)nullptr, (unsigned long long*)nullptr, s->xy.get(), s->conic.get(), s->depth.get(), s->rect.get(), s->touched.get());
+            timer.mark(kStagePreprocess);
         }
-        ok = ok && hipMemsetAsync(s->ranges.p, 0, (size_t)tiles * sizeof(uint2), st) == hipSuccess;
+        ok = ok && hipMemsetAsync(s->ranges.get(), 0, (size_t)tiles * sizeof(uint2), st) == hipSuccess;
         if (P > 0) {
-            size_t scan_bytes = s->scan_tmp.cap, sort_bytes = s->sort_tmp.cap;
-            ok = ok && hipcub::DeviceScan::ExclusiveSum(s->scan_tmp.p, scan_bytes, (const unsigned int*)s->touched.p, (unsigned int*)s->offsets.p,
+            size_t scan_bytes = s->scan_tmp.capacity(), sort_bytes = s->sort_tmp.capacity();
+            ok = ok && hipcub::DeviceScan::ExclusiveSum(s->scan_tmp.get(), scan_bytes, (const unsigned int*)s->touched.get(), s->offsets.get(),
                                                         N, st) == hipSuccess;
-            ARTALK_LAUNCH(splat_emit_kernel, dim3(nblk), dim3(256), 0, st, N, v.gx, (const uint4*)s->rect.p, (const unsigned int*)s->touched.p,
-                          (const unsigned int*)s->offsets.p, (const float*)s->depth.p, (unsigned long long*)s->keys_in.p,
-                          (unsigned int*)s->vals_in.p, P);
-            mark(kStageScanEmit);
-            ok = ok && hipcub::DeviceRadixSort::SortPairs(s->sort_tmp.p, sort_bytes, (const unsigned long long*)s->keys_in.p,
-                                                          (unsigned long long*)s->keys_out.p, (const unsigned int*)s->vals_in.p,
-                                                          (unsigned int*)s->vals_out.p, (int)P, 0, 32 + splat_bits(tiles), st) == hipSuccess;
-            mark(kStageSort);
-            ARTALK_LAUNCH(splat_ranges_kernel, dim3((P + 255) / 256), dim3(256), 0, st, P, (const unsigned long long*)s->keys_out.p,
-                          (uint2*)s->ranges.p, tiles);
-            mark(kStageRanges);
+            ARTALK_LAUNCH(splat_emit_kernel, dim3(nblk), dim3(256), 0, st, N, v.gx, (const uint4*)s->rect.get(), (const unsigned int*)s->touched.get(),
+                          (const unsigned int*)s->offsets.get(), (const float*)s->depth.get(), s->keys_in.get(), s->vals_in.get(), P);
+            timer.mark(kStageScanEmit);
+            ok = ok && hipcub::DeviceRadixSort::SortPairs(s->sort_tmp.get(), sort_bytes, (const unsigned long long*)s->keys_in.get(),
+                                                          s->keys_out.get(), (const unsigned int*)s->vals_in.get(), s->vals_out.get(), (int)P, 0, 32 + splat_bits(tiles), st) == hipSuccess;
+            timer.mark(kStageSort);
+            ARTALK_LAUNCH(splat_ranges_kernel, dim3((P + 255) / 256), dim3(256), 0, st, P, (const unsigned long long*)s->keys_out.get(), s->ranges.get(), tiles);
+            timer.mark(kStageRanges);
         }
         const float* col_t = colors_dev ? colors_dev + (long)t * colors_stride : nullptr;
         const int vec = (((unsigned long long)col_t) & 15) == 0 ? 1 : 0;
-        ARTALK_LAUNCH(splat_blend_kernel, dim3(v.gx, v.gy), dim3(256), 0, st, v, (const uint2*)s->ranges.p, (const unsigned int*)s->vals_out.p,
-                      (const float2*)s->xy.p, (const float4*)s->conic.p, col_t, vec, bg_dev_or_null, out_dev + (long)t * kSplatCh * HW);
-        mark(kStageBlend);
+        ARTALK_LAUNCH(splat_blend_kernel, dim3(v.gx, v.gy), dim3(256), 0, st, v, (const uint2*)s->ranges.get(), (const unsigned int*)s->vals_out.get(),
+                      (const float2*)s->xy.get(), (const float4*)s->conic.get(), col_t, vec, bg_dev_or_null, out_dev + (long)t * kSplatCh * HW);
+        timer.mark(kStageBlend);
     }
-    if (s->timing && !ev.empty()) {
-        (void)hipEventSynchronize(ev.back());
-        for (size_t k = 1; k < ev.size(); ++k) {
-            float ms = 0.f;
-            if (ev_stage[k] >= 0 && hipEventElapsedTime(&ms, ev[k - 1], ev[k]) == hipSuccess) s->stage_ms[ev_stage[k]] += ms;
-        }
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
+    timer.finish(s->stage_ms, kSplatStages);
     if (!ok || hipGetLastError() != hipSuccess) { s->err = "a launch failed"; return ARTALK_EHIP; }
     return ARTALK_OK;
 }

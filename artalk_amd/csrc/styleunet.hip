@@ -20,6 +20,7 @@
 
 #include "artalk_hip.h"
 #include "common.h"
+#include "device_mem.h"
 
 namespace artalk {
 
@@ -339,8 +340,8 @@ struct artalk_styleunet {
     int64_t frame_floats = 0;
     std::map<std::string, SuSlot> slots;
     std::vector<std::string> order;
-    std::vector<void*> allocs;
-    float* ws = nullptr;
+    std::vector<DevBuf<float>> weights;      // every uploaded tensor
+    DevBuf<float> ws;
     // device weights
     SuConv first, final_conv;
     std::vector<SuConv> dn1, dn2, dnsk, up1, up2, upsk, cs0, cs2, ch0, ch2;
@@ -350,7 +351,7 @@ struct artalk_styleunet {
     std::vector<SuMod> sconv, rgb;
     std::vector<const float*> noise_buf;
     // timing of the conv kernel (tools/styleunet_bench.py)
-    std::vector<hipEvent_t> ev; size_t ev_used = 0; double conv_ms = 0, total_ms = 0;
+    std::vector<Event> ev; size_t ev_used = 0; double conv_ms = 0, total_ms = 0;      // ev: start / stop pairs, kept from call to call
     std::string err;
 };
 
@@ -430,7 +431,7 @@ struct SuRun {
     int64_t off = 0, peak = 0;      // a stack: what a block needs only inside itself is released at its end (one stream: reuse is ordered)
     float* alloc(int64_t per_frame) {
         per_frame = (per_frame + 3) & ~(int64_t)3;
-        float* p = dry ? nullptr : u->ws + off;      // off counts floats: of one frame (dry) or of the n frames of this slab
+        float* p = dry ? nullptr : u->ws.get() + off;      // off counts floats: of one frame (dry) or of the n frames of this slab
         off += per_frame * (dry ? 1 : n);
         if (off > peak) peak = off;
         return p;
@@ -447,10 +448,10 @@ struct SuRun {
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (u->timing) {
             if (u->ev_used + 2 > u->ev.size()) {
-                hipEvent_t a0, a1;
-                if (hipEventCreate(&a0) == hipSuccess && hipEventCreate(&a1) == hipSuccess) { u->ev.push_back(a0); u->ev.push_back(a1); }
+                Event a0, a1;
+                if (a0.create() && a1.create()) { u->ev.push_back(std::move(a0)); u->ev.push_back(std::move(a1)); }
             }
-            if (u->ev_used + 2 <= u->ev.size()) { e0 = u->ev[u->ev_used]; e1 = u->ev[u->ev_used + 1]; u->ev_used += 2; }
+            if (u->ev_used + 2 <= u->ev.size()) { e0 = u->ev[u->ev_used].get(); e1 = u->ev[u->ev_used + 1].get(); u->ev_used += 2; }
         }
         launch_conv(a, s, e0, e1);
     }
@@ -569,17 +570,30 @@ struct SuRun {
 
 }  // namespace
 
+// the per-layer noise arguments of artalk_styleunet_forward and artalk_gaga_render (ptrs == NULL: the module's own noise)
+int artalk::su_check_noise(int num_layers, const float* const* ptrs, const int64_t* strides, std::string* err) {
+    if (!ptrs) return ARTALK_OK;
+    if (!strides) { *err = "noise_batch_strides must not be NULL when noise_ptrs is given"; return ARTALK_EINVAL; }
+    for (int l = 0; l < num_layers; ++l) {
+        const int64_t r = 1 << ((l + 5) / 2);
+        if (!ptrs[l]) { *err = "noise_ptrs[" + std::to_string(l) + "] is NULL"; return ARTALK_EINVAL; }
+        if (strides[l] != 0 && strides[l] < r * r) {
+            *err = "noise_batch_strides[" + std::to_string(l) + "] must be 0 or at least " + std::to_string(r * r);
+            return ARTALK_EINVAL;
+        }
+    }
+    return ARTALK_OK;
+}
+
 extern "C" {
 
 const char* artalk_styleunet_last_error(const artalk_styleunet* u) { return u ? u->err.c_str() : g_su_error.c_str(); }
 
 void artalk_styleunet_destroy(artalk_styleunet* u) {
     if (!u) return;
-    if (!u->allocs.empty() || !u->ev.empty()) {
+    if (!u->weights.empty() || !u->ev.empty()) {      // (else nothing was ever taken from the device)
         (void)hipSetDevice(u->device);
         (void)hipDeviceSynchronize();
-        for (void* p : u->allocs) if (p) (void)hipFree(p);
-        for (hipEvent_t e : u->ev) (void)hipEventDestroy(e);
     }
     delete u;
 }
@@ -667,11 +681,9 @@ int artalk_styleunet_finalize(artalk_styleunet* u) {
     if (hipSetDevice(u->device) != hipSuccess) return su_fail(u, ARTALK_EHIP, "hipSetDevice failed");
     bool ok = true;
     auto upload = [&](const std::vector<float>& v) -> const float* {
-        void* p = nullptr;
-        if (hipMalloc(&p, (v.empty() ? 1 : v.size()) * sizeof(float)) != hipSuccess) { ok = false; return nullptr; }
-        u->allocs.push_back(p);
-        if (!v.empty() && hipMemcpy(p, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) ok = false;
-        return (const float*)p;
+        u->weights.emplace_back();
+        if (!u->weights.back().upload(v.data(), v.size())) ok = false;
+        return u->weights.back().get();
     };
     auto host = [&](const std::string& k) -> const std::vector<float>& { return u->slots[k].host; };
     // [Cout][Cin][k][k] -> [k k][Cin][Cout]
@@ -748,12 +760,9 @@ int artalk_styleunet_finalize(artalk_styleunet* u) {
     }
     u->noise_buf.resize(u->num_layers);
     for (int l = 0; l < u->num_layers; ++l) u->noise_buf[l] = upload(host(d + "noises.noise" + std::to_string(l)));
-    void* ws = nullptr;
-    if (ok && hipMalloc(&ws, (size_t)u->frame_floats * u->slab_max * sizeof(float)) != hipSuccess) {
+    if (ok && !u->ws.alloc((size_t)u->frame_floats * u->slab_max)) {
         return su_fail(u, ARTALK_EHIP, "hipMalloc of the workspace failed (" + std::to_string(u->frame_floats * u->slab_max * 4) + " bytes)");
     }
-    if (ws) u->allocs.push_back(ws);
-    u->ws = (float*)ws;
     if (!ok || hipDeviceSynchronize() != hipSuccess) return su_fail(u, ARTALK_EHIP, "uploading the weights failed");
     for (auto& kv : u->slots) { std::vector<float>().swap(kv.second.host); }
     u->finalized = true;
@@ -797,26 +806,19 @@ int artalk_styleunet_forward(artalk_styleunet* u, const float* x_dev, int B, con
     if (!u->finalized) return su_fail(u, ARTALK_ESTATE, "artalk_styleunet_forward before artalk_styleunet_finalize");
     if (B < 0) return su_fail(u, ARTALK_EINVAL, "B must not be negative");
     if (!x_dev || !out_dev) return su_fail(u, ARTALK_EINVAL, "x and out must not be NULL");
-    if (noise_ptrs_or_null) {
-        if (!noise_batch_strides) return su_fail(u, ARTALK_EINVAL, "noise_batch_strides must not be NULL when noise_ptrs is given");
-        for (int l = 0; l < u->num_layers; ++l) {
-            const int64_t r = 1 << ((l + 5) / 2);
-            if (!noise_ptrs_or_null[l]) return su_fail(u, ARTALK_EINVAL, "noise_ptrs[" + std::to_string(l) + "] is NULL");
-            if (noise_batch_strides[l] != 0 && noise_batch_strides[l] < r * r)
-                return su_fail(u, ARTALK_EINVAL, "noise_batch_strides[" + std::to_string(l) + "] must be 0 or at least " + std::to_string(r * r));
-        }
-    }
+    const int rc = su_check_noise(u->num_layers, noise_ptrs_or_null, noise_batch_strides, &u->err);
+    if (rc != ARTALK_OK) return rc;
     if (B == 0) return ARTALK_OK;
     (void)hipSetDevice(u->device);
     hipStream_t s = (hipStream_t)stream;
     const long SS = (long)u->S * u->S;
     std::vector<const float*> np(u->num_layers);
     std::vector<int64_t> ns(u->num_layers);
-    hipEvent_t t0 = nullptr, t1 = nullptr;
+    Event t0, t1;
     if (u->timing) {
         u->ev_used = 0;
-        if (hipEventCreate(&t0) != hipSuccess || hipEventCreate(&t1) != hipSuccess) return su_fail(u, ARTALK_EHIP, "hipEventCreate failed");
-        (void)hipEventRecord(t0, s);
+        if (!t0.create() || !t1.create()) return su_fail(u, ARTALK_EHIP, "hipEventCreate failed");
+        (void)hipEventRecord(t0.get(), s);
     }
     for (int b0 = 0; b0 < B; b0 += u->slab) {
         const int n = B - b0 < u->slab ? B - b0 : u->slab;
@@ -829,14 +831,13 @@ int artalk_styleunet_forward(artalk_styleunet* u, const float* x_dev, int B, con
     }
     if (hipGetLastError() != hipSuccess) return su_fail(u, ARTALK_EHIP, "kernel launch failed");
     if (u->timing) {
-        (void)hipEventRecord(t1, s);
-        if (hipEventSynchronize(t1) != hipSuccess) return su_fail(u, ARTALK_EHIP, "the call failed on the device");
+        (void)hipEventRecord(t1.get(), s);
+        if (hipEventSynchronize(t1.get()) != hipSuccess) return su_fail(u, ARTALK_EHIP, "the call failed on the device");
         float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, t0, t1);
+        (void)hipEventElapsedTime(&ms, t0.get(), t1.get());
         u->total_ms = ms;
         u->conv_ms = 0;
-        for (size_t i = 0; i + 1 < u->ev_used; i += 2) { float k = 0.f; if (hipEventElapsedTime(&k, u->ev[i], u->ev[i + 1]) == hipSuccess) u->conv_ms += k; }
-        (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
+        for (size_t i = 0; i + 1 < u->ev_used; i += 2) { float k = 0.f; if (hipEventElapsedTime(&k, u->ev[i].get(), u->ev[i + 1].get()) == hipSuccess) u->conv_ms += k; }
     }
     return ARTALK_OK;
 }
