@@ -37,6 +37,7 @@ SYMBOLS = [
     "artalk_styleunet_create", "artalk_styleunet_set_tensor", "artalk_styleunet_finalize", "artalk_styleunet_forward",
     "artalk_styleunet_set_slab", "artalk_styleunet_set_timing", "artalk_styleunet_get_timing", "artalk_styleunet_destroy",
     "artalk_styleunet_last_error", "artalk_op_conv2d", "artalk_op_resample2",
+    "artalk_styleunet_set_precision", "artalk_styleunet_get_precision", "artalk_op_conv2d_ex", "artalk_styleunet_get_launch_timing",
     "artalk_flame_dims", "artalk_styleunet_dims",
     "artalk_gaga_create", "artalk_gaga_set_avatar", "artalk_gaga_set_forehead", "artalk_gaga_set_watermark", "artalk_gaga_reset_state",
     "artalk_gaga_set_slab", "artalk_gaga_render", "artalk_gaga_set_timing", "artalk_gaga_get_timing", "artalk_gaga_destroy",
@@ -266,6 +267,15 @@ def lib() -> C.CDLL:
         L.artalk_op_conv2d.restype = i32
         L.artalk_op_resample2.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
         L.artalk_op_resample2.restype = i32
+    if hasattr(L, "artalk_styleunet_set_precision"):      # (an older build loaded through ARTALK_LIB for an A/B run lacks the bf16 modes)
+        L.artalk_styleunet_set_precision.argtypes = [vp, i32]
+        L.artalk_styleunet_set_precision.restype = i32
+        L.artalk_styleunet_get_precision.argtypes = [vp]
+        L.artalk_styleunet_get_precision.restype = i32
+        L.artalk_styleunet_get_launch_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int32), i32]
+        L.artalk_styleunet_get_launch_timing.restype = i32
+        L.artalk_op_conv2d_ex.argtypes = L.artalk_op_conv2d.argtypes[:-1] + [i32, vp]
+        L.artalk_op_conv2d_ex.restype = i32
     if hasattr(L, "artalk_gaga_create"):      # (an older build loaded through ARTALK_LIB for an A/B run lacks the GAGAvatar head)
         pi = C.POINTER(i32)
         L.artalk_flame_dims.argtypes = [vp, pi, pi, C.POINTER(f32)]

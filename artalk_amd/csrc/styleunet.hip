@@ -5,6 +5,7 @@
 //   conv_mfma_kernel   k x k (1 or 3), stride 1, zero padding k / 2: M = B H W pixels, N = Cout, K = k k Cin on
 //                      v_mfma_f32_32x32x2f32, with the input scale (modulation) as prologue and, as epilogue in this order, output
 //                      scale (demodulation), gain, noise, bias, LeakyReLU 0.2, SFT and residual
+//                      (its bf16x3 / bf16 counterpart, selected by artalk_styleunet_set_precision, is styleunet_bf16.hip)
 //   resample2_kernel   bilinear x2 (0.25 / 0.75, edges clamped) and x0.5 (2 x 2 mean), align_corners = False
 //   linear / normstyle / demod kernels: the GEMV-sized style path, one wave per output value, fixed summation order
 //
@@ -21,25 +22,11 @@
 #include "artalk_hip.h"
 #include "common.h"
 #include "device_mem.h"
+#include "styleunet_conv.h"
 
 namespace artalk {
 
 // ------------------------------------------------------------------ convolution ------------------------------------------------------
-struct ConvArgs {
-    const float* x; long x_bstride;      // [B][H][W][Cin]; elements between two samples (0: one image for every sample)
-    const float* w;                      // [k k][Cin][Cout]
-    float* out;                          // [B][H][W][Cout]
-    int B, H, W, Cin, Cout, k;
-    const float* in_scale; long in_scale_ld;      // [B][in_scale_ld >= Cin] or null
-    const float* out_scale;              // [B][Cout] or null
-    float gain;                          // 1: none
-    const float* noise; long noise_bstride; const float* noise_w;      // [B or 1][H][W], one device float; null: none
-    const float* bias;                   // [Cout] or null
-    int lrelu;
-    const float* sft_scale; const float* sft_shift;      // [B][H][W][Cout] or null (both or neither)
-    const float* res;                    // [B][H][W][Cout] or null
-};
-
 constexpr int CV_BM = 128, CV_BK = 16;
 constexpr int CV_LDA = CV_BM + 32;      // pitches = 32 mod 64 banks: the two half-waves of a fragment read (k, k + 1) hit disjoint banks
 constexpr int CV_LDB = 96;
@@ -165,30 +152,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvArgs a) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) acc[j] += mid[j];
 
-    // ---- epilogue: lane (r, h) holds output channel n0 + 32 j + r of pixels 32 wave + 8 q + 4 h + e ----
-    const float nw = a.noise ? a.noise_w[0] : 0.f;
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int co = n0 + j * 32 + r;
-        if (co >= a.Cout) continue;
-        const float bv = a.bias ? a.bias[co] : 0.f;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const long m = m0 + wave * 32 + 8 * (v >> 2) + 4 * h + (v & 3);
-            if (m >= M) continue;
-            const int b = (int)(m / HW);
-            float o = acc[j][v];
-            if (a.out_scale) o *= a.out_scale[(long)b * a.Cout + co];
-            if (a.gain != 1.f) o *= a.gain;
-            if (a.noise) o += nw * a.noise[(long)b * a.noise_bstride + (m - (long)b * HW)];
-            o += bv;
-            if (a.lrelu) o = o >= 0.f ? o : o * 0.2f;
-            const long idx = m * a.Cout + co;
-            if (a.sft_scale) o = o * a.sft_scale[idx] + a.sft_shift[idx];
-            if (a.res) o += a.res[idx];
-            a.out[idx] = o;
-        }
-    }
+    conv_epilogue<NT>(a, acc, m0, n0, wave, r, h, M, HW);
 }
 
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -328,7 +292,7 @@ namespace {
 
 struct SuSlot { std::vector<int64_t> shape; std::vector<float> host; bool set = false; };
 
-struct SuConv { const float* w = nullptr; const float* b = nullptr; int cin = 0, cout = 0, k = 0; };
+struct SuConv { const float* w = nullptr; const float* b = nullptr; int cin = 0, cout = 0, k = 0; const void* wp = nullptr; };      // wp: packed for the bf16 modes
 struct SuMod { SuConv c; const float* wsq = nullptr; const float* nw = nullptr; int mod_off = 0; };      // nw, wsq: style convs only
 
 }  // namespace
@@ -336,11 +300,13 @@ struct SuMod { SuConv c; const float* wsq = nullptr; const float* nw = nullptr; 
 struct artalk_styleunet {
     int device = 0, in_dim = 0, out_dim = 0, S = 0, L = 0, num_layers = 0;
     bool finalized = false, timing = false;
+    int precision = CONV_PRECISION_F32;      // of the convolutions (artalk_styleunet_set_precision)
     int slab_max = 1, slab = 1;
     int64_t frame_floats = 0;
     std::map<std::string, SuSlot> slots;
     std::vector<std::string> order;
     std::vector<DevBuf<float>> weights;      // every uploaded tensor
+    std::vector<DevBuf<uint16_t>> packed;    // bf16 hi / lo planes of every conv weight: empty until a bf16 mode is first selected
     DevBuf<float> ws;
     // device weights
     SuConv first, final_conv;
@@ -352,6 +318,8 @@ struct artalk_styleunet {
     std::vector<const float*> noise_buf;
     // timing of the conv kernel (tools/styleunet_bench.py)
     std::vector<Event> ev; size_t ev_used = 0; double conv_ms = 0, total_ms = 0;      // ev: start / stop pairs, kept from call to call
+    std::vector<int32_t> ev_geom;            // per timed launch: frames, H, Cin, Cout, k
+    std::vector<double> launch_ms;           // per timed launch of the last call
     std::string err;
 };
 
@@ -451,9 +419,13 @@ struct SuRun {
                 Event a0, a1;
                 if (a0.create() && a1.create()) { u->ev.push_back(std::move(a0)); u->ev.push_back(std::move(a1)); }
             }
-            if (u->ev_used + 2 <= u->ev.size()) { e0 = u->ev[u->ev_used].get(); e1 = u->ev[u->ev_used + 1].get(); u->ev_used += 2; }
+            if (u->ev_used + 2 <= u->ev.size()) {
+                e0 = u->ev[u->ev_used].get(); e1 = u->ev[u->ev_used + 1].get(); u->ev_used += 2;
+                for (int v : {n, H, c.cin, c.cout, c.k}) u->ev_geom.push_back(v);
+            }
         }
-        launch_conv(a, s, e0, e1);
+        if (u->precision != CONV_PRECISION_F32) launch_conv_bf16(a, c.wp, u->precision, s, e0, e1);
+        else launch_conv(a, s, e0, e1);
     }
     void resample(const float* x, float* out, int H, int C, int up) {
         if (dry) return;
@@ -567,6 +539,26 @@ struct SuRun {
                                 activation);
     }
 };
+
+// Packs every conv weight for the bf16 modes (once per module; the null stream, and waits for it).
+bool su_pack_bf16(artalk_styleunet* u) {
+    if (!u->packed.empty()) return true;
+    std::vector<SuConv*> all = {&u->first, &u->final_conv, &u->sc1.c, &u->rgb1.c};
+    for (auto* v : {&u->dn1, &u->dn2, &u->dnsk, &u->up1, &u->up2, &u->upsk, &u->cs0, &u->cs2, &u->ch0, &u->ch2})
+        for (SuConv& c : *v) all.push_back(&c);
+    for (auto* v : {&u->sconv, &u->rgb})
+        for (SuMod& m : *v) all.push_back(&m.c);
+    bool ok = true;
+    for (SuConv* c : all) {
+        u->packed.emplace_back();
+        if (!u->packed.back().alloc(conv_packed_elems(c->cin, c->cout, c->k))) { ok = false; break; }
+        c->wp = u->packed.back().get();
+        launch_conv_pack(c->w, u->packed.back().get(), c->cin, c->cout, c->k, nullptr);
+    }
+    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) ok = false;
+    if (!ok) u->packed.clear();
+    return ok;
+}
 
 }  // namespace
 
@@ -765,8 +757,26 @@ int artalk_styleunet_finalize(artalk_styleunet* u) {
     }
     if (!ok || hipDeviceSynchronize() != hipSuccess) return su_fail(u, ARTALK_EHIP, "uploading the weights failed");
     for (auto& kv : u->slots) { std::vector<float>().swap(kv.second.host); }
+    if (u->precision != CONV_PRECISION_F32 && !su_pack_bf16(u)) return su_fail(u, ARTALK_EHIP, "packing the conv weights for the bf16 modes failed");
     u->finalized = true;
     return ARTALK_OK;
+}
+
+int artalk_styleunet_set_precision(artalk_styleunet* u, int mode) {
+    if (!u) { g_su_error = "handle is NULL"; return ARTALK_EINVAL; }
+    if (mode != CONV_PRECISION_F32 && mode != CONV_PRECISION_BF16X3 && mode != CONV_PRECISION_BF16)
+        return su_fail(u, ARTALK_EINVAL, "precision must be 0 (f32), 1 (bf16x3) or 2 (bf16)");
+    if (mode != CONV_PRECISION_F32 && u->finalized) {      // (before finalize the mode is only remembered)
+        if (hipSetDevice(u->device) != hipSuccess) return su_fail(u, ARTALK_EHIP, "hipSetDevice failed");
+        if (!su_pack_bf16(u)) return su_fail(u, ARTALK_EHIP, "packing the conv weights for the bf16 modes failed");
+    }
+    u->precision = mode;
+    return ARTALK_OK;
+}
+
+int artalk_styleunet_get_precision(const artalk_styleunet* u) {
+    if (!u) { g_su_error = "handle is NULL"; return ARTALK_EINVAL; }
+    return u->precision;
 }
 
 int artalk_styleunet_set_slab(artalk_styleunet* u, int frames) {
@@ -800,6 +810,16 @@ int artalk_styleunet_get_timing(const artalk_styleunet* u, double* conv_ms, doub
     return ARTALK_OK;
 }
 
+int artalk_styleunet_get_launch_timing(const artalk_styleunet* u, double* launch_ms, int32_t* geometry, int n) {
+    if (!u) { g_su_error = "handle is NULL"; return ARTALK_EINVAL; }
+    const int have = (int)u->launch_ms.size();
+    for (int i = 0; i < have && i < n; ++i) {
+        if (launch_ms) launch_ms[i] = u->launch_ms[i];
+        if (geometry) for (int e = 0; e < 5; ++e) geometry[5 * i + e] = u->ev_geom[5 * (size_t)i + e];
+    }
+    return have;
+}
+
 int artalk_styleunet_forward(artalk_styleunet* u, const float* x_dev, int B, const float* const* noise_ptrs_or_null,
                              const int64_t* noise_batch_strides, int activation, float* out_dev, void* stream) {
     if (!u) { g_su_error = "handle is NULL"; return ARTALK_EINVAL; }
@@ -817,6 +837,7 @@ int artalk_styleunet_forward(artalk_styleunet* u, const float* x_dev, int B, con
     Event t0, t1;
     if (u->timing) {
         u->ev_used = 0;
+        u->ev_geom.clear();
         if (!t0.create() || !t1.create()) return su_fail(u, ARTALK_EHIP, "hipEventCreate failed");
         (void)hipEventRecord(t0.get(), s);
     }
@@ -837,27 +858,50 @@ int artalk_styleunet_forward(artalk_styleunet* u, const float* x_dev, int B, con
         (void)hipEventElapsedTime(&ms, t0.get(), t1.get());
         u->total_ms = ms;
         u->conv_ms = 0;
-        for (size_t i = 0; i + 1 < u->ev_used; i += 2) { float k = 0.f; if (hipEventElapsedTime(&k, u->ev[i].get(), u->ev[i + 1].get()) == hipSuccess) u->conv_ms += k; }
+        u->launch_ms.assign(u->ev_used / 2, 0.0);
+        for (size_t i = 0; i + 1 < u->ev_used; i += 2) {
+            float k = 0.f;
+            if (hipEventElapsedTime(&k, u->ev[i].get(), u->ev[i + 1].get()) == hipSuccess) { u->conv_ms += k; u->launch_ms[i / 2] = k; }
+        }
     }
     return ARTALK_OK;
 }
 
-int artalk_op_conv2d(const float* x, int64_t x_bstride, const float* w, float* out, int B, int H, int W, int Cin, int Cout, int k,
-                     const float* in_scale, const float* out_scale, float gain, const float* noise, int64_t noise_bstride,
-                     const float* noise_weight, const float* bias, int lrelu, const float* sft_scale, const float* sft_shift,
-                     const float* residual, void* stream) {
+int artalk_op_conv2d_ex(const float* x, int64_t x_bstride, const float* w, float* out, int B, int H, int W, int Cin, int Cout, int k,
+                        const float* in_scale, const float* out_scale, float gain, const float* noise, int64_t noise_bstride,
+                        const float* noise_weight, const float* bias, int lrelu, const float* sft_scale, const float* sft_shift,
+                        const float* residual, int precision, void* stream) {
     if (!x || !w || !out) return ARTALK_EINVAL;
     if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || (k != 1 && k != 3)) return ARTALK_EINVAL;
     if ((int64_t)B * H * W > (int64_t)1 << 30 || (int64_t)H * W > INT_MAX) return ARTALK_EINVAL;
     if (x_bstride != 0 && x_bstride < (int64_t)H * W * Cin) return ARTALK_EINVAL;
     if (noise && (!noise_weight || (noise_bstride != 0 && noise_bstride < (int64_t)H * W))) return ARTALK_EINVAL;
     if ((sft_scale == nullptr) != (sft_shift == nullptr)) return ARTALK_EINVAL;
+    if (precision != CONV_PRECISION_F32 && precision != CONV_PRECISION_BF16X3 && precision != CONV_PRECISION_BF16) return ARTALK_EINVAL;
     ConvArgs a{};
     a.x = x; a.x_bstride = x_bstride; a.w = w; a.out = out; a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.k = k;
     a.in_scale = in_scale; a.in_scale_ld = Cin; a.out_scale = out_scale; a.gain = gain; a.noise = noise; a.noise_bstride = noise_bstride; a.noise_w = noise_weight;
     a.bias = bias; a.lrelu = lrelu; a.sft_scale = sft_scale; a.sft_shift = sft_shift; a.res = residual;
-    launch_conv(a, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+    hipStream_t s = (hipStream_t)stream;
+    if (precision == CONV_PRECISION_F32) {
+        launch_conv(a, s);
+        return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+    }
+    // the packed weight lives for this call only: pack and conv run on the caller's stream, and the call waits for them before it frees
+    DevBuf<uint16_t> packed;
+    if (!packed.alloc(conv_packed_elems(Cin, Cout, k))) return ARTALK_EHIP;
+    launch_conv_pack(w, packed.get(), Cin, Cout, k, s);
+    launch_conv_bf16(a, packed.get(), precision, s);
+    const bool ok = hipGetLastError() == hipSuccess;
+    return hipStreamSynchronize(s) == hipSuccess && ok ? ARTALK_OK : ARTALK_EHIP;
+}
+
+int artalk_op_conv2d(const float* x, int64_t x_bstride, const float* w, float* out, int B, int H, int W, int Cin, int Cout, int k,
+                     const float* in_scale, const float* out_scale, float gain, const float* noise, int64_t noise_bstride,
+                     const float* noise_weight, const float* bias, int lrelu, const float* sft_scale, const float* sft_shift,
+                     const float* residual, void* stream) {
+    return artalk_op_conv2d_ex(x, x_bstride, w, out, B, H, W, Cin, Cout, k, in_scale, out_scale, gain, noise, noise_bstride, noise_weight, bias,
+                               lrelu, sft_scale, sft_shift, residual, CONV_PRECISION_F32, stream);
 }
 
 int artalk_op_resample2(const float* x, float* out, int B, int H, int W, int C, int up, void* stream) {

@@ -24,7 +24,7 @@ from .model import BitwiseARModel
 class ARTAvatarInferEngine:
     def __init__(self, load_gaga=False, fix_pose=False, clip_length=750, device="cuda",
                  ckpt_path="./assets/ARTalk_wav2vec.pt", config_path=None, state_dict=None, config=None, model=None,
-                 calibration=None, precision=None, gaga=None, gaga_flame=None):
+                 calibration=None, precision=None, gaga=None, gaga_flame=None, gaga_precision=None):
         """Arguments of the reference class, plus (all optional): ``state_dict`` / ``config`` instead of a checkpoint file, ``model``
         (an already loaded BitwiseARModel), and ``calibration`` - the f16x3 site scales to start from: a ``save_scales`` file or a
         ``{site: exponent}`` dict (``load_scales``), or a sequence of 16 kHz audio tensors to calibrate on once here (``calibrate``).
@@ -32,7 +32,9 @@ class ARTAvatarInferEngine:
         ``precision``: the GEMM arithmetic (``BitwiseARModel.set_precision``: 'f16x3', 'f32' or 'bf16'); None keeps the model's.
         ``gaga``: an ``artalk_amd.gaga.GAGAvatar`` or the path of an avatar pack (``GAGAvatar.load``), with ``gaga_flame``, an
         ``artalk_amd.flame.FLAMEModel`` built with ``scale=5.0``: the photoreal head behind ``rendering(shape_id=<avatar id>)``.
-        Both can also be plugged into ``engine.GAGAvatar`` / ``engine.GAGAvatar_flame`` later, like ``flame_model``."""
+        Both can also be plugged into ``engine.GAGAvatar`` / ``engine.GAGAvatar_flame`` later, like ``flame_model``.
+        ``gaga_precision``: the arithmetic of the head's upsampler convolutions (``GAGAvatar.set_precision``: 'f32', 'bf16x3' or
+        'bf16'); None keeps the head's."""
         if load_gaga and gaga is None:
             raise NotImplementedError("load_gaga=True needs gaga=: an artalk_amd.gaga.GAGAvatar or the path of an avatar pack.  The "
                                       "reference builds its avatars with DINOv2 from torch.hub, which is not part of this package: "
@@ -75,6 +77,8 @@ class ARTAvatarInferEngine:
         if gaga is not None:
             from .gaga import GAGAvatar
             self.GAGAvatar = gaga if isinstance(gaga, GAGAvatar) else GAGAvatar.load(gaga, device=device)
+            if gaga_precision is not None:
+                self.GAGAvatar.set_precision(gaga_precision)
 
     def set_style_motion(self, style_motion):
         if isinstance(style_motion, str):

@@ -190,6 +190,16 @@ class GAGAvatar:
             return frames
         return int(capi.lib().artalk_gaga_set_slab(self._h, frames))
 
+    def set_precision(self, name):
+        """The arithmetic of the upsampler's convolutions (``StyleUNet.set_precision``: 'f32', 'bf16x3' or 'bf16').  The upsampler's
+        handle does not change, so the library object and with it the forehead EMA state survive a switch."""
+        self.upsampler.set_precision(name)
+        return self
+
+    @property
+    def precision(self):
+        return self.upsampler.precision
+
     def build_forward_batch(self, motion_code, flame_model):
         """The reference's two-step form.  The batch here is a handle for ``forward_expression``: the motion rows (a copy: unlike the
         reference, ``motion_code`` is not modified), the FLAME model and ``t_transform`` (T, 3, 4), the per-frame cameras.  The vertices

@@ -1,8 +1,9 @@
 """Device stand-in for the reference's ``StyleUNet`` (``app/GAGAvatar/modules/style_unet.py``), the upsampler that turns the
 32-channel splat image of the GAGAvatar head into RGB: a U-Net encoder whose up path feeds SFT conditions into a StyleGAN2 decoder.
-Forward only, exact fp32, all frames of a call in one library call on top of ``artalk_styleunet_*`` (``include/artalk_hip.h``,
-``csrc/styleunet.hip``).  What is computed is written out in DESIGN.md ("StyleUNet upsampler").  Only synthetic weights are checked:
-parity on real GAGAvatar checkpoints is unpinned.  There is no CPU fallback.
+Forward only, exact fp32 by default (``set_precision``: the convolutions in bf16x3 or bf16), all frames of a call in one library call on
+top of ``artalk_styleunet_*`` (``include/artalk_hip.h``, ``csrc/styleunet.hip``, ``csrc/styleunet_bf16.hip``).  What is computed is
+written out in DESIGN.md ("StyleUNet upsampler").  Only synthetic weights are checked: parity on real GAGAvatar checkpoints is
+unpinned.  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -18,6 +19,7 @@ from .weights import _rng
 UNET_CHANNELS = {4: 256, 8: 256, 16: 256, 32: 256, 64: 128, 128: 64, 256: 32, 512: 16, 1024: 8}
 DECODER_CHANNELS = {s: 2 * c for s, c in UNET_CHANNELS.items()}
 STYLE_FEAT, NUM_MLP = 512, 8
+PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16": 2}      # the modes of artalk_styleunet_set_precision
 
 
 def _check_size(out_size):
@@ -148,6 +150,27 @@ class StyleUNet:
         self._h = None
         self._loaded = False
         self._pending = None
+        self._precision = "f32"
+
+    # ---- precision of the convolutions ----
+    @property
+    def precision(self):
+        return self._precision
+
+    def set_precision(self, name):
+        """``"f32"`` (the default, exact fp32), ``"bf16x3"`` (three bf16 MFMA products per operand pair: within a few 1e-5 of fp32 on the
+        synthetic weights) or ``"bf16"`` (one product: a throughput mode, grey levels off).  DESIGN.md section 5, "Precision modes".
+        Accepted at any time: before the weights are on the device it is remembered, and it survives ``load_state_dict``."""
+        if name not in PRECISIONS:
+            raise ValueError(f"precision must be one of {', '.join(PRECISIONS)}, got {name!r}")
+        if self._h is not None:
+            self._apply_precision(name)
+        self._precision = name
+        return self
+
+    def _apply_precision(self, name):
+        if capi.lib().artalk_styleunet_set_precision(self._h, PRECISIONS[name]) != capi.OK:
+            raise RuntimeError("artalk_styleunet_set_precision failed: " + self._err())
 
     # ---- torch.nn.Module look-alikes ----
     def eval(self):
@@ -200,6 +223,7 @@ class StyleUNet:
         if rc != capi.OK:
             raise RuntimeError("artalk_styleunet_create failed: " + L.artalk_styleunet_last_error(None).decode())
         self._h = h
+        self._apply_precision(self._precision)      # host only before finalize: the mode is remembered, finalize packs for it
         errors = []
         for key, val in state_dict.items():
             t = val.detach().cpu() if isinstance(val, torch.Tensor) else torch.from_numpy(np.asarray(val))

@@ -258,7 +258,7 @@ int artalk_splat_get_timing(const artalk_splat* s, double* stage_ms, int n, long
 void artalk_splat_destroy(artalk_splat* s);
 const char* artalk_splat_last_error(const artalk_splat* s);
 
-/* StyleUNet upsampler of the GAGAvatar head, forward only, exact fp32: a stand-in for StyleUNet(in_size = out_size)
+/* StyleUNet upsampler of the GAGAvatar head, forward only, exact fp32 by default (precision modes below): a stand-in for StyleUNet(in_size = out_size)
  * (app/GAGAvatar/modules/style_unet.py), the consumer of the splat image.  What is computed is defined in DESIGN.md ("StyleUNet
  * upsampler").  Checked on synthetic weights only; parity on real GAGAvatar checkpoints is unpinned.
  * artalk_styleunet_create: out_size a power of two in 8..1024, in_dim / out_dim in 1..4096; host work only (the device is first touched by
@@ -277,12 +277,26 @@ const char* artalk_splat_last_error(const artalk_splat* s);
  * artalk_styleunet_set_slab: frames per pass over the workspace; 0 = the default chosen at create time (4 GiB of workspace, at most 64
  * frames), which is also the largest value accepted.  Returns the value in force.
  * artalk_styleunet_set_timing / get_timing (tools/styleunet_bench.py): with timing on, a call times its conv launches with event pairs
- * and WAITS at its end; get_timing returns the summed conv kernel time and the whole call's time of the last call, in ms.
+ * and WAITS at its end; get_timing returns the summed conv kernel time and the whole call's time of the last call, in ms;
+ * get_launch_timing returns the number of conv launches of the last timed call and fills, for the first n of them in launch order,
+ * launch_ms[i] and geometry[5 i ..] = frames, H (= W), Cin, Cout, k (either array may be NULL).
  * artalk_op_conv2d: one launch of the conv kernel on CHANNELS-LAST tensors.  x [B][H][W][Cin] (x_bstride elements between samples, 0 =
  * one image for all), w [k k][Cin][Cout] (k = 1 or 3, stride 1, zero padding k / 2), out [B][H][W][Cout].  Prologue: in_scale [B][Cin].
  * Epilogue, each part optional (NULL / gain 1 / lrelu 0), in this order: out_scale [B][Cout], gain, + noise_weight[0] *
  * noise [B or 1][H][W] (noise_bstride 0 = shared), + bias [Cout], LeakyReLU 0.2, * sft_scale + sft_shift and + residual (all
- * [B][H][W][Cout]).  artalk_op_resample2: channels-last bilinear x2 (up != 0) or x0.5 (H, W even), align_corners = False. */
+ * [B][H][W][Cout]).  artalk_op_resample2: channels-last bilinear x2 (up != 0) or x0.5 (H, W even), align_corners = False.
+ * Precision modes of the convolutions ("Precision modes"): 0 = f32 (the default, exact fp32), 1 = bf16x3 (operands
+ * split into bf16 hi + lo, three products on v_mfma_f32_32x32x16_bf16: within a few 1e-5 of fp32 on the synthetic weights), 2 = bf16 (one
+ * product: a throughput mode, several 8-bit grey levels off at out_size 64).  Accumulation and the epilogue stay fp32, and everything
+ * that is not a convolution keeps its kernels; bf16 has fp32's exponent range, so no mode needs scales, calibration or a range guard.
+ * artalk_styleunet_set_precision: ARTALK_EINVAL for a NULL handle or an unknown mode.  Before finalize the mode is only remembered (host
+ * work only); after finalize the first selection of a non-zero mode packs the conv weights on the device (+4 bytes per conv weight,
+ * waits for the device once) - a module that never selects one allocates nothing.  Switching changes neither the handle nor the
+ * workspace nor the slab, results stay bit-identical from run to run and for any split of the frames in every mode, and mode 0 gives
+ * the bits it gave before.  artalk_styleunet_get_precision: the mode in force, or ARTALK_EINVAL for a NULL handle.
+ * artalk_op_conv2d_ex: artalk_op_conv2d with a precision argument, from the same fp32 weights; precision 0 IS artalk_op_conv2d.  In modes
+ * 1 and 2 it packs the weight into a block it owns, on the caller's stream, WAITS for that stream and frees the block.  Every refusal
+ * (an unknown precision included) comes before the device is touched. */
 typedef struct artalk_styleunet artalk_styleunet;
 int artalk_styleunet_create(int device_id, int in_dim, int out_dim, int out_size, artalk_styleunet** out);
 int artalk_styleunet_set_tensor(artalk_styleunet* u, const char* key, const void* host_ptr, int ndim, const int64_t* shape);
@@ -292,12 +306,19 @@ int artalk_styleunet_forward(artalk_styleunet* u, const float* x_dev, int B, con
 int artalk_styleunet_set_slab(artalk_styleunet* u, int frames);
 int artalk_styleunet_set_timing(artalk_styleunet* u, int enable);
 int artalk_styleunet_get_timing(const artalk_styleunet* u, double* conv_ms, double* total_ms);
+int artalk_styleunet_get_launch_timing(const artalk_styleunet* u, double* launch_ms, int32_t* geometry, int n);
 void artalk_styleunet_destroy(artalk_styleunet* u);
 const char* artalk_styleunet_last_error(const artalk_styleunet* u);
 int artalk_op_conv2d(const float* x, int64_t x_bstride, const float* w, float* out, int B, int H, int W, int Cin, int Cout, int k,
                      const float* in_scale, const float* out_scale, float gain, const float* noise, int64_t noise_bstride,
                      const float* noise_weight, const float* bias, int lrelu, const float* sft_scale, const float* sft_shift,
                      const float* residual, void* stream);
+int artalk_styleunet_set_precision(artalk_styleunet* u, int mode);
+int artalk_styleunet_get_precision(const artalk_styleunet* u);
+int artalk_op_conv2d_ex(const float* x, int64_t x_bstride, const float* w, float* out, int B, int H, int W, int Cin, int Cout, int k,
+                        const float* in_scale, const float* out_scale, float gain, const float* noise, int64_t noise_bstride,
+                        const float* noise_weight, const float* bias, int lrelu, const float* sft_scale, const float* sft_shift,
+                        const float* residual, int precision, void* stream);
 int artalk_op_resample2(const float* x, float* out, int B, int H, int W, int C, int up, void* stream);
 
 /* Read-only views of a handle, for objects that borrow it (artalk_gaga below).  Both return the handle's device index, or ARTALK_EINVAL for

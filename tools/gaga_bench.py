@@ -15,6 +15,12 @@ image per frame against 3.29 ms of upsampler.
 
     python tools/gaga_bench.py --out profiles/gaga_bench.json
 
+``--precision f32|bf16x3|bf16`` runs the above with the upsampler's convolutions in that mode (the default is f32; the chain's upsampler
+is the same module, so it follows).  ``--precision all`` compares the modes instead (no chain): in every round of the one process the
+three modes alternate, each with a plain call and a stage-timed call, so the baseline is the f32 mode of the same build in the same rounds.
+
+    python tools/gaga_bench.py --precision all --out profiles/gaga_precision_bench.json
+
 Prints one JSON line; --out also writes it to a file.  Needs the GPU: without one it fails.
 """
 import argparse
@@ -73,6 +79,7 @@ def main():
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--precision", choices=("f32", "bf16x3", "bf16", "all"), default="f32")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
 
@@ -111,6 +118,49 @@ def main():
     lib_call = lambda: head.render_clip(codes, flame, randomize_noise=False)
     lib_call()      # builds the library object
     slab = head.slab_in_force()
+    if args.precision == "all":
+        modes = ("f32", "bf16x3", "bf16")
+        handle = head._h.value
+        frames = {}
+        for m in modes:
+            head.set_precision(m)
+            head.reset_motion_state()
+            frames[m] = lib_call()
+            for _ in range(args.warmup):
+                timed(lib_call)
+        call, stage = {m: [] for m in modes}, {m: [] for m in modes}
+        st = (C.c_double * len(STAGES))()
+        for _ in range(args.rounds):
+            for m in modes:
+                head.set_precision(m)
+                L.artalk_gaga_set_timing(head._h, 0)
+                call[m].append(timed(lib_call)[0])
+                L.artalk_gaga_set_timing(head._h, 1)
+                lib_call()
+                L.artalk_gaga_get_timing(head._h, st, len(STAGES))
+                stage[m].append(list(st))
+        L.artalk_gaga_set_timing(head._h, 0)
+        assert head._h.value == handle, "a switch rebuilt the library object"
+        f32 = statistics.median(call["f32"])
+        res = {
+            "workload": f"GAGAvatar.render_clip, S = {S}, V = {V}, N = {N}, T = {T} frames per call in slabs of {slab}, synthetic FLAME asset, "
+                        f"avatar and upsampler weights, stored noise, {mark.shape[1]} x {mark.shape[2]} watermark, 68 forehead vertices; HIP "
+                        f"events, {args.warmup} warm-up calls per mode, {args.rounds} rounds in one process, each round running the upsampler "
+                        f"modes f32, bf16x3, bf16 in turn: a plain call and a stage-timed call",
+            "modes": {m: {"ms_per_call": {"median": statistics.median(call[m]), "min": min(call[m]), "max": max(call[m])},
+                          "ms_per_frame": statistics.median(call[m]) / T, "frames_per_s": 1e3 * T / statistics.median(call[m]),
+                          "speedup_over_f32": f32 / statistics.median(call[m]),
+                          "stage_ms_per_frame": {n: statistics.median(s[i] for s in stage[m]) / T for i, n in enumerate(STAGES)},
+                          "max_abs_difference_to_f32_frames": float((frames[m] - frames["f32"]).abs().max())} for m in modes},
+        }
+        line = json.dumps(res)
+        print(line)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        return
+    head.set_precision(args.precision)
     upper = {"state": None}
 
     def chain():
@@ -158,7 +208,7 @@ def main():
     stages = {n: statistics.median(s[i] for s in stage_ms) / T for i, n in enumerate(STAGES)}
     total = sum(stages.values())
     res = {
-        "workload": f"GAGAvatar.render_clip, S = {S}, V = {V}, N = {N}, T = {T} frames per call in slabs of {slab}, synthetic FLAME asset, avatar "
+        "workload": f"GAGAvatar.render_clip, upsampler precision {args.precision}, S = {S}, V = {V}, N = {N}, T = {T} frames per call in slabs of {slab}, synthetic FLAME asset, avatar "
                     f"and upsampler weights, stored noise, {mark.shape[1]} x {mark.shape[2]} watermark, 68 forehead vertices; codes and frames "
                     f"on the device, output allocated inside the timed call; HIP events, {args.warmup} warm-up calls, median of {args.rounds} "
                     f"rounds alternating the call, the stage-timed call and the chain of separate Python calls",
