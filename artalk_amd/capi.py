@@ -43,6 +43,10 @@ SYMBOLS = [
     "artalk_gaga_set_slab", "artalk_gaga_render", "artalk_gaga_set_timing", "artalk_gaga_get_timing", "artalk_gaga_destroy",
     "artalk_gaga_last_error", "artalk_gaga_cameras", "artalk_op_gaga_flame_inputs", "artalk_op_gaga_forehead", "artalk_op_gaga_means",
     "artalk_op_gaga_finish", "artalk_op_gaga_check",
+    "artalk_gsgen_create", "artalk_gsgen_set_tensor", "artalk_gsgen_finalize", "artalk_gsgen_planes", "artalk_gsgen_generate",
+    "artalk_gsgen_set_timing", "artalk_gsgen_get_timing", "artalk_gsgen_dims", "artalk_gsgen_destroy", "artalk_gsgen_last_error",
+    "artalk_op_conv2d_relu", "artalk_op_gs_local_input", "artalk_op_gs_global_input", "artalk_op_gs_concat_dir",
+    "artalk_op_gs_local_attr", "artalk_op_gs_global_attr",
 ]
 
 # ARTALK_ATTN_* of include/artalk_hip.h: the kernels of attention.hip, as artalk_op_attention_plan names them
@@ -316,6 +320,39 @@ def lib() -> C.CDLL:
         L.artalk_op_gaga_finish.restype = i32
         L.artalk_op_gaga_check.argtypes = [i32, i32, i32, vp, i32, i32, i32, i32, i64, i32, i32, C.c_char_p, i32]
         L.artalk_op_gaga_check.restype = i32
+    if hasattr(L, "artalk_gsgen_create"):      # (an older build loaded through ARTALK_LIB for an A/B run lacks the Gaussian generators)
+        L.artalk_gsgen_create.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
+        L.artalk_gsgen_create.restype = i32
+        L.artalk_gsgen_set_tensor.argtypes = [vp, C.c_char_p, vp, i32, C.POINTER(i64)]
+        L.artalk_gsgen_set_tensor.restype = i32
+        L.artalk_gsgen_finalize.argtypes = [vp]
+        L.artalk_gsgen_finalize.restype = i32
+        L.artalk_gsgen_planes.argtypes = [vp, i32, vp, vp, vp]
+        L.artalk_gsgen_planes.restype = i32
+        L.artalk_gsgen_generate.argtypes = [vp] * 10
+        L.artalk_gsgen_generate.restype = i32
+        L.artalk_gsgen_set_timing.argtypes = [vp, i32]
+        L.artalk_gsgen_set_timing.restype = i32
+        L.artalk_gsgen_get_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.artalk_gsgen_get_timing.restype = i32
+        L.artalk_gsgen_dims.argtypes = [vp] + [C.POINTER(C.c_int32)] * 6
+        L.artalk_gsgen_dims.restype = i32
+        L.artalk_gsgen_destroy.argtypes = [vp]
+        L.artalk_gsgen_destroy.restype = None
+        L.artalk_gsgen_last_error.argtypes = [vp]
+        L.artalk_gsgen_last_error.restype = C.c_char_p
+        L.artalk_op_conv2d_relu.argtypes = [vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp]
+        L.artalk_op_conv2d_relu.restype = i32
+        L.artalk_op_gs_local_input.argtypes = [vp, vp, vp, i32, i32, vp]
+        L.artalk_op_gs_local_input.restype = i32
+        L.artalk_op_gs_global_input.argtypes = [vp, vp, vp, i32, i32, i32, vp]
+        L.artalk_op_gs_global_input.restype = i32
+        L.artalk_op_gs_concat_dir.argtypes = [vp, vp, vp, i32, i32, vp]
+        L.artalk_op_gs_concat_dir.restype = i32
+        L.artalk_op_gs_local_attr.argtypes = [vp, vp, i32, i32, i64, vp, vp, vp, vp, vp, vp]
+        L.artalk_op_gs_local_attr.restype = i32
+        L.artalk_op_gs_global_attr.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+        L.artalk_op_gs_global_attr.restype = i32
     L.artalk_savgol.argtypes = [vp, vp, vp, i32, vp]
     L.artalk_savgol.restype = i32
     L.artalk_set_profiling.argtypes = [vp, i32]

@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvArgs a) {
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // The tile choice depends on Cout alone (never on B), so the K order of an output value does not depend on how frames are batched.
-static void launch_conv(const ConvArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
+void launch_conv(const ConvArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
     const long M = (long)a.B * a.H * a.W;
     if (M <= 0) return;
     const bool va = a.Cin % 8 == 0 && aligned16(a.x) && a.x_bstride % 4 == 0 && (!a.in_scale || (aligned16(a.in_scale) && a.in_scale_ld % 4 == 0));

@@ -1,5 +1,6 @@
 // What the StyleUNet convolution kernels share (styleunet.hip: exact fp32; styleunet_bf16.hip: the bf16x3 and bf16 modes): the
-// arguments of one launch, the fp32 epilogue, and the host entry points of the bf16 kernels.  Private to csrc/.
+// arguments of one launch, the fp32 epilogue, and the host entry points of the kernels (the fp32 one also serves gsgen.hip).
+// Private to csrc/.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,13 +19,14 @@ struct ConvArgs {
     const float* noise; long noise_bstride; const float* noise_w;      // [B or 1][H][W], one device float; null: none
     const float* bias;                   // [Cout] or null
     int lrelu;
+    int relu;                            // plain ReLU, in the slot of the LeakyReLU (0: off; the Gaussian generators, gsgen.hip)
     const float* sft_scale; const float* sft_shift;      // [B][H][W][Cout] or null (both or neither)
     const float* res;                    // [B][H][W][Cout] or null
 };
 
 // The epilogue of a 128-pixel x 32 NT-channel workgroup tile whose wave `wave` holds pixels 32 wave .. 32 wave + 31 in 32x32 MFMA
 // accumulators: lane (r, h) holds output channel n0 + 32 j + r of pixels 32 wave + 8 q + 4 h + e (register 4 q + e).  In this order:
-// output scale (demodulation), gain, noise, bias, LeakyReLU 0.2, SFT and residual, all fp32.
+// output scale (demodulation), gain, noise, bias, LeakyReLU 0.2 or ReLU, SFT and residual, all fp32.
 template <int NT>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs a, const f32x16 (&acc)[NT], long m0, int n0, int wave, int r, int h, long M, int HW) {
     const float nw = a.noise ? a.noise_w[0] : 0.f;
@@ -44,6 +46,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs a, const f32x16 (&a
             if (a.noise) o += nw * a.noise[(long)b * a.noise_bstride + (m - (long)b * HW)];
             o += bv;
             if (a.lrelu) o = o >= 0.f ? o : o * 0.2f;
+            if (a.relu) o = o > 0.f ? o : 0.f;
             const long idx = m * a.Cout + co;
             if (a.sft_scale) o = o * a.sft_scale[idx] + a.sft_shift[idx];
             if (a.res) o += a.res[idx];
@@ -51,6 +54,9 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs a, const f32x16 (&a
         }
     }
 }
+
+// One exact-fp32 conv (styleunet.hip).  e0 / e1: events around the launch, or null.
+void launch_conv(const ConvArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 
 // ---- bf16 modes (styleunet_bf16.hip) ----
 // A conv weight packed for the bf16 kernels: two planes (hi, then lo) of [Cout][Kp] bf16, the K index being tap * Cinp + ci with Cin

@@ -2,8 +2,9 @@
 photoreal RGB frames out, from one library call per clip on top of ``artalk_gaga_*`` (``include/artalk_hip.h``, ``csrc/gaga.hip``).
 What is computed is written out in DESIGN.md section 5 ("GAGAvatar head").
 
-The identity half (DINOv2 through ``torch.hub``, the DPT head, the three ``*GSGenerator``s) runs once per avatar and is not built here: its
-result, the avatar's Gaussians, comes in as data - a *pack* exported from a machine that runs the reference.
+The identity half (DINOv2 through ``torch.hub``, the DPT head, the three ``*GSGenerator``s) runs once per avatar: its result, the
+avatar's Gaussians, comes in as data - a *pack* exported from a machine that runs the reference - or from
+``artalk_amd.gsgen.GSGenerators.build_avatar`` through ``add_avatar``.  DINOv2 and its DPT head are not built.
 There is no CPU fallback.
 """
 from __future__ import annotations
@@ -171,6 +172,13 @@ class GAGAvatar:
     def set_avatar_id(self, avatar_id):
         self.all_gagavatar_id[avatar_id]      # KeyError for an unknown id, like the reference's dict lookup
         self._tracked_name = avatar_id
+
+    def add_avatar(self, name, avatar):
+        """Adds or replaces an identity (ours): ``avatar`` as in the constructor, for instance what
+        ``artalk_amd.gsgen.GSGenerators.build_avatar`` returns.  Replacing the tracked identity takes effect on the next clip."""
+        self.all_gagavatar_id[name] = _check_avatar(name, avatar, self.n_dynamic)
+        if self._uploaded == name:
+            self._uploaded = None
 
     def reset_motion_state(self):
         """Unset the forehead EMA: the next frame is taken as it is, like the reference's very first frame."""

@@ -329,7 +329,8 @@ int artalk_styleunet_dims(const artalk_styleunet* u, int* in_dim, int* out_dim, 
 
 /* The per-frame path of the GAGAvatar head: motion codes -> RGB frames, a stand-in for GAGAvatar.build_forward_batch + forward_expression
  * (app/GAGAvatar/models.py:63-138).  What is computed is defined in DESIGN.md section 5 ("GAGAvatar head").  The identity side (DINOv2, the
- * Gaussian generators) runs once per avatar elsewhere; its result, the avatar's Gaussians, comes in as data.
+ * Gaussian generators) runs once per avatar elsewhere (the generators: artalk_gsgen_* below); its result, the avatar's Gaussians, comes in
+ * as data.
  * artalk_gaga_create: borrows a FLAME handle (V vertices, NB betas, built with scale 5), a splat rasteriser and a StyleUNet (32 -> 3 channels
  * at S x S), all on `device_id` and all outliving this object.  ARTALK_EINVAL with a message (artalk_gaga_last_error(NULL)) for a NULL handle
  * or out, NB < 100, or V / NB / S that are not the borrowed handles'.  With V > 3913 the forehead indices are the reference's 68.
@@ -382,6 +383,60 @@ int artalk_op_gaga_means(const float* verts_dev, const float* xyz_dev, float* me
 int artalk_op_gaga_finish(float* img_dev, int F, int S, const float* rgba_dev_or_null, int h, int w, void* stream);
 int artalk_op_gaga_check(int V, int S, int N, const int32_t* idx_host, int K, int wm_h, int wm_w, int T, int64_t motion_stride, int have_avatar,
                          int unet_finalized, char* msg, int msg_cap);
+
+/* The Gaussian generators of the GAGAvatar head's identity side, forward only, exact fp32, one avatar per call: a stand-in for
+ * LinearGSGenerator, the two ConvGSGenerators, build_points_planes, the direction encoding and the assembly of _gs_params
+ * (app/GAGAvatar/models.py:65-87, 141-233, 236-252).  What is computed is defined in DESIGN.md section 5 ("Gaussian generators"); its
+ * output is what artalk_gaga_set_avatar takes.  DINOv2 and its DPT head, which produce the two features, are not built.  Checked on
+ * synthetic weights only: parity on real GAGAvatar checkpoints is unpinned, and so is the reading of pytorch3d's HarmonicEmbedding.
+ * artalk_gsgen_create: V rows of head_base (5023), Dh its width (256), Dg the width of the DINO class token (768), C the channels of the
+ * feature map (256), P the plane size (296); N = V + 2 P P Gaussians.  Host work only.  ARTALK_EINVAL with a message
+ * (artalk_gsgen_last_error(NULL)) for a NULL out, a negative device, (Dh + Dg) % 4 != 0, an odd C, P < 3, or a size outside V 1..2^22,
+ * Dh / Dg 1..16384, C 2..4096, P 3..4096.
+ * artalk_gsgen_set_tensor: one entry of the reference module's state_dict(), fp32 in host memory, in torch's layout, with exactly its name
+ * and shape: head_base, gs_generator_g.feature_layers.{0,2,4,6}.{weight,bias}, gs_generator_g.{color,opacity,scale,rotation}_layers.
+ * {0,2}.{weight,bias}, gs_generator_l{0,1}.gaussian_conv.{0,2,4,6}.{weight,bias}.  ARTALK_EKEY "Unexpected key in state_dict: K",
+ * ARTALK_EINVAL "size mismatch for K", ARTALK_ESTATE after finalize.
+ * artalk_gsgen_finalize: ARTALK_EMISSING "Missing key(s) in state_dict: ..." (the first 8); otherwise transposes the weights on the host,
+ * uploads them and allocates the workspace (about 0.3 GB at the reference's sizes).
+ * artalk_gsgen_planes (host only): transform [3][4] = [R | t] -> points_out [P P][3] (plane_points, pixel y P + x), dir_out [3],
+ * direnc_out [27]; each out pointer may be NULL.  Evaluated in double from the float32 matrix, rounded once.  ARTALK_EINVAL for a NULL or
+ * non-finite transform or P outside 3..4096.
+ * artalk_gsgen_generate: feature0_dev [C][P][P] and feature1_dev [Dg] on the device, the avatar's transform on the host -> xyz [N][3],
+ * colors [N][32], opacities [N], scales [N][3], rotations [N][4] on the device: rows 0 .. V - 1 from the global generator (their xyz
+ * zero), rows V + g P P + y P + x from local generator g.  Runs on the caller's stream and does not synchronise; bit-identical from run
+ * to run.  ARTALK_ESTATE before finalize; ARTALK_EINVAL before the device is touched for a NULL handle or pointer or a non-finite transform.
+ * artalk_gsgen_set_timing / get_timing (tools/gsgen_bench.py): with timing on, a call times its conv launches with event pairs and WAITS
+ * at its end; get_timing returns the summed conv kernel time and the whole call's time of the last call, in ms.
+ * artalk_gsgen_dims: returns the device index (ARTALK_EINVAL for a NULL handle); every out pointer may be NULL.
+ * artalk_op_conv2d_relu: artalk_op_conv2d with only a bias (may be NULL) and the plain ReLU (relu != 0) as its epilogue; with relu == 0
+ * it gives artalk_op_conv2d's bits.
+ * artalk_op_gs_*: one launch of one kernel on device arrays; direnc and transform are host pointers.  local_input: f_feature0 [C][P][P] ->
+ * [P P][W], W = C + 27 rounded up to a multiple of 8, the padding zero (the conv's vector loads).  global_input: head_base [V][Dh],
+ * feature1 [Dg] -> [V][Dh + Dg].  concat_dir: feat [V][H] -> [V][W], W = H + 27 rounded up likewise.  local_attr:
+ * the 41-channel conv output [P P][41] -> rows row0 .. row0 + P P - 1 of the five avatar arrays, sign +1 (l0) or -1 (l1).  global_attr:
+ * the four heads' outputs [V][32], [V], [V][3], [V][4] -> rows 0 .. V - 1 of the five avatar arrays. */
+typedef struct artalk_gsgen artalk_gsgen;
+int artalk_gsgen_create(int device_id, int V, int Dh, int Dg, int C, int P, artalk_gsgen** out);
+int artalk_gsgen_set_tensor(artalk_gsgen* g, const char* key, const void* host_ptr, int ndim, const int64_t* shape);
+int artalk_gsgen_finalize(artalk_gsgen* g);
+int artalk_gsgen_planes(const float* transform_3x4_host, int P, float* points_out, float* dir_out, float* direnc_out);
+int artalk_gsgen_generate(artalk_gsgen* g, const float* feature0_dev, const float* feature1_dev, const float* transform_3x4_host, float* xyz_dev,
+                          float* colors_dev, float* opacities_dev, float* scales_dev, float* rotations_dev, void* stream);
+int artalk_gsgen_set_timing(artalk_gsgen* g, int enable);
+int artalk_gsgen_get_timing(const artalk_gsgen* g, double* conv_ms, double* total_ms);
+int artalk_gsgen_dims(const artalk_gsgen* g, int* V, int* Dh, int* Dg, int* C, int* P, int* finalized);
+void artalk_gsgen_destroy(artalk_gsgen* g);
+const char* artalk_gsgen_last_error(const artalk_gsgen* g);
+int artalk_op_conv2d_relu(const float* x, int64_t x_bstride, const float* w, float* out, int B, int H, int W, int Cin, int Cout, int k,
+                          const float* bias, int relu, void* stream);
+int artalk_op_gs_local_input(const float* feature0_dev, const float* direnc_host, float* out_dev, int C, int P, void* stream);
+int artalk_op_gs_global_input(const float* head_base_dev, const float* feature1_dev, float* out_dev, int V, int Dh, int Dg, void* stream);
+int artalk_op_gs_concat_dir(const float* feat_dev, const float* direnc_host, float* out_dev, int V, int H, void* stream);
+int artalk_op_gs_local_attr(const float* conv_out_dev, const float* transform_3x4_host, int P, int sign, int64_t row0, float* xyz_dev,
+                            float* colors_dev, float* opacities_dev, float* scales_dev, float* rotations_dev, void* stream);
+int artalk_op_gs_global_attr(const float* colors_in_dev, const float* opacities_in_dev, const float* scales_in_dev, const float* rotations_in_dev,
+                             int V, float* xyz_dev, float* colors_dev, float* opacities_dev, float* scales_dev, float* rotations_dev, void* stream);
 
 /* Numerical health of the work enqueued since the last artalk_infer / artalk_stream_begin started.  Every call ends with an
  * asynchronous copy of the device status word to pinned host memory.  artalk_get_status WAITS for that copy (an event wait:
