@@ -47,6 +47,11 @@ SYMBOLS = [
     "artalk_gsgen_set_timing", "artalk_gsgen_get_timing", "artalk_gsgen_dims", "artalk_gsgen_destroy", "artalk_gsgen_last_error",
     "artalk_op_conv2d_relu", "artalk_op_gs_local_input", "artalk_op_gs_global_input", "artalk_op_gs_concat_dir",
     "artalk_op_gs_local_attr", "artalk_op_gs_global_attr",
+    "artalk_dino_create", "artalk_dino_set_tensor", "artalk_dino_finalize", "artalk_dino_prepare_image", "artalk_dino_forward",
+    "artalk_dino_read", "artalk_dino_set_timing", "artalk_dino_get_timing", "artalk_dino_dims", "artalk_dino_destroy", "artalk_dino_last_error",
+    "artalk_op_dino_resize_aa", "artalk_op_dino_normalize", "artalk_op_dino_im2col", "artalk_op_dino_tokens", "artalk_op_dino_layernorm",
+    "artalk_op_dino_strip", "artalk_op_dino_shuffle", "artalk_op_dino_gather_s2", "artalk_op_dino_concat", "artalk_op_dino_resize_ac",
+    "artalk_op_dino_add_relu", "artalk_op_dino_output",
 ]
 
 # ARTALK_ATTN_* of include/artalk_hip.h: the kernels of attention.hip, as artalk_op_attention_plan names them
@@ -353,6 +358,33 @@ def lib() -> C.CDLL:
         L.artalk_op_gs_local_attr.restype = i32
         L.artalk_op_gs_global_attr.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
         L.artalk_op_gs_global_attr.restype = i32
+    if hasattr(L, "artalk_dino_create"):      # (an older build loaded through ARTALK_LIB for an A/B run lacks DINOBase)
+        for name, args, res in (
+                ("dino_create", [i32, i32, i32, i32, i32, i32, C.POINTER(vp)], i32),
+                ("dino_set_tensor", [vp, C.c_char_p, vp, i32, C.POINTER(i64)], i32),
+                ("dino_finalize", [vp], i32),
+                ("dino_prepare_image", [vp, vp, i32, i32, vp, vp], i32),
+                ("dino_forward", [vp, vp, i32, i32, vp, vp, vp], i32),
+                ("dino_read", [vp, C.c_char_p, vp, i64, vp], i32),
+                ("dino_set_timing", [vp, i32], i32),
+                ("dino_get_timing", [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)], i32),
+                ("dino_dims", [vp] + [C.POINTER(C.c_int32)] * 6, i32),
+                ("dino_destroy", [vp], None),
+                ("dino_last_error", [vp], C.c_char_p),
+                ("op_dino_resize_aa", [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp], i32),
+                ("op_dino_normalize", [vp, vp, i64, vp], i32),
+                ("op_dino_im2col", [vp, vp, i32, vp], i32),
+                ("op_dino_tokens", [vp, vp, vp, vp, i32, i32, vp], i32),
+                ("op_dino_layernorm", [vp, vp, vp, vp, i32, i32, vp], i32),
+                ("op_dino_strip", [vp, vp, i32, i32, vp], i32),
+                ("op_dino_shuffle", [vp, vp, vp, i32, i32, i32, vp], i32),
+                ("op_dino_gather_s2", [vp, vp, i32, i32, vp], i32),
+                ("op_dino_concat", [vp, vp, vp, i64, i32, vp], i32),
+                ("op_dino_resize_ac", [vp, vp, i32, i32, i32, i32, i32, vp], i32),
+                ("op_dino_add_relu", [vp, vp, vp, vp, i64, vp], i32),
+                ("op_dino_output", [vp, vp, i64, i32, vp, vp, i32, vp], i32)):
+            f = getattr(L, "artalk_" + name)
+            f.argtypes, f.restype = args, res
     L.artalk_savgol.argtypes = [vp, vp, vp, i32, vp]
     L.artalk_savgol.restype = i32
     L.artalk_set_profiling.argtypes = [vp, i32]

@@ -24,7 +24,7 @@ from .model import BitwiseARModel
 class ARTAvatarInferEngine:
     def __init__(self, load_gaga=False, fix_pose=False, clip_length=750, device="cuda",
                  ckpt_path="./assets/ARTalk_wav2vec.pt", config_path=None, state_dict=None, config=None, model=None,
-                 calibration=None, precision=None, gaga=None, gaga_flame=None, gaga_precision=None):
+                 calibration=None, precision=None, gaga=None, gaga_flame=None, gaga_precision=None, gaga_ckpt=None, gaga_tracked=None):
         """Arguments of the reference class, plus (all optional): ``state_dict`` / ``config`` instead of a checkpoint file, ``model``
         (an already loaded BitwiseARModel), and ``calibration`` - the f16x3 site scales to start from: a ``save_scales`` file or a
         ``{site: exponent}`` dict (``load_scales``), or a sequence of 16 kHz audio tensors to calibrate on once here (``calibrate``).
@@ -34,8 +34,11 @@ class ARTAvatarInferEngine:
         ``artalk_amd.flame.FLAMEModel`` built with ``scale=5.0``: the photoreal head behind ``rendering(shape_id=<avatar id>)``.
         Both can also be plugged into ``engine.GAGAvatar`` / ``engine.GAGAvatar_flame`` later, like ``flame_model``.
         ``gaga_precision``: the arithmetic of the head's upsampler convolutions (``GAGAvatar.set_precision``: 'f32', 'bf16x3' or
-        'bf16'); None keeps the head's."""
-        if load_gaga and gaga is None:
+        'bf16'); None keeps the head's.
+        ``gaga_ckpt`` / ``gaga_tracked`` instead of ``gaga``: the reference's two files, ``GAGAvatar.pt`` and ``tracked.pt``, each as a
+        dict or as a path that ``torch.load(weights_only=True)`` can read (``GAGAvatar.from_checkpoint``): the avatars are then built
+        on the device from their tracked photos."""
+        if load_gaga and gaga is None and gaga_ckpt is None:
             raise NotImplementedError("load_gaga=True needs gaga=: an artalk_amd.gaga.GAGAvatar or the path of an avatar pack.  The "
                                       "reference builds its avatars with DINOv2 from torch.hub, which is not part of this package: "
                                       "export a pack on a machine that runs the reference (INTEGRATION.md section 1d)")
@@ -77,8 +80,31 @@ class ARTAvatarInferEngine:
         if gaga is not None:
             from .gaga import GAGAvatar
             self.GAGAvatar = gaga if isinstance(gaga, GAGAvatar) else GAGAvatar.load(gaga, device=device)
-            if gaga_precision is not None:
-                self.GAGAvatar.set_precision(gaga_precision)
+        elif gaga_ckpt is not None:
+            from .gaga import GAGAvatar
+            if gaga_tracked is None:
+                raise ValueError("gaga_ckpt= needs gaga_tracked=: the tracked identities (tracked.pt), as a dict or a path")
+            ckpt = self._load_plain(gaga_ckpt, "gaga_ckpt")
+            if "model" in ckpt and "head_base" not in ckpt:
+                ckpt = ckpt["model"]
+            self.GAGAvatar = GAGAvatar.from_checkpoint(ckpt, self._load_plain(gaga_tracked, "gaga_tracked"), flame=gaga_flame, device=device)
+        if self.GAGAvatar is not None and gaga_precision is not None:
+            self.GAGAvatar.set_precision(gaga_precision)
+
+    @staticmethod
+    def _load_plain(what, name):
+        """A dict as it is; a path through torch.load(weights_only=True).  A file that needs pickle is refused."""
+        if isinstance(what, dict):
+            return what
+        import pickle
+        try:
+            got = torch.load(what, map_location="cpu", weights_only=True)
+        except pickle.UnpicklingError as e:
+            raise ValueError(f"{name}={what!r} cannot be read with weights_only=True (it needs pickle, which is not run here): load it "
+                             f"yourself where you trust it and pass the dict ({str(e).splitlines()[0]})") from None
+        if not isinstance(got, dict):
+            raise ValueError(f"{name}={what!r} holds a {type(got).__name__}, not a dict")
+        return got
 
     def set_style_motion(self, style_motion):
         if isinstance(style_motion, str):

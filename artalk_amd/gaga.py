@@ -4,7 +4,8 @@ What is computed is written out in DESIGN.md section 5 ("GAGAvatar head").
 
 The identity half (DINOv2 through ``torch.hub``, the DPT head, the three ``*GSGenerator``s) runs once per avatar: its result, the
 avatar's Gaussians, comes in as data - a *pack* exported from a machine that runs the reference - or from
-``artalk_amd.gsgen.GSGenerators.build_avatar`` through ``add_avatar``.  DINOv2 and its DPT head are not built.
+``artalk_amd.gsgen.GSGenerators.build_avatar`` through ``add_avatar``, or, with ``GAGAvatar.from_checkpoint``, is made here from the
+identity's tracked photo by ``artalk_amd.dino.DINOBase`` and the generators the first time ``set_avatar_id`` names it.
 There is no CPU fallback.
 """
 from __future__ import annotations
@@ -84,10 +85,12 @@ class GAGAvatar:
     The device is first touched by ``render_clip``.  The forehead EMA state lives in the library object and survives clips and
     ``set_avatar_id``, as ``upper_points`` does in the reference; ``reset_motion_state`` (ours) unsets it."""
 
-    def __init__(self, avatars, upsampler, water_mark=None, image_size=512, n_dynamic=5023, forehead_indices=None, device="cuda"):
+    def __init__(self, avatars, upsampler, water_mark=None, image_size=512, n_dynamic=5023, forehead_indices=None, device="cuda", _tracked=None):
         self.image_size, self.n_dynamic = int(image_size), int(n_dynamic)
         self.device = torch.device(device)
-        if not isinstance(avatars, dict) or not avatars:
+        # from_checkpoint: the identities still to be turned into Gaussians, and the two modules that do it
+        self._tracked, self._dino, self._gsgen, self.flame_model = _tracked, None, None, None
+        if not isinstance(avatars, dict) or not (avatars or _tracked):
             raise ValueError("avatars must be a non-empty dict")
         self.all_gagavatar_id = {k: _check_avatar(k, v, self.n_dynamic) for k, v in avatars.items()}
         if isinstance(upsampler, StyleUNet):
@@ -135,6 +138,75 @@ class GAGAvatar:
         return cls(pack["avatars"], pack["upsampler"], water_mark=wm, image_size=size, n_dynamic=int(pack["n_dynamic"]),
                    forehead_indices=forehead_indices, device=device)
 
+    @classmethod
+    def from_checkpoint(cls, model_state_dict, tracked, water_mark=None, flame=None, device="cuda", image_size=None, heads=None,
+                        forehead_indices=None):
+        """The whole head from the reference's two files (ours): ``model_state_dict`` is the ``model`` dict of ``GAGAvatar.pt``
+        (``upsampler.*`` -> the StyleUNet, ``head_base`` / ``gs_generator_*`` -> ``GSGenerators``, ``base_model.*`` -> ``DINOBase``; the
+        sizes are read off the tensors - ``image_size`` off the upsampler's largest noise buffer - and ``heads`` defaults to vit_dim / 64), ``tracked`` the dict of ``tracked.pt``:
+        ``{id: {"image" (3, h, w) in [0, 1], "transform_matrix", "shapecode"}}``.  An identity is turned into Gaussians the first time
+        ``set_avatar_id`` names it (the reference does so in its first ``forward_expression``) and kept.  ``flame``: the scale-5
+        ``FLAMEModel``, kept in ``flame_model`` for whoever renders."""
+        from .dino import DINOBase
+        from .gsgen import GSGenerators
+        sd = model_state_dict
+        for k in ("head_base", "base_model.dino_model.pos_embed", "base_model.dino_model.cls_token", "base_model.output_conv.weight"):
+            if k not in sd:
+                raise ValueError(f"the checkpoint lacks {k!r}: pass the 'model' dict of GAGAvatar.pt")
+        if not isinstance(tracked, dict) or not tracked:
+            raise ValueError("tracked must be a non-empty dict")
+        tr = {name: cls._check_tracked(name, e) for name, e in tracked.items()}
+        vit_dim = int(sd["base_model.dino_model.cls_token"].shape[-1])
+        tokens = int(sd["base_model.dino_model.pos_embed"].shape[-2])
+        grid = int(round((tokens - 1) ** 0.5))
+        if grid * grid + 1 != tokens:
+            raise ValueError(f"pos_embed holds {tokens} positions, which is no square grid and a class token")
+        depth = 1 + max(int(k.split(".")[3]) for k in sd if k.startswith("base_model.dino_model.blocks."))
+        out_dim = int(sd["base_model.output_conv.weight"].shape[0])
+        n_verts, head_dim = (int(v) for v in sd["head_base"].shape)
+        if image_size is None:
+            image_size = max([int(v.shape[-1]) for k, v in sd.items() if k.startswith("upsampler.") and ".noises.noise" in k] or [512])
+        head = cls({}, {k[len("upsampler."):]: v for k, v in sd.items() if k.startswith("upsampler.")}, water_mark=water_mark,
+                   image_size=image_size, n_dynamic=n_verts, forehead_indices=forehead_indices, device=device, _tracked=tr)
+        head._dino = DINOBase(out_dim, vit_dim, depth, int(heads) if heads else vit_dim // 64, grid, device=device).load_state_dict(sd)
+        head._gsgen = GSGenerators(n_verts, head_dim, vit_dim, out_dim, 8 * grid, device=device).load_state_dict(sd)
+        head.flame_model = flame
+        return head
+
+    @staticmethod
+    def _check_tracked(name, e):
+        if not isinstance(e, dict):
+            raise ValueError(f"tracked identity {name!r} must be a dict")
+        for k in ("image", "transform_matrix", "shapecode"):
+            if k not in e:
+                raise ValueError(f"tracked identity {name!r} lacks {k!r}")
+        img = torch.as_tensor(e["image"]).detach().float()      # the reference: torch.tensor(value).float() for what is no tensor
+        if img.dim() != 3 or img.shape[0] != 3:
+            raise ValueError(f"tracked identity {name!r}: image must be (3, h, w), got {tuple(img.shape)}")
+        tm = torch.as_tensor(e["transform_matrix"]).detach().to(dtype=torch.float32, device="cpu")
+        if tuple(tm.shape[-2:]) not in ((3, 4), (4, 4)):
+            raise ValueError(f"tracked identity {name!r}: transform_matrix must be (3, 4), got {tuple(tm.shape)}")
+        return {"image": img, "transform_matrix": tm, "shapecode": torch.as_tensor(e["shapecode"]).detach().float().cpu()}
+
+    def add_avatar_image(self, name, image, transform_matrix, shapecode):
+        """Adds or replaces a tracked identity of a head built by ``from_checkpoint`` (ours); its Gaussians are made the next time
+        ``set_avatar_id`` names it."""
+        if self._dino is None:
+            raise RuntimeError("this head holds finished avatars only: build it with GAGAvatar.from_checkpoint to add identities by image")
+        self._tracked[name] = self._check_tracked(name, {"image": image, "transform_matrix": transform_matrix, "shapecode": shapecode})
+        self.all_gagavatar_id.pop(name, None)
+        if self._uploaded == name:
+            self._uploaded = None
+
+    def _generate(self, name):
+        e = self._tracked[name]
+        f0, f1 = self._dino.forward(self._dino.prepare_image(e["image"]))
+        self.add_avatar(name, self._gsgen.build_avatar(f0, f1, e["transform_matrix"], e["shapecode"]))
+
+    def _default_id(self):
+        names = list(self.all_gagavatar_id) + [k for k in (self._tracked or {}) if k not in self.all_gagavatar_id]
+        return "11.jpg" if "11.jpg" in names else names[0]
+
     def save(self, path):
         if self._upsampler_sd is None:
             raise RuntimeError("this head was built around a loaded StyleUNet: construct it from the state dict to save a pack")
@@ -170,6 +242,8 @@ class GAGAvatar:
 
     # ---- the reference's methods ----
     def set_avatar_id(self, avatar_id):
+        if avatar_id not in self.all_gagavatar_id and self._tracked and avatar_id in self._tracked:
+            self._generate(avatar_id)
         self.all_gagavatar_id[avatar_id]      # KeyError for an unknown id, like the reference's dict lookup
         self._tracked_name = avatar_id
 
@@ -213,7 +287,7 @@ class GAGAvatar:
         reference, ``motion_code`` is not modified), the FLAME model and ``t_transform`` (T, 3, 4), the per-frame cameras.  The vertices
         and the forehead EMA are produced inside the library call that ``forward_expression`` makes, so the EMA advances there."""
         if self._tracked_name is None:
-            self.set_avatar_id("11.jpg" if "11.jpg" in self.all_gagavatar_id else next(iter(self.all_gagavatar_id)))
+            self.set_avatar_id(self._default_id())
         motion_code = self._check_motion(motion_code)
         tm = self.all_gagavatar_id[self._tracked_name]["transform_matrix"]
         return {"motion_code": motion_code.clone(), "flame_model": flame_model,
@@ -270,7 +344,7 @@ class GAGAvatar:
                 if L.artalk_gaga_set_slab(h, self._slab) < 0:
                     raise ValueError("artalk_gaga_set_slab refused: " + self._err())
         if self._tracked_name is None:
-            self.set_avatar_id("11.jpg" if "11.jpg" in self.all_gagavatar_id else next(iter(self.all_gagavatar_id)))
+            self.set_avatar_id(self._default_id())
         if self._uploaded != self._tracked_name:
             av = self.all_gagavatar_id[self._tracked_name]
             if av["shapecode"].numel() != flame_model.n_betas - 100:

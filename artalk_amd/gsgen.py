@@ -4,7 +4,7 @@
 library call on top of ``artalk_gsgen_*`` (``include/artalk_hip.h``, ``csrc/gsgen.hip``).  What is computed is written out in DESIGN.md
 section 5 ("Gaussian generators").  Forward only, exact fp32, one avatar per call.
 
-DINOv2 and its DPT head, which make the two features, are not built.  Only synthetic weights are checked: parity on real GAGAvatar
+DINOv2 and its DPT head, which make the two features, are ``artalk_amd.dino.DINOBase``.  Only synthetic weights are checked: parity on real GAGAvatar
 checkpoints is unpinned, and so is the reading of pytorch3d's ``HarmonicEmbedding`` (pytorch3d was not at hand).  There is no CPU fallback.
 """
 from __future__ import annotations

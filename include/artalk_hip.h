@@ -389,7 +389,7 @@ int artalk_op_gaga_check(int V, int S, int N, const int32_t* idx_host, int K, in
  * (app/GAGAvatar/models.py:65-87, 141-233, 236-252).  What is computed is defined in DESIGN.md section 5 ("Gaussian generators"); its
  * output is what artalk_gaga_set_avatar takes.  DINOv2 and its DPT head, which produce the two features, are not built.  Checked on
  * synthetic weights only: parity on real GAGAvatar checkpoints is unpinned, and so is the reading of pytorch3d's HarmonicEmbedding.
- * artalk_gsgen_create: V rows of head_base (5023), Dh its width (256), Dg the width of the DINO class token (768), C the channels of the
+ * artalk_gsgen_create: V rows of head_base (5023), Dh its width (256), Dg the width of the DINO global vector (768: the normed first patch token, see artalk_dino_forward), C the channels of the
  * feature map (256), P the plane size (296); N = V + 2 P P Gaussians.  Host work only.  ARTALK_EINVAL with a message
  * (artalk_gsgen_last_error(NULL)) for a NULL out, a negative device, (Dh + Dg) % 4 != 0, an odd C, P < 3, or a size outside V 1..2^22,
  * Dh / Dg 1..16384, C 2..4096, P 3..4096.
@@ -437,6 +437,73 @@ int artalk_op_gs_local_attr(const float* conv_out_dev, const float* transform_3x
                             float* colors_dev, float* opacities_dev, float* scales_dev, float* rotations_dev, void* stream);
 int artalk_op_gs_global_attr(const float* colors_in_dev, const float* opacities_in_dev, const float* scales_in_dev, const float* rotations_in_dev,
                              int V, float* xyz_dev, float* colors_dev, float* opacities_dev, float* scales_dev, float* rotations_dev, void* stream);
+
+/* DINOBase of the GAGAvatar head's identity side, forward only, exact fp32, one image per call: a stand-in for
+ * app/GAGAvatar/modules/dino_base.py - the ImageNet normalisation, the DINOv2 ViT (patch 14, LayerScale, no register tokens), the last
+ * four blocks' normed patch tokens and the DPT-style head.  What is computed is defined in DESIGN.md section 5 ("DINO features"); its
+ * two outputs are what artalk_gsgen_generate takes.  Checked on synthetic weights only: parity on the real GAGAvatar.pt, the upstream
+ * checkpoint's key names and torchvision's resize are unpinned.  Not built: position-embedding interpolation, register tokens, batches,
+ * lower-precision modes, only_global / output_size.
+ * artalk_dino_create: vit_dim the ViT's width (768), depth its blocks (12), heads (12), grid the patches a side (37: a 518 x 518 image),
+ * output_dim the channels of the feature plane (256), whose side is P = 8 grid.  The MLP is 4 vit_dim wide; the head's hidden width 256
+ * and projection widths 256 / 512 / 1024 / 1024 are the reference's constants.  Host work only.  ARTALK_EINVAL with a message
+ * (artalk_dino_last_error(NULL)) for a NULL out, a negative device, depth < 4, a head width vit_dim / heads other than 64 or 32, vit_dim
+ * not a multiple of 32 in 32..4096, grid outside 2..64, output_dim outside 1..1024.
+ * artalk_dino_set_tensor: one entry of the reference module's state_dict() (the names under base_model.), fp32 in host memory, in torch's
+ * layout: dino_model.{cls_token,pos_embed,mask_token (accepted, unused, may be absent)}, dino_model.patch_embed.proj.*,
+ * dino_model.blocks.N.{norm1,attn.qkv,attn.proj,norm2,mlp.fc1,mlp.fc2}.{weight,bias}, dino_model.blocks.N.{ls1,ls2}.gamma,
+ * dino_model.norm.*, projects.N.*, resize_layers.{0,1,3}.*, layer_rn.N.weight, refinenet.N.{resConfUnit1,resConfUnit2}.{conv1,conv2}.*
+ * (refinenet.0.resConfUnit1 is loaded and never run), refinenet.N.out_conv.*, output_conv.*.  ARTALK_EKEY "Unexpected key in state_dict:
+ * K", ARTALK_EINVAL "size mismatch for K" (a pos_embed of another grid: the message says that position embeddings are not interpolated),
+ * ARTALK_ESTATE after finalize.
+ * artalk_dino_finalize: ARTALK_EMISSING "Missing key(s) in state_dict: ..." (the first 8); otherwise transposes and pads the weights on
+ * the host, uploads them and allocates the workspace (about 0.45 GB at the reference's sizes).
+ * artalk_dino_prepare_image: image [3][height][width] in host or device memory -> out_dev [3][14 grid][14 grid], torch's antialiased
+ * bilinear resize (the reference's build_forward_batch); values are not normalised.  A host image has been read when the call returns (the call
+ * waits for its copy); a device image is read on the stream.
+ * artalk_dino_forward: image_dev [3][height][width] in [0, 1] on the device -> feature0_dev [output_dim][P][P] and feature1_dev [vit_dim]
+ * (the normed first patch token of the last block).  Runs on the caller's stream and does not synchronise; bit-identical from run to run.
+ * ARTALK_ESTATE before finalize; ARTALK_EINVAL before the device is touched for a NULL handle or pointer, a non-square image or a size
+ * other than 14 grid.
+ * artalk_dino_read: after a forward call on the same stream, copies an intermediate to out_dev: "tap0".."tap3" [grid grid][vit_dim] (the
+ * normed patch tokens of the last four blocks), "rn0".."rn3" [H H][256] channels-last with H = 4 grid, 2 grid, grid, (grid - 1) / 2 + 1
+ * (the layer_rn outputs); n must be the exact count.
+ * artalk_dino_set_timing / get_timing (tools/dino_bench.py): with timing on, a forward call marks its stages with events and WAITS at its
+ * end; stage_ms [4]: ViT and head GEMMs, attention, the head's convs, everything else.
+ * artalk_dino_dims: returns the device index (ARTALK_EINVAL for a NULL handle); every out pointer may be NULL.
+ * artalk_op_dino_*: one launch of one kernel on device arrays; ARTALK_EINVAL for a NULL pointer, a size out of range or a misaligned
+ * pointer (16 bytes where a channel count must be a multiple of 4).  resize_aa: x [C][Hi][Wi] -> [C][Ho][Wo], or [Ho][Wo][C] with
+ * channels_last; normalize (C = 3): the ImageNet mean / std applied to the result.  normalize: [3][n].  im2col: [3][14 g][14 g] ->
+ * [g g][608], column c 196 + ky 14 + kx, zeros from 588.  tokens: X[t] = (t ? patch[t - 1] : cls) + pos[t].  layernorm: eps 1e-6,
+ * affine, any D % 4 == 0.  strip: [1 + G][D] -> [G][D].  shuffle: the GEMM result [g g][s s Co] of a k = s transposed conv -> [s g][s g][Co]
+ * + bias.  gather_s2: [g][g][C] -> [Ho Ho][9 C], the windows of a 3 x 3 stride-2 pad-1 conv.  concat: img [n][3] ++ feat [n][C] ->
+ * [n][W], W = 3 + C rounded up to a multiple of 8, the padding zero.  resize_ac: channels-last bilinear, align_corners = True.
+ * add_relu: sum = a + b (b NULL: a) to sum_out (may be NULL), max(sum, 0) to relu_out.  output: x [n][C] -> [C][n], and tok [D] -> f1
+ * (tok NULL: no). */
+typedef struct artalk_dino artalk_dino;
+int artalk_dino_create(int device_id, int vit_dim, int depth, int heads, int grid, int output_dim, artalk_dino** out);
+int artalk_dino_set_tensor(artalk_dino* d, const char* key, const void* host_ptr, int ndim, const int64_t* shape);
+int artalk_dino_finalize(artalk_dino* d);
+int artalk_dino_prepare_image(artalk_dino* d, const float* image, int height, int width, float* out_dev, void* stream);
+int artalk_dino_forward(artalk_dino* d, const float* image_dev, int height, int width, float* feature0_dev, float* feature1_dev, void* stream);
+int artalk_dino_read(artalk_dino* d, const char* what, float* out_dev, int64_t n, void* stream);
+int artalk_dino_set_timing(artalk_dino* d, int enable);
+int artalk_dino_get_timing(const artalk_dino* d, double* stage_ms, double* total_ms);
+int artalk_dino_dims(const artalk_dino* d, int* vit_dim, int* depth, int* heads, int* grid, int* output_dim, int* finalized);
+void artalk_dino_destroy(artalk_dino* d);
+const char* artalk_dino_last_error(const artalk_dino* d);
+int artalk_op_dino_resize_aa(const float* x, float* out, int C, int Hi, int Wi, int Ho, int Wo, int channels_last, int normalize, void* stream);
+int artalk_op_dino_normalize(const float* x, float* out, int64_t n, void* stream);
+int artalk_op_dino_im2col(const float* img, float* col, int grid, void* stream);
+int artalk_op_dino_tokens(const float* patch, const float* cls, const float* pos, float* X, int T, int D, void* stream);
+int artalk_op_dino_layernorm(const float* X, float* Y, const float* w, const float* b, int M, int D, void* stream);
+int artalk_op_dino_strip(const float* tap, float* out, int G, int D, void* stream);
+int artalk_op_dino_shuffle(const float* r, const float* bias, float* out, int grid, int s, int Co, void* stream);
+int artalk_op_dino_gather_s2(const float* x, float* col, int grid, int C, void* stream);
+int artalk_op_dino_concat(const float* img, const float* feat, float* out, int64_t n, int C, void* stream);
+int artalk_op_dino_resize_ac(const float* x, float* out, int Hi, int Wi, int Ho, int Wo, int C, void* stream);
+int artalk_op_dino_add_relu(const float* a, const float* b, float* sum_out, float* relu_out, int64_t n, void* stream);
+int artalk_op_dino_output(const float* x, float* out, int64_t n, int C, const float* tok, float* f1, int D, void* stream);
 
 /* Numerical health of the work enqueued since the last artalk_infer / artalk_stream_begin started.  Every call ends with an
  * asynchronous copy of the device status word to pinned host memory.  artalk_get_status WAITS for that copy (an event wait:
