@@ -29,7 +29,7 @@ SYMBOLS = [
     "artalk_op_bsq_history_ex", "artalk_op_ar_bits_next", "artalk_op_vq_embed", "artalk_op_ar_begin", "artalk_op_dec_input", "artalk_op_dec_finish", "artalk_op_enc_input_zero", "artalk_op_style_input", "artalk_op_add_row", "artalk_op_style_finish", "artalk_op_broadcast16", "artalk_op_session_gather", "artalk_op_session_scatter", "artalk_op_absmax",
     "artalk_op_gemm_rows", "artalk_op_layernorm_rows", "artalk_op_attention_rows", "artalk_op_gemm_rows_layout", "artalk_op_rows_dry_run",
     "artalk_op_w2v_front_rows", "artalk_op_pool_silu_rows", "artalk_op_posconv_rows",
-    "artalk_op_attention_plan", "artalk_op_attention_rows_cus",
+    "artalk_op_attention_plan", "artalk_op_attention_rows_cus", "artalk_op_gemm_blocked",
     "artalk_infer_samples", "artalk_set_tail_skip", "artalk_conv_tail_geometry", "artalk_conv_tail_class",
     "artalk_render_create", "artalk_render_mesh", "artalk_render_set_slab", "artalk_render_destroy", "artalk_render_last_error",
     "artalk_splat_create", "artalk_splat_render", "artalk_splat_set_timing", "artalk_splat_get_timing", "artalk_splat_destroy",
@@ -515,7 +515,9 @@ def lib() -> C.CDLL:
         L.artalk_op_attention_plan.restype = i32
         L.artalk_op_attention_rows_cus.argtypes = L.artalk_op_attention_rows.argtypes[:-1] + [i32, C.POINTER(C.c_int32), vp]
         L.artalk_op_attention_rows_cus.restype = i32
-    if hasattr(L, "artalk_op_w2v_front_rows"):      # (an older build loaded through ARTALK_LIB lacks the chunk-strided wav2vec2 entry points)
+    if hasattr(L, "artalk_op_gemm_blocked"):      # (an older build loaded through ARTALK_LIB lacks the blocked-sum entry point)
+        L.artalk_op_gemm_blocked.argtypes, L.artalk_op_gemm_blocked.restype = L.artalk_op_gemm.argtypes, i32
+    if hasattr(L, "artalk_op_w2v_front_rows"):     # (an older build loaded through ARTALK_LIB lacks the chunk-strided wav2vec2 entry points)
         L.artalk_op_w2v_front_rows.argtypes = [vp, i64, C.POINTER(i64), i32, i32, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, vp]
         L.artalk_op_w2v_front_rows.restype = i32
         L.artalk_op_pool_silu_rows.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, i64, i64, i64, vp]

@@ -379,6 +379,7 @@ struct DnRun {
               bool bias = true) {
         GemmArgs a;
         a.A = A; a.lda = lda; a.W = l.w; a.ldw = K; a.bias = bias ? l.b : nullptr; a.C = C; a.ldc = N; a.M = M; a.N = N; a.K = K; a.act = act; a.exact = 1;
+        a.ksum_blocks = 1;      // fc2 sums over K = 4 dim: one chain that long is outside the head's allowance ("DINO features")
         if (gate) { a.gate = gate; a.ldg = 0; }
         if (R) { a.R = R; a.ldr = N; }
         launch_gemm(a, s);

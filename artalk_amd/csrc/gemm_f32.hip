@@ -17,17 +17,22 @@
 namespace artalk {
 
 
-// TAG only separates instantiations: 64x64 launches captured into the AR/VAE hipGraph use TAG=1 so that the eager 64x64
-// launches (TAG=0: wav2vec2 encoder + AdaLN table, the dominant kernel of the path) form one kernel symbol whose every launch is
+// TAG separates instantiations.  0 and 1 are the same code: 64x64 launches captured into the AR/VAE hipGraph use TAG=1 so that the eager
+// 64x64 launches (TAG=0: wav2vec2 encoder + AdaLN table, the dominant kernel of the path) form one kernel symbol whose every launch is
 // bracketed by HIP events in bench.py and listed as one row by rocprofv3.
+// TAG=2 (GemmArgs::ksum_blocks, the DINO launches) sums K in two levels, the scheme and block depth of conv_mfma_kernel: every KBLK = 256
+// of K (of the slab, when split) the accumulators are added into a second set and restart from zero, and the last, possibly short, block
+// joins at the end.  One chain over K = 3072 measured 2.8 ... 8.1 x the error of a float32 CPU GEMM ("DINO features").  It
+// rides on TAG, not on a parameter of its own, because a further template parameter would rename every existing instantiation.
 template <int BM, int BN, int WM, int WN, int BK, int AMODE, int TAG = 0>
 __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const GemmArgs g) {
+    constexpr int KBLK = TAG == 2 ? 256 : 0;
     constexpr int LDS_LD = BK + 4;                 // floats; the +4 pad keeps the ds_read_b128 fragment reads conflict-free
     constexpr int TPR = BK / 4, RPP = 256 / TPR;   // staging: threads per row, rows per pass
     constexpr int NQ = BK / 8;                     // 16-byte chunks of a fragment per lane (lane half h holds k in [h*BK/2, (h+1)*BK/2))
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
     constexpr int A_LD = BM / RPP, B_LD = BN / RPP;
-    static_assert(WM * WN == 4 && TM >= 1 && TN >= 1 && A_LD >= 1 && B_LD >= 1, "tile config");
+    static_assert(WM * WN == 4 && TM >= 1 && TN >= 1 && A_LD >= 1 && B_LD >= 1 && KBLK % BK == 0, "tile config");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* As = smem;                     // [2][BM][LDS_LD]
     float* Bs = smem + 2 * BM * LDS_LD;   // [2][BN][LDS_LD]
@@ -83,6 +88,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const GemmArgs g) {
 
     f32x16 acc[TM][TN];
     zero_acc(acc);
+    f32x16 blocks[KBLK > 0 ? TM : 1][KBLK > 0 ? TN : 1];      // KBLK > 0: the sum of the finished blocks
+    if (KBLK > 0) zero_acc(blocks);
 
     // K % 32 == 0 is required by the callers, so K / BK is exact for BK = 16 and 32; split-K: this workgroup owns K steps [kt0, nk)
     int kt0, nkt;
@@ -114,8 +121,30 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const GemmArgs g) {
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[j][q][e], a[i][q][e], acc[i][j], 0, 0, 0);   // C^T: epilogue_tile32
+        if constexpr (KBLK > 0) {
+            if ((kt - kt0 + 1) % (KBLK / BK) == 0) {      // a block is complete (wave-uniform)
+                // Not to be speculated: hipcc otherwise forms blocks + acc in every step and selects, and that read of the accumulators
+                // drains the MFMA chain in front of every barrier (fc2 at ViT-B: 151 us against 127 us with one chain).
+                asm volatile("");
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) {
+                        blocks[i][j] += acc[i][j];
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+                    }
+            }
+        }
         if (kt + 1 < nk) lstore(buf ^ 1);
         __syncthreads();
+    }
+    if constexpr (KBLK > 0) {      // the last block joins the others (after the loop, not in it: as above)
+        asm volatile("");
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) acc[i][j] += blocks[i][j];
     }
 
     // ---- epilogue: the weight fragment is the A operand, so lane (r, h) holds 4 x 4 consecutive columns of row r (common.h) ----
@@ -139,7 +168,9 @@ static void launch_cfg(const GemmArgs& g, hipStream_t s) {
     const int tiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
     const size_t lds = 2 * (BM + BN) * (BK + 4) * sizeof(float);
     dim3 grid(tiles, g.splitk, g.batch);
-    if (g.amode == 0 && g.graph_tag && BM == 64 && BN == 64)
+    if (g.amode == 0 && g.ksum_blocks)
+        ARTALK_LAUNCH((gemm_f32_kernel<BM, BN, WM, WN, BK, 0, 2>), grid, dim3(256), lds, s, g);
+    else if (g.amode == 0 && g.graph_tag && BM == 64 && BN == 64)
         ARTALK_LAUNCH((gemm_f32_kernel<BM, BN, WM, WN, BK, 0, 1>), grid, dim3(256), lds, s, g);
     else if (g.amode == 0)
         ARTALK_LAUNCH((gemm_f32_kernel<BM, BN, WM, WN, BK, 0>), grid, dim3(256), lds, s, g);

@@ -85,8 +85,15 @@ struct GemmArgs {
     int cus = 0;         // compute units the launch may use (0 = the whole device): grid of the one-workgroup-per-CU persistent kernels when the model runs on a CU partition
     int force_cfg = -1;  // >= 0: tile configuration override (tuning/tests)
     int graph_tag = 0;   // 1 for launches inside the captured AR/VAE body (separate kernel symbol, same code)
+    // 1: the fp32 MFMA kernel sums K in blocks - every 256 of K (of its slab, when split) the running sums are added into a second set
+    // and restart from zero - so that a K of 3072 does not pile its rounding onto one chain (dino.hip; the default is one chain over K).
+    // Read by launch_gemm alone, for amode 0.  Kernels of its own (gemm_f32.hip, TAG = 2): the launches that leave it off run the
+    // instantiations they always ran.  (The field fills what was padding in front of `status`: the size of the struct and the offset
+    // of every other field are what they were.)
+    int ksum_blocks = 0;
     int* status = nullptr;   // model status word: bit 3 is raised when a value leaves the range of the P8 format (c_p8 results, fp32 A split while staging)
 };
+static_assert(sizeof(GemmArgs) == 328, "GemmArgs is the kernel argument of every GEMM kernel: ksum_blocks was to fill padding, not to move a field");
 void launch_gemm(const GemmArgs& g, hipStream_t s);
 void launch_splitk_reduce(const GemmArgs& g, hipStream_t s);   // epilogue pass of a split-K GEMM (g.splitk > 1)
 struct LnArgs;

@@ -25,6 +25,17 @@ int artalk_op_gemm(const float* A, int64_t lda, const float* W, const float* bia
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
 }
 
+// artalk_op_gemm with GemmArgs::ksum_blocks on: the kernels the DINO object launches (K summed in blocks of 256)
+int artalk_op_gemm_blocked(const float* A, int64_t lda, const float* W, const float* bias, const float* gate, const float* R, float* C,
+                           int M, int N, int K, int act, void* stream) {
+    if (!A || !W || !C || K % 32 != 0 || M < 0 || N <= 0) return ARTALK_EINVAL;
+    GemmArgs g;
+    g.A = A; g.lda = lda; g.W = W; g.ldw = K; g.bias = bias; g.C = C; g.ldc = N; g.gate = gate; g.ldg = N; g.R = R; g.ldr = N;
+    g.M = M; g.N = N; g.K = K; g.act = act; g.ksum_blocks = 1;
+    launch_gemm(g, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+
 int artalk_op_gemm_ex(const float* A, int64_t lda, const float* W, const float* bias, float* C, int M, int N, int K, int act,
                       int force_cfg, void* stream) {
     if (!A || !W || !C || K % 32 != 0 || M < 0 || N <= 0 || force_cfg < -1 || force_cfg == 0 || force_cfg > 4) return ARTALK_EINVAL;

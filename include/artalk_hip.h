@@ -621,6 +621,10 @@ int artalk_set_cu_mask(artalk_model* m, const uint32_t* mask, int n_words);
 /* C[M,N] = R + gate * act(A[M,K] W[N,K]^T + bias); act: 0 none, 1 gelu(erf), 2 gelu(tanh), 3 leaky_relu(0.2). K % 32 == 0 */
 int artalk_op_gemm(const float* A, int64_t lda, const float* W, const float* bias, const float* gate, const float* R,
                    float* C, int M, int N, int K, int act, void* stream);
+/* same arguments and tiles, K summed in blocks: every 256 of K the running sums are added into a second set and restart from zero.
+ * The kernels the DINO object's linear layers run (artalk_dino_forward), for the parity tests at K = 768 and 3072. */
+int artalk_op_gemm_blocked(const float* A, int64_t lda, const float* W, const float* bias, const float* gate, const float* R,
+                           float* C, int M, int N, int K, int act, void* stream);
 /* same, with an explicit tile configuration (4: 128x128 BK16, 2: 64x64, 1: 128x64, 3: 32x128; -1: heuristic) for tuning */
 int artalk_op_gemm_ex(const float* A, int64_t lda, const float* W, const float* bias, float* C, int M, int N, int K, int act,
                       int force_cfg, void* stream);
