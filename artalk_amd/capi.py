@@ -38,6 +38,7 @@ SYMBOLS = [
     "artalk_styleunet_set_slab", "artalk_styleunet_set_timing", "artalk_styleunet_get_timing", "artalk_styleunet_destroy",
     "artalk_styleunet_last_error", "artalk_op_conv2d", "artalk_op_resample2",
     "artalk_styleunet_set_precision", "artalk_styleunet_get_precision", "artalk_op_conv2d_ex", "artalk_styleunet_get_launch_timing",
+    "artalk_op_conv2d_plan",
     "artalk_flame_dims", "artalk_styleunet_dims",
     "artalk_gaga_create", "artalk_gaga_set_avatar", "artalk_gaga_set_forehead", "artalk_gaga_set_watermark", "artalk_gaga_reset_state",
     "artalk_gaga_set_slab", "artalk_gaga_render", "artalk_gaga_set_timing", "artalk_gaga_get_timing", "artalk_gaga_destroy",
@@ -285,6 +286,9 @@ def lib() -> C.CDLL:
         L.artalk_styleunet_get_launch_timing.restype = i32
         L.artalk_op_conv2d_ex.argtypes = L.artalk_op_conv2d.argtypes[:-1] + [i32, vp]
         L.artalk_op_conv2d_ex.restype = i32
+    if hasattr(L, "artalk_op_conv2d_plan"):      # (an older build loaded through ARTALK_LIB lacks the conv planner's entry point)
+        L.artalk_op_conv2d_plan.argtypes = [C.c_uint64, i64, C.c_uint64, C.c_uint64, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32), i32]
+        L.artalk_op_conv2d_plan.restype = i32
     if hasattr(L, "artalk_gaga_create"):      # (an older build loaded through ARTALK_LIB for an A/B run lacks the GAGAvatar head)
         pi = C.POINTER(i32)
         L.artalk_flame_dims.argtypes = [vp, pi, pi, C.POINTER(f32)]
@@ -559,3 +563,26 @@ def conv_tail_class(valid: int, samples_per_chunk: int = 64000) -> int:
     if rc < 0:
         raise ValueError(f"artalk_conv_tail_class({valid}) failed ({rc})")
     return rc
+
+
+CONV_PLAN_FIELDS = ("NT", "VA", "VB", "NP", "grid_x", "grid_y", "steps", "Cinp", "Kp")
+
+
+def conv2d_plan(x_addr: int, x_bstride: int, w_addr: int, in_scale_addr: int, B: int, H: int, W: int, Cin: int, Cout: int, k: int,
+                precision: int) -> dict:
+    """``artalk_op_conv2d_plan`` as a dict over CONV_PLAN_FIELDS: the instantiation and grid ``artalk_op_conv2d_ex`` runs for these
+    arguments (addresses are only looked at for presence and alignment; in_scale_addr 0 = no input scale).  Host only: needs no GPU."""
+    out = (C.c_int32 * len(CONV_PLAN_FIELDS))()
+    rc = int(lib().artalk_op_conv2d_plan(x_addr, x_bstride, w_addr, in_scale_addr, B, H, W, Cin, Cout, k, precision, out, len(out)))
+    if rc < 0:
+        raise ValueError(f"artalk_op_conv2d_plan refused its arguments ({rc})")
+    assert rc == len(CONV_PLAN_FIELDS), rc
+    return dict(zip(CONV_PLAN_FIELDS, out))
+
+
+def conv_kernel_name(plan: dict) -> str:
+    """The instantiation a plan of ``conv2d_plan`` names, as the sources spell it."""
+    tf = lambda v: "true" if v else "false"
+    if plan["NP"] == 0:
+        return f"conv_mfma_kernel<{plan['NT']},{tf(plan['VA'])},{tf(plan['VB'])}>"
+    return f"conv_bf16_kernel<{plan['NT']},{plan['NP']},{tf(plan['VA'])}>"

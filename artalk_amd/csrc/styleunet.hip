@@ -27,7 +27,6 @@
 namespace artalk {
 
 // ------------------------------------------------------------------ convolution ------------------------------------------------------
-constexpr int CV_BM = 128, CV_BK = 16;
 constexpr int CV_LDA = CV_BM + 32;      // pitches = 32 mod 64 banks: the two half-waves of a fragment read (k, k + 1) hit disjoint banks
 constexpr int CV_LDB = 96;
 
@@ -157,20 +156,37 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvArgs a) {
 
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-// The tile choice depends on Cout alone (never on B), so the K order of an output value does not depend on how frames are batched.
-void launch_conv(const ConvArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+ConvPlan plan_conv(const ConvArgs& a, int precision) {
     const long M = (long)a.B * a.H * a.W;
-    if (M <= 0) return;
-    const bool va = a.Cin % 8 == 0 && aligned16(a.x) && a.x_bstride % 4 == 0 && (!a.in_scale || (aligned16(a.in_scale) && a.in_scale_ld % 4 == 0));
-    const bool vb = a.Cout % 4 == 0 && aligned16(a.w);
-    const int nt = a.Cout <= 32 ? 1 : 2;
-    const dim3 grid((unsigned)((M + CV_BM - 1) / CV_BM), (unsigned)((a.Cout + 32 * nt - 1) / (32 * nt))), block(256);
+    ConvPlan p{};
+    p.nt = a.Cout <= 32 ? 1 : 2;
+    p.va = a.Cin % 8 == 0 && aligned16(a.x) && a.x_bstride % 4 == 0 && (!a.in_scale || (aligned16(a.in_scale) && a.in_scale_ld % 4 == 0));
+    p.gy = (unsigned)((a.Cout + 32 * p.nt - 1) / (32 * p.nt));
+    if (precision == CONV_PRECISION_F32) {
+        p.vb = a.Cout % 4 == 0 && aligned16(a.w);
+        p.gx = (unsigned)((M + CV_BM - 1) / CV_BM);
+        p.nsteps = a.k * a.k * ((a.Cin + CV_BK - 1) / CV_BK);
+    } else {
+        p.vb = -1;
+        p.np = precision == CONV_PRECISION_BF16X3 ? 3 : 1;
+        p.gx = (unsigned)((M + CB_BM - 1) / CB_BM);
+        p.cinp = conv_packed_cinp(a.Cin); p.kp = conv_packed_kp(a.Cin, a.k);
+        p.nsteps = p.kp / CB_BK;
+    }
+    return p;
+}
+
+void launch_conv(const ConvArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+    if ((long)a.B * a.H * a.W <= 0) return;
+    const ConvPlan p = plan_conv(a, CONV_PRECISION_F32);
+    const bool va = p.va, vb = p.vb;
+    const dim3 grid(p.gx, p.gy), block(256);
 #define CV_GO(NT, VA, VB)                                                                                              \
     do {                                                                                                               \
         if (e0) hipExtLaunchKernelGGL((conv_mfma_kernel<NT, VA, VB>), grid, block, 0, s, e0, e1, 0, a);                \
         else ARTALK_LAUNCH((conv_mfma_kernel<NT, VA, VB>), grid, block, 0, s, a);                                      \
     } while (0)
-    if (nt == 1) {
+    if (p.nt == 1) {
         if (va && vb) CV_GO(1, true, true); else if (va) CV_GO(1, true, false); else if (vb) CV_GO(1, false, true); else CV_GO(1, false, false);
     } else {
         if (va && vb) CV_GO(2, true, true); else if (va) CV_GO(2, true, false); else if (vb) CV_GO(2, false, true); else CV_GO(2, false, false);
@@ -867,17 +883,36 @@ int artalk_styleunet_forward(artalk_styleunet* u, const float* x_dev, int B, con
     return ARTALK_OK;
 }
 
+// what artalk_op_conv2d_ex and artalk_op_conv2d_plan refuse in the arguments they share
+static bool conv_op_shape_ok(const void* x, int64_t x_bstride, const void* w, int B, int H, int W, int Cin, int Cout, int k, int precision) {
+    if (!x || !w) return false;
+    if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || (k != 1 && k != 3)) return false;
+    if ((int64_t)B * H * W > (int64_t)1 << 30 || (int64_t)H * W > INT_MAX) return false;
+    if (x_bstride != 0 && x_bstride < (int64_t)H * W * Cin) return false;
+    return precision == CONV_PRECISION_F32 || precision == CONV_PRECISION_BF16X3 || precision == CONV_PRECISION_BF16;
+}
+
+int artalk_op_conv2d_plan(uint64_t x_addr, int64_t x_bstride, uint64_t w_addr, uint64_t in_scale_addr, int B, int H, int W, int Cin, int Cout,
+                          int k, int precision, int32_t* out, int n) {
+    const void *x = (const void*)(uintptr_t)x_addr, *w = (const void*)(uintptr_t)w_addr;
+    if (!conv_op_shape_ok(x, x_bstride, w, B, H, W, Cin, Cout, k, precision) || n < 0 || (n > 0 && !out)) return ARTALK_EINVAL;
+    ConvArgs a{};
+    a.x = (const float*)x; a.x_bstride = x_bstride; a.w = (const float*)w; a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.k = k;
+    a.in_scale = (const float*)(uintptr_t)in_scale_addr; a.in_scale_ld = Cin;
+    const ConvPlan p = plan_conv(a, precision);
+    const int32_t v[] = {p.nt, p.va, p.vb, p.np, (int32_t)p.gx, (int32_t)p.gy, p.nsteps, p.cinp, p.kp};
+    const int count = (int)(sizeof(v) / sizeof(v[0]));
+    for (int i = 0; i < n && i < count; ++i) out[i] = v[i];
+    return count;
+}
+
 int artalk_op_conv2d_ex(const float* x, int64_t x_bstride, const float* w, float* out, int B, int H, int W, int Cin, int Cout, int k,
                         const float* in_scale, const float* out_scale, float gain, const float* noise, int64_t noise_bstride,
                         const float* noise_weight, const float* bias, int lrelu, const float* sft_scale, const float* sft_shift,
                         const float* residual, int precision, void* stream) {
-    if (!x || !w || !out) return ARTALK_EINVAL;
-    if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || (k != 1 && k != 3)) return ARTALK_EINVAL;
-    if ((int64_t)B * H * W > (int64_t)1 << 30 || (int64_t)H * W > INT_MAX) return ARTALK_EINVAL;
-    if (x_bstride != 0 && x_bstride < (int64_t)H * W * Cin) return ARTALK_EINVAL;
+    if (!out || !conv_op_shape_ok(x, x_bstride, w, B, H, W, Cin, Cout, k, precision)) return ARTALK_EINVAL;
     if (noise && (!noise_weight || (noise_bstride != 0 && noise_bstride < (int64_t)H * W))) return ARTALK_EINVAL;
     if ((sft_scale == nullptr) != (sft_shift == nullptr)) return ARTALK_EINVAL;
-    if (precision != CONV_PRECISION_F32 && precision != CONV_PRECISION_BF16X3 && precision != CONV_PRECISION_BF16) return ARTALK_EINVAL;
     ConvArgs a{};
     a.x = x; a.x_bstride = x_bstride; a.w = w; a.out = out; a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.k = k;
     a.in_scale = in_scale; a.in_scale_ld = Cin; a.out_scale = out_scale; a.gain = gain; a.noise = noise; a.noise_bstride = noise_bstride; a.noise_w = noise_weight;

@@ -27,7 +27,7 @@ namespace artalk {
 typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
-constexpr int CB_BM = 128, CB_BK = 32, CB_LD = CB_BK + 8;
+constexpr int CB_LD = CB_BK + 8;
 
 __global__ __launch_bounds__(256) void conv_pack_kernel(const float* __restrict__ w, __bf16* __restrict__ out, int Cin, int Cout, int kk, int Cinp,
                                                         int Kp) {
@@ -191,8 +191,6 @@ __global__ __launch_bounds__(256) void conv_bf16_kernel(ConvArgs a, const __bf16
     conv_epilogue<NT>(a, acc, m0, n0, wave, r, h, M, HW);
 }
 
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 void launch_conv_pack(const float* w, void* packed, int Cin, int Cout, int k, hipStream_t s) {
     const int Cinp = conv_packed_cinp(Cin), Kp = conv_packed_kp(Cin, k);
     const long n = (long)Cout * Kp;
@@ -201,13 +199,12 @@ void launch_conv_pack(const float* w, void* packed, int Cin, int Cout, int k, hi
 
 // The tile choice depends on Cout alone (never on B), as for the fp32 kernel.
 void launch_conv_bf16(const ConvArgs& a, const void* packed, int precision, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
-    const long M = (long)a.B * a.H * a.W;
-    if (M <= 0) return;
-    const bool va = a.Cin % 8 == 0 && aligned16(a.x) && a.x_bstride % 4 == 0 && (!a.in_scale || (aligned16(a.in_scale) && a.in_scale_ld % 4 == 0));
-    const int nt = a.Cout <= 32 ? 1 : 2;
-    const int Cinp = conv_packed_cinp(a.Cin), Kp = conv_packed_kp(a.Cin, a.k);
+    if ((long)a.B * a.H * a.W <= 0) return;
+    const ConvPlan p = plan_conv(a, precision);
+    const bool va = p.va;
+    const int Cinp = p.cinp, Kp = p.kp;
     const __bf16* wp = reinterpret_cast<const __bf16*>(packed);
-    const dim3 grid((unsigned)((M + CB_BM - 1) / CB_BM), (unsigned)((a.Cout + 32 * nt - 1) / (32 * nt))), block(256);
+    const dim3 grid(p.gx, p.gy), block(256);
 #define CB_GO(NT, NP, VA)                                                                                                  \
     do {                                                                                                                   \
         if (e0) hipExtLaunchKernelGGL((conv_bf16_kernel<NT, NP, VA>), grid, block, 0, s, e0, e1, 0, a, wp, Cinp, Kp);      \
@@ -217,7 +214,7 @@ void launch_conv_bf16(const ConvArgs& a, const void* packed, int precision, hipS
     do {                                                                                                                   \
         if (precision == CONV_PRECISION_BF16X3) CB_GO(NT, 3, VA); else CB_GO(NT, 1, VA);                                   \
     } while (0)
-    if (nt == 1) { if (va) CB_NP(1, true); else CB_NP(1, false); }
+    if (p.nt == 1) { if (va) CB_NP(1, true); else CB_NP(1, false); }
     else         { if (va) CB_NP(2, true); else CB_NP(2, false); }
 #undef CB_NP
 #undef CB_GO

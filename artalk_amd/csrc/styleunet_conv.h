@@ -55,6 +55,10 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs a, const f32x16 (&a
     }
 }
 
+// Workgroup tiles: pixels x K depth of one step (the N extent is 32 NT).  conv_mfma_kernel (CV_) and conv_bf16_kernel (CB_).
+constexpr int CV_BM = 128, CV_BK = 16;
+constexpr int CB_BM = 128, CB_BK = 32;
+
 // One exact-fp32 conv (styleunet.hip).  e0 / e1: events around the launch, or null.
 void launch_conv(const ConvArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 
@@ -62,9 +66,23 @@ void launch_conv(const ConvArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipE
 // A conv weight packed for the bf16 kernels: two planes (hi, then lo) of [Cout][Kp] bf16, the K index being tap * Cinp + ci with Cin
 // padded to Cinp (a multiple of 8, one MFMA fragment) and K = k k Cinp padded to Kp (a multiple of 32, one K step); padding is zero.
 constexpr int CONV_PRECISION_F32 = 0, CONV_PRECISION_BF16X3 = 1, CONV_PRECISION_BF16 = 2;
+static_assert(CB_BK == 32, "conv_packed_kp pads K to one step of conv_bf16_kernel");
 inline int conv_packed_cinp(int Cin) { return (Cin + 7) & ~7; }
 inline int conv_packed_kp(int Cin, int k) { return (k * k * conv_packed_cinp(Cin) + 31) & ~31; }
 inline size_t conv_packed_elems(int Cin, int Cout, int k) { return (size_t)2 * Cout * conv_packed_kp(Cin, k); }      // 2-byte elements
+
+// Which instantiation a launch runs and on what grid: the one choice launch_conv and launch_conv_bf16 switch on (styleunet.hip; host
+// only, asked without a device through artalk_op_conv2d_plan).  Of `a` it looks at the shape, x, x_bstride, w, in_scale and
+// in_scale_ld; pointers are looked at for presence and alignment, never dereferenced.
+//   nt      1 for Cout <= 32, else 2: the tile depends on Cout alone (never on B), so the K order of an output value does not depend
+//           on how frames are batched
+//   va      vector loads of x and in_scale: Cin % 8 == 0, x and in_scale 16-byte aligned, x_bstride % 4 == 0 and in_scale_ld % 4 == 0
+//   vb      fp32 only (-1 in the bf16 modes, which read the packed copy): vector loads of w: Cout % 4 == 0 and w 16-byte aligned
+//   np      products per MFMA step: 0 fp32, 3 bf16x3, 1 bf16
+//   nsteps  K steps of the main loop: k k ceil(Cin / CV_BK) in fp32, kp / CB_BK in the bf16 modes
+//   cinp, kp: the packed weight's paddings (0 in fp32)
+struct ConvPlan { int nt, va, vb, np; unsigned gx, gy; int nsteps, cinp, kp; };
+ConvPlan plan_conv(const ConvArgs& a, int precision);
 
 // w [k k][Cin][Cout] fp32 -> packed (conv_packed_elems 2-byte elements, 16-byte aligned)
 void launch_conv_pack(const float* w, void* packed, int Cin, int Cout, int k, hipStream_t s);

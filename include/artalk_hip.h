@@ -296,7 +296,15 @@ const char* artalk_splat_last_error(const artalk_splat* s);
  * the bits it gave before.  artalk_styleunet_get_precision: the mode in force, or ARTALK_EINVAL for a NULL handle.
  * artalk_op_conv2d_ex: artalk_op_conv2d with a precision argument, from the same fp32 weights; precision 0 IS artalk_op_conv2d.  In modes
  * 1 and 2 it packs the weight into a block it owns, on the caller's stream, WAITS for that stream and frees the block.  Every refusal
- * (an unknown precision included) comes before the device is touched. */
+ * (an unknown precision included) comes before the device is touched.
+ * artalk_op_conv2d_plan: which kernel instantiation artalk_op_conv2d_ex runs for these arguments and on what grid - plan_conv, the one host
+ * function launch_conv and launch_conv_bf16 switch on, asked without a device.  x_addr, w_addr and in_scale_addr (0: no input scale) are
+ * addresses that are looked at for presence and 16-byte alignment and never dereferenced.  Fills out[0 .. min(n, 9)) with NT (1: Cout <=
+ * 32, else 2), VA (1: vector loads of x and in_scale - Cin % 8 == 0, x and in_scale 16-byte aligned, x_bstride % 4 == 0), VB (fp32: 1 for
+ * vector loads of w - Cout % 4 == 0 and w 16-byte aligned; -1 in modes 1 and 2, which read the packed copy), NP (products per step: 0 fp32,
+ * 3 bf16x3, 1 bf16), grid x (128-pixel tiles), grid y (32 NT-channel tiles), the K steps of the main loop, and the packed weight's Cinp
+ * and Kp (0 in fp32): conv_mfma_kernel<NT, VA, VB> or conv_bf16_kernel<NT, NP, VA>.  Returns 9, the number of values, or ARTALK_EINVAL
+ * for what artalk_op_conv2d_ex refuses in these arguments (and for n < 0, or n > 0 with a NULL out).  Host work only. */
 typedef struct artalk_styleunet artalk_styleunet;
 int artalk_styleunet_create(int device_id, int in_dim, int out_dim, int out_size, artalk_styleunet** out);
 int artalk_styleunet_set_tensor(artalk_styleunet* u, const char* key, const void* host_ptr, int ndim, const int64_t* shape);
@@ -319,6 +327,8 @@ int artalk_op_conv2d_ex(const float* x, int64_t x_bstride, const float* w, float
                         const float* in_scale, const float* out_scale, float gain, const float* noise, int64_t noise_bstride,
                         const float* noise_weight, const float* bias, int lrelu, const float* sft_scale, const float* sft_shift,
                         const float* residual, int precision, void* stream);
+int artalk_op_conv2d_plan(uint64_t x_addr, int64_t x_bstride, uint64_t w_addr, uint64_t in_scale_addr, int B, int H, int W, int Cin, int Cout,
+                          int k, int precision, int32_t* out, int n);
 int artalk_op_resample2(const float* x, float* out, int B, int H, int W, int C, int up, void* stream);
 
 /* Read-only views of a handle, for objects that borrow it (artalk_gaga below).  Both return the handle's device index, or ARTALK_EINVAL for
