@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("ARTALK_LIB") or os.path.join(_HERE, "libartalk_hip.so
 
 OK, EINVAL, EKEY, EMISSING, EHIP, ESTATE, ECAPACITY, EBUSY = 0, -1, -2, -3, -4, -5, -6, -7
 DTYPE_F32, DTYPE_I64 = 0, 1
+FRAMES_RGB24, FRAMES_YUV420P = 1, 2      # ARTALK_FRAMES_* of include/artalk_hip.h
 
 # every symbol include/artalk_hip.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
@@ -44,6 +45,8 @@ SYMBOLS = [
     "artalk_gaga_set_slab", "artalk_gaga_render", "artalk_gaga_set_timing", "artalk_gaga_get_timing", "artalk_gaga_destroy",
     "artalk_gaga_last_error", "artalk_gaga_cameras", "artalk_op_gaga_flame_inputs", "artalk_op_gaga_forehead", "artalk_op_gaga_means",
     "artalk_op_gaga_finish", "artalk_op_gaga_check",
+    "artalk_frames_bytes", "artalk_frames_pack", "artalk_frames_last_error", "artalk_op_frames_check", "artalk_op_gaga_finish_pack",
+    "artalk_gaga_render_u8",
     "artalk_gsgen_create", "artalk_gsgen_set_tensor", "artalk_gsgen_finalize", "artalk_gsgen_planes", "artalk_gsgen_generate",
     "artalk_gsgen_set_timing", "artalk_gsgen_get_timing", "artalk_gsgen_dims", "artalk_gsgen_destroy", "artalk_gsgen_last_error",
     "artalk_op_conv2d_relu", "artalk_op_gs_local_input", "artalk_op_gs_global_input", "artalk_op_gs_concat_dir",
@@ -329,6 +332,19 @@ def lib() -> C.CDLL:
         L.artalk_op_gaga_finish.restype = i32
         L.artalk_op_gaga_check.argtypes = [i32, i32, i32, vp, i32, i32, i32, i32, i64, i32, i32, C.c_char_p, i32]
         L.artalk_op_gaga_check.restype = i32
+    if hasattr(L, "artalk_frames_pack"):      # (an older build loaded through ARTALK_LIB for an A/B run lacks the 8-bit frames)
+        L.artalk_frames_bytes.argtypes = [i32, i32, i32]
+        L.artalk_frames_bytes.restype = i64
+        L.artalk_frames_pack.argtypes = [vp, i32, i32, i32, i32, vp, vp]
+        L.artalk_frames_pack.restype = i32
+        L.artalk_frames_last_error.argtypes = []
+        L.artalk_frames_last_error.restype = C.c_char_p
+        L.artalk_op_frames_check.argtypes = [i32, i32, i32, i32, i32, i32, C.c_char_p, i32]
+        L.artalk_op_frames_check.restype = i32
+        L.artalk_op_gaga_finish_pack.argtypes = [vp, i32, i32, vp, i32, i32, i32, vp, vp]
+        L.artalk_op_gaga_finish_pack.restype = i32
+        L.artalk_gaga_render_u8.argtypes = [vp, vp, i64, i32, C.POINTER(vp), C.POINTER(i64), i32, i32, vp, vp, vp]
+        L.artalk_gaga_render_u8.restype = i32
     if hasattr(L, "artalk_gsgen_create"):      # (an older build loaded through ARTALK_LIB for an A/B run lacks the Gaussian generators)
         L.artalk_gsgen_create.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
         L.artalk_gsgen_create.restype = i32

@@ -1,4 +1,4 @@
-// Owners of what the host side takes from the HIP runtime: device blocks, pinned host blocks, events, the events of a stage timer.
+// Owners of what the host side takes from the HIP runtime: device blocks, pinned host blocks, events, streams, the events of a stage timer.
 // Host code only.  Every type is move-only, takes nothing in its constructor and gives back what it holds in its destructor, so an
 // object made of them is destroyed by `delete` and an early return leaks nothing.  A call that fails leaves its object empty
 // (capacity 0), clears the runtime's last error - the caller reports the failure once, and it does not come back from a later
@@ -76,6 +76,23 @@ public:
 private:
     struct Destroy { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
     std::unique_ptr<std::remove_pointer_t<hipEvent_t>, Destroy> e_;
+};
+
+// A non-blocking stream of the current device (a copy stream beside the caller's)
+class Stream {
+public:
+    hipStream_t get() const { return s_.get(); }
+    bool create() {
+        if (s_) return true;
+        hipStream_t s = nullptr;
+        if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); return false; }
+        s_.reset(s);
+        return true;
+    }
+
+private:
+    struct Destroy { void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); } };
+    std::unique_ptr<std::remove_pointer_t<hipStream_t>, Destroy> s_;
 };
 
 // Time per stage of one call, from events on the call's stream: the interval that ENDS at a mark belongs to the mark's stage

@@ -6,6 +6,7 @@
 //   gaga_forehead_kernel       EMA over frames of K listed vertices; its state outlives the call               (models.py:120-125)
 //   gaga_means_kernel          per-frame Gaussian centres: V skinned vertices, then the avatar's static points (models.py:90)
 //   gaga_finish_kernel         clamp(0, 1) and the watermark blend, in place                                   (models.py:95, 131-138)
+//   (frames.hip)               the same clamp and blend fused with the packing into 8-bit frames, for artalk_gaga_render_u8
 //   artalk_gaga_cameras        host only: head-rotation codes -> the view / projection matrices the rasteriser reads (models.py:127)
 //
 // All fp32 and element-wise (no reductions, no atomics): bit-identical from run to run.  The EMA and the blend use torch's rounding
@@ -22,6 +23,7 @@
 #include "artalk_hip.h"
 #include "common.h"
 #include "device_mem.h"
+#include "kernels.h"
 
 namespace artalk {
 
@@ -180,6 +182,11 @@ struct artalk_gaga {
     DevBuf<float> betas, pose, verts, means, img;
     DevBuf<int32_t> radii;
     PinnedBuf<float> codes_host;      // [frames][3]
+    // 8-bit frames out (artalk_gaga_render_u8): the upsampler's fp32 slab, the stream of the copies to the host and its two events
+    int cap_rgb = 0;
+    DevBuf<float> rgb;
+    Stream copy_stream;
+    Event packed, copied;
     bool timing = false;
     double stage_ms[kGagaStages] = {0, 0, 0, 0, 0};
     std::string err;
@@ -385,19 +392,32 @@ int artalk_gaga_get_timing(const artalk_gaga* g, double* stage_ms, int n) {
     return kGagaStages;
 }
 
-int artalk_gaga_render(artalk_gaga* g, const float* motion_dev, int64_t motion_stride, int T, const float* const* noise_ptrs_or_null,
-                       const int64_t* noise_batch_strides, int activation, float* out_dev, void* stream) {
+// The loop of artalk_gaga_render and artalk_gaga_render_u8.  format == 0: fp32 frames into out_dev, finished in place.  Otherwise the
+// upsampler writes each slab into g->rgb and the fused finish-and-pack kernel writes its 8-bit frames into out_u8 (and, with out_host, a
+// copy on g->copy_stream follows each slab's pack kernel).
+static int gaga_render_any(artalk_gaga* g, const float* motion_dev, int64_t motion_stride, int T, const float* const* noise_ptrs_or_null,
+                           const int64_t* noise_batch_strides, int activation, float* out_dev, int format, uint8_t* out_u8, uint8_t* out_host,
+                           void* stream) {
     if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
-    if (!motion_dev || !out_dev) return gaga_fail(g, ARTALK_EINVAL, "motion and out must not be NULL");
+    if (!motion_dev || (format ? !out_u8 : !out_dev)) return gaga_fail(g, ARTALK_EINVAL, "motion and out must not be NULL");
     int finalized = 0;
     (void)artalk_styleunet_dims(g->unet, nullptr, nullptr, nullptr, &finalized, nullptr);
     const int rc = check_render(T, motion_stride, g->have_avatar, finalized != 0, &g->err);
     if (rc != ARTALK_OK) return rc;
     const int rcn = su_check_noise(g->num_layers, noise_ptrs_or_null, noise_batch_strides, &g->err);
     if (rcn != ARTALK_OK) return rcn;
+    if (format) {
+        const int rcf = frames_check(format, T, g->S, g->S, true, true, &g->err);
+        if (rcf != ARTALK_OK) return rcf;
+    }
     if (T == 0) return ARTALK_OK;
     if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
     hipStream_t s = (hipStream_t)stream;
+    if (format) {      // the call waits on its stream and orders a second stream against it: not inside a capture
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); return gaga_fail(g, ARTALK_EHIP, "hipStreamIsCapturing failed"); }
+        if (cap != hipStreamCaptureStatusNone) return gaga_fail(g, ARTALK_EINVAL, "artalk_gaga_render_u8 waits on its stream: it cannot run during stream capture");
+    }
     const int V = g->V, N = g->N, S = g->S, NB = g->NB;
     const long SS = (long)S * S;
     const int slab = gaga_slab(g);
@@ -412,6 +432,15 @@ int artalk_gaga_render(artalk_gaga* g, const float* motion_dev, int64_t motion_s
             return gaga_fail(g, ARTALK_EHIP, "hipMalloc of the scratch for " + std::to_string(frames) + " frames failed");
         g->cap_frames = frames; g->cap_N = N;
     }
+    const int64_t fbytes = format ? frames_bytes(format, S, S) : 0;
+    if (format && frames > g->cap_rgb) {
+        (void)hipDeviceSynchronize();
+        g->cap_rgb = 0; g->rgb.reset();
+        if (!g->rgb.alloc((size_t)frames * 3 * SS)) return gaga_fail(g, ARTALK_EHIP, "hipMalloc of the fp32 slab for " + std::to_string(frames) + " frames failed");
+        g->cap_rgb = frames;
+    }
+    if (out_host && (!g->copy_stream.create() || !g->packed.create() || !g->copied.create()))
+        return gaga_fail(g, ARTALK_EHIP, "creating the copy stream or its events failed");
     if (!g->codes_host.grow((size_t)T * 3, 0, 1, s)) return gaga_fail(g, ARTALK_EHIP, "hipHostMalloc failed");
     // the first wait of the call: the head-rotation codes become the cameras, which the rasteriser reads on the host
     if (hipMemcpy2DAsync(g->codes_host.get(), 3 * sizeof(float), motion_dev + 100, (size_t)motion_stride * sizeof(float), 3 * sizeof(float), (size_t)T,
@@ -444,16 +473,50 @@ int artalk_gaga_render(artalk_gaga* g, const float* motion_dev, int64_t motion_s
         if (rc2 != ARTALK_OK) return gaga_fail(g, rc2, std::string("artalk_splat_render failed: ") + artalk_splat_last_error(g->splat));
         timer.mark(kGagaSplat);
         if (noise_ptrs_or_null) for (int l = 0; l < g->num_layers; ++l) np[l] = noise_ptrs_or_null[l] + (long)f0 * noise_batch_strides[l];
-        float* out = out_dev + (long)f0 * 3 * SS;
+        float* out = format ? g->rgb.get() : out_dev + (long)f0 * 3 * SS;
         rc2 = artalk_styleunet_forward(g->unet, g->img.get(), n, noise_ptrs_or_null ? np.data() : nullptr, noise_batch_strides, activation, out, s);
         if (rc2 != ARTALK_OK) return gaga_fail(g, rc2, std::string("artalk_styleunet_forward failed: ") + artalk_styleunet_last_error(g->unet));
         timer.mark(kGagaUpsampler);
-        launch_gaga_finish(out, g->wm.get(), g->wm_h, g->wm_w, S, n, s);
+        if (!format) {
+            launch_gaga_finish(out, g->wm.get(), g->wm_h, g->wm_w, S, n, s);
+        } else {
+            uint8_t* o8 = out_u8 + (int64_t)f0 * fbytes;
+            launch_frames_finish_pack(out, g->wm.get(), g->wm_h, g->wm_w, S, n, format, o8, s);
+            if (out_host) {      // out_u8 holds the whole clip: nothing this copy reads is written again
+                if (hipEventRecord(g->packed.get(), s) != hipSuccess || hipStreamWaitEvent(g->copy_stream.get(), g->packed.get(), 0) != hipSuccess ||
+                    hipMemcpyAsync(out_host + (int64_t)f0 * fbytes, o8, (size_t)((int64_t)n * fbytes), hipMemcpyDeviceToHost, g->copy_stream.get()) != hipSuccess) {
+                    (void)hipGetLastError();
+                    return gaga_fail(g, ARTALK_EHIP, "copying a slab's frames to the host failed");
+                }
+            }
+        }
         timer.mark(kGagaFinish);
+    }
+    if (out_host) {      // a synchronisation of the caller's stream covers the host buffer
+        if (hipEventRecord(g->copied.get(), g->copy_stream.get()) != hipSuccess || hipStreamWaitEvent(s, g->copied.get(), 0) != hipSuccess) {
+            (void)hipGetLastError();
+            return gaga_fail(g, ARTALK_EHIP, "ordering the caller's stream behind the last copy failed");
+        }
     }
     timer.finish(g->stage_ms, kGagaStages);
     if (hipGetLastError() != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "a launch failed");
     return ARTALK_OK;
+}
+
+int artalk_gaga_render(artalk_gaga* g, const float* motion_dev, int64_t motion_stride, int T, const float* const* noise_ptrs_or_null,
+                       const int64_t* noise_batch_strides, int activation, float* out_dev, void* stream) {
+    return gaga_render_any(g, motion_dev, motion_stride, T, noise_ptrs_or_null, noise_batch_strides, activation, out_dev, 0, nullptr, nullptr, stream);
+}
+
+int artalk_gaga_render_u8(artalk_gaga* g, const float* motion_dev, int64_t motion_stride, int T, const float* const* noise_ptrs_or_null,
+                          const int64_t* noise_batch_strides, int activation, int format, uint8_t* out_dev, uint8_t* out_host_or_null,
+                          void* stream) {
+    if (g && format != ARTALK_FRAMES_RGB24 && format != ARTALK_FRAMES_YUV420P) return gaga_fail(g, ARTALK_EINVAL, "unknown frame format " + std::to_string(format));
+    const int rc = gaga_render_any(g, motion_dev, motion_stride, T, noise_ptrs_or_null, noise_batch_strides, activation, nullptr, format,
+                                   out_dev, out_host_or_null, stream);
+    // a call that failed between two slabs leaves no copy in flight: the caller may free both buffers
+    if (rc != ARTALK_OK && g && out_host_or_null && g->copy_stream.get()) (void)hipStreamSynchronize(g->copy_stream.get());
+    return rc;
 }
 
 // ---- single launches and the host checks, for the tests

@@ -276,6 +276,15 @@ void launch_flame_skin(const float* vposed, const float* rot, const float* J, co
 // StyleUNet (styleunet.hip), host only: the per-layer noise arguments of a forward call (ptrs == NULL: none given).  ARTALK_OK, or
 // ARTALK_EINVAL with the message in *err
 int su_check_noise(int num_layers, const float* const* ptrs, const int64_t* strides, std::string* err);
+// Frames out (frames.hip): fp32 planar frames [F][3][H][W] -> 8-bit frames in `format` (ARTALK_FRAMES_*), [F][frames_bytes].  The
+// finish form reads an S x S image and applies gaga_finish_kernel's clamp and watermark blend (wm [4][h][w] or null) first, bit for bit.
+// The caller has passed frames_check (host only: ARTALK_OK, or ARTALK_EINVAL with the message in *err); frames_bytes: bytes per frame
+// or a negative error.
+constexpr int kFramesMaxSide = 16384;
+int64_t frames_bytes(int format, int H, int W);
+int frames_check(int format, int F, int H, int W, bool have_src, bool have_out, std::string* err);
+void launch_frames_pack(const float* src, long F, int H, int W, int format, uint8_t* out, hipStream_t s);
+void launch_frames_finish_pack(const float* img, const float* wm, int h, int w, int S, long F, int format, uint8_t* out, hipStream_t s);
 // headroom audit: *slot = max(*slot, bits of max |x|) over rows x cols (cols % 8 == 0) of a P8 (is_p8: written with scale 2^p8_exp) or fp32 buffer
 void launch_absmax(const float* buf, int rows, int cols, long ld, int is_p8, unsigned int* slot, hipStream_t s, int junk_period = 0,
                    int junk_from = 0, int p8_exp = kActExp);

@@ -5,7 +5,8 @@ at ``inference.py:225-237``, the Gradio handler at ``:99-125``) keeps working fo
 codes.  Rendering (``inference.py:59-87``: FLAME mesh / GAGAvatar, PyAV muxing) is downstream of the drop-in
 boundary: ``rendering`` only forwards to what the caller plugs in - the FLAME model and the mesh renderer
 (``artalk_amd.flame.FLAMEModel``, ``artalk_amd.render.RenderMesh``) or the GAGAvatar head with its scale-5 FLAME model
-(``artalk_amd.gaga.GAGAvatar``); the identity side of GAGAvatar and muxing are out of scope.
+(``artalk_amd.gaga.GAGAvatar``), and with ``output=`` hands the frames over in 8 bits as an encoder takes them
+(``artalk_amd.frames``); the identity side of GAGAvatar, encoding and muxing are out of scope.
 """
 from __future__ import annotations
 
@@ -230,12 +231,21 @@ class ARTAvatarInferEngine:
 
     smooth_motion_savgol_device = smooth_motion_savgol
 
-    def rendering(self, audio, pred_motions, shape_id="mesh", shape_code=None, save_name="ARTAvatar.mp4"):
+    def rendering(self, audio, pred_motions, shape_id="mesh", shape_code=None, save_name="ARTAvatar.mp4", *, output=None):
         """Downstream of the boundary (inference.py:59-87).  Produces the vertices the reference's mesh branch would
         feed its renderer when a FLAME model has been plugged in.  With a renderer plugged into ``engine.mesh_renderer`` as well
         (``artalk_amd.render.RenderMesh``) it returns what the reference stacks into ``pred_images`` (inference.py:70-72, :83):
         a ``(T, 3, S, S)`` tensor in [0, 1], on the device and from one batched call over all frames (the reference renders frame by
-        frame and moves each image to the host).  Writing the video (PyAV muxing) is not part of this package."""
+        frame and moves each image to the host).
+
+        ``output="rgb24"`` or ``"yuv420p"`` (keyword only) returns, on both branches, the frames as a video encoder takes them
+        (``artalk_amd.frames``): uint8 ``(T, S, S, 3)`` or ``(T, S * 3 // 2, S)`` on the device, the reference's
+        ``(x * 255).astype(np.uint8)`` hand-over (inference.py:83-86, app/utils_videos.py) without the host round trip;
+        ``artalk_amd.frames.write_y4m`` writes the second as a file any encoder reads.  It needs images: with no renderer plugged in it
+        raises ``ValueError``.  Muxing and the audio track (PyAV) are not part of this package."""
+        if output is not None:
+            from .frames import format_code, pack_frames
+            format_code(output)      # ValueError for an unknown format, before anything runs
         head = getattr(self, "GAGAvatar", None)      # (engines assembled without __init__ have no such attribute)
         if shape_id != "mesh" and head is not None:
             # inference.py:73-79 in one library call: (T, 3, S, S) in [0, 1] on the device
@@ -243,11 +253,14 @@ class ARTAvatarInferEngine:
             if flame is None:
                 raise RuntimeError("plug an artalk_amd.flame.FLAMEModel built with scale=5.0 into engine.GAGAvatar_flame")
             head.set_avatar_id(shape_id)
-            return head.render_clip(pred_motions, flame)
+            return head.render_clip(pred_motions, flame) if output is None else head.render_clip(pred_motions, flame, out=output)
         if shape_id != "mesh" or self.flame_model is None:
             raise NotImplementedError("rendering is outside the audio->motion path; plug a FLAME model into "
                                       "engine.flame_model to get vertices (and an artalk_amd.render.RenderMesh into "
                                       "engine.mesh_renderer to get images), or pass pred_motions to the reference renderer")
+        if output is not None and getattr(self, "mesh_renderer", None) is None:
+            raise ValueError(f"output={output!r} needs images: plug an artalk_amd.render.RenderMesh into engine.mesh_renderer "
+                             "(without a renderer the mesh branch returns vertices)")
         if shape_code is None:
             shape_code = audio.new_zeros(1, 300).to(self.device).expand(pred_motions.shape[0], -1)
         else:
@@ -258,4 +271,5 @@ class ARTAvatarInferEngine:
         renderer = getattr(self, "mesh_renderer", None)      # (engines assembled without __init__ have no such attribute)
         if renderer is None:
             return verts
-        return renderer(verts)[0] / 255.0
+        images = renderer(verts)[0] / 255.0
+        return images if output is None else pack_frames(images, output)      # the reference's / 255.0 * 255.0 round trip

@@ -15,6 +15,7 @@ import ctypes as C
 import torch
 
 from . import capi
+from . import frames as _frames
 from . import splat as _splat
 from .styleunet import StyleUNet, noise_resolution
 
@@ -293,8 +294,8 @@ class GAGAvatar:
         return {"motion_code": motion_code.clone(), "flame_model": flame_model,
                 "t_transform": camera_matrices(motion_code[:, 100:103].cpu(), tm)[2].to(motion_code.device)}
 
-    def forward_expression(self, batch, randomize_noise=True, noise=None):
-        return self.render_clip(batch["motion_code"], batch["flame_model"], randomize_noise=randomize_noise, noise=noise)
+    def forward_expression(self, batch, randomize_noise=True, noise=None, out="float"):
+        return self.render_clip(batch["motion_code"], batch["flame_model"], randomize_noise=randomize_noise, noise=noise, out=out)
 
     # ---- the fast path ----
     @staticmethod
@@ -361,12 +362,21 @@ class GAGAvatar:
         return None if self._h is None else int(capi.lib().artalk_gaga_set_slab(self._h, self._slab))
 
     @torch.no_grad()
-    def render_clip(self, motion_codes, flame_model, randomize_noise=True, noise=None):
+    def render_clip(self, motion_codes, flame_model, randomize_noise=True, noise=None, out="float", host=False):
         """motion_codes (T, 106) on the device -> (T, 3, S, S) in [0, 1] on the device, from one library call.  ``flame_model``: an
         ``artalk_amd.flame.FLAMEModel`` built with ``scale=5.0``.  Unlike the reference, ``motion_codes`` is NOT modified (there
         ``transform_emoca_to_p3d`` flips the sign of columns 100 and 102 in place through a view).  ``randomize_noise=True`` draws the
         StyleGAN noise with torch's generator once per slab (the reference: once per frame); ``False`` uses the stored buffers;
-        ``noise`` - per layer a device tensor (T or 1, 1, r, r) - overrides both."""
+        ``noise`` - per layer a device tensor (T or 1, 1, r, r) - overrides both.
+
+        ``out="rgb24"`` or ``"yuv420p"`` returns the frames as a video encoder takes them instead (``artalk_amd.frames``): uint8
+        ``(T, S, S, 3)`` or ``(T, S * 3 // 2, S)``, byte-equal to ``pack_frames(render_clip(...), out)``, from one
+        ``artalk_gaga_render_u8`` call that never holds the fp32 clip.  With ``host=True`` the result is a pinned CPU tensor, filled slab
+        by slab while the next slab renders; the method synchronises the current stream before it returns it."""
+        if out != "float":
+            fmt = _frames.format_code(out)
+        elif host:
+            raise ValueError('host=True needs out="rgb24" or out="yuv420p"')
         m = self._check_motion(motion_codes)
         if (m.device.index or 0) != (self.device.index if self.device.index is not None else torch.cuda.current_device()):
             raise RuntimeError(f"motion_codes lives on {m.device}, the head on {self.device}")
@@ -376,12 +386,16 @@ class GAGAvatar:
         T = int(m.shape[0])
         stride = int(m.stride(0)) if T > 1 else int(m.shape[1])
         S, nl = self.image_size, self.upsampler.num_layers
-        out = torch.empty(T, 3, S, S, dtype=torch.float32, device=m.device)
         L = capi.lib()
         with torch.cuda.device(m.device):
+            if out == "float":
+                res = torch.empty(T, 3, S, S, dtype=torch.float32, device=m.device)
+            else:
+                res = torch.empty(_frames.frame_shape(out, T, S, S), dtype=torch.uint8, device=m.device)
+            res_host = torch.empty(res.shape, dtype=torch.uint8, pin_memory=True) if host else None
             self._ensure(flame_model)
             if T == 0:
-                return out
+                return res_host if host else res
             if noise is None and randomize_noise:
                 slab = self.slab_in_force()
                 parts = [[torch.empty(min(slab, T - f0), 1, noise_resolution(i), noise_resolution(i), device=m.device).normal_()
@@ -399,10 +413,17 @@ class GAGAvatar:
                     keep.append(n.detach().float().contiguous())
                 ptrs = (C.c_void_p * nl)(*[t.data_ptr() for t in keep])
                 strides = (C.c_int64 * nl)(*[0 if t.shape[0] == 1 else t.shape[2] * t.shape[3] for t in keep])
-            rc = L.artalk_gaga_render(self._h, capi.ptr(m), stride, T, ptrs, strides, int(self.upsampler.activation), capi.ptr(out),
-                                      capi.current_stream_ptr())
+            if out == "float":
+                rc = L.artalk_gaga_render(self._h, capi.ptr(m), stride, T, ptrs, strides, int(self.upsampler.activation), capi.ptr(res),
+                                          capi.current_stream_ptr())
+            else:
+                rc = L.artalk_gaga_render_u8(self._h, capi.ptr(m), stride, T, ptrs, strides, int(self.upsampler.activation), fmt,
+                                             capi.ptr(res), capi.ptr(res_host), capi.current_stream_ptr())
+                if host:
+                    torch.cuda.current_stream().synchronize()      # (also after a failure: a copy may be in flight)
+        name = "artalk_gaga_render" if out == "float" else "artalk_gaga_render_u8"
         if rc == capi.EINVAL:
-            raise ValueError("artalk_gaga_render refused: " + self._err())
+            raise ValueError(name + " refused: " + self._err())
         if rc != capi.OK:
-            raise RuntimeError("artalk_gaga_render failed: " + self._err())
-        return out
+            raise RuntimeError(name + " failed: " + self._err())
+        return res_host if host else res

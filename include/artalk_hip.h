@@ -394,6 +394,44 @@ int artalk_op_gaga_finish(float* img_dev, int F, int S, const float* rgba_dev_or
 int artalk_op_gaga_check(int V, int S, int N, const int32_t* idx_host, int K, int wm_h, int wm_w, int T, int64_t motion_stride, int have_avatar,
                          int unet_finalized, char* msg, int msg_cap);
 
+/* Frames out: fp32 planar frames [F][3][H][W] in [0, 1] on the device -> 8-bit frames as a video encoder takes them, a stand-in for the
+ * hand-over of inference.py:83-86 and app/utils_videos.py:8-36 (x * 255, .cpu(), astype(uint8), transpose, rgb24 -> yuv420p in the
+ * encoder).  What is computed is defined in DESIGN.md section 5 ("Frames out").
+ * Quantisation: q(v) = (uint8)(clamp(v, 0, 1) * 255.0f), truncation like astype(np.uint8); NaN -> 0.  The clamp is the one deviation: the
+ * reference wraps values outside [0, 1].
+ * ARTALK_FRAMES_RGB24: out[f][y][x][c] = q(src[f][c][y][x]), H W 3 bytes a frame (PyAV's "rgb24" from an (H, W, 3) array).
+ * ARTALK_FRAMES_YUV420P: BT.601 limited range in integers (>> arithmetic) from the quantised R, G, B: Y = ((66 R + 129 G + 25 B + 128) >> 8)
+ * + 16 per pixel; per 2 x 2 block Rm = (R00 + R01 + R10 + R11 + 2) >> 2 (Gm, Bm likewise), U = ((-38 Rm - 74 Gm + 112 Bm + 128) >> 8) + 128,
+ * V = ((112 Rm - 94 Gm - 18 Bm + 128) >> 8) + 128.  A frame is Y [H][W], U [H/2][W/2], V [H/2][W/2], contiguous: H W 3 / 2 bytes, the I420
+ * frame PyAV's "yuv420p" takes from an (H 3 / 2, W) array and a Y4M file holds.  Parity with libswscale's own rgb24 -> yuv420p (its rounding
+ * and chroma filter) is unpinned.
+ * artalk_frames_bytes: bytes per frame, or ARTALK_EINVAL (an unknown format, H or W outside 1..16384, yuv420p with an odd H or W).
+ * artalk_frames_pack: one launch on `stream`, no wait; src and out need no alignment beyond their element's (the kernel takes its wide
+ * path where the addresses allow it and gives the same bytes elsewhere).  Bit-identical from run to run.  F == 0 succeeds and launches
+ * nothing.  ARTALK_EINVAL with a message (artalk_frames_last_error) before the device is touched: an unknown format, H or W outside
+ * 1..16384, yuv420p with an odd H or W, F < 0, a NULL pointer with F > 0, more than 2^39 groups of four pixels.
+ * artalk_op_frames_check (host only): the same checks on plain numbers; returns the code and copies the message.
+ * artalk_op_gaga_finish_pack: one launch of the fused kernel artalk_gaga_render_u8 runs: img [F][3][S][S] (not modified), rgba [4][h][w] or
+ * NULL -> out [F][artalk_frames_bytes(format, S, S)], byte-equal to artalk_op_gaga_finish followed by artalk_frames_pack.
+ * artalk_gaga_render_u8: artalk_gaga_render (arguments, waits, refusals and the forehead EMA exactly as there) with 8-bit frames out:
+ * the upsampler writes each slab into fp32 scratch the head owns (allocated on the first such call; the fp32 clip is never
+ * materialised) and the fused clamp / watermark / pack kernel writes the slab's frames into out_dev [T][artalk_frames_bytes(format, S, S)].
+ * With out_host_or_null (pinned memory, T frames) every slab's bytes are also copied to the host on a copy stream the head owns, behind an
+ * event recorded after the slab's pack kernel, so the copy overlaps the next slab; before returning the call makes `stream` wait for the
+ * last copy, so that a synchronisation of `stream` covers the host buffer; a call that fails waits for the copies it has started.  ARTALK_EINVAL in addition: an unknown format, yuv420p with an
+ * odd S, a NULL out_dev, a `stream` that is being captured. */
+#define ARTALK_FRAMES_RGB24 1
+#define ARTALK_FRAMES_YUV420P 2
+int64_t artalk_frames_bytes(int format, int H, int W);
+int artalk_frames_pack(const float* src_dev, int F, int H, int W, int format, uint8_t* out_dev, void* stream);
+const char* artalk_frames_last_error(void);
+int artalk_op_frames_check(int format, int F, int H, int W, int have_src, int have_out, char* msg, int msg_cap);
+int artalk_op_gaga_finish_pack(const float* img_dev, int F, int S, const float* rgba_dev_or_null, int h, int w, int format, uint8_t* out_dev,
+                               void* stream);
+int artalk_gaga_render_u8(artalk_gaga* g, const float* motion_dev, int64_t motion_stride, int T, const float* const* noise_ptrs_or_null,
+                          const int64_t* noise_batch_strides, int activation, int format, uint8_t* out_dev, uint8_t* out_host_or_null,
+                          void* stream);
+
 /* The Gaussian generators of the GAGAvatar head's identity side, forward only, exact fp32, one avatar per call: a stand-in for
  * LinearGSGenerator, the two ConvGSGenerators, build_points_planes, the direction encoding and the assembly of _gs_params
  * (app/GAGAvatar/models.py:65-87, 141-233, 236-252).  What is computed is defined in DESIGN.md section 5 ("Gaussian generators"); its

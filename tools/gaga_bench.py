@@ -21,6 +21,14 @@ three modes alternate, each with a plain call and a stage-timed call, so the bas
 
     python tools/gaga_bench.py --precision all --out profiles/gaga_precision_bench.json
 
+``--output all`` compares the forms in which a clip leaves the head (no chain): in every round of the one process ``float`` (the call
+above), ``float+host`` (the same frames, ``.cpu()``, then ``(x * 255).astype(uint8)`` and the transpose in numpy: the reference's
+hand-over with the host conversion timed), ``rgb24`` and ``yuv420p`` (``render_clip(out=...)``, device only) and both with ``host=True``
+alternate, by the wall clock between device synchronisations, each with a plain call and a stage-timed call whose ``finish`` stage is
+the fused clamp / watermark / pack kernel.
+
+    python tools/gaga_bench.py --output all --out profiles/gaga_output_bench.json
+
 Prints one JSON line; --out also writes it to a file.  Needs the GPU: without one it fails.
 """
 import argparse
@@ -80,6 +88,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--precision", choices=("f32", "bf16x3", "bf16", "all"), default="f32")
+    ap.add_argument("--output", choices=("float", "all"), default="float")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
 
@@ -161,6 +170,78 @@ def main():
                 f.write(line + "\n")
         return
     head.set_precision(args.precision)
+    if args.output == "all":
+        import time
+        from artalk_amd.frames import frame_bytes, pack_frames
+
+        def host_hand_over():      # the reference's hand-over (inference.py:83-86), the conversion on one host thread
+            x = lib_call().cpu().numpy()
+            return np.ascontiguousarray((x * 255.0).astype(np.uint8).transpose(0, 2, 3, 1))
+
+        variants = {"float": lib_call, "float+host": host_hand_over}
+        for f in ("rgb24", "yuv420p"):
+            variants[f] = lambda f=f: head.render_clip(codes, flame, randomize_noise=False, out=f)
+            variants[f + "+host"] = lambda f=f: head.render_clip(codes, flame, randomize_noise=False, out=f, host=True)
+
+        def wall(fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            return 1e3 * (time.perf_counter() - t0), out
+
+        head.reset_motion_state()
+        ref = lib_call()
+        same = {}
+        for name, fn in variants.items():      # every variant shows the same frames (the EMA restarts before each)
+            head.reset_motion_state()
+            out = fn()
+            if name == "float":
+                same[name] = bool(torch.equal(out, ref))
+            elif name == "float+host":      # the reference's cast wraps where ours clamps: the frames are in [0, 1], so none does
+                same[name] = bool(np.array_equal(out, pack_frames(ref, "rgb24").cpu().numpy()))
+            else:
+                same[name] = bool(torch.equal(out.cpu(), pack_frames(ref, name.split("+")[0]).cpu()))
+            for _ in range(args.warmup):
+                wall(fn)
+        ms, stage = {n: [] for n in variants}, {n: [] for n in variants}
+        st = (C.c_double * len(STAGES))()
+        for _ in range(args.rounds):
+            for name, fn in variants.items():
+                L.artalk_gaga_set_timing(head._h, 0)
+                ms[name].append(wall(fn)[0])
+                L.artalk_gaga_set_timing(head._h, 1)
+                fn()
+                L.artalk_gaga_get_timing(head._h, st, len(STAGES))
+                stage[name].append(list(st))
+        L.artalk_gaga_set_timing(head._h, 0)
+        base = statistics.median(ms["float"])
+        per_frame = {name: 12 * S * S if name.startswith("float") else frame_bytes(name.split("+")[0], S, S) for name in variants}
+
+        def entry(name):
+            stages = {n: statistics.median(s[i] for s in stage[name]) / T for i, n in enumerate(STAGES)}
+            return {"ms_per_frame": {"median": statistics.median(ms[name]) / T, "min": min(ms[name]) / T, "max": max(ms[name]) / T},
+                    "frames_per_s": 1e3 * T / statistics.median(ms[name]), "relative_to_float": statistics.median(ms[name]) / base,
+                    "bytes_per_frame_out": per_frame[name],
+                    "stage_ms_per_frame": stages, "finish_or_pack_share": stages["finish"] / sum(stages.values()),
+                    "equals_the_float_frames_packed": same[name]}
+
+        res = {
+            "workload": f"GAGAvatar.render_clip by output, upsampler precision {args.precision}, S = {S}, V = {V}, N = {N}, T = {T} frames per call "
+                        f"in slabs of {slab}, synthetic FLAME asset, avatar and upsampler weights, stored noise, {mark.shape[1]} x "
+                        f"{mark.shape[2]} watermark, 68 forehead vertices; wall clock between device synchronisations (the host variants "
+                        f"include host work), {args.warmup} warm-up calls per variant, {args.rounds} rounds in one process, each round running "
+                        f"every variant in turn: a plain call and a stage-timed call.  float+host: .cpu(), then (x * 255).astype(uint8) and "
+                        f"the transpose in numpy; +host of the 8-bit variants: pinned host tensor filled slab by slab on a copy stream",
+            "variants": {name: entry(name) for name in variants},
+        }
+        line = json.dumps(res)
+        print(line)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        return
     upper = {"state": None}
 
     def chain():

@@ -102,6 +102,22 @@ static void walk_event() {
     CHECK(g.get() == nullptr);
 }
 
+static void walk_stream() {
+    Stream s;
+    CHECK(s.get() == nullptr);
+    const bool ok = s.create();
+    CHECK(ok == (s.get() != nullptr));
+    if (ok) ++g_taken;
+    else CHECK(hipGetLastError() == g_quiet);
+    hipStream_t h = s.get();
+    CHECK(s.create() == ok && s.get() == h);             // a second create keeps the stream
+    Stream t(std::move(s));
+    CHECK(s.get() == nullptr && t.get() == h);
+    Stream u;
+    u = std::move(t);
+    CHECK(t.get() == nullptr && u.get() == h);
+}
+
 static void walk_timer() {
     double ms[3] = {0, 0, 0};
     {
@@ -140,6 +156,7 @@ int main() {
     walk_block<PinnedBuf<float>>();
     walk_devbuf();
     walk_event();
+    walk_stream();
     walk_timer();
     std::printf("device_mem_check: %d checks held (%s)\n", g_checks, g_taken ? "with a device" : "no device: failure paths");
     return 0;
