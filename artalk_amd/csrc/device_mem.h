@@ -1,4 +1,4 @@
-// Owners of what the host side takes from the HIP runtime: device blocks, pinned host blocks, events, streams, the events of a stage timer.
+// Owners of what the host side takes from the HIP runtime: device blocks, pinned host blocks, events, streams, the events of a stage or call timer.
 // Host code only.  Every type is move-only, takes nothing in its constructor and gives back what it holds in its destructor, so an
 // object made of them is destroyed by `delete` and an early return leaks nothing.  A call that fails leaves its object empty
 // (capacity 0), clears the runtime's last error - the caller reports the failure once, and it does not come back from a later
@@ -121,6 +121,68 @@ private:
     bool on_ = false;
     std::vector<Event> ev_;      // ev_[k] closes an interval of stage stage_[k]
     std::vector<int> stage_;
+};
+
+// Time of one call on its stream, and of the launches inside it that ask for a start / stop pair of events (launch_conv takes one).
+// The pairs come from a pool kept from call to call.  total_ms() and pair_ms() are those of the last call that end() saw through with
+// the timer enabled.  Disabled, no method makes a HIP call.
+class CallTimer {
+public:
+    // records the call's start; false: the call's own two events cannot be made (nothing is timed then)
+    bool begin(hipStream_t s, bool enabled) {
+        s_ = s; on_ = enabled; used_ = 0;
+        if (!on_) return true;
+        if (!t0_.create() || !t1_.create()) { on_ = false; return false; }
+        (void)hipEventRecord(t0_.get(), s_);
+        return true;
+    }
+    // the next pair of the pool, which grows by two events when it has none left; null pointers when disabled or when an event
+    // cannot be made.  true: a pair was handed out
+    bool pair(hipEvent_t* e0, hipEvent_t* e1) {
+        *e0 = *e1 = nullptr;
+        if (!on_) return false;
+        if (used_ + 2 > pool_.size()) {
+            Event a0, a1;
+            if (a0.create() && a1.create()) { pool_.push_back(std::move(a0)); pool_.push_back(std::move(a1)); }
+        }
+        if (used_ + 2 > pool_.size()) return false;
+        *e0 = pool_[used_].get(); *e1 = pool_[used_ + 1].get(); used_ += 2;
+        return true;
+    }
+    // records the call's end and waits for it; false: the device reported a failure.  A pair whose time cannot be read counts 0.
+    bool end() {
+        if (!on_) return true;
+        (void)hipEventRecord(t1_.get(), s_);
+        if (hipEventSynchronize(t1_.get()) != hipSuccess) { (void)hipGetLastError(); return false; }
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, t0_.get(), t1_.get()) != hipSuccess) (void)hipGetLastError();
+        total_ms_ = ms;
+        pair_ms_.assign(used_ / 2, 0.0);
+        for (size_t i = 0; i + 1 < used_; i += 2) {
+            float k = 0.f;
+            if (hipEventElapsedTime(&k, pool_[i].get(), pool_[i + 1].get()) == hipSuccess) pair_ms_[i / 2] = k; else (void)hipGetLastError();
+        }
+        return true;
+    }
+    double total_ms() const { return total_ms_; }
+    const std::vector<double>& pair_ms() const { return pair_ms_; }      // in the order the pairs were handed out
+    double pairs_ms() const { double t = 0; for (double v : pair_ms_) t += v; return t; }
+    bool empty() const { return pool_.empty() && !t0_.get() && !t1_.get(); }      // nothing was ever taken from the device
+
+private:
+    hipStream_t s_ = nullptr;
+    bool on_ = false;
+    Event t0_, t1_;
+    std::vector<Event> pool_;      // start / stop pairs, the first used_ of them handed out in this call
+    size_t used_ = 0;
+    double total_ms_ = 0;
+    std::vector<double> pair_ms_;
+};
+
+// Offsets of the blocks of a workspace, in floats, every block 16-byte aligned (vector loads)
+struct WsLayout {
+    int64_t off = 0;
+    int64_t take(int64_t n) { const int64_t at = off; off += (n + 3) & ~(int64_t)3; return at; }
 };
 
 // zero-filled device block whose pointer goes into `pool` (a null entry records a failure): the engine's weight and workspace pools

@@ -16,7 +16,6 @@
 
 #include <climits>
 #include <cmath>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -24,6 +23,7 @@
 #include "common.h"
 #include "device_mem.h"
 #include "styleunet_conv.h"
+#include "weight_store.h"
 
 namespace artalk {
 
@@ -261,7 +261,6 @@ using namespace artalk;
 
 namespace {
 
-struct DnSlot { std::vector<int64_t> shape; std::vector<float> host; bool set = false; bool optional = false; };
 struct DnLin { const float* w = nullptr; const float* b = nullptr; };
 struct DnBlock { const float *n1w, *n1b, *n2w, *n2b, *ls1, *ls2; DnLin qkv, proj, fc1, fc2; };
 struct DnConv { const float* w = nullptr; const float* b = nullptr; int cin = 0, cinp = 0, cout = 0, k = 1; };
@@ -274,9 +273,7 @@ enum { DN_ST_GEMM = 0, DN_ST_ATTN = 1, DN_ST_CONV = 2, DN_ST_REST = 3, DN_STAGES
 struct artalk_dino {
     int device = 0, D = 0, depth = 0, heads = 0, HD = 0, g = 0, od = 0;
     bool finalized = false, timing = false;
-    std::map<std::string, DnSlot> slots;
-    std::vector<std::string> order;
-    std::vector<DevBuf<float>> weights;
+    WeightStore store;
     DevBuf<float> ws, stage;
     int64_t ws_floats = 0;
     const float *cls = nullptr, *pos = nullptr, *normw = nullptr, *normb = nullptr;
@@ -286,7 +283,8 @@ struct artalk_dino {
     DnConv rn[4], outc;
     DnFuse fuse[4];
     StageTimer timer;
-    double stage_ms[DN_STAGES] = {0, 0, 0, 0}, total_ms = 0;
+    CallTimer call;      // total_ms only: the stages are the StageTimer's
+    double stage_ms[DN_STAGES] = {0, 0, 0, 0};
     std::string err;
 };
 
@@ -296,11 +294,7 @@ namespace {
 
 int dn_fail(artalk_dino* d, int rc, const std::string& msg) { d->err = msg; return rc; }
 
-void dn_slot(artalk_dino* d, const std::string& name, std::vector<int64_t> shape, bool optional = false) {
-    DnSlot& s = d->slots[name];
-    s.shape = std::move(shape); s.optional = optional;
-    d->order.push_back(name);
-}
+void dn_slot(artalk_dino* d, const std::string& name, std::vector<int64_t> shape, bool optional = false) { d->store.declare(name, std::move(shape), optional); }
 void dn_wb(artalk_dino* d, const std::string& name, std::vector<int64_t> wshape, bool bias = true) {
     const int64_t cout = wshape[0];
     dn_slot(d, name + ".weight", std::move(wshape));
@@ -344,10 +338,8 @@ void dn_manifest(artalk_dino* d) {
 inline int dn_h3(int g) { return (g - 1) / 2 + 1; }
 
 // The workspace, in floats, every block 16-byte aligned.
-struct DnWs {
-    int64_t off = 0;
+struct DnWs : WsLayout {
     int64_t img, col, patch, X, Y, qkv, O, hid, tap[4], proj, gemm, part, feat, imgr, cat, rn[4], A, B, C, out;
-    int64_t take(int64_t n) { const int64_t at = off; off += (n + 3) & ~(int64_t)3; return at; }
     explicit DnWs(const artalk_dino* d) {
         const int64_t g = d->g, G = g * g, T = G + 1, D = d->D, S = DN_PATCH * g, P = 8 * g, h3 = dn_h3(d->g);
         const int64_t hw[4] = {16 * G, 4 * G, G, h3 * h3};
@@ -513,7 +505,7 @@ const char* artalk_dino_last_error(const artalk_dino* d) { return d ? d->err.c_s
 
 void artalk_dino_destroy(artalk_dino* d) {
     if (!d) return;
-    if (!d->weights.empty() || d->stage.capacity()) {      // (else nothing was ever taken from the device)
+    if (d->store.on_device() || d->stage.capacity()) {      // (else nothing was ever taken from the device)
         (void)hipSetDevice(d->device);
         (void)hipDeviceSynchronize();
     }
@@ -544,100 +536,68 @@ int artalk_dino_set_tensor(artalk_dino* d, const char* key, const void* host_ptr
     if (!d) { g_dn_error = "handle is NULL"; return ARTALK_EINVAL; }
     if (!key || !host_ptr || !shape) return dn_fail(d, ARTALK_EINVAL, "key, host_ptr and shape must not be NULL");
     if (d->finalized) return dn_fail(d, ARTALK_ESTATE, "weights are final after artalk_dino_finalize; create a new handle");
-    auto it = d->slots.find(key);
-    if (it == d->slots.end()) return dn_fail(d, ARTALK_EKEY, std::string("Unexpected key in state_dict: ") + key);
-    DnSlot& sl = it->second;
-    bool same = (int)sl.shape.size() == ndim;
-    for (int i = 0; same && i < ndim; ++i) same = sl.shape[i] == shape[i];
-    if (!same) {
-        if (std::string(key) == "dino_model.pos_embed" && ndim == 3)
-            return dn_fail(d, ARTALK_EINVAL, "size mismatch for dino_model.pos_embed: it holds " + std::to_string(shape[1]) + " positions, a grid of " +
-                                                 std::to_string(d->g) + " x " + std::to_string(d->g) + " takes " + std::to_string(d->g * d->g + 1) +
-                                                 " (position embeddings are not interpolated)");
-        return dn_fail(d, ARTALK_EINVAL, std::string("size mismatch for ") + key);
-    }
-    int64_t n = 1;
-    for (int64_t v : sl.shape) n *= v;
-    sl.host.assign((const float*)host_ptr, (const float*)host_ptr + n);
-    sl.set = true;
-    return ARTALK_OK;
+    const int rc = d->store.set(key, host_ptr, ndim, shape, &d->err);
+    if (rc == ARTALK_EINVAL && std::string(key) == "dino_model.pos_embed" && ndim == 3)      // a wrong shape: say which grid it is for
+        d->err = "size mismatch for dino_model.pos_embed: it holds " + std::to_string(shape[1]) + " positions, a grid of " + std::to_string(d->g) + " x " +
+                 std::to_string(d->g) + " takes " + std::to_string(d->g * d->g + 1) + " (position embeddings are not interpolated)";
+    return rc;
 }
 
 int artalk_dino_finalize(artalk_dino* d) {
     if (!d) { g_dn_error = "handle is NULL"; return ARTALK_EINVAL; }
     if (d->finalized) return dn_fail(d, ARTALK_ESTATE, "artalk_dino_finalize was already called");
-    std::string missing;
-    int nmiss = 0;
-    for (const std::string& k : d->order) {
-        const DnSlot& sl = d->slots[k];
-        if (!sl.set && !sl.optional) { if (nmiss++ < 8) missing += (missing.empty() ? "" : ", ") + k; }
-    }
-    if (nmiss) return dn_fail(d, ARTALK_EMISSING, "Missing key(s) in state_dict: " + missing + (nmiss > 8 ? ", ..." : ""));
+    if (d->store.missing(&d->err)) return ARTALK_EMISSING;
     if (hipSetDevice(d->device) != hipSuccess) return dn_fail(d, ARTALK_EHIP, "hipSetDevice failed");
-    bool ok = true;
-    auto upload = [&](const std::vector<float>& v) -> const float* {
-        d->weights.emplace_back();
-        if (!d->weights.back().upload(v.data(), v.size())) ok = false;
-        return d->weights.back().get();
-    };
-    auto host = [&](const std::string& k) -> const std::vector<float>& { return d->slots[k].host; };
-    auto raw = [&](const std::string& k) { return upload(host(k)); };
-    auto lin = [&](const std::string& n) { DnLin l; l.w = raw(n + ".weight"); l.b = raw(n + ".bias"); return l; };
-    // torch's [Cout][Cin][k][k] -> [k k][cinp][Cout]; the input channels start at row `shift` (the concat's image channels come first
-    // in both, so shift is 0), zero rows for the padding
+    WeightStore& st = d->store;
+    auto lin = [&](const std::string& n) { DnLin l; l.w = st.upload(n + ".weight"); l.b = st.upload(n + ".bias"); return l; };
+    // the concat's image channels come first in the reference too: its input channels keep their rows
     auto conv = [&](const std::string& n, int cin, int cout, int k, bool bias) {
         DnConv l; l.cin = cin; l.cinp = dn_pad8(cin); l.cout = cout; l.k = k;
-        const std::vector<float>& w = host(n + ".weight");
-        const int kk = k * k;
-        std::vector<float> t((size_t)kk * l.cinp * cout, 0.f);
-        for (int o = 0; o < cout; ++o)
-            for (int i = 0; i < cin; ++i)
-                for (int q = 0; q < kk; ++q) t[((size_t)q * l.cinp + i) * cout + o] = w[((size_t)o * cin + i) * kk + q];
-        l.w = upload(t);
-        l.b = bias ? raw(n + ".bias") : nullptr;
+        l.w = st.upload(pack_conv_weight(st.host(n + ".weight"), cout, cin, l.cinp, k));
+        l.b = bias ? st.upload(n + ".bias") : nullptr;
         return l;
     };
     const int D = d->D;
     const std::string m = "dino_model.";
-    d->cls = raw(m + "cls_token");
-    d->pos = raw(m + "pos_embed");
+    d->cls = st.upload(m + "cls_token");
+    d->pos = st.upload(m + "pos_embed");
     {      // [D][588] -> [D][608]
-        const std::vector<float>& w = host(m + "patch_embed.proj.weight");
+        const std::vector<float>& w = st.host(m + "patch_embed.proj.weight");
         std::vector<float> t((size_t)D * DN_PKP, 0.f);
         for (int o = 0; o < D; ++o)
             for (int k = 0; k < DN_PK; ++k) t[(size_t)o * DN_PKP + k] = w[(size_t)o * DN_PK + k];
-        d->patch.w = upload(t);
-        d->patch.b = raw(m + "patch_embed.proj.bias");
+        d->patch.w = st.upload(t);
+        d->patch.b = st.upload(m + "patch_embed.proj.bias");
     }
     d->blocks.resize(d->depth);
     for (int i = 0; i < d->depth; ++i) {
         const std::string b = m + "blocks." + std::to_string(i) + ".";
         DnBlock& k = d->blocks[i];
-        k.n1w = raw(b + "norm1.weight"); k.n1b = raw(b + "norm1.bias"); k.n2w = raw(b + "norm2.weight"); k.n2b = raw(b + "norm2.bias");
-        k.ls1 = raw(b + "ls1.gamma"); k.ls2 = raw(b + "ls2.gamma");
+        k.n1w = st.upload(b + "norm1.weight"); k.n1b = st.upload(b + "norm1.bias"); k.n2w = st.upload(b + "norm2.weight"); k.n2b = st.upload(b + "norm2.bias");
+        k.ls1 = st.upload(b + "ls1.gamma"); k.ls2 = st.upload(b + "ls2.gamma");
         k.qkv = lin(b + "attn.qkv"); k.proj = lin(b + "attn.proj"); k.fc1 = lin(b + "mlp.fc1"); k.fc2 = lin(b + "mlp.fc2");
     }
-    d->normw = raw(m + "norm.weight"); d->normb = raw(m + "norm.bias");
+    d->normw = st.upload(m + "norm.weight"); d->normb = st.upload(m + "norm.bias");
     for (int i = 0; i < 4; ++i) d->projects[i] = lin("projects." + std::to_string(i));      // [Ci][D][1][1] is [Ci][D]
     for (int i = 0; i < 2; ++i) {      // ConvTranspose2d weight [Ci][Co][s][s] -> [(dy s + dx) Co + co][ci]
         const int C = DN_PROJ[i], sc = i == 0 ? 4 : 2, ss = sc * sc;
-        const std::vector<float>& w = host("resize_layers." + std::to_string(i) + ".weight");
+        const std::vector<float>& w = st.host("resize_layers." + std::to_string(i) + ".weight");
         std::vector<float> t((size_t)ss * C * C);
         for (int ci = 0; ci < C; ++ci)
             for (int co = 0; co < C; ++co)
                 for (int q = 0; q < ss; ++q) t[((size_t)q * C + co) * C + ci] = w[((size_t)ci * C + co) * ss + q];
-        d->up[i].w = upload(t);
-        d->up[i].b = raw("resize_layers." + std::to_string(i) + ".bias");
+        d->up[i].w = st.upload(t);
+        d->up[i].b = st.upload("resize_layers." + std::to_string(i) + ".bias");
     }
     {      // Conv2d weight [Co][Ci][3][3] -> [co][(ky 3 + kx) Ci + ci]
         const int C = DN_PROJ[3];
-        const std::vector<float>& w = host("resize_layers.3.weight");
+        const std::vector<float>& w = st.host("resize_layers.3.weight");
         std::vector<float> t((size_t)C * 9 * C);
         for (int co = 0; co < C; ++co)
             for (int ci = 0; ci < C; ++ci)
                 for (int q = 0; q < 9; ++q) t[((size_t)co * 9 + q) * C + ci] = w[((size_t)co * C + ci) * 9 + q];
-        d->down.w = upload(t);
-        d->down.b = raw("resize_layers.3.bias");
+        d->down.w = st.upload(t);
+        d->down.b = st.upload("resize_layers.3.bias");
     }
     for (int i = 0; i < 4; ++i) d->rn[i] = conv("layer_rn." + std::to_string(i), DN_PROJ[i] + 3, DN_HID, 3, false);
     for (int i = 0; i < 4; ++i) {
@@ -652,10 +612,10 @@ int artalk_dino_finalize(artalk_dino* d) {
         f.u2c2 = conv(r + "resConfUnit2.conv2", DN_HID, DN_HID, 3, true);
     }
     d->outc = conv("output_conv", DN_HID, d->od, 3, true);
-    if (ok && !d->ws.alloc((size_t)d->ws_floats))
+    if (st.ok() && !d->ws.alloc((size_t)d->ws_floats))
         return dn_fail(d, ARTALK_EHIP, "hipMalloc of the workspace failed (" + std::to_string(d->ws_floats * 4) + " bytes)");
-    if (!ok || hipDeviceSynchronize() != hipSuccess) return dn_fail(d, ARTALK_EHIP, "uploading the weights failed");
-    for (auto& kv : d->slots) { std::vector<float>().swap(kv.second.host); }
+    if (!st.ok() || hipDeviceSynchronize() != hipSuccess) return dn_fail(d, ARTALK_EHIP, "uploading the weights failed");
+    st.release_host();
     d->finalized = true;
     return ARTALK_OK;
 }
@@ -680,7 +640,7 @@ int artalk_dino_set_timing(artalk_dino* d, int enable) {
 int artalk_dino_get_timing(const artalk_dino* d, double* stage_ms, double* total_ms) {
     if (!d) { g_dn_error = "handle is NULL"; return ARTALK_EINVAL; }
     if (stage_ms) for (int i = 0; i < DN_STAGES; ++i) stage_ms[i] = d->stage_ms[i];
-    if (total_ms) *total_ms = d->total_ms;
+    if (total_ms) *total_ms = d->call.total_ms();
     return ARTALK_OK;
 }
 
@@ -716,21 +676,13 @@ int artalk_dino_forward(artalk_dino* d, const float* image_dev, int height, int 
     if (!d->finalized) return dn_fail(d, ARTALK_ESTATE, "artalk_dino_forward before artalk_dino_finalize");
     (void)hipSetDevice(d->device);
     hipStream_t s = (hipStream_t)stream;
-    Event t0, t1;
-    if (d->timing) {
-        if (!t0.create() || !t1.create()) return dn_fail(d, ARTALK_EHIP, "hipEventCreate failed");
-        (void)hipEventRecord(t0.get(), s);
-    }
+    if (!d->call.begin(s, d->timing)) return dn_fail(d, ARTALK_EHIP, "hipEventCreate failed");
     d->timer.start(s, d->timing);
     DnRun run{d, s};
     run.run(image_dev, feature0_dev, feature1_dev);
     if (hipGetLastError() != hipSuccess) return dn_fail(d, ARTALK_EHIP, "kernel launch failed");
+    if (!d->call.end()) return dn_fail(d, ARTALK_EHIP, "the call failed on the device");
     if (d->timing) {
-        (void)hipEventRecord(t1.get(), s);
-        if (hipEventSynchronize(t1.get()) != hipSuccess) return dn_fail(d, ARTALK_EHIP, "the call failed on the device");
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, t0.get(), t1.get());
-        d->total_ms = ms;
         for (double& v : d->stage_ms) v = 0;
         d->timer.finish(d->stage_ms, DN_STAGES);
     }

@@ -20,7 +20,6 @@
 
 #include <climits>
 #include <cmath>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -28,6 +27,7 @@
 #include "common.h"
 #include "device_mem.h"
 #include "styleunet_conv.h"
+#include "weight_store.h"
 
 namespace artalk {
 
@@ -183,7 +183,6 @@ using namespace artalk;
 
 namespace {
 
-struct GsSlot { std::vector<int64_t> shape; std::vector<float> host; bool set = false; };
 struct GsLayer { std::string name; const float* w = nullptr; const float* b = nullptr; int cin = 0, cinp = 0, cout = 0, k = 1; };      // cinp: cin as stored
 
 }  // namespace
@@ -191,14 +190,12 @@ struct GsLayer { std::string name; const float* w = nullptr; const float* b = nu
 struct artalk_gsgen {
     int device = 0, V = 0, Dh = 0, Dg = 0, C = 0, P = 0, Hl = 0, Hc = 0;
     bool finalized = false, timing = false;
-    std::map<std::string, GsSlot> slots;
-    std::vector<std::string> order;
-    std::vector<DevBuf<float>> weights;
+    WeightStore store;
     DevBuf<float> ws;
     int64_t ws_floats = 0;
     const float* head_base = nullptr;
     GsLayer feat[4], head[4][2], local[2][4];
-    std::vector<Event> ev; size_t ev_used = 0; double conv_ms = 0, total_ms = 0;      // ev: start / stop pairs, kept from call to call
+    CallTimer timer;      // the call, and a pair of events per conv launch
     std::string err;
 };
 
@@ -214,17 +211,14 @@ int gs_fail(artalk_gsgen* g, int rc, const std::string& msg) { g->err = msg; ret
 // k = 0: a Linear, whose weight is [cout][cin] in the state dict and runs as a 1 x 1 conv
 void gs_add(artalk_gsgen* g, GsLayer& l, const std::string& name, int cin, int cout, int k) {
     l.name = name; l.cin = cin; l.cinp = cin; l.cout = cout; l.k = k ? k : 1;
-    if (k == 0) g->slots[name + ".weight"].shape = {cout, cin};
-    else g->slots[name + ".weight"].shape = {cout, cin, k, k};
-    g->slots[name + ".bias"].shape = {cout};
-    g->order.push_back(name + ".weight");
-    g->order.push_back(name + ".bias");
+    if (k == 0) g->store.declare(name + ".weight", {cout, cin});
+    else g->store.declare(name + ".weight", {cout, cin, k, k});
+    g->store.declare(name + ".bias", {cout});
 }
 
 // keys in the order of the reference module's state_dict()
 void gs_manifest(artalk_gsgen* g) {
-    g->slots["head_base"].shape = {g->V, g->Dh};
-    g->order.push_back("head_base");
+    g->store.declare("head_base", {g->V, g->Dh});
     const std::string gg = "gs_generator_g.";
     for (int i = 0; i < 4; ++i) gs_add(g, g->feat[i], gg + "feature_layers." + std::to_string(2 * i), i ? g->Hl : g->Dh + g->Dg, g->Hl, 0);
     for (int h = 0; h < 4; ++h) {
@@ -243,10 +237,8 @@ void gs_manifest(artalk_gsgen* g) {
 }
 
 // The workspace, in floats, every block 16-byte aligned (the conv's vector loads).
-struct GsWs {
-    int64_t off = 0;
+struct GsWs : WsLayout {
     int64_t xin, a, b, o, gin, ga, gb, gcat, gh, hout[4];
-    int64_t take(int64_t n) { const int64_t at = off; off += (n + 3) & ~(int64_t)3; return at; }
     explicit GsWs(const artalk_gsgen* g) {
         const int64_t PP = (int64_t)g->P * g->P, V = g->V;
         xin = take(PP * gs_pad8(g->C + GS_DIR)); a = take(PP * g->Hc); b = take(PP * g->Hc); o = take(PP * GS_OUT);
@@ -262,13 +254,7 @@ struct GsRun {
         a.x = x; a.x_bstride = (long)H * W * l.cinp; a.w = l.w; a.out = out; a.B = 1; a.H = H; a.W = W; a.Cin = l.cinp; a.Cout = l.cout; a.k = l.k;
         a.gain = 1.f; a.bias = l.b; a.relu = relu;
         hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (g->timing) {
-            if (g->ev_used + 2 > g->ev.size()) {
-                Event a0, a1;
-                if (a0.create() && a1.create()) { g->ev.push_back(std::move(a0)); g->ev.push_back(std::move(a1)); }
-            }
-            if (g->ev_used + 2 <= g->ev.size()) { e0 = g->ev[g->ev_used].get(); e1 = g->ev[g->ev_used + 1].get(); g->ev_used += 2; }
-        }
+        g->timer.pair(&e0, &e1);
         launch_conv(a, s, e0, e1);
     }
     void run(const float* f0, const float* f1, const GsPlane& pl, const GsDir& d, float* xyz, float* colors, float* opacities, float* scales,
@@ -314,7 +300,7 @@ const char* artalk_gsgen_last_error(const artalk_gsgen* g) { return g ? g->err.c
 
 void artalk_gsgen_destroy(artalk_gsgen* g) {
     if (!g) return;
-    if (!g->weights.empty() || !g->ev.empty()) {      // (else nothing was ever taken from the device)
+    if (g->store.on_device() || !g->timer.empty()) {      // (else nothing was ever taken from the device)
         (void)hipSetDevice(g->device);
         (void)hipDeviceSynchronize();
     }
@@ -341,53 +327,27 @@ int artalk_gsgen_set_tensor(artalk_gsgen* g, const char* key, const void* host_p
     if (!g) { g_gs_error = "handle is NULL"; return ARTALK_EINVAL; }
     if (!key || !host_ptr || !shape) return gs_fail(g, ARTALK_EINVAL, "key, host_ptr and shape must not be NULL");
     if (g->finalized) return gs_fail(g, ARTALK_ESTATE, "weights are final after artalk_gsgen_finalize; create a new handle");
-    auto it = g->slots.find(key);
-    if (it == g->slots.end()) return gs_fail(g, ARTALK_EKEY, std::string("Unexpected key in state_dict: ") + key);
-    GsSlot& sl = it->second;
-    bool same = (int)sl.shape.size() == ndim;
-    for (int i = 0; same && i < ndim; ++i) same = sl.shape[i] == shape[i];
-    if (!same) return gs_fail(g, ARTALK_EINVAL, std::string("size mismatch for ") + key);
-    int64_t n = 1;
-    for (int64_t v : sl.shape) n *= v;
-    sl.host.assign((const float*)host_ptr, (const float*)host_ptr + n);
-    sl.set = true;
-    return ARTALK_OK;
+    return g->store.set(key, host_ptr, ndim, shape, &g->err);
 }
 
 int artalk_gsgen_finalize(artalk_gsgen* g) {
     if (!g) { g_gs_error = "handle is NULL"; return ARTALK_EINVAL; }
     if (g->finalized) return gs_fail(g, ARTALK_ESTATE, "artalk_gsgen_finalize was already called");
-    std::string missing;
-    int nmiss = 0;
-    for (const std::string& k : g->order)
-        if (!g->slots[k].set) { if (nmiss++ < 8) missing += (missing.empty() ? "" : ", ") + k; }
-    if (nmiss) return gs_fail(g, ARTALK_EMISSING, "Missing key(s) in state_dict: " + missing + (nmiss > 8 ? ", ..." : ""));
+    if (g->store.missing(&g->err)) return ARTALK_EMISSING;
     if (hipSetDevice(g->device) != hipSuccess) return gs_fail(g, ARTALK_EHIP, "hipSetDevice failed");
-    bool ok = true;
-    auto upload = [&](const std::vector<float>& v) -> const float* {
-        g->weights.emplace_back();
-        if (!g->weights.back().upload(v.data(), v.size())) ok = false;
-        return g->weights.back().get();
-    };
-    // torch's [Cout][Cin][k][k] (a Linear: k = 1) -> [k k][cinp][Cout], zero rows for the padded input channels
+    WeightStore& st = g->store;
     auto pack = [&](GsLayer& l) {
-        const std::vector<float>& w = g->slots[l.name + ".weight"].host;
-        const int kk = l.k * l.k;
-        std::vector<float> t((size_t)kk * l.cinp * l.cout, 0.f);
-        for (int o = 0; o < l.cout; ++o)
-            for (int i = 0; i < l.cin; ++i)
-                for (int q = 0; q < kk; ++q) t[((size_t)q * l.cinp + i) * l.cout + o] = w[((size_t)o * l.cin + i) * kk + q];
-        l.w = upload(t);
-        l.b = upload(g->slots[l.name + ".bias"].host);
+        l.w = st.upload(pack_conv_weight(st.host(l.name + ".weight"), l.cout, l.cin, l.cinp, l.k));
+        l.b = st.upload(l.name + ".bias");
     };
-    g->head_base = upload(g->slots["head_base"].host);
+    g->head_base = st.upload("head_base");
     for (GsLayer& l : g->feat) pack(l);
     for (auto& h : g->head) for (GsLayer& l : h) pack(l);
     for (auto& lg : g->local) for (GsLayer& l : lg) pack(l);
-    if (ok && !g->ws.alloc((size_t)g->ws_floats))
+    if (st.ok() && !g->ws.alloc((size_t)g->ws_floats))
         return gs_fail(g, ARTALK_EHIP, "hipMalloc of the workspace failed (" + std::to_string(g->ws_floats * 4) + " bytes)");
-    if (!ok || hipDeviceSynchronize() != hipSuccess) return gs_fail(g, ARTALK_EHIP, "uploading the weights failed");
-    for (auto& kv : g->slots) { std::vector<float>().swap(kv.second.host); }
+    if (!st.ok() || hipDeviceSynchronize() != hipSuccess) return gs_fail(g, ARTALK_EHIP, "uploading the weights failed");
+    st.release_host();
     g->finalized = true;
     return ARTALK_OK;
 }
@@ -411,8 +371,8 @@ int artalk_gsgen_set_timing(artalk_gsgen* g, int enable) {
 
 int artalk_gsgen_get_timing(const artalk_gsgen* g, double* conv_ms, double* total_ms) {
     if (!g) { g_gs_error = "handle is NULL"; return ARTALK_EINVAL; }
-    if (conv_ms) *conv_ms = g->conv_ms;
-    if (total_ms) *total_ms = g->total_ms;
+    if (conv_ms) *conv_ms = g->timer.pairs_ms();
+    if (total_ms) *total_ms = g->timer.total_ms();
     return ARTALK_OK;
 }
 
@@ -442,27 +402,11 @@ int artalk_gsgen_generate(artalk_gsgen* g, const float* feature0_dev, const floa
     if (!gs_planes_setup(transform_3x4_host, g->P, &pl, &d)) return gs_fail(g, ARTALK_EINVAL, "transform holds a value that is not finite");
     (void)hipSetDevice(g->device);
     hipStream_t s = (hipStream_t)stream;
-    Event t0, t1;
-    if (g->timing) {
-        g->ev_used = 0;
-        if (!t0.create() || !t1.create()) return gs_fail(g, ARTALK_EHIP, "hipEventCreate failed");
-        (void)hipEventRecord(t0.get(), s);
-    }
+    if (!g->timer.begin(s, g->timing)) return gs_fail(g, ARTALK_EHIP, "hipEventCreate failed");
     GsRun run{g, s};
     run.run(feature0_dev, feature1_dev, pl, d, xyz_dev, colors_dev, opacities_dev, scales_dev, rotations_dev);
     if (hipGetLastError() != hipSuccess) return gs_fail(g, ARTALK_EHIP, "kernel launch failed");
-    if (g->timing) {
-        (void)hipEventRecord(t1.get(), s);
-        if (hipEventSynchronize(t1.get()) != hipSuccess) return gs_fail(g, ARTALK_EHIP, "the call failed on the device");
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, t0.get(), t1.get());
-        g->total_ms = ms;
-        g->conv_ms = 0;
-        for (size_t i = 0; i + 1 < g->ev_used; i += 2) {
-            float k = 0.f;
-            if (hipEventElapsedTime(&k, g->ev[i].get(), g->ev[i + 1].get()) == hipSuccess) g->conv_ms += k;
-        }
-    }
+    if (!g->timer.end()) return gs_fail(g, ARTALK_EHIP, "the call failed on the device");
     return ARTALK_OK;
 }
 

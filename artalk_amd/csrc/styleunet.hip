@@ -15,7 +15,6 @@
 
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -23,6 +22,7 @@
 #include "common.h"
 #include "device_mem.h"
 #include "styleunet_conv.h"
+#include "weight_store.h"
 
 namespace artalk {
 
@@ -306,8 +306,6 @@ using namespace artalk;
 // ------------------------------------------------------------------ the module -------------------------------------------------------
 namespace {
 
-struct SuSlot { std::vector<int64_t> shape; std::vector<float> host; bool set = false; };
-
 struct SuConv { const float* w = nullptr; const float* b = nullptr; int cin = 0, cout = 0, k = 0; const void* wp = nullptr; };      // wp: packed for the bf16 modes
 struct SuMod { SuConv c; const float* wsq = nullptr; const float* nw = nullptr; int mod_off = 0; };      // nw, wsq: style convs only
 
@@ -319,9 +317,7 @@ struct artalk_styleunet {
     int precision = CONV_PRECISION_F32;      // of the convolutions (artalk_styleunet_set_precision)
     int slab_max = 1, slab = 1;
     int64_t frame_floats = 0;
-    std::map<std::string, SuSlot> slots;
-    std::vector<std::string> order;
-    std::vector<DevBuf<float>> weights;      // every uploaded tensor
+    WeightStore store;                       // the manifest, and every uploaded tensor
     std::vector<DevBuf<uint16_t>> packed;    // bf16 hi / lo planes of every conv weight: empty until a bf16 mode is first selected
     DevBuf<float> ws;
     // device weights
@@ -333,8 +329,8 @@ struct artalk_styleunet {
     std::vector<SuMod> sconv, rgb;
     std::vector<const float*> noise_buf;
     // timing of the conv kernel (tools/styleunet_bench.py)
-    std::vector<Event> ev; size_t ev_used = 0; double conv_ms = 0, total_ms = 0;      // ev: start / stop pairs, kept from call to call
-    std::vector<int32_t> ev_geom;            // per timed launch: frames, H, Cin, Cout, k
+    CallTimer timer;                         // the call, and a pair of events per conv launch
+    std::vector<int32_t> ev_geom;           // per timed launch: frames, H, Cin, Cout, k
     std::vector<double> launch_ms;           // per timed launch of the last call
     std::string err;
 };
@@ -347,10 +343,7 @@ int su_fail(artalk_styleunet* u, int rc, const std::string& msg) { u->err = msg;
 
 int su_ch(int size) { return size <= 32 ? 256 : 8192 / size; }      // 64: 128, 128: 64, 256: 32, 512: 16, 1024: 8
 
-void su_add(artalk_styleunet* u, const std::string& name, std::vector<int64_t> shape) {
-    u->slots[name].shape = std::move(shape);
-    u->order.push_back(name);
-}
+void su_add(artalk_styleunet* u, const std::string& name, std::vector<int64_t> shape) { u->store.declare(name, std::move(shape)); }
 
 void su_manifest(artalk_styleunet* u) {
     const int L = u->L, S = u->S, F = 512;
@@ -430,16 +423,8 @@ struct SuRun {
         a.noise = noise; a.noise_bstride = noise_bstride; a.noise_w = m ? m->nw : nullptr;
         a.bias = c.b; a.lrelu = lrelu; a.sft_scale = sft_scale; a.sft_shift = sft_shift; a.res = res;
         hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (u->timing) {
-            if (u->ev_used + 2 > u->ev.size()) {
-                Event a0, a1;
-                if (a0.create() && a1.create()) { u->ev.push_back(std::move(a0)); u->ev.push_back(std::move(a1)); }
-            }
-            if (u->ev_used + 2 <= u->ev.size()) {
-                e0 = u->ev[u->ev_used].get(); e1 = u->ev[u->ev_used + 1].get(); u->ev_used += 2;
-                for (int v : {n, H, c.cin, c.cout, c.k}) u->ev_geom.push_back(v);
-            }
-        }
+        if (u->timer.pair(&e0, &e1))
+            for (int v : {n, H, c.cin, c.cout, c.k}) u->ev_geom.push_back(v);
         if (u->precision != CONV_PRECISION_F32) launch_conv_bf16(a, c.wp, u->precision, s, e0, e1);
         else launch_conv(a, s, e0, e1);
     }
@@ -599,7 +584,7 @@ const char* artalk_styleunet_last_error(const artalk_styleunet* u) { return u ? 
 
 void artalk_styleunet_destroy(artalk_styleunet* u) {
     if (!u) return;
-    if (!u->weights.empty() || !u->ev.empty()) {      // (else nothing was ever taken from the device)
+    if (u->store.on_device() || !u->timer.empty()) {     // (else nothing was ever taken from the device)
         (void)hipSetDevice(u->device);
         (void)hipDeviceSynchronize();
     }
@@ -622,7 +607,7 @@ int artalk_styleunet_create(int device_id, int in_dim, int out_dim, int out_size
     SuRun dry{u, 1, nullptr, true};
     // (the dry run reads channel counts only: fill them from the manifest)
     auto shape_conv = [&](const std::string& n, SuConv& c) {
-        const auto& sh = u->slots[n + ".weight"].shape;
+        const auto& sh = u->store.shape(n + ".weight");
         const size_t o = sh.size() == 5 ? 1 : 0;
         c.cout = (int)sh[o]; c.cin = (int)sh[o + 1]; c.k = (int)sh[o + 2];
     };
@@ -665,57 +650,30 @@ int artalk_styleunet_set_tensor(artalk_styleunet* u, const char* key, const void
     if (!u) { g_su_error = "handle is NULL"; return ARTALK_EINVAL; }
     if (!key || !host_ptr || !shape) return su_fail(u, ARTALK_EINVAL, "key, host_ptr and shape must not be NULL");
     if (u->finalized) return su_fail(u, ARTALK_ESTATE, "weights are final after artalk_styleunet_finalize (packed copies exist); create a new handle");
-    auto it = u->slots.find(key);
-    if (it == u->slots.end()) return su_fail(u, ARTALK_EKEY, std::string("Unexpected key in state_dict: ") + key);
-    SuSlot& sl = it->second;
-    bool same = (int)sl.shape.size() == ndim;
-    for (int i = 0; same && i < ndim; ++i) same = sl.shape[i] == shape[i];
-    if (!same) return su_fail(u, ARTALK_EINVAL, std::string("size mismatch for ") + key);
-    int64_t n = 1;
-    for (int64_t v : sl.shape) n *= v;
-    sl.host.assign((const float*)host_ptr, (const float*)host_ptr + n);
-    sl.set = true;
-    return ARTALK_OK;
+    return u->store.set(key, host_ptr, ndim, shape, &u->err);
 }
 
 int artalk_styleunet_finalize(artalk_styleunet* u) {
     if (!u) { g_su_error = "handle is NULL"; return ARTALK_EINVAL; }
     if (u->finalized) return su_fail(u, ARTALK_ESTATE, "artalk_styleunet_finalize was already called");
-    std::string missing;
-    int nmiss = 0;
-    for (const std::string& k : u->order)
-        if (!u->slots[k].set) { if (nmiss++ < 8) missing += (missing.empty() ? "" : ", ") + k; }
-    if (nmiss) return su_fail(u, ARTALK_EMISSING, "Missing key(s) in state_dict: " + missing + (nmiss > 8 ? ", ..." : ""));
+    if (u->store.missing(&u->err)) return ARTALK_EMISSING;
     if (hipSetDevice(u->device) != hipSuccess) return su_fail(u, ARTALK_EHIP, "hipSetDevice failed");
-    bool ok = true;
-    auto upload = [&](const std::vector<float>& v) -> const float* {
-        u->weights.emplace_back();
-        if (!u->weights.back().upload(v.data(), v.size())) ok = false;
-        return u->weights.back().get();
-    };
-    auto host = [&](const std::string& k) -> const std::vector<float>& { return u->slots[k].host; };
-    // [Cout][Cin][k][k] -> [k k][Cin][Cout]
+    WeightStore& st = u->store;
     auto pack = [&](const std::string& n, SuConv& c, bool bias) {
-        const std::vector<float>& w = host(n + ".weight");
-        const int kk = c.k * c.k;
-        std::vector<float> t(w.size());
-        for (int o = 0; o < c.cout; ++o)
-            for (int i = 0; i < c.cin; ++i)
-                for (int q = 0; q < kk; ++q) t[((size_t)q * c.cin + i) * c.cout + o] = w[((size_t)o * c.cin + i) * kk + q];
-        c.w = upload(t);
-        c.b = bias ? upload(host(n + ".bias")) : nullptr;
+        c.w = st.upload(pack_conv_weight(st.host(n + ".weight"), c.cout, c.cin, c.cin, c.k));
+        c.b = bias ? st.upload(n + ".bias") : nullptr;
     };
     std::vector<float> modw((size_t)u->mod_total * 512, 0.f), modb((size_t)u->mod_total, 0.f);
     auto pack_mod = [&](const std::string& n, SuMod& m, bool style) {
         pack(n + ".modulated_conv", m.c, false);
-        m.c.b = upload(host(n + ".bias"));
-        const std::vector<float>& mw = host(n + ".modulated_conv.modulation.weight");
-        const std::vector<float>& mb = host(n + ".modulated_conv.modulation.bias");
+        m.c.b = st.upload(n + ".bias");
+        const std::vector<float>& mw = st.host(n + ".modulated_conv.modulation.weight");
+        const std::vector<float>& mb = st.host(n + ".modulated_conv.modulation.bias");
         std::memcpy(&modw[(size_t)m.mod_off * 512], mw.data(), mw.size() * sizeof(float));
         std::memcpy(&modb[m.mod_off], mb.data(), mb.size() * sizeof(float));
         if (style) {
-            m.nw = upload(host(n + ".weight"));
-            const std::vector<float>& w = host(n + ".modulated_conv.weight");
+            m.nw = st.upload(n + ".weight");
+            const std::vector<float>& w = st.host(n + ".modulated_conv.weight");
             const int kk = m.c.k * m.c.k;
             std::vector<float> sq((size_t)m.c.cout * m.c.cin);
             for (size_t e = 0; e < sq.size(); ++e) {
@@ -723,7 +681,7 @@ int artalk_styleunet_finalize(artalk_styleunet* u) {
                 for (int q = 0; q < kk; ++q) acc += w[e * kk + q] * w[e * kk + q];
                 sq[e] = acc;
             }
-            m.wsq = upload(sq);
+            m.wsq = st.upload(sq);
         }
     };
     const int nb = u->L - 2;
@@ -744,35 +702,35 @@ int artalk_styleunet_finalize(artalk_styleunet* u) {
     }
     pack_mod(d + "style_conv1", u->sc1, true);
     pack_mod(d + "to_rgb1", u->rgb1, false);
-    u->mod_w = upload(modw);
-    u->mod_b = upload(modb);
+    u->mod_w = st.upload(modw);
+    u->mod_b = st.upload(modb);
     {   // final_linear reads the 4 x 4 x 256 feature channels-last: column c 16 + p of the reference becomes p 256 + c
-        const std::vector<float>& w = host("final_linear.weight");
+        const std::vector<float>& w = st.host("final_linear.weight");
         std::vector<float> t(w.size());
         for (int o = 0; o < 512; ++o)
             for (int c = 0; c < 256; ++c)
                 for (int p = 0; p < 16; ++p) t[(size_t)o * 4096 + p * 256 + c] = w[(size_t)o * 4096 + c * 16 + p];
-        u->lin_w = upload(t);
-        u->lin_b = upload(host("final_linear.bias"));
+        u->lin_w = st.upload(t);
+        u->lin_b = st.upload("final_linear.bias");
     }
     for (int j = 0; j < 8; ++j) {
-        u->mlp_w[j] = upload(host(d + "style_mlp." + std::to_string(2 * j + 1) + ".weight"));
-        u->mlp_b[j] = upload(host(d + "style_mlp." + std::to_string(2 * j + 1) + ".bias"));
+        u->mlp_w[j] = st.upload(d + "style_mlp." + std::to_string(2 * j + 1) + ".weight");
+        u->mlp_b[j] = st.upload(d + "style_mlp." + std::to_string(2 * j + 1) + ".bias");
     }
     {   // constant input [1][512][4][4] -> [4][4][512]
-        const std::vector<float>& w = host(d + "constant_input.weight");
+        const std::vector<float>& w = st.host(d + "constant_input.weight");
         std::vector<float> t(w.size());
         for (int c = 0; c < 512; ++c)
             for (int p = 0; p < 16; ++p) t[(size_t)p * 512 + c] = w[(size_t)c * 16 + p];
-        u->const_in = upload(t);
+        u->const_in = st.upload(t);
     }
     u->noise_buf.resize(u->num_layers);
-    for (int l = 0; l < u->num_layers; ++l) u->noise_buf[l] = upload(host(d + "noises.noise" + std::to_string(l)));
-    if (ok && !u->ws.alloc((size_t)u->frame_floats * u->slab_max)) {
+    for (int l = 0; l < u->num_layers; ++l) u->noise_buf[l] = st.upload(d + "noises.noise" + std::to_string(l));
+    if (st.ok() && !u->ws.alloc((size_t)u->frame_floats * u->slab_max)) {
         return su_fail(u, ARTALK_EHIP, "hipMalloc of the workspace failed (" + std::to_string(u->frame_floats * u->slab_max * 4) + " bytes)");
     }
-    if (!ok || hipDeviceSynchronize() != hipSuccess) return su_fail(u, ARTALK_EHIP, "uploading the weights failed");
-    for (auto& kv : u->slots) { std::vector<float>().swap(kv.second.host); }
+    if (!st.ok() || hipDeviceSynchronize() != hipSuccess) return su_fail(u, ARTALK_EHIP, "uploading the weights failed");
+    st.release_host();
     if (u->precision != CONV_PRECISION_F32 && !su_pack_bf16(u)) return su_fail(u, ARTALK_EHIP, "packing the conv weights for the bf16 modes failed");
     u->finalized = true;
     return ARTALK_OK;
@@ -821,8 +779,8 @@ int artalk_styleunet_set_timing(artalk_styleunet* u, int enable) {
 
 int artalk_styleunet_get_timing(const artalk_styleunet* u, double* conv_ms, double* total_ms) {
     if (!u) { g_su_error = "handle is NULL"; return ARTALK_EINVAL; }
-    if (conv_ms) *conv_ms = u->conv_ms;
-    if (total_ms) *total_ms = u->total_ms;
+    if (conv_ms) *conv_ms = u->timer.pairs_ms();
+    if (total_ms) *total_ms = u->timer.total_ms();
     return ARTALK_OK;
 }
 
@@ -850,13 +808,8 @@ int artalk_styleunet_forward(artalk_styleunet* u, const float* x_dev, int B, con
     const long SS = (long)u->S * u->S;
     std::vector<const float*> np(u->num_layers);
     std::vector<int64_t> ns(u->num_layers);
-    Event t0, t1;
-    if (u->timing) {
-        u->ev_used = 0;
-        u->ev_geom.clear();
-        if (!t0.create() || !t1.create()) return su_fail(u, ARTALK_EHIP, "hipEventCreate failed");
-        (void)hipEventRecord(t0.get(), s);
-    }
+    if (u->timing) u->ev_geom.clear();
+    if (!u->timer.begin(s, u->timing)) return su_fail(u, ARTALK_EHIP, "hipEventCreate failed");
     for (int b0 = 0; b0 < B; b0 += u->slab) {
         const int n = B - b0 < u->slab ? B - b0 : u->slab;
         for (int l = 0; l < u->num_layers; ++l) {
@@ -867,19 +820,8 @@ int artalk_styleunet_forward(artalk_styleunet* u, const float* x_dev, int B, con
         run.run(x_dev + (long)b0 * u->in_dim * SS, np.data(), ns.data(), activation, out_dev + (long)b0 * u->out_dim * SS);
     }
     if (hipGetLastError() != hipSuccess) return su_fail(u, ARTALK_EHIP, "kernel launch failed");
-    if (u->timing) {
-        (void)hipEventRecord(t1.get(), s);
-        if (hipEventSynchronize(t1.get()) != hipSuccess) return su_fail(u, ARTALK_EHIP, "the call failed on the device");
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, t0.get(), t1.get());
-        u->total_ms = ms;
-        u->conv_ms = 0;
-        u->launch_ms.assign(u->ev_used / 2, 0.0);
-        for (size_t i = 0; i + 1 < u->ev_used; i += 2) {
-            float k = 0.f;
-            if (hipEventElapsedTime(&k, u->ev[i].get(), u->ev[i + 1].get()) == hipSuccess) { u->conv_ms += k; u->launch_ms[i / 2] = k; }
-        }
-    }
+    if (!u->timer.end()) return su_fail(u, ARTALK_EHIP, "the call failed on the device");
+    if (u->timing) u->launch_ms = u->timer.pair_ms();
     return ARTALK_OK;
 }
 

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import capi
+from ._intake import load_tensors
 from .weights import _rng
 
 PATCH, HIDDEN, PROJ = 14, 256, (256, 512, 1024, 1024)
@@ -156,22 +157,17 @@ class DINOBase:
         if L.artalk_dino_create(self.device.index or 0, self.vit_dim, self.depth, self.heads, self.grid, self.output_dim, C.byref(h)) != capi.OK:
             raise RuntimeError("artalk_dino_create failed: " + L.artalk_dino_last_error(None).decode())
         errors = []
-        try:
+
+        def own():      # of the whole checkpoint: the module's keys, their prefix stripped
             for key, val in state_dict.items():
-                if whole:
-                    if key.startswith(IGNORED_PREFIXES):
-                        continue
-                    if not key.startswith(PREFIX):
-                        errors.append("Unexpected key in state_dict: " + key)
-                        continue
-                    key = key[len(PREFIX):]
-                t = val.detach().cpu() if isinstance(val, torch.Tensor) else torch.from_numpy(np.asarray(val))
-                t = t.to(torch.float32).contiguous()
-                shape = (C.c_int64 * max(t.dim(), 1))(*t.shape)
-                if L.artalk_dino_set_tensor(h, key.encode(), C.c_void_p(t.data_ptr()), t.dim(), shape) != capi.OK:
-                    errors.append(L.artalk_dino_last_error(h).decode())
-            if not errors and L.artalk_dino_finalize(h) != capi.OK:
-                errors.append(L.artalk_dino_last_error(h).decode())
+                if not whole:
+                    yield key, val
+                elif key.startswith(PREFIX):
+                    yield key[len(PREFIX):], val
+                elif not key.startswith(IGNORED_PREFIXES):
+                    errors.append("Unexpected key in state_dict: " + key)
+        try:
+            load_tensors(L, "dino", h, own(), errors)
             if errors:
                 raise RuntimeError("Error(s) in loading state_dict for DINOBase:\n\t" + "\n\t".join(errors[:12]))
         except BaseException:

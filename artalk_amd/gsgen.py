@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import capi
+from ._intake import load_tensors
 from .gaga import AVATAR_FIELDS
 from .weights import _rng
 
@@ -141,18 +142,8 @@ class GSGenerators:
         h = C.c_void_p()
         if L.artalk_gsgen_create(self.device.index or 0, *self._dims(), C.byref(h)) != capi.OK:
             raise RuntimeError("artalk_gsgen_create failed: " + L.artalk_gsgen_last_error(None).decode())
-        errors = []
         try:
-            for key, val in state_dict.items():
-                if key.startswith(IGNORED_PREFIXES):
-                    continue
-                t = val.detach().cpu() if isinstance(val, torch.Tensor) else torch.from_numpy(np.asarray(val))
-                t = t.to(torch.float32).contiguous()
-                shape = (C.c_int64 * max(t.dim(), 1))(*t.shape)
-                if L.artalk_gsgen_set_tensor(h, key.encode(), C.c_void_p(t.data_ptr()), t.dim(), shape) != capi.OK:
-                    errors.append(L.artalk_gsgen_last_error(h).decode())
-            if not errors and L.artalk_gsgen_finalize(h) != capi.OK:
-                errors.append(L.artalk_gsgen_last_error(h).decode())
+            errors = load_tensors(L, "gsgen", h, ((k, v) for k, v in state_dict.items() if not k.startswith(IGNORED_PREFIXES)))
             if errors:
                 raise RuntimeError("Error(s) in loading state_dict for GSGenerators:\n\t" + "\n\t".join(errors[:12]))
         except BaseException:

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import capi
+from ._intake import load_tensors
 from .weights import _rng
 
 UNET_CHANNELS = {4: 256, 8: 256, 16: 256, 32: 256, 64: 128, 128: 64, 256: 32, 512: 16, 1024: 8}
@@ -224,17 +225,7 @@ class StyleUNet:
             raise RuntimeError("artalk_styleunet_create failed: " + L.artalk_styleunet_last_error(None).decode())
         self._h = h
         self._apply_precision(self._precision)      # host only before finalize: the mode is remembered, finalize packs for it
-        errors = []
-        for key, val in state_dict.items():
-            t = val.detach().cpu() if isinstance(val, torch.Tensor) else torch.from_numpy(np.asarray(val))
-            t = t.to(torch.float32).contiguous()
-            shape = (C.c_int64 * max(t.dim(), 1))(*t.shape)
-            rc = L.artalk_styleunet_set_tensor(self._h, key.encode(), C.c_void_p(t.data_ptr()), t.dim(), shape)
-            if rc != capi.OK:
-                errors.append(self._err())
-        rc = L.artalk_styleunet_finalize(self._h) if not errors else capi.EINVAL
-        if rc != capi.OK and not errors:
-            errors.append(self._err())
+        errors = load_tensors(L, "styleunet", self._h, state_dict.items())
         if errors:
             raise RuntimeError("Error(s) in loading state_dict for StyleUNet:\n\t" + "\n\t".join(errors[:12]))
         self._loaded = True
