@@ -40,6 +40,7 @@ SYMBOLS = [
     "artalk_styleunet_last_error", "artalk_op_conv2d", "artalk_op_resample2",
     "artalk_styleunet_set_precision", "artalk_styleunet_get_precision", "artalk_op_conv2d_ex", "artalk_styleunet_get_launch_timing",
     "artalk_op_conv2d_plan",
+    "artalk_op_su_linear", "artalk_op_su_normstyle", "artalk_op_su_demod", "artalk_op_su_add", "artalk_op_su_to_nhwc", "artalk_op_su_to_nchw",
     "artalk_flame_dims", "artalk_styleunet_dims",
     "artalk_gaga_create", "artalk_gaga_set_avatar", "artalk_gaga_set_forehead", "artalk_gaga_set_watermark", "artalk_gaga_reset_state",
     "artalk_gaga_set_slab", "artalk_gaga_render", "artalk_gaga_set_timing", "artalk_gaga_get_timing", "artalk_gaga_destroy",
@@ -292,6 +293,12 @@ def lib() -> C.CDLL:
     if hasattr(L, "artalk_op_conv2d_plan"):      # (an older build loaded through ARTALK_LIB lacks the conv planner's entry point)
         L.artalk_op_conv2d_plan.argtypes = [C.c_uint64, i64, C.c_uint64, C.c_uint64, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32), i32]
         L.artalk_op_conv2d_plan.restype = i32
+    if hasattr(L, "artalk_op_su_linear"):      # (an older build loaded through ARTALK_LIB lacks the style path's entry points)
+        for name, args in (("linear", [vp, vp, vp, vp, i32, i32, i32, i32, vp]), ("normstyle", [vp, vp, i32, i32, vp]),
+                           ("demod", [vp, i64, vp, vp, i32, i32, i32, vp]), ("add", [vp, vp, vp, i64, vp]),
+                           ("to_nhwc", [vp, vp, i32, i32, i64, vp]), ("to_nchw", [vp, vp, i32, i32, i64, i32, vp])):
+            fn = getattr(L, "artalk_op_su_" + name)
+            fn.argtypes, fn.restype = args, i32
     if hasattr(L, "artalk_gaga_create"):      # (an older build loaded through ARTALK_LIB for an A/B run lacks the GAGAvatar head)
         pi = C.POINTER(i32)
         L.artalk_flame_dims.argtypes = [vp, pi, pi, C.POINTER(f32)]

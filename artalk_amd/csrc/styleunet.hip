@@ -298,6 +298,28 @@ __global__ __launch_bounds__(256) void demod_kernel(const float* __restrict__ s,
 }
 
 static inline unsigned blocks256(long n) { return (unsigned)((n + 255) / 256); }
+static inline unsigned waves4(long n) { return (unsigned)((n + 3) / 4); }      // workgroups of four waves, one wave per output value
+
+// One launcher per kernel, each with its grid: SuRun and the artalk_op_su_* entry points both launch through these, so the grid a
+// kernel-level test runs is the grid the network runs.
+static void launch_linear(const float* x, const float* W, const float* bias, float* y, int B, int In, int Out, int lrelu, hipStream_t s) {
+    ARTALK_LAUNCH(linear_kernel, dim3(waves4((long)B * Out)), dim3(256), 0, s, x, W, bias, y, B, In, Out, lrelu);
+}
+static void launch_normstyle(const float* x, float* y, int B, int n, hipStream_t s) {
+    ARTALK_LAUNCH(normstyle_kernel, dim3(B), dim3(64), 0, s, x, y, n);
+}
+static void launch_demod(const float* sm, long ld, const float* wsq, float* d, int B, int Cin, int Cout, hipStream_t s) {
+    ARTALK_LAUNCH(demod_kernel, dim3(waves4((long)B * Cout)), dim3(256), 0, s, sm, ld, wsq, d, B, Cin, Cout);
+}
+static void launch_add(const float* a, const float* b, float* out, long n, hipStream_t s) {
+    ARTALK_LAUNCH(add_kernel, dim3(blocks256(n)), dim3(256), 0, s, a, b, out, n);
+}
+static void launch_to_nhwc(const float* x, float* out, int B, int C, long HW, hipStream_t s) {
+    ARTALK_LAUNCH(nchw_to_nhwc_kernel, dim3(blocks256((long)B * C * HW)), dim3(256), 0, s, x, out, B, C, HW);
+}
+static void launch_to_nchw(const float* x, float* out, int B, int C, long HW, int sigmoid, hipStream_t s) {
+    ARTALK_LAUNCH(nhwc_to_nchw_kernel, dim3(blocks256((long)B * C * HW)), dim3(256), 0, s, x, out, B, C, HW, sigmoid);
+}
 
 }  // namespace artalk
 
@@ -435,7 +457,7 @@ struct SuRun {
     }
     void linear(const float* x, const float* W, const float* b, float* y, int In, int Out, int lrelu) {
         if (dry) return;
-        ARTALK_LAUNCH(linear_kernel, dim3((unsigned)(((long)n * Out + 3) / 4)), dim3(256), 0, s, x, W, b, y, n, In, Out, lrelu);
+        launch_linear(x, W, b, y, n, In, Out, lrelu, s);
     }
 
     // noise: per layer the pointer of this slab's first frame and the frame stride
@@ -443,7 +465,7 @@ struct SuRun {
         const int S = u->S, L = u->L;
         const long SS = (long)S * S;
         float* xin = alloc(SS * u->in_dim);
-        if (!dry) ARTALK_LAUNCH(nchw_to_nhwc_kernel, dim3(blocks256((long)n * u->in_dim * SS)), dim3(256), 0, s, x, xin, n, u->in_dim, SS);
+        if (!dry) launch_to_nhwc(x, xin, n, u->in_dim, SS, s);
         float* feat = alloc(SS * u->first.cout);
         conv(u->first, xin, SS * u->in_dim, feat, S, 1);
         auto resblock = [&](const SuConv& c1, const SuConv& c2, const SuConv& sk, const float* in, int H, int up) -> float* {
@@ -480,7 +502,7 @@ struct SuRun {
             const long hw = (long)cur * cur;
             const int c = u->up1[i].cin;
             float* sum = alloc(hw * c);      // (stays: the block's output is stacked above it)
-            if (!dry) ARTALK_LAUNCH(add_kernel, dim3(blocks256((long)n * hw * c)), dim3(256), 0, s, feat, skips[i], sum, (long)n * hw * c);
+            if (!dry) launch_add(feat, skips[i], sum, (long)n * hw * c, s);
             feat = resblock(u->up1[i], u->up2[i], u->upsk[i], sum, cur, 1);
             cur *= 2;
             const long ohw = (long)cur * cur;
@@ -499,7 +521,7 @@ struct SuRun {
         }
         // ---- style path ----
         float* lat = alloc(512);
-        if (!dry) ARTALK_LAUNCH(normstyle_kernel, dim3(n), dim3(64), 0, s, code, lat, 512);
+        if (!dry) launch_normstyle(code, lat, n, 512, s);
         for (int j = 0; j < 8; ++j) {
             float* nx = alloc(512);
             linear(lat, u->mlp_w[j], u->mlp_b[j], nx, 512, 512, 1);
@@ -509,8 +531,7 @@ struct SuRun {
         linear(lat, u->mod_w, u->mod_b, smod, 512, u->mod_total, 0);
         auto styleconv = [&](const SuMod& m, const float* in, long in_bstride, float* out, int H, int layer, const float* sc, const float* sh) {
             float* d = alloc(m.c.cout);
-            if (!dry) ARTALK_LAUNCH(demod_kernel, dim3((unsigned)(((long)n * m.c.cout + 3) / 4)), dim3(256), 0, s, smod + m.mod_off, (long)u->mod_total,
-                                    m.wsq, d, n, m.c.cin, m.c.cout);
+            if (!dry) launch_demod(smod + m.mod_off, (long)u->mod_total, m.wsq, d, n, m.c.cin, m.c.cout, s);
             conv(m.c, in, in_bstride, out, H, 1, nullptr, &m, dry ? nullptr : smod + m.mod_off, d, dry ? nullptr : noise[layer],
                  dry ? 0 : (long)nstride[layer], sc, sh);
         };
@@ -536,8 +557,7 @@ struct SuRun {
             off = mark;
             o = o2; skip = sk2; cur *= 2;
         }
-        if (!dry) ARTALK_LAUNCH(nhwc_to_nchw_kernel, dim3(blocks256((long)n * u->out_dim * SS)), dim3(256), 0, s, skip, out_dev, n, u->out_dim, SS,
-                                activation);
+        if (!dry) launch_to_nchw(skip, out_dev, n, u->out_dim, SS, activation, s);
     }
 };
 
@@ -886,6 +906,53 @@ int artalk_op_resample2(const float* x, float* out, int B, int H, int W, int C, 
     if (!up && ((H | W) & 1)) return ARTALK_EINVAL;
     const long total = (long)B * (up ? 4L * H * W : (long)(H / 2) * (W / 2)) * C;
     ARTALK_LAUNCH(resample2_kernel, dim3(blocks256(total)), dim3(256), 0, (hipStream_t)stream, x, out, B, H, W, C, up);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+
+// The style path and layout kernels alone, through the launchers SuRun uses (tests/test_styleunet_glue_gpu.py).  Beyond what the header
+// names they refuse a size whose grid would not fit a launch.
+static inline bool su_grid_ok(int64_t blocks) { return blocks <= INT_MAX; }
+
+int artalk_op_su_linear(const float* x, const float* W, const float* bias_or_null, float* y, int B, int In, int Out, int lrelu, void* stream) {
+    if (!x || !W || !y || B < 1 || In < 1 || Out < 1 || !su_grid_ok(((int64_t)B * Out + 3) / 4)) return ARTALK_EINVAL;
+    launch_linear(x, W, bias_or_null, y, B, In, Out, lrelu, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+
+int artalk_op_su_normstyle(const float* x, float* y, int B, int n, void* stream) {
+    if (!x || !y || B < 1 || n < 1) return ARTALK_EINVAL;
+    launch_normstyle(x, y, B, n, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+
+int artalk_op_su_demod(const float* s, int64_t ld, const float* wsq, float* d, int B, int Cin, int Cout, void* stream) {
+    if (!s || !wsq || !d || B < 1 || Cin < 1 || Cout < 1 || ld < Cin || !su_grid_ok(((int64_t)B * Cout + 3) / 4)) return ARTALK_EINVAL;
+    launch_demod(s, (long)ld, wsq, d, B, Cin, Cout, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+
+int artalk_op_su_add(const float* a, const float* b, float* out, int64_t n, void* stream) {
+    if (!a || !b || !out || n < 1 || !su_grid_ok((n + 255) / 256)) return ARTALK_EINVAL;
+    launch_add(a, b, out, (long)n, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+
+// B C HW as a product of three positive values that fits a launch (no overflow on the way)
+static bool su_layout_ok(const void* x, const void* out, int B, int C, int64_t HW) {
+    if (!x || !out || B < 1 || C < 1 || HW < 1) return false;
+    const int64_t cap = (int64_t)INT_MAX * 256;
+    return HW <= cap / B / C;
+}
+
+int artalk_op_su_to_nhwc(const float* x, float* out, int B, int C, int64_t HW, void* stream) {
+    if (!su_layout_ok(x, out, B, C, HW)) return ARTALK_EINVAL;
+    launch_to_nhwc(x, out, B, C, (long)HW, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+
+int artalk_op_su_to_nchw(const float* x, float* out, int B, int C, int64_t HW, int sigmoid, void* stream) {
+    if (!su_layout_ok(x, out, B, C, HW)) return ARTALK_EINVAL;
+    launch_to_nchw(x, out, B, C, (long)HW, sigmoid, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
 }
 

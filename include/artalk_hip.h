@@ -331,6 +331,22 @@ int artalk_op_conv2d_plan(uint64_t x_addr, int64_t x_bstride, uint64_t w_addr, u
                           int k, int precision, int32_t* out, int n);
 int artalk_op_resample2(const float* x, float* out, int B, int H, int W, int C, int up, void* stream);
 
+/* The style path and layout kernels of the StyleUNet alone, one launch each through the launcher (and so the grid) the network uses, on
+ * the given stream, without waiting.  All arrays are dense float32 on the device.  ARTALK_EINVAL for a NULL required pointer, a
+ * non-positive dimension or ld < Cin, before the device is touched.
+ * su_linear:    y [B][Out] = act(x [B][In] . W [Out][In] + bias [Out] (NULL: none)); lrelu != 0: LeakyReLU 0.2 after the bias.
+ * su_normstyle: y [B][n] = x [B][n] * rsqrt(mean over n of x^2 + 1e-8), row by row (NormStyleCode).
+ * su_demod:     d [B][Cout] = rsqrt(sum over ci of s[b][ci]^2 * wsq [Cout][Cin] + 1e-8); row b of s starts at s + b * ld, ld >= Cin.
+ * su_add:       out [n] = a [n] + b [n].
+ * su_to_nhwc:   x [B][C][HW] -> out [B][HW][C].
+ * su_to_nchw:   x [B][HW][C] -> out [B][C][HW], through 1 / (1 + exp(-v)) when sigmoid != 0. */
+int artalk_op_su_linear(const float* x, const float* W, const float* bias_or_null, float* y, int B, int In, int Out, int lrelu, void* stream);
+int artalk_op_su_normstyle(const float* x, float* y, int B, int n, void* stream);
+int artalk_op_su_demod(const float* s, int64_t ld, const float* wsq, float* d, int B, int Cin, int Cout, void* stream);
+int artalk_op_su_add(const float* a, const float* b, float* out, int64_t n, void* stream);
+int artalk_op_su_to_nhwc(const float* x, float* out, int B, int C, int64_t HW, void* stream);
+int artalk_op_su_to_nchw(const float* x, float* out, int B, int C, int64_t HW, int sigmoid, void* stream);
+
 /* Read-only views of a handle, for objects that borrow it (artalk_gaga below).  Both return the handle's device index, or ARTALK_EINVAL for
  * a NULL handle; every out pointer may be NULL.  artalk_styleunet_dims: *finalized is 1 after artalk_styleunet_finalize, *slab is the
  * slab in force. */
