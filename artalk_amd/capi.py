@@ -48,6 +48,9 @@ SYMBOLS = [
     "artalk_op_gaga_finish", "artalk_op_gaga_check",
     "artalk_frames_bytes", "artalk_frames_pack", "artalk_frames_last_error", "artalk_op_frames_check", "artalk_op_gaga_finish_pack",
     "artalk_gaga_render_u8",
+    "artalk_splat_render_sets", "artalk_gaga_pool_reserve", "artalk_gaga_pool_set", "artalk_gaga_pool_clear", "artalk_gaga_stream_open",
+    "artalk_gaga_stream_close", "artalk_gaga_stream_reset", "artalk_gaga_render_streams", "artalk_op_gaga_flame_inputs_sets",
+    "artalk_op_gaga_forehead_streams", "artalk_op_gaga_means_sets", "artalk_op_gaga_streams_check", "artalk_gaga_streams_slab",
     "artalk_gsgen_create", "artalk_gsgen_set_tensor", "artalk_gsgen_finalize", "artalk_gsgen_planes", "artalk_gsgen_generate",
     "artalk_gsgen_set_timing", "artalk_gsgen_get_timing", "artalk_gsgen_dims", "artalk_gsgen_destroy", "artalk_gsgen_last_error",
     "artalk_op_conv2d_relu", "artalk_op_gs_local_input", "artalk_op_gs_global_input", "artalk_op_gs_concat_dir",
@@ -352,6 +355,33 @@ def lib() -> C.CDLL:
         L.artalk_op_gaga_finish_pack.restype = i32
         L.artalk_gaga_render_u8.argtypes = [vp, vp, i64, i32, C.POINTER(vp), C.POINTER(i64), i32, i32, vp, vp, vp]
         L.artalk_gaga_render_u8.restype = i32
+    if hasattr(L, "artalk_gaga_render_streams"):      # (an older build loaded through ARTALK_LIB for an A/B run lacks the live streams)
+        L.artalk_splat_render_sets.argtypes = L.artalk_splat_render.argtypes[:-1] + [vp, i32, i64, i64, i64, i64, i64, vp]
+        L.artalk_splat_render_sets.restype = i32
+        L.artalk_gaga_pool_reserve.argtypes = [vp, i32, i32]
+        L.artalk_gaga_pool_reserve.restype = i32
+        L.artalk_gaga_pool_set.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.artalk_gaga_pool_set.restype = i32
+        L.artalk_gaga_pool_clear.argtypes = [vp, i32]
+        L.artalk_gaga_pool_clear.restype = i32
+        L.artalk_gaga_stream_open.argtypes = [vp, C.POINTER(i32)]
+        L.artalk_gaga_stream_open.restype = i32
+        L.artalk_gaga_stream_close.argtypes = [vp, i32]
+        L.artalk_gaga_stream_close.restype = i32
+        L.artalk_gaga_stream_reset.argtypes = [vp, i32]
+        L.artalk_gaga_stream_reset.restype = i32
+        L.artalk_gaga_render_streams.argtypes = [vp, vp, i64, i32, vp, vp, vp, C.POINTER(vp), C.POINTER(i64), i32, i32, vp, vp, vp, vp]
+        L.artalk_gaga_render_streams.restype = i32
+        L.artalk_gaga_streams_slab.argtypes = [vp]
+        L.artalk_gaga_streams_slab.restype = i32
+        L.artalk_op_gaga_flame_inputs_sets.argtypes = [vp, i64, vp, vp, vp, i32, i32, vp, vp, vp]
+        L.artalk_op_gaga_flame_inputs_sets.restype = i32
+        L.artalk_op_gaga_forehead_streams.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+        L.artalk_op_gaga_forehead_streams.restype = i32
+        L.artalk_op_gaga_means_sets.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
+        L.artalk_op_gaga_means_sets.restype = i32
+        L.artalk_op_gaga_streams_check.argtypes = [i32, i32, i32, i32, i64, vp, vp, vp, vp, i32, vp, i32, i32, i32, C.c_char_p, i32]
+        L.artalk_op_gaga_streams_check.restype = i32
     if hasattr(L, "artalk_gsgen_create"):      # (an older build loaded through ARTALK_LIB for an A/B run lacks the Gaussian generators)
         L.artalk_gsgen_create.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
         L.artalk_gsgen_create.restype = i32

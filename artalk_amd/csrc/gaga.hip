@@ -6,6 +6,12 @@
 //   gaga_forehead_kernel       EMA over frames of K listed vertices; its state outlives the call               (models.py:120-125)
 //   gaga_means_kernel          per-frame Gaussian centres: V skinned vertices, then the avatar's static points (models.py:90)
 //   gaga_finish_kernel         clamp(0, 1) and the watermark blend, in place                                   (models.py:95, 131-138)
+// Live streams ("Live streams through the head"): avatars stay resident in a pool of slots, every stream has an EMA
+// state of its own, and every frame of artalk_gaga_render_streams names its motion row, its stream and its slot:
+//   gaga_flame_inputs_sets_kernel     as gaga_flame_inputs_kernel, the motion row from frame_row, the shapecode from the frame's slot
+//   gaga_forehead_streams_kernel      one workgroup per stream present in the slab, over that stream's frames in listed order
+//   gaga_means_sets_kernel            as gaga_means_kernel, rows V .. N-1 from the frame's slot
+//   gaga_gather_codes_kernel          the head-rotation codes of the listed rows, packed for the one copy to the host
 //   (frames.hip)               the same clamp and blend fused with the packing into 8-bit frames, for artalk_gaga_render_u8
 //   artalk_gaga_cameras        host only: head-rotation codes -> the view / projection matrices the rasteriser reads (models.py:127)
 //
@@ -104,6 +110,87 @@ __global__ void gaga_finish_kernel(float* __restrict__ img, const float* __restr
     img[idx] = v;
 }
 
+// ---- live streams: the same three steps with one indirection per frame
+// as gaga_flame_inputs_kernel; frame t reads motion row rows[t] and the shapecode of pool slot slots[t] (shape_pool [slots][NS])
+__global__ void gaga_flame_inputs_sets_kernel(const float* __restrict__ motion, long stride, const int64_t* __restrict__ rows,
+                                              const int32_t* __restrict__ slots, const float* __restrict__ shape_pool, int NS,
+                                              float* __restrict__ betas, float* __restrict__ pose, int T) {
+    const int NB = NS + 100, W = NB + 15;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)T * W) return;
+    const int t = (int)(idx / W), c = (int)(idx - (long)t * W);
+    const float* m = motion + (long)rows[t] * stride;
+    if (c < NB) {
+        betas[(long)t * NB + c] = c < NS ? shape_pool[(long)slots[t] * NS + c] : m[c - NS];
+    } else {
+        const int p = c - NB;
+        pose[(long)t * 15 + p] = (p >= 6 && p < 9) ? m[103 + (p - 6)] : 0.f;
+    }
+}
+
+// Workgroup e serves one stream: its state and flag are row pool_row[e] of state_pool [rows][K][3] / flag_pool [rows], its frames are
+// frames[off[e] .. off[e + 1]) - indices into verts [..][V][3], each at most once, walked in this order.  The arithmetic is
+// gaga_forehead_kernel's.  No two workgroups share a row or a frame, so nothing crosses a workgroup.  A stream's loads do not depend on
+// the recurrence, only its stores do: they are issued eight frames ahead (a frame is listed once, so no store reaches a later load).
+constexpr int kForeheadAhead = 8;
+__global__ __launch_bounds__(256) void gaga_forehead_streams_kernel(float* __restrict__ verts, const int32_t* __restrict__ index, int K, int V,
+                                                                    const int32_t* __restrict__ pool_row, const int32_t* __restrict__ off,
+                                                                    const int32_t* __restrict__ frames, float* __restrict__ state_pool,
+                                                                    int* __restrict__ flag_pool) {
+#pragma clang fp contract(off)
+    const int e = blockIdx.x;
+    const int begin = off[e], n = off[e + 1] - begin;
+    if (n <= 0) return;      // (the whole workgroup) a stream without frames keeps its state and its flag
+    const long row = pool_row[e];
+    const bool was_set = flag_pool[row] != 0;
+    __syncthreads();      // every thread has read the flag before thread 0 writes it
+    float* state = state_pool + row * K * 3;
+    const int32_t* fr = frames + begin;
+    const long per = (long)V * 3;
+    for (int i = threadIdx.x; i < K * 3; i += blockDim.x) {
+        const int k = i / 3, c = i - k * 3;
+        float* p = verts + (long)index[k] * 3 + c;
+        float s = state[i];
+        bool set = was_set;
+        for (int j0 = 0; j0 < n; j0 += kForeheadAhead) {
+            float cur[kForeheadAhead];
+            long at[kForeheadAhead];
+#pragma unroll
+            for (int u = 0; u < kForeheadAhead; ++u) {
+                at[u] = j0 + u < n ? (long)fr[j0 + u] * per : 0;
+                cur[u] = j0 + u < n ? p[at[u]] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < kForeheadAhead; ++u) {
+                if (j0 + u >= n) break;
+                if (!set) { s = cur[u]; set = true; }
+                else { s = 0.98f * s + 0.02f * cur[u]; p[at[u]] = s; }
+            }
+        }
+        state[i] = s;
+    }
+    if (threadIdx.x == 0 && K > 0) flag_pool[row] = 1;
+}
+
+// as gaga_means_kernel; frame f takes rows V .. N-1 from xyz_pool [slots][N][3] at slot slots[f]
+__global__ void gaga_means_sets_kernel(const float* __restrict__ verts, const float* __restrict__ xyz_pool, const int32_t* __restrict__ slots,
+                                       float* __restrict__ means, int F, int V, int N) {
+    const long per = (long)N * 3, idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)F * per) return;
+    const int f = (int)(idx / per);
+    const long e = idx - (long)f * per;
+    means[idx] = e < (long)V * 3 ? verts[(long)f * V * 3 + e] : xyz_pool[(long)slots[f] * per + e];
+}
+
+// codes [T][3] = motion[rows[t]][100:103]
+__global__ void gaga_gather_codes_kernel(const float* __restrict__ motion, long stride, const int64_t* __restrict__ rows, float* __restrict__ codes,
+                                         int T) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= T * 3) return;
+    const int t = idx / 3;
+    codes[idx] = motion[(long)rows[t] * stride + 100 + (idx - t * 3)];
+}
+
 static inline unsigned gaga_blocks(long n) { return (unsigned)((n + 255) / 256); }
 
 static void launch_gaga_flame_inputs(const float* motion, long stride, const float* shapecode, int NS, float* betas, float* pose, int T,
@@ -115,6 +202,19 @@ static void launch_gaga_forehead(float* verts, const int32_t* index, int K, int 
 }
 static void launch_gaga_means(const float* verts, const float* xyz, float* means, int F, int V, int N, hipStream_t s) {
     ARTALK_LAUNCH(gaga_means_kernel, dim3(gaga_blocks((long)F * N * 3)), dim3(256), 0, s, verts, xyz, means, F, V, N);
+}
+static void launch_gaga_flame_inputs_sets(const float* motion, long stride, const int64_t* rows, const int32_t* slots, const float* shape_pool,
+                                          int NS, float* betas, float* pose, int T, hipStream_t s) {
+    ARTALK_LAUNCH(gaga_flame_inputs_sets_kernel, dim3(gaga_blocks((long)T * (NS + 115))), dim3(256), 0, s, motion, stride, rows, slots, shape_pool,
+                  NS, betas, pose, T);
+}
+static void launch_gaga_forehead_streams(float* verts, const int32_t* index, int K, int V, int n_streams, const int32_t* pool_row,
+                                         const int32_t* off, const int32_t* frames, float* state_pool, int* flag_pool, hipStream_t s) {
+    ARTALK_LAUNCH(gaga_forehead_streams_kernel, dim3(n_streams), dim3(256), 0, s, verts, index, K, V, pool_row, off, frames, state_pool, flag_pool);
+}
+static void launch_gaga_means_sets(const float* verts, const float* xyz_pool, const int32_t* slots, float* means, int F, int V, int N,
+                                   hipStream_t s) {
+    ARTALK_LAUNCH(gaga_means_sets_kernel, dim3(gaga_blocks((long)F * N * 3)), dim3(256), 0, s, verts, xyz_pool, slots, means, F, V, N);
 }
 static void launch_gaga_finish(float* img, const float* wm, int h, int w, int S, int F, hipStream_t s) {
     ARTALK_LAUNCH(gaga_finish_kernel, dim3(gaga_blocks((long)F * 3 * S * S)), dim3(256), 0, s, img, wm, h, w, S, F);
@@ -151,6 +251,29 @@ static int check_render(int T, int64_t motion_stride, bool have_avatar, bool fin
     return ARTALK_OK;
 }
 
+// the frame lists of artalk_gaga_render_streams against the streams (open[id] != 0: open) and the slots (filled[slot] != 0: occupied)
+static int check_frames(int T, const int64_t* row, const int32_t* stream, const int32_t* slot, const uint8_t* open, int n_ids,
+                        const uint8_t* filled, int n_slots, std::string* err) {
+    if (T < 0) { *err = "T must not be negative"; return ARTALK_EINVAL; }
+    if (!row || !stream || !slot) { *err = "frame_row, frame_stream and frame_slot must not be NULL"; return ARTALK_EINVAL; }
+    for (int t = 0; t < T; ++t) {
+        const std::string f = "frame " + std::to_string(t);
+        if (row[t] < 0) { *err = f + ": motion row " + std::to_string(row[t]) + " is negative"; return ARTALK_EINVAL; }
+        if (stream[t] < 0 || stream[t] >= n_ids) { *err = f + ": stream " + std::to_string(stream[t]) + " was never opened"; return ARTALK_EINVAL; }
+        if (!open || !open[stream[t]]) { *err = f + ": stream " + std::to_string(stream[t]) + " is closed"; return ARTALK_EINVAL; }
+        if (slot[t] < 0 || slot[t] >= n_slots) {
+            *err = f + ": slot " + std::to_string(slot[t]) + " is outside the pool's [0, " + std::to_string(n_slots) + ")";
+            return ARTALK_EINVAL;
+        }
+        if (!filled || !filled[slot[t]]) { *err = f + ": slot " + std::to_string(slot[t]) + " is empty (artalk_gaga_pool_set)"; return ARTALK_EINVAL; }
+    }
+    return ARTALK_OK;
+}
+static int check_pool(int V, int slots, int N, std::string* err) {
+    if (slots < 1 || slots > 4096) { *err = "slots must be in 1..4096"; return ARTALK_EINVAL; }
+    return check_avatar(V, N, err);
+}
+
 }  // namespace artalk
 
 using namespace artalk;
@@ -174,6 +297,21 @@ struct artalk_gaga {
     DevBuf<int32_t> index;
     DevBuf<float> state;         // [K][3]
     DevBuf<int> flag;
+    // resident avatars (artalk_gaga_pool_*): one slab per attribute, [slots][..]; the avatar above is no slot
+    int pool_slots = 0, pool_N = 0;
+    DevBuf<float> p_xyz, p_colors, p_opac, p_scales, p_rots, p_shape;
+    std::vector<uint8_t> pool_filled;      // [slots]
+    std::vector<float> pool_transform;     // [slots][12], host
+    // live streams: stream_open[id] / stream_row[id] for every id ever handed out (ids are not reused, rows are)
+    std::vector<uint8_t> stream_open;
+    std::vector<int32_t> stream_row;
+    int streams_open = 0, cap_streams = 0;
+    DevBuf<float> s_state;       // [cap_streams][K][3]
+    DevBuf<int> s_flag;          // [cap_streams]
+    // the frame lists of one artalk_gaga_render_streams call, on their way to the device
+    PinnedBuf<char> plan_host;
+    DevBuf<char> plan_dev;
+    DevBuf<float> codes_dev;     // [frames][3]
     // watermark
     DevBuf<float> wm;
     int wm_h = 0, wm_w = 0;
@@ -205,11 +343,66 @@ int gaga_default_slab(const artalk_gaga* g, int N) {
     return (int)(n < 1 ? 1 : n > 64 ? 64 : n);
 }
 
-int gaga_slab(const artalk_gaga* g) {
+// N < 0: the single avatar's (what artalk_gaga_set_slab reports); a stream call passes the pool's
+int gaga_slab(const artalk_gaga* g, int N = -1) {
     int unet_slab = 1;
     (void)artalk_styleunet_dims(g->unet, nullptr, nullptr, nullptr, nullptr, &unet_slab);
-    const int want = g->slab_req > 0 ? g->slab_req : gaga_default_slab(g, g->have_avatar ? g->N : g->V);
+    const int want = g->slab_req > 0 ? g->slab_req : gaga_default_slab(g, N >= 0 ? N : g->have_avatar ? g->N : g->V);
     return want < unet_slab ? want : unet_slab;
+}
+
+// the frame lists of artalk_gaga_render_streams, host arrays of T entries each
+struct GagaFrames { const int64_t* row; const int32_t* stream; const int32_t* slot; };
+
+// The lists as the kernels read them, one block on the device: rows [T] int64, slots [T], and the forehead kernel's CSR over every
+// (slab, stream present in it) pair in slab order - ent_row [E] (the stream's row of the state pool), off [E + 1] into frames [T], whose
+// values count from the start of their slab.  Slab k launches entries slab_ent[k] .. slab_ent[k + 1]; off[slab_ent[k + 1]] closes it.
+struct GagaPlan {
+    const int64_t* rows = nullptr;
+    const int32_t *slots = nullptr, *ent_row = nullptr, *off = nullptr, *frames = nullptr;
+    std::vector<int> slab_ent;
+};
+
+bool gaga_upload_plan(artalk_gaga* g, const GagaFrames& fr, int T, int slab, GagaPlan* plan, hipStream_t s) {
+    const size_t t = (size_t)T, bytes = t * 8 + (4 * t + 1) * 4;
+    if (!g->plan_host.grow(bytes, 0, 1, s) || !g->plan_dev.grow(bytes, 1, 4, s)) return false;
+    // the pinned block is free here: every earlier call, on whichever stream, waited on that stream after this upload - for the rotation
+    // codes, or on its way out when something failed in between
+    char* h = g->plan_host.get();
+    int64_t* rows = (int64_t*)h;
+    int32_t* slots = (int32_t*)(h + t * 8);
+    int32_t *ent_row = slots + t, *off = ent_row + t, *frames = off + t + 1;
+    std::memcpy(rows, fr.row, t * 8);
+    std::memcpy(slots, fr.slot, t * 4);
+    int E = 0;
+    plan->slab_ent.clear();
+    std::vector<int32_t> ids;                  // the streams of the slab, by first appearance
+    std::vector<std::vector<int32_t>> lists;
+    for (int f0 = 0; f0 < T; f0 += slab) {
+        const int n = T - f0 < slab ? T - f0 : slab;
+        plan->slab_ent.push_back(E);
+        ids.clear(); lists.clear();
+        for (int j = 0; j < n; ++j) {
+            size_t e = 0;
+            while (e < ids.size() && ids[e] != fr.stream[f0 + j]) ++e;
+            if (e == ids.size()) { ids.push_back(fr.stream[f0 + j]); lists.emplace_back(); }
+            lists[e].push_back(j);
+        }
+        int at = f0;
+        for (size_t e = 0; e < ids.size(); ++e, ++E) {
+            ent_row[E] = g->stream_row[ids[e]];
+            off[E] = at;
+            for (int32_t j : lists[e]) frames[at++] = j;
+        }
+    }
+    off[E] = T;
+    plan->slab_ent.push_back(E);
+    if (hipMemcpyAsync(g->plan_dev.get(), h, bytes, hipMemcpyHostToDevice, s) != hipSuccess) { (void)hipGetLastError(); return false; }
+    const char* d = g->plan_dev.get();
+    plan->rows = (const int64_t*)d;
+    plan->slots = (const int32_t*)(d + t * 8);
+    plan->ent_row = plan->slots + t; plan->off = plan->ent_row + t; plan->frames = plan->off + t + 1;
+    return true;
 }
 
 }  // namespace
@@ -342,8 +535,12 @@ int artalk_gaga_set_forehead(artalk_gaga* g, const int32_t* idx, int K) {
     if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
     const int rc = check_forehead(g->V, idx, K, &g->err);
     if (rc != ARTALK_OK) return rc;
+    if (g->streams_open > 0 && K != g->K)
+        return gaga_fail(g, ARTALK_ESTATE, "K = " + std::to_string(K) + " differs from the " + std::to_string(g->K) + " vertices the " +
+                                           std::to_string(g->streams_open) + " open streams keep a state for: close them first");
     if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
     (void)hipDeviceSynchronize();
+    if (K != g->K) { g->s_state.reset(); g->s_flag.reset(); g->cap_streams = 0; }      // (no stream is open) rows of another width
     g->index.reset(); g->flag.reset(); g->state.reset(); g->K = 0;
     if (K == 0) return ARTALK_OK;
     if (!g->index.alloc((size_t)K) || !g->flag.alloc(1) || !g->state.alloc((size_t)K * 3)) {
@@ -380,6 +577,11 @@ int artalk_gaga_set_slab(artalk_gaga* g, int frames) {
     return gaga_slab(g);
 }
 
+int artalk_gaga_streams_slab(const artalk_gaga* g) {
+    if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
+    return gaga_slab(g, g->pool_slots > 0 ? g->pool_N : -1);
+}
+
 int artalk_gaga_set_timing(artalk_gaga* g, int enable) {
     if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
     g->timing = enable != 0;
@@ -392,17 +594,23 @@ int artalk_gaga_get_timing(const artalk_gaga* g, double* stage_ms, int n) {
     return kGagaStages;
 }
 
-// The loop of artalk_gaga_render and artalk_gaga_render_u8.  format == 0: fp32 frames into out_dev, finished in place.  Otherwise the
+// The loop of artalk_gaga_render, artalk_gaga_render_u8 and (fr != null) artalk_gaga_render_streams.  format == 0: fp32 frames into out_dev, finished in place.  Otherwise the
 // upsampler writes each slab into g->rgb and the fused finish-and-pack kernel writes its 8-bit frames into out_u8 (and, with out_host, a
-// copy on g->copy_stream follows each slab's pack kernel).
+// copy on g->copy_stream follows each slab's pack kernel).  With fr, frame t takes motion row fr->row[t], the resident avatar of slot
+// fr->slot[t] and the EMA state of stream fr->stream[t]; everything from the splat image on is the same code.
 static int gaga_render_any(artalk_gaga* g, const float* motion_dev, int64_t motion_stride, int T, const float* const* noise_ptrs_or_null,
                            const int64_t* noise_batch_strides, int activation, float* out_dev, int format, uint8_t* out_u8, uint8_t* out_host,
-                           void* stream) {
+                           void* stream, const char* name, const GagaFrames* fr = nullptr) {
     if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
     if (!motion_dev || (format ? !out_u8 : !out_dev)) return gaga_fail(g, ARTALK_EINVAL, "motion and out must not be NULL");
     int finalized = 0;
     (void)artalk_styleunet_dims(g->unet, nullptr, nullptr, nullptr, &finalized, nullptr);
-    const int rc = check_render(T, motion_stride, g->have_avatar, finalized != 0, &g->err);
+    if (fr) {
+        const int rcs = check_frames(T, fr->row, fr->stream, fr->slot, g->stream_open.data(), (int)g->stream_open.size(), g->pool_filled.data(),
+                                     g->pool_slots, &g->err);
+        if (rcs != ARTALK_OK) return rcs;
+    }
+    const int rc = check_render(T, motion_stride, fr || g->have_avatar, finalized != 0, &g->err);
     if (rc != ARTALK_OK) return rc;
     const int rcn = su_check_noise(g->num_layers, noise_ptrs_or_null, noise_batch_strides, &g->err);
     if (rcn != ARTALK_OK) return rcn;
@@ -416,11 +624,11 @@ static int gaga_render_any(artalk_gaga* g, const float* motion_dev, int64_t moti
     if (format) {      // the call waits on its stream and orders a second stream against it: not inside a capture
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); return gaga_fail(g, ARTALK_EHIP, "hipStreamIsCapturing failed"); }
-        if (cap != hipStreamCaptureStatusNone) return gaga_fail(g, ARTALK_EINVAL, "artalk_gaga_render_u8 waits on its stream: it cannot run during stream capture");
+        if (cap != hipStreamCaptureStatusNone) return gaga_fail(g, ARTALK_EINVAL, std::string(name) + " waits on its stream: it cannot run during stream capture");
     }
-    const int V = g->V, N = g->N, S = g->S, NB = g->NB;
+    const int V = g->V, N = fr ? g->pool_N : g->N, S = g->S, NB = g->NB;
     const long SS = (long)S * S;
-    const int slab = gaga_slab(g);
+    const int slab = gaga_slab(g, N);
     const int frames = T < slab ? T : slab;
     if (frames > g->cap_frames || N > g->cap_N) {
         (void)hipDeviceSynchronize();
@@ -442,14 +650,30 @@ static int gaga_render_any(artalk_gaga* g, const float* motion_dev, int64_t moti
     if (out_host && (!g->copy_stream.create() || !g->packed.create() || !g->copied.create()))
         return gaga_fail(g, ARTALK_EHIP, "creating the copy stream or its events failed");
     if (!g->codes_host.grow((size_t)T * 3, 0, 1, s)) return gaga_fail(g, ARTALK_EHIP, "hipHostMalloc failed");
+    GagaPlan plan;
+    if (fr) {
+        if (!g->codes_dev.grow((size_t)T * 3, 1, 4, s)) return gaga_fail(g, ARTALK_EHIP, "hipMalloc of the rotation codes failed");
+        if (!gaga_upload_plan(g, *fr, T, slab, &plan, s)) {      // (nothing is in flight: the upload is the function's last step)
+            return gaga_fail(g, ARTALK_EHIP, "uploading the frame lists failed");
+        }
+        ARTALK_LAUNCH(gaga_gather_codes_kernel, dim3(gaga_blocks((long)T * 3)), dim3(256), 0, s, motion_dev, (long)motion_stride, plan.rows,
+                      g->codes_dev.get(), T);
+    }
     // the first wait of the call: the head-rotation codes become the cameras, which the rasteriser reads on the host
-    if (hipMemcpy2DAsync(g->codes_host.get(), 3 * sizeof(float), motion_dev + 100, (size_t)motion_stride * sizeof(float), 3 * sizeof(float), (size_t)T,
+    if (fr ? (hipMemcpyAsync(g->codes_host.get(), g->codes_dev.get(), (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
+              hipStreamSynchronize(s) != hipSuccess) :
+        hipMemcpy2DAsync(g->codes_host.get(), 3 * sizeof(float), motion_dev + 100, (size_t)motion_stride * sizeof(float), 3 * sizeof(float), (size_t)T,
                          hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
         (void)hipGetLastError();
+        if (fr) (void)hipStreamSynchronize(s);      // the frame lists may still be on their way up from the pinned block
         return gaga_fail(g, ARTALK_EHIP, "reading the rotation codes failed");
     }
     std::vector<float> view((size_t)T * 16), proj((size_t)T * 16);
-    (void)artalk_gaga_cameras(g->codes_host.get(), 3, T, g->transform, view.data(), proj.data(), nullptr);
+    if (!fr) (void)artalk_gaga_cameras(g->codes_host.get(), 3, T, g->transform, view.data(), proj.data(), nullptr);
+    else
+        for (int t = 0; t < T; ++t)      // every frame under its slot's [R | t]
+            (void)artalk_gaga_cameras(g->codes_host.get() + (size_t)t * 3, 3, 1, g->pool_transform.data() + (size_t)fr->slot[t] * 12,
+                                      view.data() + (size_t)t * 16, proj.data() + (size_t)t * 16, nullptr);
 
     StageTimer timer;
     timer.start(s, g->timing);
@@ -459,18 +683,34 @@ static int gaga_render_any(artalk_gaga* g, const float* motion_dev, int64_t moti
     for (int f0 = 0; f0 < T; f0 += slab) {
         const int n = T - f0 < slab ? T - f0 : slab;
         timer.mark(-1);      // (what lies between two slabs counts to no stage)
-        launch_gaga_flame_inputs(motion_dev + (long)f0 * motion_stride, (long)motion_stride, g->shapecode.get(), NB - 100, g->betas.get(),
-                                 g->pose.get(), n, s);
+        if (fr) launch_gaga_flame_inputs_sets(motion_dev, (long)motion_stride, plan.rows + f0, plan.slots + f0, g->p_shape.get(), NB - 100,
+                                              g->betas.get(), g->pose.get(), n, s);
+        else launch_gaga_flame_inputs(motion_dev + (long)f0 * motion_stride, (long)motion_stride, g->shapecode.get(), NB - 100, g->betas.get(),
+                                      g->pose.get(), n, s);
         if (artalk_flame_verts(g->flame, g->betas.get(), g->pose.get(), n, g->verts.get(), s) != ARTALK_OK)
             return gaga_fail(g, ARTALK_EHIP, std::string("artalk_flame_verts failed: ") + artalk_flame_last_error(g->flame));
         timer.mark(kGagaInputsFlame);
-        if (g->K > 0) launch_gaga_forehead(g->verts.get(), g->index.get(), g->K, n, V, g->state.get(), g->flag.get(), s);
-        launch_gaga_means(g->verts.get(), g->xyz.get(), g->means.get(), n, V, N, s);
-        timer.mark(kGagaForeheadMeans);
-        int rc2 = artalk_splat_render(g->splat, N, n, S, S, g->means.get(), (int64_t)N * 3, g->colors.get(), 0, g->opac.get(), 0, g->scales.get(), 0,
+        int rc2;
+        if (fr) {
+            const int e0 = plan.slab_ent[(size_t)(f0 / slab)], e1 = plan.slab_ent[(size_t)(f0 / slab) + 1];
+            if (g->K > 0) launch_gaga_forehead_streams(g->verts.get(), g->index.get(), g->K, V, e1 - e0, plan.ent_row + e0, plan.off + e0, plan.frames,
+                                                       g->s_state.get(), g->s_flag.get(), s);
+            launch_gaga_means_sets(g->verts.get(), g->p_xyz.get(), plan.slots + f0, g->means.get(), n, V, N, s);
+            timer.mark(kGagaForeheadMeans);
+            rc2 = artalk_splat_render_sets(g->splat, N, n, S, S, g->means.get(), (int64_t)N * 3, g->p_colors.get(), 0, g->p_opac.get(), 0,
+                                           g->p_scales.get(), 0, g->p_rots.get(), 0, view.data() + (size_t)f0 * 16, proj.data() + (size_t)f0 * 16, n,
+                                           tanfov, tanfov, 1.0f, nullptr, g->img.get(), g->radii.get(), fr->slot + f0, g->pool_slots, 0,
+                                           (int64_t)N * kGagaCh, N, (int64_t)N * 3, (int64_t)N * 4, s);
+        } else {
+            if (g->K > 0) launch_gaga_forehead(g->verts.get(), g->index.get(), g->K, n, V, g->state.get(), g->flag.get(), s);
+            launch_gaga_means(g->verts.get(), g->xyz.get(), g->means.get(), n, V, N, s);
+            timer.mark(kGagaForeheadMeans);
+            rc2 = artalk_splat_render(g->splat, N, n, S, S, g->means.get(), (int64_t)N * 3, g->colors.get(), 0, g->opac.get(), 0, g->scales.get(), 0,
                                       g->rots.get(), 0, view.data() + (size_t)f0 * 16, proj.data() + (size_t)f0 * 16, n, tanfov, tanfov, 1.0f,
                                       nullptr, g->img.get(), g->radii.get(), s);
-        if (rc2 != ARTALK_OK) return gaga_fail(g, rc2, std::string("artalk_splat_render failed: ") + artalk_splat_last_error(g->splat));
+        }
+        if (rc2 != ARTALK_OK)
+            return gaga_fail(g, rc2, std::string(fr ? "artalk_splat_render_sets" : "artalk_splat_render") + " failed: " + artalk_splat_last_error(g->splat));
         timer.mark(kGagaSplat);
         if (noise_ptrs_or_null) for (int l = 0; l < g->num_layers; ++l) np[l] = noise_ptrs_or_null[l] + (long)f0 * noise_batch_strides[l];
         float* out = format ? g->rgb.get() : out_dev + (long)f0 * 3 * SS;
@@ -505,7 +745,8 @@ static int gaga_render_any(artalk_gaga* g, const float* motion_dev, int64_t moti
 
 int artalk_gaga_render(artalk_gaga* g, const float* motion_dev, int64_t motion_stride, int T, const float* const* noise_ptrs_or_null,
                        const int64_t* noise_batch_strides, int activation, float* out_dev, void* stream) {
-    return gaga_render_any(g, motion_dev, motion_stride, T, noise_ptrs_or_null, noise_batch_strides, activation, out_dev, 0, nullptr, nullptr, stream);
+    return gaga_render_any(g, motion_dev, motion_stride, T, noise_ptrs_or_null, noise_batch_strides, activation, out_dev, 0, nullptr, nullptr, stream,
+                           "artalk_gaga_render");
 }
 
 int artalk_gaga_render_u8(artalk_gaga* g, const float* motion_dev, int64_t motion_stride, int T, const float* const* noise_ptrs_or_null,
@@ -513,8 +754,162 @@ int artalk_gaga_render_u8(artalk_gaga* g, const float* motion_dev, int64_t motio
                           void* stream) {
     if (g && format != ARTALK_FRAMES_RGB24 && format != ARTALK_FRAMES_YUV420P) return gaga_fail(g, ARTALK_EINVAL, "unknown frame format " + std::to_string(format));
     const int rc = gaga_render_any(g, motion_dev, motion_stride, T, noise_ptrs_or_null, noise_batch_strides, activation, nullptr, format,
-                                   out_dev, out_host_or_null, stream);
+                                   out_dev, out_host_or_null, stream, "artalk_gaga_render_u8");
     // a call that failed between two slabs leaves no copy in flight: the caller may free both buffers
+    if (rc != ARTALK_OK && g && out_host_or_null && g->copy_stream.get()) (void)hipStreamSynchronize(g->copy_stream.get());
+    return rc;
+}
+
+// ---- resident avatars
+int artalk_gaga_pool_reserve(artalk_gaga* g, int slots, int N) {
+    if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
+    const int rc = check_pool(g->V, slots, N, &g->err);
+    if (rc != ARTALK_OK) return rc;
+    if (g->pool_slots > 0 && g->streams_open > 0)
+        return gaga_fail(g, ARTALK_ESTATE, "the pool cannot be reserved again while " + std::to_string(g->streams_open) + " streams are open");
+    if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
+    (void)hipDeviceSynchronize();      // an earlier call may still read the pool that is replaced
+    g->pool_slots = g->pool_N = 0;
+    g->pool_filled.clear(); g->pool_transform.clear();
+    for (DevBuf<float>* b : {&g->p_xyz, &g->p_colors, &g->p_opac, &g->p_scales, &g->p_rots, &g->p_shape}) b->reset();
+    const size_t n = (size_t)slots * N;
+    if (!g->p_xyz.alloc(n * 3) || !g->p_colors.alloc(n * kGagaCh) || !g->p_opac.alloc(n) || !g->p_scales.alloc(n * 3) || !g->p_rots.alloc(n * 4) ||
+        !g->p_shape.alloc((size_t)slots * (g->NB - 100))) {
+        for (DevBuf<float>* b : {&g->p_xyz, &g->p_colors, &g->p_opac, &g->p_scales, &g->p_rots, &g->p_shape}) b->reset();
+        return gaga_fail(g, ARTALK_EHIP, "hipMalloc of a pool of " + std::to_string(slots) + " avatars of " + std::to_string(N) + " Gaussians failed");
+    }
+    g->pool_slots = slots; g->pool_N = N;
+    g->pool_filled.assign((size_t)slots, 0);
+    g->pool_transform.assign((size_t)slots * 12, 0.f);
+    return ARTALK_OK;
+}
+
+static int gaga_check_slot(artalk_gaga* g, int slot) {
+    if (slot >= 0 && slot < g->pool_slots) return ARTALK_OK;
+    return gaga_fail(g, ARTALK_EINVAL, "slot " + std::to_string(slot) + " is outside the pool's [0, " + std::to_string(g->pool_slots) + ")");
+}
+
+int artalk_gaga_pool_set(artalk_gaga* g, int slot, int N, const float* xyz, const float* colors, const float* opacities, const float* scales,
+                         const float* rotations, const float* shapecode, const float* transform_3x4) {
+    if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
+    if (!xyz || !colors || !opacities || !scales || !rotations || !transform_3x4 || (g->NB > 100 && !shapecode))
+        return gaga_fail(g, ARTALK_EINVAL, "xyz, colors, opacities, scales, rotations, shapecode and transform must not be NULL");
+    int rc = check_avatar(g->V, N, &g->err);
+    if (rc == ARTALK_OK) rc = gaga_check_slot(g, slot);
+    if (rc != ARTALK_OK) return rc;
+    if (N != g->pool_N)
+        return gaga_fail(g, ARTALK_EINVAL, "N (" + std::to_string(N) + ") is not the pool's " + std::to_string(g->pool_N) + ": resident avatars share N");
+    if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
+    if (g->pool_filled[(size_t)slot]) (void)hipDeviceSynchronize();      // an earlier call may still read the avatar that is replaced
+    g->pool_filled[(size_t)slot] = 0;
+    const size_t n = (size_t)N, at = (size_t)slot * n, NS = (size_t)(g->NB - 100);
+    const auto up = [](float* dst, const float* src, size_t count) {
+        return count == 0 || hipMemcpy(dst, src, count * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+    };
+    if (!up(g->p_xyz.get() + at * 3, xyz, n * 3) || !up(g->p_colors.get() + at * kGagaCh, colors, n * kGagaCh) ||
+        !up(g->p_opac.get() + at, opacities, n) || !up(g->p_scales.get() + at * 3, scales, n * 3) || !up(g->p_rots.get() + at * 4, rotations, n * 4) ||
+        !up(g->p_shape.get() + (size_t)slot * NS, shapecode, NS)) {
+        (void)hipGetLastError();
+        return gaga_fail(g, ARTALK_EHIP, "uploading the avatar failed");
+    }
+    (void)hipDeviceSynchronize();      // the slot is whole before any stream reads it
+    std::memcpy(g->pool_transform.data() + (size_t)slot * 12, transform_3x4, 12 * sizeof(float));
+    g->pool_filled[(size_t)slot] = 1;
+    return ARTALK_OK;
+}
+
+int artalk_gaga_pool_clear(artalk_gaga* g, int slot) {
+    if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
+    const int rc = gaga_check_slot(g, slot);
+    if (rc != ARTALK_OK) return rc;
+    if (!g->pool_filled[(size_t)slot]) return ARTALK_OK;
+    if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
+    (void)hipDeviceSynchronize();
+    g->pool_filled[(size_t)slot] = 0;
+    return ARTALK_OK;
+}
+
+// ---- per-stream forehead state
+static int gaga_zero_row(artalk_gaga* g, int row) {      // the device is idle; it is idle again afterwards
+    const size_t w = (size_t)(g->K ? g->K : 1) * 3;
+    if (hipMemset(g->s_flag.get() + row, 0, sizeof(int)) != hipSuccess || hipMemset(g->s_state.get() + (size_t)row * w, 0, w * sizeof(float)) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) {
+        (void)hipGetLastError();
+        return gaga_fail(g, ARTALK_EHIP, "hipMemset failed");
+    }
+    return ARTALK_OK;
+}
+
+static int gaga_check_stream(artalk_gaga* g, int id) {
+    if (id < 0 || id >= (int)g->stream_open.size()) return gaga_fail(g, ARTALK_EINVAL, "stream " + std::to_string(id) + " was never opened");
+    if (!g->stream_open[(size_t)id]) return gaga_fail(g, ARTALK_EINVAL, "stream " + std::to_string(id) + " is closed");
+    return ARTALK_OK;
+}
+
+int artalk_gaga_stream_open(artalk_gaga* g, int* id) {
+    if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
+    if (!id) return gaga_fail(g, ARTALK_EINVAL, "id is NULL");
+    *id = -1;
+    if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
+    (void)hipDeviceSynchronize();      // a closed stream's last call may still write the row that is handed out again
+    std::vector<char> taken((size_t)g->cap_streams, 0);
+    for (size_t i = 0; i < g->stream_open.size(); ++i)
+        if (g->stream_open[i]) taken[(size_t)g->stream_row[i]] = 1;
+    int row = 0;
+    while (row < g->cap_streams && taken[(size_t)row]) ++row;
+    if (row == g->cap_streams) {      // grow, keeping the open streams' rows
+        const int cap = g->cap_streams ? 2 * g->cap_streams : 8;
+        const size_t w = (size_t)(g->K ? g->K : 1) * 3;
+        DevBuf<float> st;
+        DevBuf<int> fl;
+        if (!st.alloc_zero((size_t)cap * w) || !fl.alloc_zero((size_t)cap)) return gaga_fail(g, ARTALK_EHIP, "hipMalloc of the stream states failed");
+        if (g->cap_streams > 0 &&
+            (hipMemcpy(st.get(), g->s_state.get(), (size_t)g->cap_streams * w * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess ||
+             hipMemcpy(fl.get(), g->s_flag.get(), (size_t)g->cap_streams * sizeof(int), hipMemcpyDeviceToDevice) != hipSuccess)) {
+            (void)hipGetLastError();
+            return gaga_fail(g, ARTALK_EHIP, "copying the stream states failed");
+        }
+        (void)hipDeviceSynchronize();
+        g->s_state = std::move(st); g->s_flag = std::move(fl);
+        g->cap_streams = cap;
+    }
+    const int rc = gaga_zero_row(g, row);
+    if (rc != ARTALK_OK) return rc;
+    g->stream_open.push_back(1);
+    g->stream_row.push_back(row);
+    ++g->streams_open;
+    *id = (int)g->stream_open.size() - 1;
+    return ARTALK_OK;
+}
+
+int artalk_gaga_stream_close(artalk_gaga* g, int id) {
+    if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
+    const int rc = gaga_check_stream(g, id);
+    if (rc != ARTALK_OK) return rc;
+    g->stream_open[(size_t)id] = 0;      // the row is cleared when it is handed out again, after a wait for the device
+    --g->streams_open;
+    return ARTALK_OK;
+}
+
+int artalk_gaga_stream_reset(artalk_gaga* g, int id) {
+    if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
+    const int rc = gaga_check_stream(g, id);
+    if (rc != ARTALK_OK) return rc;
+    if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
+    (void)hipDeviceSynchronize();
+    return gaga_zero_row(g, g->stream_row[(size_t)id]);
+}
+
+int artalk_gaga_render_streams(artalk_gaga* g, const float* motion_dev, int64_t motion_stride, int T, const int64_t* frame_row_host,
+                               const int32_t* frame_stream_host, const int32_t* frame_slot_host, const float* const* noise_ptrs_or_null,
+                               const int64_t* noise_batch_strides, int activation, int format, float* out_dev, uint8_t* out_u8,
+                               uint8_t* out_host_or_null, void* stream) {
+    if (g && format != 0 && format != ARTALK_FRAMES_RGB24 && format != ARTALK_FRAMES_YUV420P)
+        return gaga_fail(g, ARTALK_EINVAL, "unknown frame format " + std::to_string(format));
+    if (g && format == 0 && out_host_or_null) return gaga_fail(g, ARTALK_EINVAL, "out_host needs an 8-bit format");
+    const GagaFrames fr{frame_row_host, frame_stream_host, frame_slot_host};
+    const int rc = gaga_render_any(g, motion_dev, motion_stride, T, noise_ptrs_or_null, noise_batch_strides, activation, out_dev, format, out_u8,
+                                   out_host_or_null, stream, "artalk_gaga_render_streams", &fr);
     if (rc != ARTALK_OK && g && out_host_or_null && g->copy_stream.get()) (void)hipStreamSynchronize(g->copy_stream.get());
     return rc;
 }
@@ -538,6 +933,45 @@ int artalk_op_gaga_means(const float* verts_dev, const float* xyz_dev, float* me
     if (!verts_dev || !xyz_dev || !means_dev || F < 1 || V < 1 || N < V) return ARTALK_EINVAL;
     launch_gaga_means(verts_dev, xyz_dev, means_dev, F, V, N, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+
+int artalk_op_gaga_flame_inputs_sets(const float* motion_dev, int64_t motion_stride, const int64_t* frame_row_dev, const int32_t* frame_slot_dev,
+                                     const float* shapecode_pool_dev, int NB, int T, float* betas_dev, float* pose_dev, void* stream) {
+    if (!motion_dev || !frame_row_dev || !frame_slot_dev || !betas_dev || !pose_dev || T < 1 || NB < 100 || motion_stride < kGagaMotion ||
+        (NB > 100 && !shapecode_pool_dev))
+        return ARTALK_EINVAL;
+    launch_gaga_flame_inputs_sets(motion_dev, (long)motion_stride, frame_row_dev, frame_slot_dev, shapecode_pool_dev, NB - 100, betas_dev, pose_dev, T,
+                                  (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+
+int artalk_op_gaga_forehead_streams(float* verts_dev, const int32_t* idx_dev, int K, int V, int n_streams, const int32_t* pool_row_dev,
+                                    const int32_t* offsets_dev, const int32_t* frames_dev, float* state_pool_dev, int* flag_pool_dev, void* stream) {
+    if (!verts_dev || !state_pool_dev || !flag_pool_dev || K < 0 || n_streams < 0 || V < 1 || K > V || (K > 0 && !idx_dev)) return ARTALK_EINVAL;
+    if (n_streams > 0 && (!pool_row_dev || !offsets_dev || !frames_dev)) return ARTALK_EINVAL;
+    if (K == 0 || n_streams == 0) return ARTALK_OK;
+    launch_gaga_forehead_streams(verts_dev, idx_dev, K, V, n_streams, pool_row_dev, offsets_dev, frames_dev, state_pool_dev, flag_pool_dev,
+                                 (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+
+int artalk_op_gaga_means_sets(const float* verts_dev, const float* xyz_pool_dev, const int32_t* frame_slot_dev, float* means_dev, int F, int V,
+                              int N, void* stream) {
+    if (!verts_dev || !xyz_pool_dev || !frame_slot_dev || !means_dev || F < 1 || V < 1 || N < V) return ARTALK_EINVAL;
+    launch_gaga_means_sets(verts_dev, xyz_pool_dev, frame_slot_dev, means_dev, F, V, N, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
+}
+
+int artalk_op_gaga_streams_check(int V, int pool_slots, int pool_N, int T, int64_t motion_stride, const int64_t* frame_row_host,
+                                 const int32_t* frame_stream_host, const int32_t* frame_slot_host, const uint8_t* stream_open_host, int n_stream_ids,
+                                 const uint8_t* slot_filled_host, int unet_finalized, int format, int S, char* msg, int msg_cap) {
+    std::string err;
+    int rc = check_pool(V, pool_slots, pool_N, &err);
+    if (rc == ARTALK_OK) rc = check_frames(T, frame_row_host, frame_stream_host, frame_slot_host, stream_open_host, n_stream_ids, slot_filled_host, pool_slots, &err);
+    if (rc == ARTALK_OK) rc = check_render(T, motion_stride, true, unet_finalized != 0, &err);
+    if (rc == ARTALK_OK && format != 0) rc = frames_check(format, T, S, S, true, true, &err);
+    if (msg && msg_cap > 0) { std::strncpy(msg, err.c_str(), (size_t)msg_cap - 1); msg[msg_cap - 1] = 0; }
+    return rc;
 }
 
 int artalk_op_gaga_finish(float* img_dev, int F, int S, const float* rgba_dev_or_null, int h, int w, void* stream) {

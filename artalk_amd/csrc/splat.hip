@@ -11,6 +11,9 @@
 //   splat_blend_kernel              one workgroup of 256 threads per 16 x 16 tile: the tile's Gaussians pass through LDS in batches of
 //                                   256 (geometry and the 32 colours), every thread keeps T and 32 sums in registers and walks the batch
 //                                   front to back; the workgroup leaves when all its pixels have stopped
+// artalk_splat_render_sets: an attribute may also lie in a pool of sets, and every frame names its set: the address of frame t's
+// attribute is base + set[t] * set stride + t * frame stride.  The count pass, which covers all frames in one launch, reads set[t] from
+// a device copy; the per-frame launches get bases the host has moved to the frame's set.  artalk_splat_render is the call without sets.
 // Both preprocess forms run the same inlined function with floating-point contraction off, so the count the host sizes the pair buffers
 // from is the count the second pass emits; the emit kernel checks every index against the capacity all the same.
 // The number of pairs depends on the data.  artalk_splat_render therefore WAITS ONCE on its stream, after the counting pass, to read its
@@ -39,6 +42,8 @@ struct SplatCam { float V[16], P[16]; };      // row-major, row-vector conventio
 struct SplatAttrs {
     const float *means, *colors, *opac, *scales, *rots;
     long s_means, s_colors, s_opac, s_scales, s_rots;      // elements between two frames; 0: one set for every frame
+    const int* sets;                                       // device [T]: the set of every frame, or null (every frame: set 0)
+    long p_means, p_colors, p_opac, p_scales, p_rots;      // elements between two sets
 };
 struct SplatView {
     int N, H, W, gx, gy;               // gx x gy tiles
@@ -57,7 +62,8 @@ __device__ __forceinline__ int splat_tile_bound(float v, int hi) { return (int)f
 // One Gaussian of one frame.  false: culled (radius 0, no tiles).
 __device__ __forceinline__ bool splat_project(const SplatAttrs& a, const SplatView& v, const SplatCam& cam, int t, int i, SplatGeom& g) {
 #pragma clang fp contract(off)
-    const float* p = a.means + (long)t * a.s_means + (long)i * 3;
+    const long set = a.sets ? (long)a.sets[t] : 0;
+    const float* p = a.means + set * a.p_means + (long)t * a.s_means + (long)i * 3;
     const float px = p[0], py = p[1], pz = p[2];
     const float* V = cam.V;
     const float* P = cam.P;
@@ -71,8 +77,8 @@ __device__ __forceinline__ bool splat_project(const SplatAttrs& a, const SplatVi
     const float wq = hw + 1e-7f;
     const float qx = hx / wq, qy = hy / wq;
 
-    const float* sc = a.scales + (long)t * a.s_scales + (long)i * 3;
-    const float* rq = a.rots + (long)t * a.s_rots + (long)i * 4;
+    const float* sc = a.scales + set * a.p_scales + (long)t * a.s_scales + (long)i * 3;
+    const float* rq = a.rots + set * a.p_rots + (long)t * a.s_rots + (long)i * 4;
     const float s0 = v.mod * sc[0], s1 = v.mod * sc[1], s2 = v.mod * sc[2];
     const float v0 = s0 * s0, v1 = s1 * s1, v2 = s2 * s2;
     const float r = rq[0], x = rq[1], y = rq[2], z = rq[3];
@@ -115,7 +121,7 @@ __device__ __forceinline__ bool splat_project(const SplatAttrs& a, const SplatVi
     g.y1 = splat_tile_bound((cy + rad + 15.0f) / 16.0f, v.gy);
     if (g.x1 <= g.x0 || g.y1 <= g.y0) return false;
     g.x = cx; g.y = cy; g.depth = tz;
-    g.conic_op = make_float4(cc / det, -cb / det, ca / det, a.opac[(long)t * a.s_opac + i]);
+    g.conic_op = make_float4(cc / det, -cb / det, ca / det, a.opac[set * a.p_opac + (long)t * a.s_opac + i]);
     g.radius = (int)rad;
     return true;
 }
@@ -288,12 +294,13 @@ enum { kStageCount, kStagePreprocess, kStageScanEmit, kStageSort, kStageRanges, 
 struct artalk_splat {
     int device = 0;
     DevBuf<SplatCam> cams;
+    DevBuf<int> sets;          // render_sets: the set of every frame of the call
     DevBuf<unsigned long long> counts, keys_in, keys_out;
     DevBuf<float2> xy; DevBuf<float4> conic; DevBuf<float> depth; DevBuf<uint4> rect;      // per Gaussian of the frame in work
     DevBuf<unsigned int> touched, offsets, vals_in, vals_out;
     DevBuf<uint2> ranges;
     DevBuf<char> scan_tmp, sort_tmp;
-    PinnedBuf<char> host;      // cameras going up, pair counts coming down
+    PinnedBuf<char> host;      // cameras (and set indices) going up, pair counts coming down
     bool timing = false, used = false;
     double stage_ms[kSplatStages] = {0, 0, 0, 0, 0, 0};
     long long last_pairs = 0;
@@ -354,11 +361,13 @@ int artalk_splat_get_timing(const artalk_splat* s, double* stage_ms, int n, long
     return kSplatStages;
 }
 
-int artalk_splat_render(artalk_splat* s, int N, int T, int H, int W, const float* means_dev, int64_t means_stride, const float* colors_dev,
-                        int64_t colors_stride, const float* opacities_dev, int64_t opacities_stride, const float* scales_dev,
-                        int64_t scales_stride, const float* rotations_dev, int64_t rotations_stride, const float* view_host,
-                        const float* proj_host, int n_cams, float tanfovx, float tanfovy, float scale_modifier, const float* bg_dev_or_null,
-                        float* out_dev, int32_t* radii_dev, void* stream) {
+int artalk_splat_render_sets(artalk_splat* s, int N, int T, int H, int W, const float* means_dev, int64_t means_stride, const float* colors_dev,
+                             int64_t colors_stride, const float* opacities_dev, int64_t opacities_stride, const float* scales_dev,
+                             int64_t scales_stride, const float* rotations_dev, int64_t rotations_stride, const float* view_host,
+                             const float* proj_host, int n_cams, float tanfovx, float tanfovy, float scale_modifier,
+                             const float* bg_dev_or_null, float* out_dev, int32_t* radii_dev, const int32_t* set_of_frame_host, int n_sets,
+                             int64_t means_set_stride, int64_t colors_set_stride, int64_t opacities_set_stride, int64_t scales_set_stride,
+                             int64_t rotations_set_stride, void* stream) {
     if (!s) { g_splat_error = "rasteriser is NULL"; return ARTALK_EINVAL; }
     if (N < 0) { s->err = "N must not be negative"; return ARTALK_EINVAL; }
     if (T < 0) { s->err = "T must not be negative"; return ARTALK_EINVAL; }
@@ -377,6 +386,18 @@ int artalk_splat_render(artalk_splat* s, int N, int T, int H, int W, const float
         s->err = "a frame stride must not be negative";
         return ARTALK_EINVAL;
     }
+    const int32_t* sets = T > 0 ? set_of_frame_host : nullptr;
+    if (sets) {
+        if (means_set_stride < 0 || colors_set_stride < 0 || opacities_set_stride < 0 || scales_set_stride < 0 || rotations_set_stride < 0) {
+            s->err = "a set stride must not be negative";
+            return ARTALK_EINVAL;
+        }
+        for (int t = 0; t < T; ++t)
+            if (sets[t] < 0 || sets[t] >= n_sets) {
+                s->err = "frame " + std::to_string(t) + " names set " + std::to_string(sets[t]) + ", outside [0, " + std::to_string(n_sets) + ")";
+                return ARTALK_EINVAL;
+            }
+    }
     if (T == 0) return ARTALK_OK;
     if (hipSetDevice(s->device) != hipSuccess) { (void)hipGetLastError(); s->err = "hipSetDevice failed"; return ARTALK_EHIP; }
     hipStream_t st = (hipStream_t)stream;
@@ -392,7 +413,10 @@ int artalk_splat_render(artalk_splat* s, int N, int T, int H, int W, const float
     const long HW = (long)H * W;
     const int nblk = (N + 255) / 256;
     SplatAttrs a{means_dev, colors_dev, opacities_dev, scales_dev, rotations_dev,
-                 (long)means_stride, (long)colors_stride, (long)opacities_stride, (long)scales_stride, (long)rotations_stride};
+                 (long)means_stride, (long)colors_stride, (long)opacities_stride, (long)scales_stride, (long)rotations_stride,
+                 nullptr, 0, 0, 0, 0, 0};
+    if (sets) { a.p_means = (long)means_set_stride; a.p_colors = (long)colors_set_stride; a.p_opac = (long)opacities_set_stride;
+                a.p_scales = (long)scales_set_stride; a.p_rots = (long)rotations_set_stride; }
 
     StageTimer timer;
     timer.start(st, s->timing);
@@ -403,12 +427,14 @@ int artalk_splat_render(artalk_splat* s, int N, int T, int H, int W, const float
     const unsigned long long* counts_host = nullptr;
     if (N > 0) {
         const size_t cam_bytes = (size_t)n_cams * sizeof(SplatCam), cnt_bytes = (size_t)T * sizeof(unsigned long long);
-        if (!s->host.grow(cam_bytes + cnt_bytes, 0, 1, st)) { s->err = "hipHostMalloc failed"; return ARTALK_EHIP; }
+        const size_t set_bytes = sets ? (size_t)T * sizeof(int) : 0;      // behind the cameras, which are 128 bytes each
+        if (!s->host.grow(cam_bytes + cnt_bytes + set_bytes, 0, 1, st)) { s->err = "hipHostMalloc failed"; return ARTALK_EHIP; }
         size_t scan_bytes = 0;
         (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const unsigned int*)nullptr, (unsigned int*)nullptr, N, st);
         if (!splat_grow(s, s->cams, n_cams, st) || !splat_grow(s, s->counts, T, st) || !splat_grow(s, s->xy, N, st) ||
             !splat_grow(s, s->conic, N, st) || !splat_grow(s, s->depth, N, st) || !splat_grow(s, s->rect, N, st) ||
-            !splat_grow(s, s->touched, N, st) || !splat_grow(s, s->offsets, N, st) || !splat_grow(s, s->scan_tmp, scan_bytes ? scan_bytes : 16, st))
+            !splat_grow(s, s->touched, N, st) || !splat_grow(s, s->offsets, N, st) || !splat_grow(s, s->scan_tmp, scan_bytes ? scan_bytes : 16, st) ||
+            (sets && !splat_grow(s, s->sets, T, st)))
             return ARTALK_EHIP;
         // the pinned block is free here: every earlier call waited on its stream after its upload, and its download ended that wait
         SplatCam* hc = (SplatCam*)(s->host.get() + cnt_bytes);
@@ -416,16 +442,20 @@ int artalk_splat_render(artalk_splat* s, int N, int T, int H, int W, const float
             std::memcpy(hc[c].V, view_host + (size_t)c * 16, sizeof(float) * 16);
             std::memcpy(hc[c].P, proj_host + (size_t)c * 16, sizeof(float) * 16);
         }
+        if (sets) std::memcpy(s->host.get() + cnt_bytes + cam_bytes, sets, set_bytes);
         if (hipMemcpyAsync(s->cams.get(), hc, cam_bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+            (sets && hipMemcpyAsync(s->sets.get(), s->host.get() + cnt_bytes + cam_bytes, set_bytes, hipMemcpyHostToDevice, st) != hipSuccess) ||
             hipMemsetAsync(s->counts.get(), 0, cnt_bytes, st) != hipSuccess) {
             (void)hipGetLastError();
             s->err = "camera upload failed";
             return ARTALK_EHIP;
         }
         timer.mark(-1);
+        SplatAttrs ac = a;
+        ac.sets = sets ? s->sets.get() : nullptr;
         for (int t0 = 0; t0 < T; t0 += 32768) {      // (grid.y is a 16-bit quantity)
             const int n = T - t0 < 32768 ? T - t0 : 32768;
-            ARTALK_LAUNCH(splat_preprocess_kernel<true>, dim3(nblk, n), dim3(256), 0, st, a, v, (const SplatCam*)s->cams.get(), n_cams == 1 ? 0 : 1,
+            ARTALK_LAUNCH(splat_preprocess_kernel<true>, dim3(nblk, n), dim3(256), 0, st, ac, v, (const SplatCam*)s->cams.get(), n_cams == 1 ? 0 : 1,
                           t0, radii_dev, s->counts.get(), (float2*)nullptr, (float4*)nullptr, (float*)nullptr, (uint4*)nullptr,
                           (unsigned int*)nullptr);
         }
@@ -460,8 +490,11 @@ int artalk_splat_render(artalk_splat* s, int N, int T, int H, int W, const float
     for (int t = 0; t < T && ok; ++t) {
         const unsigned int P = counts_host ? (unsigned int)counts_host[t] : 0u;
         timer.mark(-1);
+        const long set = sets ? (long)sets[t] : 0;
         if (N > 0) {
-            ARTALK_LAUNCH(splat_preprocess_kernel<false>, dim3(nblk), dim3(256), 0, st, a, v, (const SplatCam*)s->cams.get(), n_cams == 1 ? 0 : 1, t,
+            SplatAttrs at = a;      // the frame's set: bases moved on the host
+            at.means += set * a.p_means; at.opac += set * a.p_opac; at.scales += set * a.p_scales; at.rots += set * a.p_rots;
+            ARTALK_LAUNCH(splat_preprocess_kernel<false>, dim3(nblk), dim3(256), 0, st, at, v, (const SplatCam*)s->cams.get(), n_cams == 1 ? 0 : 1, t,
                           (int*)nullptr, (unsigned long long*)nullptr, s->xy.get(), s->conic.get(), s->depth.get(), s->rect.get(), s->touched.get());
             timer.mark(kStagePreprocess);
         }
@@ -479,7 +512,7 @@ int artalk_splat_render(artalk_splat* s, int N, int T, int H, int W, const float
             ARTALK_LAUNCH(splat_ranges_kernel, dim3((P + 255) / 256), dim3(256), 0, st, P, (const unsigned long long*)s->keys_out.get(), s->ranges.get(), tiles);
             timer.mark(kStageRanges);
         }
-        const float* col_t = colors_dev ? colors_dev + (long)t * colors_stride : nullptr;
+        const float* col_t = colors_dev ? colors_dev + set * a.p_colors + (long)t * colors_stride : nullptr;
         const int vec = (((unsigned long long)col_t) & 15) == 0 ? 1 : 0;
         ARTALK_LAUNCH(splat_blend_kernel, dim3(v.gx, v.gy), dim3(256), 0, st, v, (const uint2*)s->ranges.get(), (const unsigned int*)s->vals_out.get(),
                       (const float2*)s->xy.get(), (const float4*)s->conic.get(), col_t, vec, bg_dev_or_null, out_dev + (long)t * kSplatCh * HW);
@@ -488,6 +521,16 @@ int artalk_splat_render(artalk_splat* s, int N, int T, int H, int W, const float
     timer.finish(s->stage_ms, kSplatStages);
     if (!ok || hipGetLastError() != hipSuccess) { s->err = "a launch failed"; return ARTALK_EHIP; }
     return ARTALK_OK;
+}
+
+int artalk_splat_render(artalk_splat* s, int N, int T, int H, int W, const float* means_dev, int64_t means_stride, const float* colors_dev,
+                        int64_t colors_stride, const float* opacities_dev, int64_t opacities_stride, const float* scales_dev,
+                        int64_t scales_stride, const float* rotations_dev, int64_t rotations_stride, const float* view_host,
+                        const float* proj_host, int n_cams, float tanfovx, float tanfovy, float scale_modifier, const float* bg_dev_or_null,
+                        float* out_dev, int32_t* radii_dev, void* stream) {
+    return artalk_splat_render_sets(s, N, T, H, W, means_dev, means_stride, colors_dev, colors_stride, opacities_dev, opacities_stride, scales_dev,
+                                    scales_stride, rotations_dev, rotations_stride, view_host, proj_host, n_cams, tanfovx, tanfovy,
+                                    scale_modifier, bg_dev_or_null, out_dev, radii_dev, nullptr, 0, 0, 0, 0, 0, 0, stream);
 }
 
 }  // extern "C"

@@ -136,12 +136,54 @@ class ARTAvatarInferEngine:
         return pred_motions
 
     # ------------------------------------------------------------------ live streams (independent sessions)
-    def open_stream(self, style_motion=None):
+    def open_stream(self, style_motion=None, shape_id=None):
         """One live stream (``BitwiseARModel.open_session``) with the engine's style clip unless ``style_motion`` ((50, 106)) is given.
-        Streams join and leave independently: ``stream_step`` takes any subset of them, ``stream.close()`` frees one."""
+        Streams join and leave independently: ``stream_step`` takes any subset of them, ``stream.close()`` frees one.
+        With a GAGAvatar head plugged in and a ``shape_id`` (an avatar id) the stream also gets a stream of the head
+        (``GAGAvatar.open_stream``), kept under the session's id for ``stream_render``; ``close_stream`` closes both halves."""
         if style_motion is None and self.style_motion is not None:
             style_motion = self.style_motion[0]
-        return self.ARTalk.open_session(style_motion)
+        head = getattr(self, "GAGAvatar", None)
+        head_stream = head.open_stream(shape_id) if head is not None and shape_id is not None else None      # (KeyError before a session exists)
+        st = self.ARTalk.open_session(style_motion)
+        if head_stream is not None:
+            self._head_streams()[st.id] = head_stream
+        return st
+
+    def _head_streams(self):
+        if not hasattr(self, "_gaga_streams"):      # (engines assembled without __init__)
+            self._gaga_streams = {}
+        return self._gaga_streams
+
+    def close_stream(self, st):
+        """Closes a stream of ``open_stream``: its session and, if it has one, its stream of the head."""
+        head_stream = self._head_streams().pop(st.id, None)
+        if head_stream is not None:
+            head_stream.close()
+        st.close()
+
+    def stream_render(self, streams, frames, spans, output=None, host=False, order="time"):
+        """Photoreal frames of what ``stream_step(smooth=True)`` or ``stream_flush`` returned for ``streams``: ``frames`` (n, R, 106) and
+        ``spans[i] = (first, count)`` -> ``(images, index)`` from one ``GAGAvatar.render_streams`` call.  ``images`` holds
+        ``sum(count)`` frames - (.., 3, S, S) in [0, 1], or with ``output="rgb24"`` / ``"yuv420p"`` the 8-bit frames of
+        ``artalk_amd.frames`` (``host=True``: in pinned memory on the CPU) - in ``order`` ("time": frame k of every stream before frame
+        k + 1 of any; "stream": stream by stream); ``index`` (CPU, int64) names every frame: (position in ``streams``, absolute frame
+        number ``first + k``).  Every stream keeps its own forehead EMA across steps.  A stream opened without ``shape_id`` raises
+        ``ValueError``."""
+        head, flame = getattr(self, "GAGAvatar", None), getattr(self, "GAGAvatar_flame", None)
+        if head is None or flame is None:
+            raise RuntimeError("stream_render needs the GAGAvatar head and its scale-5 FLAME model (engine.GAGAvatar, engine.GAGAvatar_flame)")
+        books = self._head_streams()
+        for st in streams:
+            if st.id not in books:
+                raise ValueError(f"session {st.id} was opened without shape_id (or closed): it has no stream of the head")
+        if len(spans) != len(streams):
+            raise ValueError(f"spans holds {len(spans)} entries, streams {len(streams)}")
+        images, index = head.render_streams([books[st.id] for st in streams], frames, flame, counts=[int(c) for _, c in spans], order=order,
+                                            out="float" if output is None else output, host=host)
+        if index.shape[0]:
+            index[:, 1] += torch.tensor([int(f) for f, _ in spans], dtype=torch.int64)[index[:, 0]]
+        return images, index
 
     def stream_step(self, streams, chunks, n_valid=None, smooth=False):
         """Next 4 seconds of the listed streams: ``chunks`` (n, 64000) -> (n, 100, 106) (with ``n_valid`` also the valid frame counts,

@@ -74,6 +74,40 @@ def _check_avatar(name, av, n_dynamic):
     return out
 
 
+class GagaStream:
+    """One live stream of ``GAGAvatar.open_stream``: ``id`` (never reused), ``avatar_id``, ``closed``, and ``set_avatar(id)`` (the forehead
+    EMA is kept, as the reference's ``set_avatar_id`` keeps it), ``reset()`` (the next frame is taken as it is) and ``close()``.  The
+    stream's EMA state lives in the head's library object, in a row of its own; it is opened there by the first render that lists it."""
+
+    def __init__(self, head, sid, avatar_id):
+        self._head, self.id, self.avatar_id, self.closed = head, int(sid), avatar_id, False
+        self._lib = None          # the library's stream id
+
+    def set_avatar(self, avatar_id):
+        self._check_open()
+        self._head._known_avatar(avatar_id)
+        self.avatar_id = avatar_id
+
+    def reset(self):
+        self._check_open()
+        if self._lib is not None:
+            if capi.lib().artalk_gaga_stream_reset(self._head._h, self._lib) != capi.OK:
+                raise RuntimeError("artalk_gaga_stream_reset failed: " + self._head._err())
+
+    def close(self):
+        if self.closed:
+            return
+        if self._lib is not None and self._head._h is not None:
+            if capi.lib().artalk_gaga_stream_close(self._head._h, self._lib) != capi.OK:
+                raise RuntimeError("artalk_gaga_stream_close failed: " + self._head._err())
+        self._lib, self.closed = None, True
+        self._head._streams.pop(self.id, None)
+
+    def _check_open(self):
+        if self.closed:
+            raise ValueError(f"stream {self.id} is closed")
+
+
 class GAGAvatar:
     """``GAGAvatar(avatars, upsampler, water_mark=None, image_size=512, n_dynamic=5023, forehead_indices=None, device="cuda")``.
 
@@ -123,6 +157,9 @@ class GAGAvatar:
         self._uploaded = None       # id of the avatar the library object holds
         self._index, self._borrowed = None, None
         self._slab = 0
+        # live streams: open streams by id, avatar id -> pool slot, the slots whose upload is current, the pool's size on the device
+        self._resident, self._streams, self._next_stream = 4, {}, 0
+        self._slot_of, self._fresh, self._pool = {}, set(), None
 
     # ---- packs ----
     @classmethod
@@ -198,6 +235,7 @@ class GAGAvatar:
         self.all_gagavatar_id.pop(name, None)
         if self._uploaded == name:
             self._uploaded = None
+        self._fresh.discard(self._slot_of.get(name))
 
     def _generate(self, name):
         e = self._tracked[name]
@@ -237,6 +275,11 @@ class GAGAvatar:
         if self._h is not None:
             capi.lib().artalk_gaga_destroy(self._h)
             self._h = None
+        # the pool and the streams' states went with the object: slots are uploaded and streams opened again by the next render
+        self._pool = None
+        self._fresh.clear()
+        for st in self._streams.values():
+            st._lib = None
 
     def _err(self):
         return capi.lib().artalk_gaga_last_error(self._h).decode()
@@ -254,6 +297,7 @@ class GAGAvatar:
         self.all_gagavatar_id[name] = _check_avatar(name, avatar, self.n_dynamic)
         if self._uploaded == name:
             self._uploaded = None
+        self._fresh.discard(self._slot_of.get(name))      # a resident copy is stale: the next render that needs it uploads it again
 
     def reset_motion_state(self):
         """Unset the forehead EMA: the next frame is taken as it is, like the reference's very first frame."""
@@ -306,7 +350,8 @@ class GAGAvatar:
             raise RuntimeError("GAGAvatar runs on the GPU: motion_codes must be a CUDA tensor (there is no CPU fallback)")
         return motion_codes
 
-    def _ensure(self, flame_model):
+    def _ensure(self, flame_model, avatar=True):
+        """The library object for this FLAME model and, with ``avatar``, the tracked identity uploaded as the classic path's avatar."""
         L = capi.lib()
         if self._h is not None:
             # the library object borrows three handles: another FLAME model, reloaded upsampler weights or released splat buffers
@@ -344,6 +389,8 @@ class GAGAvatar:
                         raise ValueError("artalk_gaga_set_watermark refused: " + self._err())
                 if L.artalk_gaga_set_slab(h, self._slab) < 0:
                     raise ValueError("artalk_gaga_set_slab refused: " + self._err())
+        if not avatar:
+            return
         if self._tracked_name is None:
             self.set_avatar_id(self._default_id())
         if self._uploaded != self._tracked_name:
@@ -357,6 +404,29 @@ class GAGAvatar:
             if rc != capi.OK:
                 raise ValueError("artalk_gaga_set_avatar refused: " + self._err())
             self._uploaded = self._tracked_name
+
+    def _noise_args(self, T, noise, randomize_noise, device, slab=None):
+        """The noise arguments of a render call over T frames in slabs of ``slab`` (default: ``render_clip``'s) -> (pointers, batch
+        strides, the tensors to keep alive)."""
+        nl = self.upsampler.num_layers
+        if noise is None and randomize_noise:
+            slab = self.slab_in_force() if slab is None else slab
+            parts = [[torch.empty(min(slab, T - f0), 1, noise_resolution(i), noise_resolution(i), device=device).normal_()
+                      for i in range(nl)] for f0 in range(0, T, slab)]
+            noise = [torch.cat([p[i] for p in parts]) for i in range(nl)]
+        if noise is None:
+            return None, None, None
+        if len(noise) != nl:
+            raise ValueError(f"noise must hold {nl} tensors")
+        keep = []
+        for i, n in enumerate(noise):
+            r = noise_resolution(i)
+            if not n.is_cuda or tuple(n.shape[1:]) != (1, r, r) or n.shape[0] not in (1, T):
+                raise ValueError(f"noise[{i}] must be a CUDA tensor of shape (1 or {T}, 1, {r}, {r})")
+            keep.append(n.detach().float().contiguous())
+        ptrs = (C.c_void_p * nl)(*[t.data_ptr() for t in keep])
+        strides = (C.c_int64 * nl)(*[0 if t.shape[0] == 1 else t.shape[2] * t.shape[3] for t in keep])
+        return ptrs, strides, keep
 
     def slab_in_force(self):
         return None if self._h is None else int(capi.lib().artalk_gaga_set_slab(self._h, self._slab))
@@ -385,7 +455,7 @@ class GAGAvatar:
             m = m.float().contiguous()
         T = int(m.shape[0])
         stride = int(m.stride(0)) if T > 1 else int(m.shape[1])
-        S, nl = self.image_size, self.upsampler.num_layers
+        S = self.image_size
         L = capi.lib()
         with torch.cuda.device(m.device):
             if out == "float":
@@ -396,23 +466,7 @@ class GAGAvatar:
             self._ensure(flame_model)
             if T == 0:
                 return res_host if host else res
-            if noise is None and randomize_noise:
-                slab = self.slab_in_force()
-                parts = [[torch.empty(min(slab, T - f0), 1, noise_resolution(i), noise_resolution(i), device=m.device).normal_()
-                          for i in range(nl)] for f0 in range(0, T, slab)]
-                noise = [torch.cat([p[i] for p in parts]) for i in range(nl)]
-            ptrs = strides = None
-            if noise is not None:
-                if len(noise) != nl:
-                    raise ValueError(f"noise must hold {nl} tensors")
-                keep = []
-                for i, n in enumerate(noise):
-                    r = noise_resolution(i)
-                    if not n.is_cuda or tuple(n.shape[1:]) != (1, r, r) or n.shape[0] not in (1, T):
-                        raise ValueError(f"noise[{i}] must be a CUDA tensor of shape (1 or {T}, 1, {r}, {r})")
-                    keep.append(n.detach().float().contiguous())
-                ptrs = (C.c_void_p * nl)(*[t.data_ptr() for t in keep])
-                strides = (C.c_int64 * nl)(*[0 if t.shape[0] == 1 else t.shape[2] * t.shape[3] for t in keep])
+            ptrs, strides, keep = self._noise_args(T, noise, randomize_noise, m.device)
             if out == "float":
                 rc = L.artalk_gaga_render(self._h, capi.ptr(m), stride, T, ptrs, strides, int(self.upsampler.activation), capi.ptr(res),
                                           capi.current_stream_ptr())
@@ -427,3 +481,190 @@ class GAGAvatar:
         if rc != capi.OK:
             raise RuntimeError(name + " failed: " + self._err())
         return res_host if host else res
+
+    # ---- live streams: many independent streams through one head ("Live streams through the head") ----
+    def set_resident(self, slots=4):
+        """Avatars that stay on the device at once (default 4); every open stream's avatar needs a slot.  Set before the first stream
+        is opened."""
+        slots = int(slots)
+        if slots < 1 or slots > 4096:
+            raise ValueError("slots must be in 1..4096")
+        if self._streams:
+            raise RuntimeError(f"{len(self._streams)} streams are open: set_resident comes before the first open_stream")
+        if slots != self._resident:
+            self._resident = slots
+            self._slot_of.clear()
+            self._fresh.clear()
+            self._pool = None      # the next render reserves the pool anew
+        return self
+
+    def _known_avatar(self, avatar_id):
+        if avatar_id not in self.all_gagavatar_id and self._tracked and avatar_id in self._tracked:
+            self._generate(avatar_id)
+        self.all_gagavatar_id[avatar_id]      # KeyError for an unknown id, as set_avatar_id
+
+    def open_stream(self, avatar_id):
+        """A ``GagaStream`` on ``avatar_id``: a forehead EMA state of its own, unset.  A tracked identity is turned into Gaussians here,
+        as ``set_avatar_id`` does; apart from that the device is first touched by ``render_streams``."""
+        self._known_avatar(avatar_id)
+        st = GagaStream(self, self._next_stream, avatar_id)
+        self._next_stream += 1
+        self._streams[st.id] = st
+        return st
+
+    def stream_slab_in_force(self):
+        """Frames per slab of ``render_streams`` (``artalk_gaga_streams_slab``: sized for the pool's avatars, where ``slab_in_force`` is
+        sized for the classic path's); None before the library object exists."""
+        return None if self._h is None else int(capi.lib().artalk_gaga_streams_slab(self._h))
+
+    def _plan_slots(self, streams):
+        """Books only: gives every avatar the listed streams name a slot - a free one, else one whose avatar no open stream names - and
+        returns [(avatar id, slot)] for the slots the next render has to upload (new, or stale after ``add_avatar``)."""
+        named = []
+        for st in self._streams.values():
+            if st.avatar_id not in named:
+                named.append(st.avatar_id)
+        if len(named) > self._resident:
+            raise RuntimeError(f"the open streams name {len(named)} distinct avatars, the head keeps {self._resident} resident "
+                               f"(set_resident); close a stream or build the head with more slots")
+        for st in streams:
+            if st.avatar_id in self._slot_of:
+                continue
+            taken = set(self._slot_of.values())
+            free = [k for k in range(self._resident) if k not in taken]
+            if not free:      # room is needed: an avatar no open stream names leaves (there is one: named fits)
+                idle = next(a for a in self._slot_of if a not in named)
+                free = [self._slot_of.pop(idle)]
+            self._slot_of[st.avatar_id] = free[0]
+            self._fresh.discard(free[0])
+        todo = []
+        for st in streams:
+            slot = self._slot_of[st.avatar_id]
+            if slot not in self._fresh and (st.avatar_id, slot) not in todo:
+                todo.append((st.avatar_id, slot))
+        return todo
+
+    @staticmethod
+    def plan_frames(counts, order="time", firsts=None, rows_per_stream=None):
+        """The frame lists of a ``render_streams`` call, a pure function: ``counts[i]`` frames of stream i starting at its row
+        ``firsts[i]`` (default 0) -> ``(frame_row, frame_stream_index, frame_k)``, three lists of ``sum(counts)`` ints.  ``order="time"``:
+        frame k of every listed stream that still has one, then k + 1 - what a live sender wants; ``"stream"``: each stream's frames
+        together.  ``frame_row`` is ``firsts[i] + k``, the row within stream i's own block, plus ``i * rows_per_stream`` when the blocks
+        lie one after the other in one array."""
+        counts = [int(c) for c in counts]
+        firsts = [0] * len(counts) if firsts is None else [int(f) for f in firsts]
+        if len(firsts) != len(counts):
+            raise ValueError(f"firsts holds {len(firsts)} entries, counts {len(counts)}")
+        if any(c < 0 for c in counts) or any(f < 0 for f in firsts):
+            raise ValueError("counts and firsts must not be negative")
+        if order == "time":
+            pairs = [(i, k) for k in range(max(counts, default=0)) for i, c in enumerate(counts) if k < c]
+        elif order == "stream":
+            pairs = [(i, k) for i, c in enumerate(counts) for k in range(c)]
+        else:
+            raise ValueError(f'order must be "time" or "stream", got {order!r}')
+        per = 0 if rows_per_stream is None else int(rows_per_stream)
+        return [i * per + firsts[i] + k for i, k in pairs], [i for i, _ in pairs], [k for _, k in pairs]
+
+    @torch.no_grad()
+    def render_streams(self, streams, motion_codes, flame_model, counts=None, firsts=None, order="time", randomize_noise=True, noise=None,
+                       out="float", host=False, host_buffer=None):
+        """Frames of many streams from one library call (``artalk_gaga_render_streams``).  ``streams``: n open ``GagaStream``s, each at
+        most once; ``motion_codes`` (n, R, 106) on the device - what ``stream_step(smooth=True)`` returns - with ``counts[i]`` valid rows
+        from row ``firsts[i]`` (defaults: R and 0).  Returns ``(frames, index)``: ``frames`` (sum(counts), 3, S, S) in [0, 1], or with
+        ``out="rgb24"`` / ``"yuv420p"`` the uint8 shapes of ``artalk_amd.frames`` (``host=True``: pinned, on the CPU), in the order
+        ``plan_frames(counts, order)`` gives; ``index`` a CPU int64 tensor (sum(counts), 2) of (position in ``streams``, k).  Every
+        frame equals the frame a head of its own would render for that stream: each stream's forehead EMA walks its own frames only.
+        Noise as in ``render_clip`` (a per-frame ``noise`` follows the order of ``frames``).  ``host_buffer``: with ``host=True``, a
+        pinned uint8 tensor of the result's shape to fill and return instead of a new one - it is filled slab by slab, so another
+        thread of a live sender can take a slab's frames out of it while the later slabs still render."""
+        if out != "float":
+            fmt = _frames.format_code(out)
+        elif host:
+            raise ValueError('host=True needs out="rgb24" or out="yuv420p"')
+        else:
+            fmt = 0
+        streams = list(streams)
+        for st in streams:
+            if not isinstance(st, GagaStream) or st._head is not self:
+                raise ValueError("streams must hold GagaStreams of this head (GAGAvatar.open_stream)")
+            if st.closed:
+                raise ValueError(f"stream {st.id} is closed")
+        if len({st.id for st in streams}) != len(streams):
+            raise ValueError("a stream is listed twice: one call walks each stream's frames once")
+        m = motion_codes
+        if not isinstance(m, torch.Tensor) or m.dim() != 3 or m.shape[2] < MOTION_DIM or m.shape[0] != len(streams):
+            raise ValueError(f"motion_codes must be a ({len(streams)}, R, {MOTION_DIM}) tensor: one block of rows per listed stream")
+        if not m.is_cuda:
+            raise RuntimeError("GAGAvatar runs on the GPU: motion_codes must be a CUDA tensor (there is no CPU fallback)")
+        if (m.device.index or 0) != (self.device.index if self.device.index is not None else torch.cuda.current_device()):
+            raise RuntimeError(f"motion_codes lives on {m.device}, the head on {self.device}")
+        n, R = int(m.shape[0]), int(m.shape[1])
+        counts = [R] * n if counts is None else [int(c) for c in counts]
+        firsts = [0] * n if firsts is None else [int(f) for f in firsts]
+        if len(counts) != n or len(firsts) != n:
+            raise ValueError(f"counts and firsts must hold {n} entries each")
+        rows, which, ks = self.plan_frames(counts, order, firsts, R)
+        if any(f + c > R for f, c in zip(firsts, counts)):
+            raise ValueError(f"a stream's rows firsts[i] .. firsts[i] + counts[i] must lie within its {R} rows")
+        m = m.detach()
+        if m.dtype != torch.float32 or not m.is_contiguous():
+            m = m.float().contiguous()
+        T, S, W = len(rows), self.image_size, int(m.shape[2])
+        if host_buffer is not None:
+            want = tuple(_frames.frame_shape(out, T, S, S)) if host else None
+            if (want is None or not isinstance(host_buffer, torch.Tensor) or host_buffer.dtype != torch.uint8 or tuple(host_buffer.shape) != want
+                    or not host_buffer.is_contiguous() or not host_buffer.is_pinned()):
+                raise ValueError(f"host_buffer goes with host=True and must be a contiguous pinned uint8 tensor of shape {want}")
+        index = torch.tensor([which, ks], dtype=torch.int64).t().contiguous().reshape(T, 2)
+        L = capi.lib()
+        with torch.cuda.device(m.device):
+            if out == "float":
+                res = torch.empty(T, 3, S, S, dtype=torch.float32, device=m.device)
+            else:
+                res = torch.empty(_frames.frame_shape(out, T, S, S), dtype=torch.uint8, device=m.device)
+            res_host = torch.empty(res.shape, dtype=torch.uint8, pin_memory=True) if host and host_buffer is None else host_buffer
+            todo = self._plan_slots(streams)
+            self._ensure(flame_model, avatar=False)
+            h = self._h
+            if self._pool is None and streams:
+                N = int(self.all_gagavatar_id[streams[0].avatar_id]["xyz"].shape[0])
+                rc = L.artalk_gaga_pool_reserve(h, self._resident, N)
+                if rc != capi.OK:
+                    raise (ValueError if rc == capi.EINVAL else RuntimeError)("artalk_gaga_pool_reserve failed: " + self._err())
+                self._pool = (self._resident, N)
+                self._fresh.clear()
+                todo = self._plan_slots(streams)
+            for name, slot in todo:
+                av = self.all_gagavatar_id[name]
+                if av["shapecode"].numel() != flame_model.n_betas - 100:
+                    raise ValueError(f"avatar {name!r}: shapecode holds {av['shapecode'].numel()} values, the FLAME model "
+                                     f"takes {flame_model.n_betas - 100}")
+                rc = L.artalk_gaga_pool_set(h, slot, int(av["xyz"].shape[0]), capi.ptr(av["xyz"]), capi.ptr(av["colors"]), capi.ptr(av["opacities"]),
+                                            capi.ptr(av["scales"]), capi.ptr(av["rotations"]), capi.ptr(av["shapecode"]),
+                                            capi.ptr(av["transform_matrix"]))
+                if rc != capi.OK:
+                    raise ValueError(f"artalk_gaga_pool_set refused avatar {name!r}: " + self._err())
+                self._fresh.add(slot)
+            for st in streams:
+                if st._lib is None:
+                    sid = C.c_int32(-1)
+                    if L.artalk_gaga_stream_open(h, C.byref(sid)) != capi.OK:
+                        raise RuntimeError("artalk_gaga_stream_open failed: " + self._err())
+                    st._lib = int(sid.value)
+            if T == 0:
+                return (res_host if host else res), index
+            ptrs, strides, keep = self._noise_args(T, noise, randomize_noise, m.device, self.stream_slab_in_force())
+            frame_row = (C.c_int64 * T)(*rows)
+            frame_stream = (C.c_int32 * T)(*[streams[i]._lib for i in which])
+            frame_slot = (C.c_int32 * T)(*[self._slot_of[streams[i].avatar_id] for i in which])
+            rc = L.artalk_gaga_render_streams(h, capi.ptr(m), W, T, frame_row, frame_stream, frame_slot, ptrs, strides,
+                                              int(self.upsampler.activation), fmt, capi.ptr(res) if fmt == 0 else None,
+                                              None if fmt == 0 else capi.ptr(res), capi.ptr(res_host), capi.current_stream_ptr())
+            if host:
+                torch.cuda.current_stream().synchronize()      # (also after a failure: a copy may be in flight)
+        if rc == capi.EINVAL:
+            raise ValueError("artalk_gaga_render_streams refused: " + self._err())
+        if rc != capi.OK:
+            raise RuntimeError("artalk_gaga_render_streams failed: " + self._err())
+        return (res_host if host else res), index

@@ -245,7 +245,13 @@ const char* artalk_render_last_error(const artalk_mesh_renderer* r);
  * from two threads at once.
  * artalk_splat_set_timing / artalk_splat_get_timing (tools/splat_bench.py): with timing on, a call records HIP events around its stages and
  * waits for them at its end; get_timing copies up to n of the 6 per-stage sums in ms (count pass, preprocess, scan + emit, sort, ranges,
- * blend) of the last call, its pairs and frames (each nullable), and returns 6. */
+ * blend) of the last call, its pairs and frames (each nullable), and returns 6.
+ * artalk_splat_render_sets: artalk_splat_render for attributes that lie in pools of sets (resident avatars).  set_of_frame_host: T host
+ * int32, frame t's set in [0, n_sets), read before the call returns; each attribute comes with the number of ELEMENTS between two sets,
+ * and frame t's attribute starts at base + set[t] * set stride + t * frame stride (a frame stride of 0 as above; a set stride of 0: no
+ * pool).  A colour set stride need not be a multiple of 4 floats: the 16-byte test is made on every frame's colour pointer.  Same
+ * wait, same bits: frame t equals artalk_splat_render of one frame on that frame's attributes.  set_of_frame_host == NULL is
+ * artalk_splat_render.  ARTALK_EINVAL in addition: a negative set stride, a set outside [0, n_sets). */
 typedef struct artalk_splat artalk_splat;
 int artalk_splat_create(int device_id, artalk_splat** out);
 int artalk_splat_render(artalk_splat* s, int N, int T, int H, int W, const float* means_dev, int64_t means_stride, const float* colors_dev,
@@ -253,6 +259,13 @@ int artalk_splat_render(artalk_splat* s, int N, int T, int H, int W, const float
                         int64_t scales_stride, const float* rotations_dev, int64_t rotations_stride, const float* view_host,
                         const float* proj_host, int n_cams, float tanfovx, float tanfovy, float scale_modifier, const float* bg_dev_or_null,
                         float* out_dev, int32_t* radii_dev, void* stream);
+int artalk_splat_render_sets(artalk_splat* s, int N, int T, int H, int W, const float* means_dev, int64_t means_stride, const float* colors_dev,
+                             int64_t colors_stride, const float* opacities_dev, int64_t opacities_stride, const float* scales_dev,
+                             int64_t scales_stride, const float* rotations_dev, int64_t rotations_stride, const float* view_host,
+                             const float* proj_host, int n_cams, float tanfovx, float tanfovy, float scale_modifier,
+                             const float* bg_dev_or_null, float* out_dev, int32_t* radii_dev, const int32_t* set_of_frame_host, int n_sets,
+                             int64_t means_set_stride, int64_t colors_set_stride, int64_t opacities_set_stride, int64_t scales_set_stride,
+                             int64_t rotations_set_stride, void* stream);
 int artalk_splat_set_timing(artalk_splat* s, int enable);
 int artalk_splat_get_timing(const artalk_splat* s, double* stage_ms, int n, long long* pairs, int* frames);
 void artalk_splat_destroy(artalk_splat* s);
@@ -447,6 +460,64 @@ int artalk_op_gaga_finish_pack(const float* img_dev, int F, int S, const float* 
 int artalk_gaga_render_u8(artalk_gaga* g, const float* motion_dev, int64_t motion_stride, int T, const float* const* noise_ptrs_or_null,
                           const int64_t* noise_batch_strides, int activation, int format, uint8_t* out_dev, uint8_t* out_host_or_null,
                           void* stream);
+
+/* Live streams through the head ("Live streams through the head"): many independent streams rendered by one call,
+ * each frame naming its stream and its avatar.  Nothing here changes artalk_gaga_render / _render_u8, the avatar of
+ * artalk_gaga_set_avatar or the EMA state artalk_gaga_reset_state unsets: those stay the classic path's own.
+ * Resident avatars.  artalk_gaga_pool_reserve: one device slab per attribute for `slots` avatars of N Gaussians each (all resident avatars
+ * share N), every slot empty; the [R | t] transforms stay on the host.  Waits for the device and drops an earlier pool.  ARTALK_EINVAL:
+ * a NULL handle, slots outside 1..4096, N < V; ARTALK_ESTATE: a pool exists and a stream is open; ARTALK_EHIP: hipMalloc failed (no pool
+ * then).  artalk_gaga_pool_set: fills a slot; arguments and checks of artalk_gaga_set_avatar, and ARTALK_EINVAL for a slot outside the
+ * pool (also: no pool reserved) and for an N that is not the pool's.  artalk_gaga_pool_clear empties a slot (ARTALK_EINVAL: a NULL
+ * handle, a slot outside the pool).  Overwriting or clearing an occupied slot waits for the device first.
+ * Per-stream forehead state.  artalk_gaga_stream_open: *id = a new stream whose state is unset (its first frame is taken as it is); ids
+ * count up from 0 and are never reused.  artalk_gaga_stream_reset unsets a stream's state, artalk_gaga_stream_close gives its row of the
+ * state pool ([streams][K][3] and [streams] flags on the device, grown by doubling) back.  open and reset wait for the device.
+ * ARTALK_EINVAL: a NULL handle or id pointer, an id that was never handed out, a closed stream.  While a stream is open
+ * artalk_gaga_set_forehead refuses another K with ARTALK_ESTATE (the same K, other vertices: allowed, the streams' states are kept).
+ * artalk_gaga_render_streams: T frames; frame t is rendered from motion row frame_row[t] of motion_dev (row r starts r * motion_stride
+ * floats in), with the Gaussians, shapecode and transform of pool slot frame_slot[t] and the EMA state of stream frame_stream[t].  The
+ * three lists are HOST arrays of T entries, read before the call returns.  Frames of one stream may lie anywhere in the call; the EMA
+ * walks a stream's frames in the order they are listed, reads the state at the stream's first frame of the call and writes it at its
+ * last, and carries it across slabs and calls.  A stream may name different slots on different frames (the state is the stream's).
+ * format 0: fp32 frames into out_dev [T][3][S][S] (out_u8 and out_host_or_null unused: pass NULL); ARTALK_FRAMES_RGB24 / _YUV420P: 8-bit
+ * frames into out_u8 and, with out_host_or_null, to the host as artalk_gaga_render_u8 does it.  Noise, activation, slabs, scratch, the
+ * copy stream and the waits are artalk_gaga_render's: one wait for the rotation codes per call, the rasteriser's one per slab.
+ * artalk_gaga_streams_slab: the frames per slab this call runs with - artalk_gaga_set_slab's request, else the default for the pool's N
+ * (without a pool: what artalk_gaga_set_slab reports) - never more than the StyleUNet's slab in force; ARTALK_EINVAL for a NULL handle.
+ * T == 0 succeeds and does nothing.  ARTALK_EINVAL with a message before the device is touched: a NULL handle, motion or out, a NULL
+ * list, T < 0, a row below 0, a stream id that was never opened or is closed, a slot outside the pool or empty, motion_stride < 106, a bad
+ * noise argument, an unknown format, out_host_or_null with format 0, yuv420p with an odd S, a `stream` that is being captured (8-bit
+ * formats); ARTALK_ESTATE: the upsampler is not finalized.  Rows beyond the motion array are the caller's to avoid.
+ * artalk_op_gaga_flame_inputs_sets / _forehead_streams / _means_sets: one launch each on device arrays.  flame_inputs_sets: frame_row [T]
+ * int64, frame_slot [T], shapecode_pool [slots][NB - 100] -> betas [T][NB], pose [T][15].  forehead_streams: one workgroup per listed
+ * stream e < n_streams: its state and flag are row pool_row[e] of state_pool [rows][K][3] / flag_pool [rows] (no row listed twice), its
+ * frames frames[offsets[e] .. offsets[e + 1]) index verts [..][V][3] (no frame listed twice) and are walked in this order; a stream with
+ * no frames keeps state and flag.  means_sets: xyz_pool [slots][N][3], frame_slot [F] -> means [F][N][3].
+ * artalk_op_gaga_streams_check (host only): the checks of pool_reserve (V, pool_slots, pool_N) and render_streams on plain numbers and
+ * host arrays - stream_open [n_stream_ids] (1: open) and slot_filled [pool_slots] stand for the handle's books; format 0 skips the frame
+ * format's check - returns the first failing code and copies its message. */
+int artalk_gaga_pool_reserve(artalk_gaga* g, int slots, int N);
+int artalk_gaga_pool_set(artalk_gaga* g, int slot, int N, const float* xyz, const float* colors, const float* opacities, const float* scales,
+                         const float* rotations, const float* shapecode, const float* transform_3x4);
+int artalk_gaga_pool_clear(artalk_gaga* g, int slot);
+int artalk_gaga_stream_open(artalk_gaga* g, int* id);
+int artalk_gaga_stream_close(artalk_gaga* g, int id);
+int artalk_gaga_stream_reset(artalk_gaga* g, int id);
+int artalk_gaga_render_streams(artalk_gaga* g, const float* motion_dev, int64_t motion_stride, int T, const int64_t* frame_row_host,
+                               const int32_t* frame_stream_host, const int32_t* frame_slot_host, const float* const* noise_ptrs_or_null,
+                               const int64_t* noise_batch_strides, int activation, int format, float* out_dev, uint8_t* out_u8,
+                               uint8_t* out_host_or_null, void* stream);
+int artalk_gaga_streams_slab(const artalk_gaga* g);
+int artalk_op_gaga_flame_inputs_sets(const float* motion_dev, int64_t motion_stride, const int64_t* frame_row_dev, const int32_t* frame_slot_dev,
+                                     const float* shapecode_pool_dev, int NB, int T, float* betas_dev, float* pose_dev, void* stream);
+int artalk_op_gaga_forehead_streams(float* verts_dev, const int32_t* idx_dev, int K, int V, int n_streams, const int32_t* pool_row_dev,
+                                    const int32_t* offsets_dev, const int32_t* frames_dev, float* state_pool_dev, int* flag_pool_dev, void* stream);
+int artalk_op_gaga_means_sets(const float* verts_dev, const float* xyz_pool_dev, const int32_t* frame_slot_dev, float* means_dev, int F, int V,
+                              int N, void* stream);
+int artalk_op_gaga_streams_check(int V, int pool_slots, int pool_N, int T, int64_t motion_stride, const int64_t* frame_row_host,
+                                 const int32_t* frame_stream_host, const int32_t* frame_slot_host, const uint8_t* stream_open_host, int n_stream_ids,
+                                 const uint8_t* slot_filled_host, int unet_finalized, int format, int S, char* msg, int msg_cap);
 
 /* The Gaussian generators of the GAGAvatar head's identity side, forward only, exact fp32, one avatar per call: a stand-in for
  * LinearGSGenerator, the two ConvGSGenerators, build_points_planes, the direction encoding and the assembly of _gs_params
