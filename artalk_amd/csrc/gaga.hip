@@ -6,14 +6,14 @@
 //   gaga_forehead_kernel       EMA over frames of K listed vertices; its state outlives the call               (models.py:120-125)
 //   gaga_means_kernel          per-frame Gaussian centres: V skinned vertices, then the avatar's static points (models.py:90)
 //   gaga_finish_kernel         clamp(0, 1) and the watermark blend, in place                                   (models.py:95, 131-138)
-// Live streams ("Live streams through the head"): avatars stay resident in a pool of slots, every stream has an EMA
-// state of its own, and every frame of artalk_gaga_render_streams names its motion row, its stream and its slot:
-//   gaga_flame_inputs_sets_kernel     as gaga_flame_inputs_kernel, the motion row from frame_row, the shapecode from the frame's slot
-//   gaga_forehead_streams_kernel      one workgroup per stream present in the slab, over that stream's frames in listed order
-//   gaga_means_sets_kernel            as gaga_means_kernel, rows V .. N-1 from the frame's slot
-//   gaga_gather_codes_kernel          the head-rotation codes of the listed rows, packed for the one copy to the host
+//   gaga_gather_codes_kernel   the head-rotation codes of the listed rows, packed for the one copy to the host (stream calls only)
 //   (frames.hip)               the same clamp and blend fused with the packing into 8-bit frames, for artalk_gaga_render_u8
 //   artalk_gaga_cameras        host only: head-rotation codes -> the view / projection matrices the rasteriser reads (models.py:127)
+// One path serves the classic call and live streams ("Live streams through the head"), where avatars stay resident
+// in a pool of slots, every stream has an EMA state of its own and every frame names its motion row, its stream and its slot.  The first
+// three kernels take those names as lists, and a null list means identity, as SplatAttrs::sets does in splat.hip: frame t reads motion
+// row t and slot 0, and the forehead launch is one entry over frames 0 .. n-1 on row 0 of the state it is given.  That is the classic
+// call: its avatar is a set of one slot, its state a pool of one row, and it builds and uploads no list.
 //
 // All fp32 and element-wise (no reductions, no atomics): bit-identical from run to run.  The EMA and the blend use torch's rounding
 // order - every product and sum rounded on its own, never contracted to an FMA - so they equal the torch statements bit for bit.
@@ -43,52 +43,89 @@ static const int32_t kForeheadIdx[kForeheadDefault] = {
     3158, 3157, 336,  335,  3153, 3705, 2177, 2176, 3540, 671,  672,  3863, 2134, 16,   17,   2138, 2139,
     2567, 2566, 337,  338,  3154, 3712, 2178, 2179, 3495, 674,  673,  3868, 2135, 27,   18,   1429, 1430};
 
-// one thread per (frame, column) of betas ++ full_pose: betas = shapecode ++ m[0:100]; full_pose = (0 x 6 | m[103:106] | 0 x 6)
-__global__ void gaga_flame_inputs_kernel(const float* __restrict__ motion, long stride, const float* __restrict__ shapecode, int NS,
+// one thread per (frame, column) of betas ++ full_pose: betas = shapecode ++ m[0:100]; full_pose = (0 x 6 | m[103:106] | 0 x 6).
+// Frame t reads motion row rows[t] (null: t) and the shapecode of slot slots[t] (null: 0) of shape [slots][NS]
+__global__ void gaga_flame_inputs_kernel(const float* __restrict__ motion, long stride, const int64_t* __restrict__ rows,
+                                         const int32_t* __restrict__ slots, const float* __restrict__ shape, int NS,
                                          float* __restrict__ betas, float* __restrict__ pose, int T) {
     const int NB = NS + 100, W = NB + 15;
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (long)T * W) return;
     const int t = (int)(idx / W), c = (int)(idx - (long)t * W);
-    const float* m = motion + (long)t * stride;
+    const float* m = motion + (rows ? (long)rows[t] : (long)t) * stride;
     if (c < NB) {
-        betas[(long)t * NB + c] = c < NS ? shapecode[c] : m[c - NS];
+        betas[(long)t * NB + c] = c < NS ? shape[(slots ? (long)slots[t] : 0L) * NS + c] : m[c - NS];
     } else {
         const int p = c - NB;
         pose[(long)t * 15 + p] = (p >= 6 && p < 9) ? m[103 + (p - 6)] : 0.f;
     }
 }
 
-// One workgroup; thread i owns coordinate i % 3 of listed vertex i / 3 and walks the T frames of the call in order:
-// unset state: state = cur (that frame is left as it is); otherwise state = 0.98 state + 0.02 cur, written back into the vertex.
-// state [K][3], *flag != 0: the state is set.  Both are read at the start and written at the end.
-__global__ __launch_bounds__(256) void gaga_forehead_kernel(float* __restrict__ verts /*[T][V][3]*/, const int32_t* __restrict__ index,
-                                                            int K, int T, int V, float* __restrict__ state, int* __restrict__ flag) {
+// Workgroup e serves one entry: its state and flag are row pool_row[e] of state_pool [rows][K][3] / flag_pool [rows] (flag != 0: the
+// state is set), its frames are frames[off[e] .. off[e + 1]) - indices into verts [..][V][3], each at most once, walked in this order.
+// With the three lists null the launch has one entry: row 0, frames 0 .. n-1.  Thread i owns coordinate i % 3 of listed vertex i / 3:
+// unset state: state = cur (that frame is left as it is); otherwise state = 0.98 state + 0.02 cur, written back into the vertex.  State
+// and flag are read at the start and written at the end; an entry without frames keeps both.  No two workgroups share a row or a frame,
+// so nothing crosses a workgroup.  An entry's loads do not depend on the recurrence, only its stores do: they are issued eight frames
+// ahead (a frame is listed once, so no store reaches a later load).
+constexpr int kForeheadAhead = 8;
+// one entry's walk over its n frames, the j-th of them frame_of(j) of verts: the one statement of the recurrence
+template <typename FrameOf>
+__device__ __forceinline__ void gaga_forehead_walk(float* __restrict__ verts, const int32_t* __restrict__ index, int K, int V, int n,
+                                                   float* __restrict__ state, bool was_set, FrameOf frame_of) {
 #pragma clang fp contract(off)
-    const bool was_set = *flag != 0;
-    __syncthreads();      // every thread has read the flag before thread 0 writes it
+    const long per = (long)V * 3;
     for (int i = threadIdx.x; i < K * 3; i += blockDim.x) {
         const int k = i / 3, c = i - k * 3;
         float* p = verts + (long)index[k] * 3 + c;
         float s = state[i];
         bool set = was_set;
-        for (int t = 0; t < T; ++t, p += (long)V * 3) {
-            const float cur = *p;
-            if (!set) { s = cur; set = true; }
-            else { s = 0.98f * s + 0.02f * cur; *p = s; }
+        for (int j0 = 0; j0 < n; j0 += kForeheadAhead) {
+            float cur[kForeheadAhead];
+            long at[kForeheadAhead];
+#pragma unroll
+            for (int u = 0; u < kForeheadAhead; ++u) {      // past the end: the last frame once more, loaded and not used - no branch before a load
+                at[u] = (long)frame_of(min(j0 + u, n - 1)) * per;
+                cur[u] = p[at[u]];
+            }
+#pragma unroll
+            for (int u = 0; u < kForeheadAhead; ++u) {
+                if (j0 + u >= n) break;
+                if (!set) { s = cur[u]; set = true; }
+                else { s = 0.98f * s + 0.02f * cur[u]; p[at[u]] = s; }
+            }
         }
         state[i] = s;
     }
-    if (threadIdx.x == 0 && T > 0 && K > 0) *flag = 1;
+}
+__global__ __launch_bounds__(256) void gaga_forehead_kernel(float* __restrict__ verts, const int32_t* __restrict__ index, int K, int V, int n_frames,
+                                                            const int32_t* __restrict__ pool_row, const int32_t* __restrict__ off,
+                                                            const int32_t* __restrict__ frames, float* __restrict__ state_pool,
+                                                            int* __restrict__ flag_pool) {
+    const int e = blockIdx.x;
+    const int begin = off ? off[e] : 0, n = off ? off[e + 1] - begin : n_frames;
+    if (n <= 0) return;      // (the whole workgroup)
+    const long row = pool_row ? pool_row[e] : 0;
+    const bool was_set = flag_pool[row] != 0;
+    __syncthreads();      // every thread has read the flag before thread 0 writes it
+    float* state = state_pool + row * K * 3;
+    // the null test stays out of the walk: a select per frame would put a branch before every load and undo the load-ahead
+    if (frames) {
+        const int32_t* fr = frames + begin;
+        gaga_forehead_walk(verts, index, K, V, n, state, was_set, [fr](int j) { return fr[j]; });
+    } else {
+        gaga_forehead_walk(verts, index, K, V, n, state, was_set, [](int j) { return j; });
+    }
+    if (threadIdx.x == 0 && K > 0) flag_pool[row] = 1;
 }
 
-// means [F][N][3]: rows 0 .. V-1 from the frame's vertices, rows V .. N-1 from the avatar's xyz [N][3]
-__global__ void gaga_means_kernel(const float* __restrict__ verts, const float* __restrict__ xyz, float* __restrict__ means, int F, int V, int N) {
-    const long per = (long)N * 3, idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long)F * per) return;
-    const int f = (int)(idx / per);
-    const long e = idx - (long)f * per;
-    means[idx] = e < (long)V * 3 ? verts[(long)f * V * 3 + e] : xyz[e];
+// means [F][N][3]: rows 0 .. V-1 from the frame's vertices, rows V .. N-1 from slot slots[f] (null: 0) of xyz [slots][N][3]
+__global__ void gaga_means_kernel(const float* __restrict__ verts, const float* __restrict__ xyz, const int32_t* __restrict__ slots,
+                                  float* __restrict__ means, int F, int V, int N) {
+    const long per = (long)N * 3, e = (long)blockIdx.x * blockDim.x + threadIdx.x;      // grid: x over a frame's elements, y over frames
+    if (e >= per) return;
+    for (int f = blockIdx.y; f < F; f += gridDim.y)
+        means[f * per + e] = e < (long)V * 3 ? verts[(long)f * V * 3 + e] : xyz[(slots ? (long)slots[f] : 0L) * per + e];
 }
 
 // in place on img [F][3][S][S]: clamp(0, 1); on the bottom-right h x w patch a = alpha * 0.8, p = p * (1 - a) + rgb * a.
@@ -110,78 +147,6 @@ __global__ void gaga_finish_kernel(float* __restrict__ img, const float* __restr
     img[idx] = v;
 }
 
-// ---- live streams: the same three steps with one indirection per frame
-// as gaga_flame_inputs_kernel; frame t reads motion row rows[t] and the shapecode of pool slot slots[t] (shape_pool [slots][NS])
-__global__ void gaga_flame_inputs_sets_kernel(const float* __restrict__ motion, long stride, const int64_t* __restrict__ rows,
-                                              const int32_t* __restrict__ slots, const float* __restrict__ shape_pool, int NS,
-                                              float* __restrict__ betas, float* __restrict__ pose, int T) {
-    const int NB = NS + 100, W = NB + 15;
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long)T * W) return;
-    const int t = (int)(idx / W), c = (int)(idx - (long)t * W);
-    const float* m = motion + (long)rows[t] * stride;
-    if (c < NB) {
-        betas[(long)t * NB + c] = c < NS ? shape_pool[(long)slots[t] * NS + c] : m[c - NS];
-    } else {
-        const int p = c - NB;
-        pose[(long)t * 15 + p] = (p >= 6 && p < 9) ? m[103 + (p - 6)] : 0.f;
-    }
-}
-
-// Workgroup e serves one stream: its state and flag are row pool_row[e] of state_pool [rows][K][3] / flag_pool [rows], its frames are
-// frames[off[e] .. off[e + 1]) - indices into verts [..][V][3], each at most once, walked in this order.  The arithmetic is
-// gaga_forehead_kernel's.  No two workgroups share a row or a frame, so nothing crosses a workgroup.  A stream's loads do not depend on
-// the recurrence, only its stores do: they are issued eight frames ahead (a frame is listed once, so no store reaches a later load).
-constexpr int kForeheadAhead = 8;
-__global__ __launch_bounds__(256) void gaga_forehead_streams_kernel(float* __restrict__ verts, const int32_t* __restrict__ index, int K, int V,
-                                                                    const int32_t* __restrict__ pool_row, const int32_t* __restrict__ off,
-                                                                    const int32_t* __restrict__ frames, float* __restrict__ state_pool,
-                                                                    int* __restrict__ flag_pool) {
-#pragma clang fp contract(off)
-    const int e = blockIdx.x;
-    const int begin = off[e], n = off[e + 1] - begin;
-    if (n <= 0) return;      // (the whole workgroup) a stream without frames keeps its state and its flag
-    const long row = pool_row[e];
-    const bool was_set = flag_pool[row] != 0;
-    __syncthreads();      // every thread has read the flag before thread 0 writes it
-    float* state = state_pool + row * K * 3;
-    const int32_t* fr = frames + begin;
-    const long per = (long)V * 3;
-    for (int i = threadIdx.x; i < K * 3; i += blockDim.x) {
-        const int k = i / 3, c = i - k * 3;
-        float* p = verts + (long)index[k] * 3 + c;
-        float s = state[i];
-        bool set = was_set;
-        for (int j0 = 0; j0 < n; j0 += kForeheadAhead) {
-            float cur[kForeheadAhead];
-            long at[kForeheadAhead];
-#pragma unroll
-            for (int u = 0; u < kForeheadAhead; ++u) {
-                at[u] = j0 + u < n ? (long)fr[j0 + u] * per : 0;
-                cur[u] = j0 + u < n ? p[at[u]] : 0.f;
-            }
-#pragma unroll
-            for (int u = 0; u < kForeheadAhead; ++u) {
-                if (j0 + u >= n) break;
-                if (!set) { s = cur[u]; set = true; }
-                else { s = 0.98f * s + 0.02f * cur[u]; p[at[u]] = s; }
-            }
-        }
-        state[i] = s;
-    }
-    if (threadIdx.x == 0 && K > 0) flag_pool[row] = 1;
-}
-
-// as gaga_means_kernel; frame f takes rows V .. N-1 from xyz_pool [slots][N][3] at slot slots[f]
-__global__ void gaga_means_sets_kernel(const float* __restrict__ verts, const float* __restrict__ xyz_pool, const int32_t* __restrict__ slots,
-                                       float* __restrict__ means, int F, int V, int N) {
-    const long per = (long)N * 3, idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long)F * per) return;
-    const int f = (int)(idx / per);
-    const long e = idx - (long)f * per;
-    means[idx] = e < (long)V * 3 ? verts[(long)f * V * 3 + e] : xyz_pool[(long)slots[f] * per + e];
-}
-
 // codes [T][3] = motion[rows[t]][100:103]
 __global__ void gaga_gather_codes_kernel(const float* __restrict__ motion, long stride, const int64_t* __restrict__ rows, float* __restrict__ codes,
                                          int T) {
@@ -193,28 +158,18 @@ __global__ void gaga_gather_codes_kernel(const float* __restrict__ motion, long 
 
 static inline unsigned gaga_blocks(long n) { return (unsigned)((n + 255) / 256); }
 
-static void launch_gaga_flame_inputs(const float* motion, long stride, const float* shapecode, int NS, float* betas, float* pose, int T,
-                                     hipStream_t s) {
-    ARTALK_LAUNCH(gaga_flame_inputs_kernel, dim3(gaga_blocks((long)T * (NS + 115))), dim3(256), 0, s, motion, stride, shapecode, NS, betas, pose, T);
+static void launch_gaga_flame_inputs(const float* motion, long stride, const int64_t* rows, const int32_t* slots, const float* shape, int NS,
+                                     float* betas, float* pose, int T, hipStream_t s) {
+    ARTALK_LAUNCH(gaga_flame_inputs_kernel, dim3(gaga_blocks((long)T * (NS + 115))), dim3(256), 0, s, motion, stride, rows, slots, shape, NS, betas,
+                  pose, T);
 }
-static void launch_gaga_forehead(float* verts, const int32_t* index, int K, int T, int V, float* state, int* flag, hipStream_t s) {
-    ARTALK_LAUNCH(gaga_forehead_kernel, dim3(1), dim3(256), 0, s, verts, index, K, T, V, state, flag);
+// `entries` workgroups over the CSR (pool_row, off, frames); all three null: one entry, n_frames frames in order on row 0
+static void launch_gaga_forehead(float* verts, const int32_t* index, int K, int V, int entries, int n_frames, const int32_t* pool_row,
+                                 const int32_t* off, const int32_t* frames, float* state_pool, int* flag_pool, hipStream_t s) {
+    ARTALK_LAUNCH(gaga_forehead_kernel, dim3(entries), dim3(256), 0, s, verts, index, K, V, n_frames, pool_row, off, frames, state_pool, flag_pool);
 }
-static void launch_gaga_means(const float* verts, const float* xyz, float* means, int F, int V, int N, hipStream_t s) {
-    ARTALK_LAUNCH(gaga_means_kernel, dim3(gaga_blocks((long)F * N * 3)), dim3(256), 0, s, verts, xyz, means, F, V, N);
-}
-static void launch_gaga_flame_inputs_sets(const float* motion, long stride, const int64_t* rows, const int32_t* slots, const float* shape_pool,
-                                          int NS, float* betas, float* pose, int T, hipStream_t s) {
-    ARTALK_LAUNCH(gaga_flame_inputs_sets_kernel, dim3(gaga_blocks((long)T * (NS + 115))), dim3(256), 0, s, motion, stride, rows, slots, shape_pool,
-                  NS, betas, pose, T);
-}
-static void launch_gaga_forehead_streams(float* verts, const int32_t* index, int K, int V, int n_streams, const int32_t* pool_row,
-                                         const int32_t* off, const int32_t* frames, float* state_pool, int* flag_pool, hipStream_t s) {
-    ARTALK_LAUNCH(gaga_forehead_streams_kernel, dim3(n_streams), dim3(256), 0, s, verts, index, K, V, pool_row, off, frames, state_pool, flag_pool);
-}
-static void launch_gaga_means_sets(const float* verts, const float* xyz_pool, const int32_t* slots, float* means, int F, int V, int N,
-                                   hipStream_t s) {
-    ARTALK_LAUNCH(gaga_means_sets_kernel, dim3(gaga_blocks((long)F * N * 3)), dim3(256), 0, s, verts, xyz_pool, slots, means, F, V, N);
+static void launch_gaga_means(const float* verts, const float* xyz, const int32_t* slots, float* means, int F, int V, int N, hipStream_t s) {
+    ARTALK_LAUNCH(gaga_means_kernel, dim3(gaga_blocks((long)N * 3), F < 65535 ? F : 65535), dim3(256), 0, s, verts, xyz, slots, means, F, V, N);
 }
 static void launch_gaga_finish(float* img, const float* wm, int h, int w, int S, int F, hipStream_t s) {
     ARTALK_LAUNCH(gaga_finish_kernel, dim3(gaga_blocks((long)F * 3 * S * S)), dim3(256), 0, s, img, wm, h, w, S, F);
@@ -280,34 +235,47 @@ using namespace artalk;
 
 namespace {
 enum { kGagaInputsFlame, kGagaForeheadMeans, kGagaSplat, kGagaUpsampler, kGagaFinish, kGagaStages };
-}
+
+// An avatar set: `slots` avatars of N Gaussians each, one device slab per attribute ([slots][N][..], shape [slots][NB - 100]).  Which
+// slots hold an avatar, and their [R | t], stay on the host, where the cameras are built.
+struct GagaSet {
+    int slots = 0, N = 0;
+    DevBuf<float> xyz, colors, opac, scales, rots, shape;
+    std::vector<uint8_t> filled;       // [slots]
+    std::vector<float> transform;      // [slots][12]
+    bool has(int slot) const { return slot >= 0 && slot < slots && filled[(size_t)slot]; }
+    void drop() {
+        slots = N = 0;
+        filled.clear(); transform.clear();
+        for (DevBuf<float>* b : {&xyz, &colors, &opac, &scales, &rots, &shape}) b->reset();
+    }
+};
+
+// A state pool of the forehead EMA: state [rows][K][3] and flag [rows] (!= 0: the row's state is set)
+struct GagaStates {
+    int rows = 0;
+    DevBuf<float> state;
+    DevBuf<int> flag;
+    void drop() { rows = 0; state.reset(); flag.reset(); }
+};
+}  // namespace
 
 struct artalk_gaga {
     int device = 0, V = 0, NB = 0, S = 0, num_layers = 0;
     artalk_flame* flame = nullptr;
     artalk_splat* splat = nullptr;
     artalk_styleunet* unet = nullptr;
-    // avatar (device copies, uploaded once by set_avatar)
-    int N = 0;
-    bool have_avatar = false;
-    DevBuf<float> xyz, colors, opac, scales, rots, shapecode;
-    float transform[12] = {};
-    // forehead EMA
+    // the classic call's avatar (artalk_gaga_set_avatar), a set of one slot, and the resident avatars (artalk_gaga_pool_*)
+    GagaSet avatar, pool;
+    // forehead EMA: the listed vertices; the classic call's state, a pool of one row, and the streams', one row per open stream.  The
+    // two are separate objects: a classic call never touches a stream's row, nor a stream call the classic row
     int K = 0;
     DevBuf<int32_t> index;
-    DevBuf<float> state;         // [K][3]
-    DevBuf<int> flag;
-    // resident avatars (artalk_gaga_pool_*): one slab per attribute, [slots][..]; the avatar above is no slot
-    int pool_slots = 0, pool_N = 0;
-    DevBuf<float> p_xyz, p_colors, p_opac, p_scales, p_rots, p_shape;
-    std::vector<uint8_t> pool_filled;      // [slots]
-    std::vector<float> pool_transform;     // [slots][12], host
+    GagaStates classic, streams;
     // live streams: stream_open[id] / stream_row[id] for every id ever handed out (ids are not reused, rows are)
     std::vector<uint8_t> stream_open;
     std::vector<int32_t> stream_row;
-    int streams_open = 0, cap_streams = 0;
-    DevBuf<float> s_state;       // [cap_streams][K][3]
-    DevBuf<int> s_flag;          // [cap_streams]
+    int streams_open = 0;
     // the frame lists of one artalk_gaga_render_streams call, on their way to the device
     PinnedBuf<char> plan_host;
     DevBuf<char> plan_dev;
@@ -343,27 +311,43 @@ int gaga_default_slab(const artalk_gaga* g, int N) {
     return (int)(n < 1 ? 1 : n > 64 ? 64 : n);
 }
 
-// N < 0: the single avatar's (what artalk_gaga_set_slab reports); a stream call passes the pool's
-int gaga_slab(const artalk_gaga* g, int N = -1) {
+// the slab for avatars of N Gaussians: the classic avatar's for artalk_gaga_set_slab and the classic call, the pool's for a stream call
+int gaga_slab(const artalk_gaga* g, int N) {
     int unet_slab = 1;
     (void)artalk_styleunet_dims(g->unet, nullptr, nullptr, nullptr, nullptr, &unet_slab);
-    const int want = g->slab_req > 0 ? g->slab_req : gaga_default_slab(g, N >= 0 ? N : g->have_avatar ? g->N : g->V);
+    const int want = g->slab_req > 0 ? g->slab_req : gaga_default_slab(g, N);
     return want < unet_slab ? want : unet_slab;
 }
+int gaga_classic_N(const artalk_gaga* g) { return g->avatar.has(0) ? g->avatar.N : g->V; }
 
 // the frame lists of artalk_gaga_render_streams, host arrays of T entries each
 struct GagaFrames { const int64_t* row; const int32_t* stream; const int32_t* slot; };
 
-// The lists as the kernels read them, one block on the device: rows [T] int64, slots [T], and the forehead kernel's CSR over every
+// Where a call's frames come from.  A classic call: its one-slot set, its one-row state and every list null - frame t is motion row t on
+// slot 0, a slab's forehead launch one entry over its frames in order.  A stream call: the pool, the streams' states and the lists as the
+// kernels read them, one block on the device (gaga_upload_plan): rows [T] int64, slots [T], and the forehead kernel's CSR over every
 // (slab, stream present in it) pair in slab order - ent_row [E] (the stream's row of the state pool), off [E + 1] into frames [T], whose
 // values count from the start of their slab.  Slab k launches entries slab_ent[k] .. slab_ent[k + 1]; off[slab_ent[k + 1]] closes it.
-struct GagaPlan {
+struct GagaSource {
+    const GagaSet* set;
+    const GagaStates* states;
+    const char* splat_call;                    // the rasteriser entry point an error names
+    long motion_step;                          // floats the motion base moves per frame of the call: the row stride, or 0 under a row list
+    const int32_t* slot_host = nullptr;        // [T]
     const int64_t* rows = nullptr;
     const int32_t *slots = nullptr, *ent_row = nullptr, *off = nullptr, *frames = nullptr;
     std::vector<int> slab_ent;
+    // slab k's forehead entries: their number, *first the first of them
+    int entries(int k, int* first) const {
+        *first = slab_ent.empty() ? 0 : slab_ent[(size_t)k];
+        return slab_ent.empty() ? 1 : slab_ent[(size_t)k + 1] - *first;
+    }
 };
+// list + i, a null list staying null
+template <typename T>
+const T* gaga_from(const T* list, long i) { return list ? list + i : nullptr; }
 
-bool gaga_upload_plan(artalk_gaga* g, const GagaFrames& fr, int T, int slab, GagaPlan* plan, hipStream_t s) {
+bool gaga_upload_plan(artalk_gaga* g, const GagaFrames& fr, int T, int slab, GagaSource* plan, hipStream_t s) {
     const size_t t = (size_t)T, bytes = t * 8 + (4 * t + 1) * 4;
     if (!g->plan_host.grow(bytes, 0, 1, s) || !g->plan_dev.grow(bytes, 1, 4, s)) return false;
     // the pinned block is free here: every earlier call, on whichever stream, waited on that stream after this upload - for the rotation
@@ -403,6 +387,63 @@ bool gaga_upload_plan(artalk_gaga* g, const GagaFrames& fr, int T, int slab, Gag
     plan->slots = (const int32_t*)(d + t * 8);
     plan->ent_row = plan->slots + t; plan->off = plan->ent_row + t; plan->frames = plan->off + t + 1;
     return true;
+}
+
+// ---- avatar sets
+// a takes `slots` empty slots for avatars of N Gaussians; what it held is gone.  The device is current.  false (a is empty): no memory
+bool gaga_set_reserve(artalk_gaga* g, GagaSet& a, int slots, int N) {
+    (void)hipDeviceSynchronize();     // an earlier call may still read the set that is replaced
+    a.drop();
+    const size_t n = (size_t)slots * N;
+    if (!a.xyz.alloc(n * 3) || !a.colors.alloc(n * kGagaCh) || !a.opac.alloc(n) || !a.scales.alloc(n * 3) || !a.rots.alloc(n * 4) ||
+        !a.shape.alloc((size_t)slots * (g->NB - 100))) {
+        a.drop();
+        return false;
+    }
+    a.slots = slots; a.N = N;
+    a.filled.assign((size_t)slots, 0);
+    a.transform.assign((size_t)slots * 12, 0.f);
+    return true;
+}
+
+// Uploads an avatar into slot `slot` of a.  After the checks every caller shares, admit() applies the caller's own rule - the pool
+// refuses a slot outside it and another N, the classic set is reserved anew for another N - and leaves a ready to take the avatar.
+template <typename Admit>
+int gaga_set_fill(artalk_gaga* g, GagaSet& a, int slot, int N, const float* xyz, const float* colors, const float* opacities, const float* scales,
+                  const float* rotations, const float* shapecode, const float* transform_3x4, Admit admit) {
+    if (!xyz || !colors || !opacities || !scales || !rotations || !transform_3x4 || (g->NB > 100 && !shapecode))
+        return gaga_fail(g, ARTALK_EINVAL, "xyz, colors, opacities, scales, rotations, shapecode and transform must not be NULL");
+    int rc = check_avatar(g->V, N, &g->err);
+    if (rc == ARTALK_OK) rc = admit();
+    if (rc != ARTALK_OK) return rc;
+    if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
+    if (a.filled[(size_t)slot]) (void)hipDeviceSynchronize();      // an earlier call may still read the avatar that is replaced
+    a.filled[(size_t)slot] = 0;
+    const size_t n = (size_t)N, at = (size_t)slot * n, NS = (size_t)(g->NB - 100);
+    const auto up = [](float* dst, const float* src, size_t count) {
+        return count == 0 || hipMemcpy(dst, src, count * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+    };
+    if (!up(a.xyz.get() + at * 3, xyz, n * 3) || !up(a.colors.get() + at * kGagaCh, colors, n * kGagaCh) || !up(a.opac.get() + at, opacities, n) ||
+        !up(a.scales.get() + at * 3, scales, n * 3) || !up(a.rots.get() + at * 4, rotations, n * 4) || !up(a.shape.get() + (size_t)slot * NS, shapecode, NS)) {
+        (void)hipGetLastError();
+        return gaga_fail(g, ARTALK_EHIP, "uploading the avatar failed");
+    }
+    (void)hipDeviceSynchronize();      // the slot is whole before any call reads it
+    std::memcpy(a.transform.data() + (size_t)slot * 12, transform_3x4, 12 * sizeof(float));
+    a.filled[(size_t)slot] = 1;
+    return ARTALK_OK;
+}
+
+// ---- state pools
+// unsets row `row` of p.  The device is idle; it is idle again afterwards
+int gaga_zero_row(artalk_gaga* g, GagaStates& p, int row) {
+    const size_t w = (size_t)(g->K ? g->K : 1) * 3;
+    if (hipMemset(p.flag.get() + row, 0, sizeof(int)) != hipSuccess || hipMemset(p.state.get() + (size_t)row * w, 0, w * sizeof(float)) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) {
+        (void)hipGetLastError();
+        return gaga_fail(g, ARTALK_EHIP, "hipMemset failed");
+    }
+    return ARTALK_OK;
 }
 
 }  // namespace
@@ -503,32 +544,19 @@ int artalk_gaga_create(int device_id, artalk_flame* flame, artalk_splat* splat, 
 int artalk_gaga_set_avatar(artalk_gaga* g, int N, const float* xyz, const float* colors, const float* opacities, const float* scales,
                            const float* rotations, const float* shapecode, const float* transform_3x4) {
     if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
-    if (!xyz || !colors || !opacities || !scales || !rotations || !transform_3x4 || (g->NB > 100 && !shapecode))
-        return gaga_fail(g, ARTALK_EINVAL, "xyz, colors, opacities, scales, rotations, shapecode and transform must not be NULL");
-    const int rc = check_avatar(g->V, N, &g->err);
-    if (rc != ARTALK_OK) return rc;
-    if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
-    (void)hipDeviceSynchronize();      // an earlier call may still read the avatar that is replaced
-    g->have_avatar = false;
-    const size_t n = (size_t)N;
-    if (!g->xyz.upload(xyz, n * 3) || !g->colors.upload(colors, n * kGagaCh) || !g->opac.upload(opacities, n) ||
-        !g->scales.upload(scales, n * 3) || !g->rots.upload(rotations, n * 4) || !g->shapecode.upload(shapecode, (size_t)(g->NB - 100)))
-        return gaga_fail(g, ARTALK_EHIP, "uploading the avatar failed");
-    std::memcpy(g->transform, transform_3x4, sizeof(g->transform));
-    g->N = N;
-    g->have_avatar = true;
-    return ARTALK_OK;
+    return gaga_set_fill(g, g->avatar, 0, N, xyz, colors, opacities, scales, rotations, shapecode, transform_3x4, [&] {
+        if (N == g->avatar.N) return ARTALK_OK;      // the one slot takes another N from call to call: it is reserved anew
+        if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
+        return gaga_set_reserve(g, g->avatar, 1, N) ? ARTALK_OK : gaga_fail(g, ARTALK_EHIP, "uploading the avatar failed");
+    });
 }
 
 int artalk_gaga_reset_state(artalk_gaga* g) {
     if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
-    if (!g->flag.get()) return ARTALK_OK;      // no indices: there is no state
+    if (g->classic.rows == 0) return ARTALK_OK;      // no indices: there is no state
     if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
     (void)hipDeviceSynchronize();
-    if (hipMemset(g->flag.get(), 0, sizeof(int)) != hipSuccess ||
-        hipMemset(g->state.get(), 0, (size_t)(g->K ? g->K : 1) * 3 * sizeof(float)) != hipSuccess)
-        return gaga_fail(g, ARTALK_EHIP, "hipMemset failed");
-    return ARTALK_OK;
+    return gaga_zero_row(g, g->classic, 0);
 }
 
 int artalk_gaga_set_forehead(artalk_gaga* g, const int32_t* idx, int K) {
@@ -540,14 +568,14 @@ int artalk_gaga_set_forehead(artalk_gaga* g, const int32_t* idx, int K) {
                                            std::to_string(g->streams_open) + " open streams keep a state for: close them first");
     if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
     (void)hipDeviceSynchronize();
-    if (K != g->K) { g->s_state.reset(); g->s_flag.reset(); g->cap_streams = 0; }      // (no stream is open) rows of another width
-    g->index.reset(); g->flag.reset(); g->state.reset(); g->K = 0;
+    if (K != g->K) g->streams.drop();      // (no stream is open) rows of another width
+    g->index.reset(); g->classic.drop(); g->K = 0;
     if (K == 0) return ARTALK_OK;
-    if (!g->index.alloc((size_t)K) || !g->flag.alloc(1) || !g->state.alloc((size_t)K * 3)) {
-        g->index.reset(); g->flag.reset();
+    if (!g->index.alloc((size_t)K) || !g->classic.flag.alloc(1) || !g->classic.state.alloc((size_t)K * 3)) {
+        g->index.reset(); g->classic.drop();
         return gaga_fail(g, ARTALK_EHIP, "hipMalloc failed");
     }
-    g->K = K;
+    g->K = K; g->classic.rows = 1;
     if (hipMemcpy(g->index.get(), idx, (size_t)K * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
         return gaga_fail(g, ARTALK_EHIP, "uploading the indices failed");
     return artalk_gaga_reset_state(g);
@@ -574,12 +602,12 @@ int artalk_gaga_set_slab(artalk_gaga* g, int frames) {
     if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
     if (frames < 0 || frames > 64) return gaga_fail(g, ARTALK_EINVAL, "slab must be in 0..64 frames (0: the default)");
     g->slab_req = frames;
-    return gaga_slab(g);
+    return gaga_slab(g, gaga_classic_N(g));
 }
 
 int artalk_gaga_streams_slab(const artalk_gaga* g) {
     if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
-    return gaga_slab(g, g->pool_slots > 0 ? g->pool_N : -1);
+    return gaga_slab(g, g->pool.slots > 0 ? g->pool.N : gaga_classic_N(g));
 }
 
 int artalk_gaga_set_timing(artalk_gaga* g, int enable) {
@@ -594,10 +622,11 @@ int artalk_gaga_get_timing(const artalk_gaga* g, double* stage_ms, int n) {
     return kGagaStages;
 }
 
-// The loop of artalk_gaga_render, artalk_gaga_render_u8 and (fr != null) artalk_gaga_render_streams.  format == 0: fp32 frames into out_dev, finished in place.  Otherwise the
-// upsampler writes each slab into g->rgb and the fused finish-and-pack kernel writes its 8-bit frames into out_u8 (and, with out_host, a
-// copy on g->copy_stream follows each slab's pack kernel).  With fr, frame t takes motion row fr->row[t], the resident avatar of slot
-// fr->slot[t] and the EMA state of stream fr->stream[t]; everything from the splat image on is the same code.
+// The loop of artalk_gaga_render, artalk_gaga_render_u8 and (fr != null) artalk_gaga_render_streams.  format == 0: fp32 frames into
+// out_dev, finished in place.  Otherwise the upsampler writes each slab into g->rgb and the fused finish-and-pack kernel writes its 8-bit
+// frames into out_u8 (and, with out_host, a copy on g->copy_stream follows each slab's pack kernel).  With fr, frame t takes motion row
+// fr->row[t], the resident avatar of slot fr->slot[t] and the EMA state of stream fr->stream[t]; without, row t, the classic avatar and
+// the classic state.  The slab loop is one code for both (GagaSource).
 static int gaga_render_any(artalk_gaga* g, const float* motion_dev, int64_t motion_stride, int T, const float* const* noise_ptrs_or_null,
                            const int64_t* noise_batch_strides, int activation, float* out_dev, int format, uint8_t* out_u8, uint8_t* out_host,
                            void* stream, const char* name, const GagaFrames* fr = nullptr) {
@@ -606,11 +635,11 @@ static int gaga_render_any(artalk_gaga* g, const float* motion_dev, int64_t moti
     int finalized = 0;
     (void)artalk_styleunet_dims(g->unet, nullptr, nullptr, nullptr, &finalized, nullptr);
     if (fr) {
-        const int rcs = check_frames(T, fr->row, fr->stream, fr->slot, g->stream_open.data(), (int)g->stream_open.size(), g->pool_filled.data(),
-                                     g->pool_slots, &g->err);
+        const int rcs = check_frames(T, fr->row, fr->stream, fr->slot, g->stream_open.data(), (int)g->stream_open.size(), g->pool.filled.data(),
+                                     g->pool.slots, &g->err);
         if (rcs != ARTALK_OK) return rcs;
     }
-    const int rc = check_render(T, motion_stride, fr || g->have_avatar, finalized != 0, &g->err);
+    const int rc = check_render(T, motion_stride, fr || g->avatar.has(0), finalized != 0, &g->err);
     if (rc != ARTALK_OK) return rc;
     const int rcn = su_check_noise(g->num_layers, noise_ptrs_or_null, noise_batch_strides, &g->err);
     if (rcn != ARTALK_OK) return rcn;
@@ -626,7 +655,11 @@ static int gaga_render_any(artalk_gaga* g, const float* motion_dev, int64_t moti
         if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); return gaga_fail(g, ARTALK_EHIP, "hipStreamIsCapturing failed"); }
         if (cap != hipStreamCaptureStatusNone) return gaga_fail(g, ARTALK_EINVAL, std::string(name) + " waits on its stream: it cannot run during stream capture");
     }
-    const int V = g->V, N = fr ? g->pool_N : g->N, S = g->S, NB = g->NB;
+    // where the call's frames come from, said once: from here on the function reads src, not fr
+    GagaSource src{fr ? &g->pool : &g->avatar, fr ? &g->streams : &g->classic, fr ? "artalk_splat_render_sets" : "artalk_splat_render",
+                   fr ? 0 : (long)motion_stride, fr ? fr->slot : nullptr};
+    const GagaSet& set = *src.set;
+    const int V = g->V, N = set.N, S = g->S, NB = g->NB;
     const long SS = (long)S * S;
     const int slab = gaga_slab(g, N);
     const int frames = T < slab ? T : slab;
@@ -650,30 +683,31 @@ static int gaga_render_any(artalk_gaga* g, const float* motion_dev, int64_t moti
     if (out_host && (!g->copy_stream.create() || !g->packed.create() || !g->copied.create()))
         return gaga_fail(g, ARTALK_EHIP, "creating the copy stream or its events failed");
     if (!g->codes_host.grow((size_t)T * 3, 0, 1, s)) return gaga_fail(g, ARTALK_EHIP, "hipHostMalloc failed");
-    GagaPlan plan;
+    // The two differences between the call kinds.  Only a stream call uploads its lists and gathers the head-rotation codes of its
+    // scattered rows into one block; the classic call copies columns 100:103 of its rows as they lie.
+    hipError_t codes;
     if (fr) {
         if (!g->codes_dev.grow((size_t)T * 3, 1, 4, s)) return gaga_fail(g, ARTALK_EHIP, "hipMalloc of the rotation codes failed");
-        if (!gaga_upload_plan(g, *fr, T, slab, &plan, s)) {      // (nothing is in flight: the upload is the function's last step)
+        if (!gaga_upload_plan(g, *fr, T, slab, &src, s)) {      // (nothing is in flight: the upload is the function's last step)
             return gaga_fail(g, ARTALK_EHIP, "uploading the frame lists failed");
         }
-        ARTALK_LAUNCH(gaga_gather_codes_kernel, dim3(gaga_blocks((long)T * 3)), dim3(256), 0, s, motion_dev, (long)motion_stride, plan.rows,
+        ARTALK_LAUNCH(gaga_gather_codes_kernel, dim3(gaga_blocks((long)T * 3)), dim3(256), 0, s, motion_dev, (long)motion_stride, src.rows,
                       g->codes_dev.get(), T);
+        codes = hipMemcpyAsync(g->codes_host.get(), g->codes_dev.get(), (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToHost, s);
+    } else {
+        codes = hipMemcpy2DAsync(g->codes_host.get(), 3 * sizeof(float), motion_dev + 100, (size_t)motion_stride * sizeof(float), 3 * sizeof(float),
+                                 (size_t)T, hipMemcpyDeviceToHost, s);
     }
     // the first wait of the call: the head-rotation codes become the cameras, which the rasteriser reads on the host
-    if (fr ? (hipMemcpyAsync(g->codes_host.get(), g->codes_dev.get(), (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
-              hipStreamSynchronize(s) != hipSuccess) :
-        hipMemcpy2DAsync(g->codes_host.get(), 3 * sizeof(float), motion_dev + 100, (size_t)motion_stride * sizeof(float), 3 * sizeof(float), (size_t)T,
-                         hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+    if (codes != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
         (void)hipGetLastError();
         if (fr) (void)hipStreamSynchronize(s);      // the frame lists may still be on their way up from the pinned block
         return gaga_fail(g, ARTALK_EHIP, "reading the rotation codes failed");
     }
     std::vector<float> view((size_t)T * 16), proj((size_t)T * 16);
-    if (!fr) (void)artalk_gaga_cameras(g->codes_host.get(), 3, T, g->transform, view.data(), proj.data(), nullptr);
-    else
-        for (int t = 0; t < T; ++t)      // every frame under its slot's [R | t]
-            (void)artalk_gaga_cameras(g->codes_host.get() + (size_t)t * 3, 3, 1, g->pool_transform.data() + (size_t)fr->slot[t] * 12,
-                                      view.data() + (size_t)t * 16, proj.data() + (size_t)t * 16, nullptr);
+    for (int t = 0; t < T; ++t)      // every frame under its slot's [R | t]
+        (void)artalk_gaga_cameras(g->codes_host.get() + (size_t)t * 3, 3, 1, set.transform.data() + (size_t)(src.slot_host ? src.slot_host[t] : 0) * 12,
+                                  view.data() + (size_t)t * 16, proj.data() + (size_t)t * 16, nullptr);
 
     StageTimer timer;
     timer.start(s, g->timing);
@@ -683,34 +717,23 @@ static int gaga_render_any(artalk_gaga* g, const float* motion_dev, int64_t moti
     for (int f0 = 0; f0 < T; f0 += slab) {
         const int n = T - f0 < slab ? T - f0 : slab;
         timer.mark(-1);      // (what lies between two slabs counts to no stage)
-        if (fr) launch_gaga_flame_inputs_sets(motion_dev, (long)motion_stride, plan.rows + f0, plan.slots + f0, g->p_shape.get(), NB - 100,
-                                              g->betas.get(), g->pose.get(), n, s);
-        else launch_gaga_flame_inputs(motion_dev + (long)f0 * motion_stride, (long)motion_stride, g->shapecode.get(), NB - 100, g->betas.get(),
-                                      g->pose.get(), n, s);
+        launch_gaga_flame_inputs(motion_dev + f0 * src.motion_step, (long)motion_stride, gaga_from(src.rows, f0), gaga_from(src.slots, f0),
+                                 set.shape.get(), NB - 100, g->betas.get(), g->pose.get(), n, s);
         if (artalk_flame_verts(g->flame, g->betas.get(), g->pose.get(), n, g->verts.get(), s) != ARTALK_OK)
             return gaga_fail(g, ARTALK_EHIP, std::string("artalk_flame_verts failed: ") + artalk_flame_last_error(g->flame));
         timer.mark(kGagaInputsFlame);
-        int rc2;
-        if (fr) {
-            const int e0 = plan.slab_ent[(size_t)(f0 / slab)], e1 = plan.slab_ent[(size_t)(f0 / slab) + 1];
-            if (g->K > 0) launch_gaga_forehead_streams(g->verts.get(), g->index.get(), g->K, V, e1 - e0, plan.ent_row + e0, plan.off + e0, plan.frames,
-                                                       g->s_state.get(), g->s_flag.get(), s);
-            launch_gaga_means_sets(g->verts.get(), g->p_xyz.get(), plan.slots + f0, g->means.get(), n, V, N, s);
-            timer.mark(kGagaForeheadMeans);
-            rc2 = artalk_splat_render_sets(g->splat, N, n, S, S, g->means.get(), (int64_t)N * 3, g->p_colors.get(), 0, g->p_opac.get(), 0,
-                                           g->p_scales.get(), 0, g->p_rots.get(), 0, view.data() + (size_t)f0 * 16, proj.data() + (size_t)f0 * 16, n,
-                                           tanfov, tanfov, 1.0f, nullptr, g->img.get(), g->radii.get(), fr->slot + f0, g->pool_slots, 0,
+        int e0 = 0;
+        const int entries = src.entries(f0 / slab, &e0);
+        if (g->K > 0) launch_gaga_forehead(g->verts.get(), g->index.get(), g->K, V, entries, n, gaga_from(src.ent_row, e0), gaga_from(src.off, e0),
+                                           src.frames, src.states->state.get(), src.states->flag.get(), s);
+        launch_gaga_means(g->verts.get(), set.xyz.get(), gaga_from(src.slots, f0), g->means.get(), n, V, N, s);
+        timer.mark(kGagaForeheadMeans);
+        // (without a slot list the rasteriser reads set 0 and none of the set strides: the call is artalk_splat_render)
+        int rc2 = artalk_splat_render_sets(g->splat, N, n, S, S, g->means.get(), (int64_t)N * 3, set.colors.get(), 0, set.opac.get(), 0,
+                                           set.scales.get(), 0, set.rots.get(), 0, view.data() + (size_t)f0 * 16, proj.data() + (size_t)f0 * 16, n,
+                                           tanfov, tanfov, 1.0f, nullptr, g->img.get(), g->radii.get(), gaga_from(src.slot_host, f0), set.slots, 0,
                                            (int64_t)N * kGagaCh, N, (int64_t)N * 3, (int64_t)N * 4, s);
-        } else {
-            if (g->K > 0) launch_gaga_forehead(g->verts.get(), g->index.get(), g->K, n, V, g->state.get(), g->flag.get(), s);
-            launch_gaga_means(g->verts.get(), g->xyz.get(), g->means.get(), n, V, N, s);
-            timer.mark(kGagaForeheadMeans);
-            rc2 = artalk_splat_render(g->splat, N, n, S, S, g->means.get(), (int64_t)N * 3, g->colors.get(), 0, g->opac.get(), 0, g->scales.get(), 0,
-                                      g->rots.get(), 0, view.data() + (size_t)f0 * 16, proj.data() + (size_t)f0 * 16, n, tanfov, tanfov, 1.0f,
-                                      nullptr, g->img.get(), g->radii.get(), s);
-        }
-        if (rc2 != ARTALK_OK)
-            return gaga_fail(g, rc2, std::string(fr ? "artalk_splat_render_sets" : "artalk_splat_render") + " failed: " + artalk_splat_last_error(g->splat));
+        if (rc2 != ARTALK_OK) return gaga_fail(g, rc2, std::string(src.splat_call) + " failed: " + artalk_splat_last_error(g->splat));
         timer.mark(kGagaSplat);
         if (noise_ptrs_or_null) for (int l = 0; l < g->num_layers; ++l) np[l] = noise_ptrs_or_null[l] + (long)f0 * noise_batch_strides[l];
         float* out = format ? g->rgb.get() : out_dev + (long)f0 * 3 * SS;
@@ -765,81 +788,41 @@ int artalk_gaga_pool_reserve(artalk_gaga* g, int slots, int N) {
     if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
     const int rc = check_pool(g->V, slots, N, &g->err);
     if (rc != ARTALK_OK) return rc;
-    if (g->pool_slots > 0 && g->streams_open > 0)
+    if (g->pool.slots > 0 && g->streams_open > 0)
         return gaga_fail(g, ARTALK_ESTATE, "the pool cannot be reserved again while " + std::to_string(g->streams_open) + " streams are open");
     if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
-    (void)hipDeviceSynchronize();      // an earlier call may still read the pool that is replaced
-    g->pool_slots = g->pool_N = 0;
-    g->pool_filled.clear(); g->pool_transform.clear();
-    for (DevBuf<float>* b : {&g->p_xyz, &g->p_colors, &g->p_opac, &g->p_scales, &g->p_rots, &g->p_shape}) b->reset();
-    const size_t n = (size_t)slots * N;
-    if (!g->p_xyz.alloc(n * 3) || !g->p_colors.alloc(n * kGagaCh) || !g->p_opac.alloc(n) || !g->p_scales.alloc(n * 3) || !g->p_rots.alloc(n * 4) ||
-        !g->p_shape.alloc((size_t)slots * (g->NB - 100))) {
-        for (DevBuf<float>* b : {&g->p_xyz, &g->p_colors, &g->p_opac, &g->p_scales, &g->p_rots, &g->p_shape}) b->reset();
+    if (!gaga_set_reserve(g, g->pool, slots, N))
         return gaga_fail(g, ARTALK_EHIP, "hipMalloc of a pool of " + std::to_string(slots) + " avatars of " + std::to_string(N) + " Gaussians failed");
-    }
-    g->pool_slots = slots; g->pool_N = N;
-    g->pool_filled.assign((size_t)slots, 0);
-    g->pool_transform.assign((size_t)slots * 12, 0.f);
     return ARTALK_OK;
 }
 
 static int gaga_check_slot(artalk_gaga* g, int slot) {
-    if (slot >= 0 && slot < g->pool_slots) return ARTALK_OK;
-    return gaga_fail(g, ARTALK_EINVAL, "slot " + std::to_string(slot) + " is outside the pool's [0, " + std::to_string(g->pool_slots) + ")");
+    if (slot >= 0 && slot < g->pool.slots) return ARTALK_OK;
+    return gaga_fail(g, ARTALK_EINVAL, "slot " + std::to_string(slot) + " is outside the pool's [0, " + std::to_string(g->pool.slots) + ")");
 }
 
 int artalk_gaga_pool_set(artalk_gaga* g, int slot, int N, const float* xyz, const float* colors, const float* opacities, const float* scales,
                          const float* rotations, const float* shapecode, const float* transform_3x4) {
     if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
-    if (!xyz || !colors || !opacities || !scales || !rotations || !transform_3x4 || (g->NB > 100 && !shapecode))
-        return gaga_fail(g, ARTALK_EINVAL, "xyz, colors, opacities, scales, rotations, shapecode and transform must not be NULL");
-    int rc = check_avatar(g->V, N, &g->err);
-    if (rc == ARTALK_OK) rc = gaga_check_slot(g, slot);
-    if (rc != ARTALK_OK) return rc;
-    if (N != g->pool_N)
-        return gaga_fail(g, ARTALK_EINVAL, "N (" + std::to_string(N) + ") is not the pool's " + std::to_string(g->pool_N) + ": resident avatars share N");
-    if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
-    if (g->pool_filled[(size_t)slot]) (void)hipDeviceSynchronize();      // an earlier call may still read the avatar that is replaced
-    g->pool_filled[(size_t)slot] = 0;
-    const size_t n = (size_t)N, at = (size_t)slot * n, NS = (size_t)(g->NB - 100);
-    const auto up = [](float* dst, const float* src, size_t count) {
-        return count == 0 || hipMemcpy(dst, src, count * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
-    };
-    if (!up(g->p_xyz.get() + at * 3, xyz, n * 3) || !up(g->p_colors.get() + at * kGagaCh, colors, n * kGagaCh) ||
-        !up(g->p_opac.get() + at, opacities, n) || !up(g->p_scales.get() + at * 3, scales, n * 3) || !up(g->p_rots.get() + at * 4, rotations, n * 4) ||
-        !up(g->p_shape.get() + (size_t)slot * NS, shapecode, NS)) {
-        (void)hipGetLastError();
-        return gaga_fail(g, ARTALK_EHIP, "uploading the avatar failed");
-    }
-    (void)hipDeviceSynchronize();      // the slot is whole before any stream reads it
-    std::memcpy(g->pool_transform.data() + (size_t)slot * 12, transform_3x4, 12 * sizeof(float));
-    g->pool_filled[(size_t)slot] = 1;
-    return ARTALK_OK;
+    return gaga_set_fill(g, g->pool, slot, N, xyz, colors, opacities, scales, rotations, shapecode, transform_3x4, [&] {
+        const int rc = gaga_check_slot(g, slot);
+        if (rc != ARTALK_OK || N == g->pool.N) return rc;
+        return gaga_fail(g, ARTALK_EINVAL, "N (" + std::to_string(N) + ") is not the pool's " + std::to_string(g->pool.N) + ": resident avatars share N");
+    });
 }
 
 int artalk_gaga_pool_clear(artalk_gaga* g, int slot) {
     if (!g) { g_gaga_error = "handle is NULL"; return ARTALK_EINVAL; }
     const int rc = gaga_check_slot(g, slot);
     if (rc != ARTALK_OK) return rc;
-    if (!g->pool_filled[(size_t)slot]) return ARTALK_OK;
+    if (!g->pool.filled[(size_t)slot]) return ARTALK_OK;
     if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
     (void)hipDeviceSynchronize();
-    g->pool_filled[(size_t)slot] = 0;
+    g->pool.filled[(size_t)slot] = 0;
     return ARTALK_OK;
 }
 
 // ---- per-stream forehead state
-static int gaga_zero_row(artalk_gaga* g, int row) {      // the device is idle; it is idle again afterwards
-    const size_t w = (size_t)(g->K ? g->K : 1) * 3;
-    if (hipMemset(g->s_flag.get() + row, 0, sizeof(int)) != hipSuccess || hipMemset(g->s_state.get() + (size_t)row * w, 0, w * sizeof(float)) != hipSuccess ||
-        hipDeviceSynchronize() != hipSuccess) {
-        (void)hipGetLastError();
-        return gaga_fail(g, ARTALK_EHIP, "hipMemset failed");
-    }
-    return ARTALK_OK;
-}
-
 static int gaga_check_stream(artalk_gaga* g, int id) {
     if (id < 0 || id >= (int)g->stream_open.size()) return gaga_fail(g, ARTALK_EINVAL, "stream " + std::to_string(id) + " was never opened");
     if (!g->stream_open[(size_t)id]) return gaga_fail(g, ARTALK_EINVAL, "stream " + std::to_string(id) + " is closed");
@@ -852,28 +835,28 @@ int artalk_gaga_stream_open(artalk_gaga* g, int* id) {
     *id = -1;
     if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
     (void)hipDeviceSynchronize();      // a closed stream's last call may still write the row that is handed out again
-    std::vector<char> taken((size_t)g->cap_streams, 0);
+    GagaStates& p = g->streams;
+    std::vector<char> taken((size_t)p.rows, 0);
     for (size_t i = 0; i < g->stream_open.size(); ++i)
         if (g->stream_open[i]) taken[(size_t)g->stream_row[i]] = 1;
     int row = 0;
-    while (row < g->cap_streams && taken[(size_t)row]) ++row;
-    if (row == g->cap_streams) {      // grow, keeping the open streams' rows
-        const int cap = g->cap_streams ? 2 * g->cap_streams : 8;
+    while (row < p.rows && taken[(size_t)row]) ++row;
+    if (row == p.rows) {      // grow, keeping the open streams' rows
+        const int cap = p.rows ? 2 * p.rows : 8;
         const size_t w = (size_t)(g->K ? g->K : 1) * 3;
         DevBuf<float> st;
         DevBuf<int> fl;
         if (!st.alloc_zero((size_t)cap * w) || !fl.alloc_zero((size_t)cap)) return gaga_fail(g, ARTALK_EHIP, "hipMalloc of the stream states failed");
-        if (g->cap_streams > 0 &&
-            (hipMemcpy(st.get(), g->s_state.get(), (size_t)g->cap_streams * w * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess ||
-             hipMemcpy(fl.get(), g->s_flag.get(), (size_t)g->cap_streams * sizeof(int), hipMemcpyDeviceToDevice) != hipSuccess)) {
+        if (p.rows > 0 && (hipMemcpy(st.get(), p.state.get(), (size_t)p.rows * w * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess ||
+                           hipMemcpy(fl.get(), p.flag.get(), (size_t)p.rows * sizeof(int), hipMemcpyDeviceToDevice) != hipSuccess)) {
             (void)hipGetLastError();
             return gaga_fail(g, ARTALK_EHIP, "copying the stream states failed");
         }
         (void)hipDeviceSynchronize();
-        g->s_state = std::move(st); g->s_flag = std::move(fl);
-        g->cap_streams = cap;
+        p.state = std::move(st); p.flag = std::move(fl);
+        p.rows = cap;
     }
-    const int rc = gaga_zero_row(g, row);
+    const int rc = gaga_zero_row(g, p, row);
     if (rc != ARTALK_OK) return rc;
     g->stream_open.push_back(1);
     g->stream_row.push_back(row);
@@ -897,7 +880,7 @@ int artalk_gaga_stream_reset(artalk_gaga* g, int id) {
     if (rc != ARTALK_OK) return rc;
     if (hipSetDevice(g->device) != hipSuccess) return gaga_fail(g, ARTALK_EHIP, "hipSetDevice failed");
     (void)hipDeviceSynchronize();
-    return gaga_zero_row(g, g->stream_row[(size_t)id]);
+    return gaga_zero_row(g, g->streams, g->stream_row[(size_t)id]);
 }
 
 int artalk_gaga_render_streams(artalk_gaga* g, const float* motion_dev, int64_t motion_stride, int T, const int64_t* frame_row_host,
@@ -918,20 +901,20 @@ int artalk_gaga_render_streams(artalk_gaga* g, const float* motion_dev, int64_t 
 int artalk_op_gaga_flame_inputs(const float* motion_dev, int64_t motion_stride, const float* shapecode_dev, int NB, int T, float* betas_dev,
                                 float* pose_dev, void* stream) {
     if (!motion_dev || !betas_dev || !pose_dev || T < 1 || NB < 100 || motion_stride < kGagaMotion || (NB > 100 && !shapecode_dev)) return ARTALK_EINVAL;
-    launch_gaga_flame_inputs(motion_dev, (long)motion_stride, shapecode_dev, NB - 100, betas_dev, pose_dev, T, (hipStream_t)stream);
+    launch_gaga_flame_inputs(motion_dev, (long)motion_stride, nullptr, nullptr, shapecode_dev, NB - 100, betas_dev, pose_dev, T, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
 }
 
 int artalk_op_gaga_forehead(float* verts_dev, const int32_t* idx_dev, int K, int T, int V, float* state_dev, int* flag_dev, void* stream) {
     if (!verts_dev || !state_dev || !flag_dev || K < 0 || T < 0 || V < 1 || K > V || (K > 0 && !idx_dev)) return ARTALK_EINVAL;
     if (K == 0 || T == 0) return ARTALK_OK;
-    launch_gaga_forehead(verts_dev, idx_dev, K, T, V, state_dev, flag_dev, (hipStream_t)stream);
+    launch_gaga_forehead(verts_dev, idx_dev, K, V, 1, T, nullptr, nullptr, nullptr, state_dev, flag_dev, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
 }
 
 int artalk_op_gaga_means(const float* verts_dev, const float* xyz_dev, float* means_dev, int F, int V, int N, void* stream) {
     if (!verts_dev || !xyz_dev || !means_dev || F < 1 || V < 1 || N < V) return ARTALK_EINVAL;
-    launch_gaga_means(verts_dev, xyz_dev, means_dev, F, V, N, (hipStream_t)stream);
+    launch_gaga_means(verts_dev, xyz_dev, nullptr, means_dev, F, V, N, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
 }
 
@@ -940,8 +923,8 @@ int artalk_op_gaga_flame_inputs_sets(const float* motion_dev, int64_t motion_str
     if (!motion_dev || !frame_row_dev || !frame_slot_dev || !betas_dev || !pose_dev || T < 1 || NB < 100 || motion_stride < kGagaMotion ||
         (NB > 100 && !shapecode_pool_dev))
         return ARTALK_EINVAL;
-    launch_gaga_flame_inputs_sets(motion_dev, (long)motion_stride, frame_row_dev, frame_slot_dev, shapecode_pool_dev, NB - 100, betas_dev, pose_dev, T,
-                                  (hipStream_t)stream);
+    launch_gaga_flame_inputs(motion_dev, (long)motion_stride, frame_row_dev, frame_slot_dev, shapecode_pool_dev, NB - 100, betas_dev, pose_dev, T,
+                             (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
 }
 
@@ -950,15 +933,15 @@ int artalk_op_gaga_forehead_streams(float* verts_dev, const int32_t* idx_dev, in
     if (!verts_dev || !state_pool_dev || !flag_pool_dev || K < 0 || n_streams < 0 || V < 1 || K > V || (K > 0 && !idx_dev)) return ARTALK_EINVAL;
     if (n_streams > 0 && (!pool_row_dev || !offsets_dev || !frames_dev)) return ARTALK_EINVAL;
     if (K == 0 || n_streams == 0) return ARTALK_OK;
-    launch_gaga_forehead_streams(verts_dev, idx_dev, K, V, n_streams, pool_row_dev, offsets_dev, frames_dev, state_pool_dev, flag_pool_dev,
-                                 (hipStream_t)stream);
+    launch_gaga_forehead(verts_dev, idx_dev, K, V, n_streams, 0, pool_row_dev, offsets_dev, frames_dev, state_pool_dev, flag_pool_dev,
+                         (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
 }
 
 int artalk_op_gaga_means_sets(const float* verts_dev, const float* xyz_pool_dev, const int32_t* frame_slot_dev, float* means_dev, int F, int V,
                               int N, void* stream) {
     if (!verts_dev || !xyz_pool_dev || !frame_slot_dev || !means_dev || F < 1 || V < 1 || N < V) return ARTALK_EINVAL;
-    launch_gaga_means_sets(verts_dev, xyz_pool_dev, frame_slot_dev, means_dev, F, V, N, (hipStream_t)stream);
+    launch_gaga_means(verts_dev, xyz_pool_dev, frame_slot_dev, means_dev, F, V, N, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
 }
 

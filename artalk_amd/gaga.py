@@ -350,6 +350,55 @@ class GAGAvatar:
             raise RuntimeError("GAGAvatar runs on the GPU: motion_codes must be a CUDA tensor (there is no CPU fallback)")
         return motion_codes
 
+    def _device_motion(self, m, dense):
+        """What both render calls ask of their motion tensor beyond its shape: on the GPU and on the head's device.  Returns it detached,
+        as float32 rows the library can walk - ``dense``: contiguous as a whole; else rows of stride 1 that do not overlap."""
+        if not m.is_cuda:
+            raise RuntimeError("GAGAvatar runs on the GPU: motion_codes must be a CUDA tensor (there is no CPU fallback)")
+        if (m.device.index or 0) != (self.device.index if self.device.index is not None else torch.cuda.current_device()):
+            raise RuntimeError(f"motion_codes lives on {m.device}, the head on {self.device}")
+        m = m.detach()
+        fits = m.is_contiguous() if dense else m.stride(1) == 1 and (m.shape[0] <= 1 or m.stride(0) >= m.shape[1])
+        return m if m.dtype == torch.float32 and fits else m.float().contiguous()
+
+    @staticmethod
+    def _format(out, host):
+        """The library's code of ``out`` (0: float frames), after the check that ``host=True`` goes with an 8-bit format."""
+        if out != "float":
+            return _frames.format_code(out)
+        if host:
+            raise ValueError('host=True needs out="rgb24" or out="yuv420p"')
+        return 0
+
+    def _result_buffers(self, out, T, device, host, host_buffer=None):
+        """The tensors a render call fills -> (the float or uint8 device tensor, the pinned host tensor or None).  ``host_buffer``: the
+        caller's pinned tensor, checked against the result's shape and used instead of a new one."""
+        S = self.image_size
+        if host_buffer is not None:
+            want = tuple(_frames.frame_shape(out, T, S, S)) if host else None
+            if (want is None or not isinstance(host_buffer, torch.Tensor) or host_buffer.dtype != torch.uint8 or tuple(host_buffer.shape) != want
+                    or not host_buffer.is_contiguous() or not host_buffer.is_pinned()):
+                raise ValueError(f"host_buffer goes with host=True and must be a contiguous pinned uint8 tensor of shape {want}")
+        shape = (T, 3, S, S) if out == "float" else _frames.frame_shape(out, T, S, S)
+        res = torch.empty(shape, dtype=torch.float32 if out == "float" else torch.uint8, device=device)
+        if host and host_buffer is None:
+            host_buffer = torch.empty(shape, dtype=torch.uint8, pin_memory=True)
+        return res, host_buffer
+
+    def _raise_rc(self, rc, name):
+        if rc == capi.EINVAL:
+            raise ValueError(name + " refused: " + self._err())
+        if rc != capi.OK:
+            raise RuntimeError(name + " failed: " + self._err())
+
+    def _avatar_args(self, name, flame_model):
+        """The avatar arguments of ``artalk_gaga_set_avatar`` and ``artalk_gaga_pool_set``: N and the seven pointers."""
+        av = self.all_gagavatar_id[name]
+        if av["shapecode"].numel() != flame_model.n_betas - 100:
+            raise ValueError(f"avatar {name!r}: shapecode holds {av['shapecode'].numel()} values, the FLAME model "
+                             f"takes {flame_model.n_betas - 100}")
+        return (int(av["xyz"].shape[0]),) + tuple(capi.ptr(av[k]) for k in tuple(AVATAR_FIELDS) + ("shapecode", "transform_matrix"))
+
     def _ensure(self, flame_model, avatar=True):
         """The library object for this FLAME model and, with ``avatar``, the tracked identity uploaded as the classic path's avatar."""
         L = capi.lib()
@@ -394,14 +443,7 @@ class GAGAvatar:
         if self._tracked_name is None:
             self.set_avatar_id(self._default_id())
         if self._uploaded != self._tracked_name:
-            av = self.all_gagavatar_id[self._tracked_name]
-            if av["shapecode"].numel() != flame_model.n_betas - 100:
-                raise ValueError(f"avatar {self._tracked_name!r}: shapecode holds {av['shapecode'].numel()} values, the FLAME model "
-                                 f"takes {flame_model.n_betas - 100}")
-            rc = L.artalk_gaga_set_avatar(self._h, int(av["xyz"].shape[0]), capi.ptr(av["xyz"]), capi.ptr(av["colors"]), capi.ptr(av["opacities"]),
-                                          capi.ptr(av["scales"]), capi.ptr(av["rotations"]), capi.ptr(av["shapecode"]),
-                                          capi.ptr(av["transform_matrix"]))
-            if rc != capi.OK:
+            if L.artalk_gaga_set_avatar(self._h, *self._avatar_args(self._tracked_name, flame_model)) != capi.OK:
                 raise ValueError("artalk_gaga_set_avatar refused: " + self._err())
             self._uploaded = self._tracked_name
 
@@ -443,26 +485,13 @@ class GAGAvatar:
         ``(T, S, S, 3)`` or ``(T, S * 3 // 2, S)``, byte-equal to ``pack_frames(render_clip(...), out)``, from one
         ``artalk_gaga_render_u8`` call that never holds the fp32 clip.  With ``host=True`` the result is a pinned CPU tensor, filled slab
         by slab while the next slab renders; the method synchronises the current stream before it returns it."""
-        if out != "float":
-            fmt = _frames.format_code(out)
-        elif host:
-            raise ValueError('host=True needs out="rgb24" or out="yuv420p"')
-        m = self._check_motion(motion_codes)
-        if (m.device.index or 0) != (self.device.index if self.device.index is not None else torch.cuda.current_device()):
-            raise RuntimeError(f"motion_codes lives on {m.device}, the head on {self.device}")
-        m = m.detach()
-        if m.dtype != torch.float32 or m.stride(1) != 1 or (m.shape[0] > 1 and m.stride(0) < m.shape[1]):
-            m = m.float().contiguous()
+        fmt = self._format(out, host)
+        m = self._device_motion(self._check_motion(motion_codes), dense=False)
         T = int(m.shape[0])
         stride = int(m.stride(0)) if T > 1 else int(m.shape[1])
-        S = self.image_size
         L = capi.lib()
         with torch.cuda.device(m.device):
-            if out == "float":
-                res = torch.empty(T, 3, S, S, dtype=torch.float32, device=m.device)
-            else:
-                res = torch.empty(_frames.frame_shape(out, T, S, S), dtype=torch.uint8, device=m.device)
-            res_host = torch.empty(res.shape, dtype=torch.uint8, pin_memory=True) if host else None
+            res, res_host = self._result_buffers(out, T, m.device, host)
             self._ensure(flame_model)
             if T == 0:
                 return res_host if host else res
@@ -475,11 +504,7 @@ class GAGAvatar:
                                              capi.ptr(res), capi.ptr(res_host), capi.current_stream_ptr())
                 if host:
                     torch.cuda.current_stream().synchronize()      # (also after a failure: a copy may be in flight)
-        name = "artalk_gaga_render" if out == "float" else "artalk_gaga_render_u8"
-        if rc == capi.EINVAL:
-            raise ValueError(name + " refused: " + self._err())
-        if rc != capi.OK:
-            raise RuntimeError(name + " failed: " + self._err())
+        self._raise_rc(rc, "artalk_gaga_render" if out == "float" else "artalk_gaga_render_u8")
         return res_host if host else res
 
     # ---- live streams: many independent streams through one head ("Live streams through the head") ----
@@ -578,12 +603,7 @@ class GAGAvatar:
         Noise as in ``render_clip`` (a per-frame ``noise`` follows the order of ``frames``).  ``host_buffer``: with ``host=True``, a
         pinned uint8 tensor of the result's shape to fill and return instead of a new one - it is filled slab by slab, so another
         thread of a live sender can take a slab's frames out of it while the later slabs still render."""
-        if out != "float":
-            fmt = _frames.format_code(out)
-        elif host:
-            raise ValueError('host=True needs out="rgb24" or out="yuv420p"')
-        else:
-            fmt = 0
+        fmt = self._format(out, host)
         streams = list(streams)
         for st in streams:
             if not isinstance(st, GagaStream) or st._head is not self:
@@ -595,10 +615,7 @@ class GAGAvatar:
         m = motion_codes
         if not isinstance(m, torch.Tensor) or m.dim() != 3 or m.shape[2] < MOTION_DIM or m.shape[0] != len(streams):
             raise ValueError(f"motion_codes must be a ({len(streams)}, R, {MOTION_DIM}) tensor: one block of rows per listed stream")
-        if not m.is_cuda:
-            raise RuntimeError("GAGAvatar runs on the GPU: motion_codes must be a CUDA tensor (there is no CPU fallback)")
-        if (m.device.index or 0) != (self.device.index if self.device.index is not None else torch.cuda.current_device()):
-            raise RuntimeError(f"motion_codes lives on {m.device}, the head on {self.device}")
+        m = self._device_motion(m, dense=True)
         n, R = int(m.shape[0]), int(m.shape[1])
         counts = [R] * n if counts is None else [int(c) for c in counts]
         firsts = [0] * n if firsts is None else [int(f) for f in firsts]
@@ -607,23 +624,11 @@ class GAGAvatar:
         rows, which, ks = self.plan_frames(counts, order, firsts, R)
         if any(f + c > R for f, c in zip(firsts, counts)):
             raise ValueError(f"a stream's rows firsts[i] .. firsts[i] + counts[i] must lie within its {R} rows")
-        m = m.detach()
-        if m.dtype != torch.float32 or not m.is_contiguous():
-            m = m.float().contiguous()
-        T, S, W = len(rows), self.image_size, int(m.shape[2])
-        if host_buffer is not None:
-            want = tuple(_frames.frame_shape(out, T, S, S)) if host else None
-            if (want is None or not isinstance(host_buffer, torch.Tensor) or host_buffer.dtype != torch.uint8 or tuple(host_buffer.shape) != want
-                    or not host_buffer.is_contiguous() or not host_buffer.is_pinned()):
-                raise ValueError(f"host_buffer goes with host=True and must be a contiguous pinned uint8 tensor of shape {want}")
+        T, W = len(rows), int(m.shape[2])
         index = torch.tensor([which, ks], dtype=torch.int64).t().contiguous().reshape(T, 2)
         L = capi.lib()
         with torch.cuda.device(m.device):
-            if out == "float":
-                res = torch.empty(T, 3, S, S, dtype=torch.float32, device=m.device)
-            else:
-                res = torch.empty(_frames.frame_shape(out, T, S, S), dtype=torch.uint8, device=m.device)
-            res_host = torch.empty(res.shape, dtype=torch.uint8, pin_memory=True) if host and host_buffer is None else host_buffer
+            res, res_host = self._result_buffers(out, T, m.device, host, host_buffer)
             todo = self._plan_slots(streams)
             self._ensure(flame_model, avatar=False)
             h = self._h
@@ -636,14 +641,7 @@ class GAGAvatar:
                 self._fresh.clear()
                 todo = self._plan_slots(streams)
             for name, slot in todo:
-                av = self.all_gagavatar_id[name]
-                if av["shapecode"].numel() != flame_model.n_betas - 100:
-                    raise ValueError(f"avatar {name!r}: shapecode holds {av['shapecode'].numel()} values, the FLAME model "
-                                     f"takes {flame_model.n_betas - 100}")
-                rc = L.artalk_gaga_pool_set(h, slot, int(av["xyz"].shape[0]), capi.ptr(av["xyz"]), capi.ptr(av["colors"]), capi.ptr(av["opacities"]),
-                                            capi.ptr(av["scales"]), capi.ptr(av["rotations"]), capi.ptr(av["shapecode"]),
-                                            capi.ptr(av["transform_matrix"]))
-                if rc != capi.OK:
+                if L.artalk_gaga_pool_set(h, slot, *self._avatar_args(name, flame_model)) != capi.OK:
                     raise ValueError(f"artalk_gaga_pool_set refused avatar {name!r}: " + self._err())
                 self._fresh.add(slot)
             for st in streams:
@@ -663,8 +661,5 @@ class GAGAvatar:
                                               None if fmt == 0 else capi.ptr(res), capi.ptr(res_host), capi.current_stream_ptr())
             if host:
                 torch.cuda.current_stream().synchronize()      # (also after a failure: a copy may be in flight)
-        if rc == capi.EINVAL:
-            raise ValueError("artalk_gaga_render_streams refused: " + self._err())
-        if rc != capi.OK:
-            raise RuntimeError("artalk_gaga_render_streams failed: " + self._err())
+        self._raise_rc(rc, "artalk_gaga_render_streams")
         return (res_host if host else res), index

@@ -493,7 +493,8 @@ int artalk_gaga_render_u8(artalk_gaga* g, const float* motion_dev, int64_t motio
  * int64, frame_slot [T], shapecode_pool [slots][NB - 100] -> betas [T][NB], pose [T][15].  forehead_streams: one workgroup per listed
  * stream e < n_streams: its state and flag are row pool_row[e] of state_pool [rows][K][3] / flag_pool [rows] (no row listed twice), its
  * frames frames[offsets[e] .. offsets[e + 1]) index verts [..][V][3] (no frame listed twice) and are walked in this order; a stream with
- * no frames keeps state and flag.  means_sets: xyz_pool [slots][N][3], frame_slot [F] -> means [F][N][3].
+ * no frames keeps state and flag.  means_sets: xyz_pool [slots][N][3], frame_slot [F] -> means [F][N][3].  Each launches the kernel of
+ * the entry point without the suffix, which passes null lists: motion row t, slot 0, one entry over frames 0 .. T-1 on row 0.
  * artalk_op_gaga_streams_check (host only): the checks of pool_reserve (V, pool_slots, pool_N) and render_streams on plain numbers and
  * host arrays - stream_open [n_stream_ids] (1: open) and slot_filled [pool_slots] stand for the handle's books; format 0 skips the frame
  * format's check - returns the first failing code and copies its message. */

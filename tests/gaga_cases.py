@@ -29,7 +29,7 @@ def random_codes(seed=3, n=16):
 
 # ---- single ops
 FLAME_INPUT_CASES = [(T, stride, NB) for T in (1, 3) for stride, NB in ((106, 100), (131, 400), (112, 100), (106, 400))]
-FOREHEAD_CASES = [(K, T, preset) for K in (1, 68) for T in (1, 2, 7) for preset in (False, True)]
+FOREHEAD_CASES = [(K, T, preset) for K in (1, 68) for T in (1, 2, 7, 8, 9, 17) for preset in (False, True)]
 MEANS_CASES = [(F, V, N) for F in (1, 3) for V, N in ((64, 64), (64, 136), (5, 300))]
 FINISH_S = 16
 FINISH_MARKS = [(5, 8), (16, 16), None]

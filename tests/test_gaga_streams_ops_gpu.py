@@ -40,7 +40,7 @@ def _bits(t):
 # ---- forehead_streams
 ROWS = 5                       # rows of the state pool; row 0 and row 4 are NaN guard rows no stream may touch
 POOL_ROW = (3, 1, 2)           # stream e's row: neither in order nor adjacent to its neighbours' the way e is
-COUNTS = (0, 1, 2, 7)
+COUNTS = (0, 1, 2, 7, 8, 9, 17)      # 8, 9, 17: one full group of the kernel's eight frames ahead, one more frame, two groups and one
 
 
 def _slab(counts, major):
@@ -103,6 +103,11 @@ FOREHEAD_CASES = [(K, counts, major)
                   for K in (1, 8, 68, 90)
                   for counts in ((7,), (0,), (2, 7), (1, 0), (7, 1, 2), (0, 2, 0), (7, 7, 7))
                   for major in ("time", "stream")]
+# the edges of the kernel's groups of eight frames; appended, so that the cases above keep their ids
+FOREHEAD_CASES += [(K, counts, major)
+                   for K in (1, 8, 68, 90)
+                   for counts in ((8,), (9, 1), (17, 8, 2))
+                   for major in ("time", "stream")]
 
 
 @pytest.mark.parametrize("K,counts,major", FOREHEAD_CASES)
@@ -162,6 +167,38 @@ def test_forehead_streams_split_launches(major):
     for a, b in zip(one, three):
         assert torch.equal(_bits(a), _bits(b))
     assert one[2].tolist() == [0, 1, 1, 1, 0] and not torch.equal(one[0], verts)
+
+
+@pytest.mark.parametrize("major,cut", (("stream", 5), ("time", 10)))
+def test_forehead_streams_split_inside_a_group_of_eight(major, cut):
+    """Streams of 17 and 9 frames in two launches cut after the first stream's fifth frame - 17 as 5 + 12, neither part a multiple of the
+    eight frames the kernel loads ahead - equal one launch and the torch loop per stream, states and flags included."""
+    V, K, counts = 97, 90, (17, 9)
+    g = torch.Generator().manual_seed(43)
+    T = sum(counts)
+    verts = torch.randn(T, V, 3, generator=g)
+    index = torch.randperm(V, generator=g)[:K].to(torch.int32)
+    pool0 = torch.randn(ROWS, K, 3, generator=g)
+    lists, rows = _slab(counts, major), list(POOL_ROW[:2])      # rows 3 (unset) and 1 (preset)
+    assert [sum(f < cut for f in l) for l in lists] == ([5, 0] if major == "stream" else [5, 5])
+
+    def run(cuts):
+        v, state = verts.cuda().clone(), pool0.cuda().clone()
+        flags = torch.tensor([0, 1, 0, 0, 0], **I32)
+        for lo, hi in zip(cuts[:-1], cuts[1:]):
+            part = [[f for f in l if lo <= f < hi] for l in lists]
+            keep = [e for e, l in enumerate(part) if l]
+            _launch(v, index.cuda(), K, [part[e] for e in keep], [rows[e] for e in keep], state, flags)
+        return v.cpu(), state.cpu(), flags.cpu()
+
+    one, two = run([0, T]), run([0, cut, T])
+    want, want_pool = verts.clone(), pool0.clone()
+    for l, r, preset in zip(lists, rows, (False, True)):
+        want[l], st = ref.ema_torch(verts[l], index.long(), pool0[r][None].clone() if preset else None)
+        want_pool[r] = st[0]
+    for got in (one, two):
+        assert torch.equal(_bits(got[0]), _bits(want)) and torch.equal(_bits(got[1]), _bits(want_pool))
+        assert got[2].tolist() == [0, 1, 0, 1, 0]
 
 
 def test_forehead_streams_without_work_is_a_no_op():
