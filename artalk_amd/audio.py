@@ -64,9 +64,24 @@ def sinc_resample_kernel(orig_freq: int, new_freq: int, lowpass_filter_width: in
     return kernels.to(torch.float32).reshape(new, -1).contiguous(), width, orig, new
 
 
+MAX_TAP_TABLE = 1 << 24      # elements; 44100 -> 16000 has 76 000, while 16001 -> 16000 would have 16000 x 16015 (about 1 GB)
+
+
+def tap_table_geometry(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
+    """(orig, new, taps per phase) of ``sinc_resample_kernel`` without building the table."""
+    g = math.gcd(int(orig_freq), int(new_freq))
+    orig, new = int(orig_freq) // g, int(new_freq) // g
+    width = math.ceil(lowpass_filter_width * orig / (min(orig, new) * rolloff))
+    return orig, new, 2 * width + orig
+
+
 def resample_mean_16k(waveform: torch.Tensor, sr: int, device="cuda", target: int = 16000) -> torch.Tensor:
     """``Resample(sr, 16000)(waveform).mean(dim=0)`` on the GPU: (channels, N) -> (ceil(N*16000/sr),) float32."""
     assert waveform.dim() == 2
+    orig, new, n_taps = tap_table_geometry(sr, target)
+    if new * n_taps > MAX_TAP_TABLE:      # (before anything is moved to the device)
+        raise ValueError(f"resampling {sr} Hz to {target} Hz reduces to {orig}:{new}, whose tap table has {new} x {n_taps} = "
+                         f"{new * n_taps} elements (limit {MAX_TAP_TABLE}); resample to a rate with a larger common divisor first")
     x = waveform.to(device=device, dtype=torch.float32).contiguous()
     nch, n = x.shape
     if sr == target:

@@ -524,7 +524,10 @@ int artalk_op_w2v_front_ex(const float* audio, int C, int n, const float* w, con
 
 int artalk_op_resample_mean(const float* x, int nch, int n, const float* taps, int orig, int nw, int width, float* out, int n_out,
                             void* stream) {
-    if (!x || !taps || !out || nch <= 0 || n <= 0 || orig <= 0 || nw <= 0 || width < 0) return ARTALK_EINVAL;
+    if (!x || !taps || !out || nch <= 0 || n <= 0 || orig <= 0 || nw <= 0 || width < 0 || n_out < 0) return ARTALK_EINVAL;
+    // the kernel's loop index is an int that advances by up to 2^20 per trip, and outputs past ceil(n * nw / orig) hear no input
+    if (n_out > 2147483647 - (1 << 20) || (long long)n_out > ((long long)n * nw + orig - 1) / orig) return ARTALK_EINVAL;
+    if (n_out == 0) return ARTALK_OK;
     launch_resample_mean(x, nch, n, taps, orig, nw, width, out, n_out, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
 }

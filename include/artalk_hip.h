@@ -810,7 +810,9 @@ int artalk_op_attention(const float* Q, const float* K, const float* V, float* O
 int artalk_op_w2v_front(const float* audio, int C, int n, const float* w, const float* bias, const float* lnw,
                         const float* lnb, float* xnorm_out, float* Y, void* stream);
 /* audio front-end of inference.py:230-231: polyphase sinc FIR (torchaudio Resample defaults) + mean over channels.
- * x [nch][n] f32, taps [nw][2*width+orig] f32 (host-built, see artalk_amd/audio.py), out [n_out], n_out = ceil(n*nw/orig) */
+ * x [nch][n] f32, taps [nw][2*width+orig] f32 (host-built, see artalk_amd/audio.py), out [n_out], the first n_out of
+ * ceil(n*nw/orig) outputs.  ARTALK_EINVAL for a NULL pointer, nch, n, orig or nw <= 0, width < 0, n_out < 0, n_out > ceil(n*nw/orig)
+ * (taken in 64 bits) or n_out > INT_MAX - 2^20; n_out == 0 launches nothing */
 int artalk_op_resample_mean(const float* x, int nch, int n, const float* taps, int orig, int nw, int width, float* out, int n_out,
                             void* stream);
 /* X [C][T][D] -> Y [C][181][D]: area pooling to {1,5,25,50,100} then SiLU */
