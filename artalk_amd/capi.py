@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("ARTALK_LIB") or os.path.join(_HERE, "libartalk_hip.so
 OK, EINVAL, EKEY, EMISSING, EHIP, ESTATE, ECAPACITY, EBUSY = 0, -1, -2, -3, -4, -5, -6, -7
 DTYPE_F32, DTYPE_I64 = 0, 1
 FRAMES_RGB24, FRAMES_YUV420P = 1, 2      # ARTALK_FRAMES_* of include/artalk_hip.h
+PCM_S16, PCM_F32, PCM_MAX_TAPS, PCM_MAX_CHANNELS = 1, 2, 1024, 8      # ARTALK_PCM_* of include/artalk_hip.h
 
 # every symbol include/artalk_hip.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
@@ -60,6 +61,9 @@ SYMBOLS = [
     "artalk_op_dino_resize_aa", "artalk_op_dino_normalize", "artalk_op_dino_im2col", "artalk_op_dino_tokens", "artalk_op_dino_layernorm",
     "artalk_op_dino_strip", "artalk_op_dino_shuffle", "artalk_op_dino_gather_s2", "artalk_op_dino_concat", "artalk_op_dino_resize_ac",
     "artalk_op_dino_add_relu", "artalk_op_dino_output",
+    "artalk_pcm_create", "artalk_pcm_destroy", "artalk_pcm_last_error", "artalk_pcm_set_rate", "artalk_pcm_open", "artalk_pcm_close",
+    "artalk_pcm_push", "artalk_pcm_end", "artalk_pcm_available", "artalk_pcm_take", "artalk_op_pcm_plan", "artalk_op_pcm_desc_bytes",
+    "artalk_op_pcm_push", "artalk_op_pcm_take",
 ]
 
 # ARTALK_ATTN_* of include/artalk_hip.h: the kernels of attention.hip, as artalk_op_attention_plan names them
@@ -122,6 +126,22 @@ class GemmRowsArgs(C.Structure):
             setattr(self, name, (C.c_int32 * 3)(*ROWMAP_IDENTITY))
         for k, v in kw.items():
             setattr(self, k, (C.c_int32 * 3)(*v) if k in ("cmap", "gmap", "ln_mmap") else v)
+
+
+class PcmDesc(C.Structure):
+    """artalk_pcm_desc of include/artalk_hip.h (field for field): one packet of one stream for ``artalk_op_pcm_push``."""
+    _fields_ = [
+        ("taps", C.c_void_p), ("data", C.c_void_p), ("carry_in", C.c_void_p), ("carry_out", C.c_void_p), ("ring", C.c_void_p),
+        ("orig", C.c_int32), ("nw", C.c_int32), ("width", C.c_int32), ("nch", C.c_int32), ("format", C.c_int32), ("frames", C.c_int32),
+        ("lead", C.c_int32), ("carry_n", C.c_int32), ("carry_from", C.c_int32), ("carry_out_n", C.c_int32), ("carry_stride", C.c_int32),
+        ("ring_cap", C.c_int32), ("ring_pos", C.c_int32), ("n_out", C.c_int32),
+        ("tile_groups", C.c_int32), ("n_tiles", C.c_int32),
+    ]
+
+
+class PcmTakeDesc(C.Structure):
+    """artalk_pcm_take_desc of include/artalk_hip.h: one row of ``artalk_op_pcm_take``."""
+    _fields_ = [("ring", C.c_void_p), ("ring_cap", C.c_int32), ("read_pos", C.c_int32), ("n_valid", C.c_int32), ("reserved", C.c_int32)]
 
 
 def config_struct(cfg: ARTalkConfig) -> ArtalkConfigStruct:
@@ -440,6 +460,25 @@ def lib() -> C.CDLL:
                 ("op_dino_resize_ac", [vp, vp, i32, i32, i32, i32, i32, vp], i32),
                 ("op_dino_add_relu", [vp, vp, vp, vp, i64, vp], i32),
                 ("op_dino_output", [vp, vp, i64, i32, vp, vp, i32, vp], i32)):
+            f = getattr(L, "artalk_" + name)
+            f.argtypes, f.restype = args, res
+    if hasattr(L, "artalk_pcm_create"):      # (an older build loaded through ARTALK_LIB for an A/B run lacks the live audio front door)
+        pi64 = C.POINTER(i64)
+        for name, args, res in (
+                ("pcm_create", [i32, i32, i32, i32, C.POINTER(vp)], i32),
+                ("pcm_destroy", [vp], None),
+                ("pcm_last_error", [vp], C.c_char_p),
+                ("pcm_set_rate", [vp, i32, vp, i32, i32, i32], i32),
+                ("pcm_open", [vp, i32, i32, i32, pi64], i32),
+                ("pcm_close", [vp, i64], i32),
+                ("pcm_push", [vp, pi64, i32, C.POINTER(vp), pi64, i32, vp], i32),
+                ("pcm_end", [vp, pi64, i32, vp], i32),
+                ("pcm_available", [vp, i64, pi64, C.POINTER(i32)], i32),
+                ("pcm_take", [vp, pi64, i32, vp, i64, pi64, vp], i32),
+                ("op_pcm_plan", [i64, i64, i32, i32, i32, i32, pi64], i32),
+                ("op_pcm_desc_bytes", [i32], i32),
+                ("op_pcm_push", [C.POINTER(PcmDesc), i32, vp, i64, vp], i32),
+                ("op_pcm_take", [C.POINTER(PcmTakeDesc), i32, vp, i64, vp, i64, i32, vp], i32)):
             f = getattr(L, "artalk_" + name)
             f.argtypes, f.restype = args, res
     L.artalk_savgol.argtypes = [vp, vp, vp, i32, vp]

@@ -78,6 +78,7 @@ class ARTAvatarInferEngine:
         self.style_motion = None
         self.GAGAvatar = None
         self.GAGAvatar_flame = gaga_flame
+        self.live_audio = None                                              # the audio front door, made by the first open_stream(audio=...)
         if gaga is not None:
             from .gaga import GAGAvatar
             self.GAGAvatar = gaga if isinstance(gaga, GAGAvatar) else GAGAvatar.load(gaga, device=device)
@@ -136,19 +137,75 @@ class ARTAvatarInferEngine:
         return pred_motions
 
     # ------------------------------------------------------------------ live streams (independent sessions)
-    def open_stream(self, style_motion=None, shape_id=None):
+    def open_stream(self, style_motion=None, shape_id=None, audio=None):
         """One live stream (``BitwiseARModel.open_session``) with the engine's style clip unless ``style_motion`` ((50, 106)) is given.
         Streams join and leave independently: ``stream_step`` takes any subset of them, ``stream.close()`` frees one.
         With a GAGAvatar head plugged in and a ``shape_id`` (an avatar id) the stream also gets a stream of the head
-        (``GAGAvatar.open_stream``), kept under the session's id for ``stream_render``; ``close_stream`` closes both halves."""
+        (``GAGAvatar.open_stream``), kept under the session's id for ``stream_render``; ``close_stream`` closes both halves.
+        ``audio=(sample_rate, channels, dtype)`` (``dtype``: "s16" or "f32") gives the stream an audio half as well, a stream of the
+        engine's ``artalk_amd.live_audio.LiveAudio``: ``stream_feed`` takes its raw PCM packets and ``stream_step(streams)`` its blocks.
+        A format the front door does not take raises ``ValueError`` before a session exists."""
         if style_motion is None and self.style_motion is not None:
             style_motion = self.style_motion[0]
+        if audio is not None:
+            from . import live_audio
+            sample_rate, channels, dtype = audio
+            live_audio.check_format(channels, dtype)
+            live_audio.rate_geometry(sample_rate)
         head = getattr(self, "GAGAvatar", None)
         head_stream = head.open_stream(shape_id) if head is not None and shape_id is not None else None      # (KeyError before a session exists)
-        st = self.ARTalk.open_session(style_motion)
+        audio_stream = self._front_door().open(sample_rate, channels, dtype) if audio is not None else None
+        try:
+            st = self.ARTalk.open_session(style_motion)
+        except Exception:
+            if audio_stream is not None:
+                audio_stream.close()
+            raise
         if head_stream is not None:
             self._head_streams()[st.id] = head_stream
+        if audio_stream is not None:
+            self._audio_streams()[st.id] = audio_stream
         return st
+
+    def _front_door(self):
+        """The engine's LiveAudio, made on first use with the model's block (64 000 samples)."""
+        if getattr(self, "live_audio", None) is None:
+            from .live_audio import LiveAudio
+            self.live_audio = LiveAudio(device=self.device, block=self.ARTalk.cfg.samples_per_chunk)
+        return self.live_audio
+
+    def _audio_streams(self):
+        if not hasattr(self, "_pcm_streams"):      # (engines assembled without __init__)
+            self._pcm_streams = {}
+        return self._pcm_streams
+
+    def _audio_of(self, streams):
+        books = self._audio_streams()
+        for st in streams:
+            if st.id not in books:
+                raise ValueError(f"session {st.id} was opened without audio= (or closed): it has no audio half")
+        return [books[st.id] for st in streams]
+
+    def stream_feed(self, streams, packets):
+        """Raw PCM in: one packet per listed stream (``bytes``, a numpy array, a CPU or CUDA tensor ``(frames, channels)`` in the
+        format the stream was opened with, of any length), resampled to 16 kHz mono on the device by one launch for all of them
+        (``LiveAudio.push``).  Nothing waits for the device."""
+        self._front_door().push(self._audio_of(streams), packets)
+
+    def stream_audio_end(self, streams):
+        """The listed streams' senders have hung up (``LiveAudio.end``): what is left becomes ready, the last block short."""
+        self._front_door().end(self._audio_of(streams))
+
+    def stream_ready(self, streams):
+        """The streams of ``streams``, in order, that ``stream_step(streams)`` can take a block from: a full 4 s, or the rest of a
+        stream that has ended."""
+        live = self._front_door()
+        return [st for st, a in zip(streams, self._audio_of(streams)) if live.ready(a)]
+
+    def stream_drained(self, st):
+        """The stream's audio has ended and every block has been stepped: after its last ``stream_step`` the loop closes it - after a
+        ``stream_flush`` when its last block was a full one, which ended nothing."""
+        return self._front_door().drained(self._audio_of([st])[0])
 
     def _head_streams(self):
         if not hasattr(self, "_gaga_streams"):      # (engines assembled without __init__)
@@ -160,6 +217,9 @@ class ARTAvatarInferEngine:
         head_stream = self._head_streams().pop(st.id, None)
         if head_stream is not None:
             head_stream.close()
+        audio_stream = self._audio_streams().pop(st.id, None)
+        if audio_stream is not None:
+            audio_stream.close()
         st.close()
 
     def stream_render(self, streams, frames, spans, output=None, host=False, order="time"):
@@ -185,7 +245,7 @@ class ARTAvatarInferEngine:
             index[:, 1] += torch.tensor([int(f) for f, _ in spans], dtype=torch.int64)[index[:, 0]]
         return images, index
 
-    def stream_step(self, streams, chunks, n_valid=None, smooth=False):
+    def stream_step(self, streams, chunks=None, n_valid=None, smooth=False):
         """Next 4 seconds of the listed streams: ``chunks`` (n, 64000) -> (n, 100, 106) (with ``n_valid`` also the valid frame counts,
         ``BitwiseARModel.step_sessions``), with ``fix_pose`` applied and dims 104: zeroed as ``inference`` does.  These are the raw codes:
         the Savitzky-Golay window of ``inference`` reaches 4 frames into the future, which a live block does not have yet.
@@ -199,8 +259,24 @@ class ARTAvatarInferEngine:
         A stream that would end shorter than 9 frames raises ``ValueError`` before anything runs, as ``inference`` does for such a clip -
         also a stream that was never stepped and is listed with ``n_valid <= 0``: that row is a flush of nothing.  A stream is
         smoothed from its first step on or not at all: one that was stepped with ``smooth=False`` before raises ``RuntimeError``
-        (the smoother would filter across the gap)."""
+        (the smoother would filter across the gap).
+
+        ``chunks=None``: every stream's next block comes from its audio half (``open_stream(audio=...)``, ``stream_feed``), and
+        ``n_valid`` is always passed - 64 000 for a full block, fewer for the last block of a stream whose audio has ended - so the
+        result has the ``n_valid`` form.  Every listed stream must be ready (``stream_ready``); the checks above run before a block
+        leaves its ring."""
+        take = None
+        if chunks is None:
+            if n_valid is not None:
+                raise ValueError("n_valid comes from the audio half when chunks is None")
+            for st in streams:
+                if st.closed:
+                    raise RuntimeError(f"session {st.id} is closed ({st.why}); open it again")
+            take = self._audio_of(streams)
+            n_valid = self._front_door().next_valid(take)
         if not smooth:
+            if take is not None:
+                chunks, n_valid = self._front_door().take(take)
             res = self.ARTalk.step_sessions(streams, chunks, n_valid=n_valid)
             pred = res[0] if n_valid is not None else res
             if self.fix_pose:
@@ -217,6 +293,8 @@ class ARTAvatarInferEngine:
         rows = [i for i, (st, (nf, last)) in enumerate(zip(streams, plan)) if not (st.smooth_done and nf == 0)]
         for i in rows:
             self._check_smoothable(streams[i], *plan[i])
+        if take is not None:
+            chunks, n_valid = self._front_door().take(take)
         res = m.step_sessions(streams, chunks, n_valid=n_valid)
         pred = res[0] if n_valid is not None else res
         frames = torch.zeros(n, 104, pred.shape[-1], dtype=pred.dtype, device=pred.device)

@@ -11,6 +11,8 @@
  *                               (batched: B independent batch-1 runs; the reference asserts B==1, app/models.py:65)
  *   artalk_savgol            <- ARTAvatarInferEngine.smooth_motion_savgol        inference.py:89-95
  *   artalk_destroy           <- object lifetime
+ *   artalk_pcm_*             <- torchaudio.load + Resample(sr, 16000)(x).mean(0)  inference.py:230-231, for a live sender: raw PCM
+ *                               packets in, the model's 16 kHz blocks out, the bits of the whole-clip call ("Live audio in" below)
  *
  * Conventions: plain pointers and sizes only; all *_dev pointers are device memory on the model's GPU;
  * every call returns 0 on success or a negative ARTALK_E* code (text via artalk_last_error); the caller
@@ -460,6 +462,80 @@ int artalk_op_gaga_finish_pack(const float* img_dev, int F, int S, const float* 
 int artalk_gaga_render_u8(artalk_gaga* g, const float* motion_dev, int64_t motion_stride, int T, const float* const* noise_ptrs_or_null,
                           const int64_t* noise_batch_strides, int activation, int format, uint8_t* out_dev, uint8_t* out_host_or_null,
                           void* stream);
+
+/* Live audio in ("Live audio in"): raw PCM packets of any size -> the model's 16 kHz mono blocks, on the device.  A
+ * streaming form of torchaudio's Resample(sr, 16000)(x).mean(dim=0) (inference.py:230-231): the 16 kHz samples are bit for bit those of
+ * artalk_op_resample_mean on the whole concatenated signal, whatever the packet sizes.  An object of its own, not tied to a model handle.
+ * Arithmetic.  Output i = j new + p is sum over k ascending of fmaf(taps[p][k], x_c[j orig - width + k], s), indices outside [0, n)
+ * skipped (not added as zeros), then the channels summed in order and divided by (float)nch.  After n_in frames group j is final when
+ * j orig + width + orig - 1 < n_in; a push emits exactly the newly final groups, new max(0, floor((n_in - width) / orig)) outputs in all, and
+ * end emits the rest up to ceil(new n / orig).  Between pushes a stream keeps the frames from index j_next orig - width on (fewer than
+ * ntaps = 2 width + orig a channel, fp32, de-interleaved) in one of two carry buffers that alternate: a launch reads one and writes the other.
+ * All counters (frames in, outputs written and taken, ended) are host-side int64; nothing reads the device to learn a count.
+ * artalk_pcm_create: `max_streams` rings of ring_blocks x block fp32 samples and their carry buffers, two pinned staging buffers.
+ * ARTALK_EINVAL before the device is touched: block < 1, ring_blocks < 2, max_streams outside 1..4096, a ring of 2^30 samples or more.
+ * device = ARTALK_PCM_NO_DEVICE: a handle without a device, for tests of the bookkeeping: every call checks, plans and counts as usual,
+ * nothing is allocated, copied or launched (packets and out_dev are not read or written).
+ * artalk_pcm_set_rate: the tap table [new][2 width + orig] of one sample rate, built by the caller exactly as the whole-clip path builds
+ * it (artalk_amd.audio.sinc_resample_kernel; 16 kHz: orig = new = 1, width = 0, one tap of 1.0), uploaded once.  ARTALK_EINVAL: ntaps above
+ * ARTALK_PCM_MAX_TAPS, new x ntaps above 2^24, a rate set before with another geometry.
+ * artalk_pcm_open: a stream of `channels` (1..8) interleaved channels in `format` (ARTALK_PCM_S16: little-endian int16, value / 32768;
+ * ARTALK_PCM_F32) at a rate that has been set; ids are never reused.  ARTALK_ECAPACITY when max_streams are open.
+ * artalk_pcm_push: packet i, frames[i] frames at data[i] (host memory, or with on_device device memory that is read in place), for stream
+ * ids[i]: ONE launch for all listed streams, whatever their rates.  Host packets and the descriptor table travel in one copy through
+ * one of two pinned staging buffers, each guarded by an event: a push waits at most for its own staging buffer to come free.
+ * artalk_pcm_end: the stream's signal ends here; emits the outputs that were waiting for frames that will not come.
+ * artalk_pcm_available (host arithmetic only): 16 kHz samples written and not yet taken, and whether the stream has ended.
+ * artalk_pcm_take: the oldest `block` samples of each listed stream into row i of out_dev (row stride out_stride floats), zero past the
+ * stream's last real sample; n_valid_host[i] = the real samples of row i (block, or fewer on the last row of an ended stream).
+ * A call is checked whole before anything is enqueued and refused with ARTALK_EINVAL (ARTALK_ESTATE for a push or end after end, and for
+ * a take of a stream that has neither a full block nor, ended, at least one sample; ARTALK_ECAPACITY for a push whose outputs would not
+ * fit the ring's free space) and nothing changed: an unknown or closed id, an id listed twice, a negative frame count, a NULL packet.
+ * Calls of one handle are stream-ordered by the caller; a handle is not thread-safe.  No call synchronises the host with the device
+ * except a push whose staging buffer is still in flight or has to grow.
+ * artalk_op_pcm_plan (host only): what a push of `frames` frames (end != 0: the end, frames ignored) does to a stream that has taken
+ * n_before frames: out[0..5] = outputs emitted, lead (frames before index 0 that the carry does not hold), carry frames in, first frame
+ * of the carry out (relative to the carry in's first frame minus lead), carry frames out, groups emitted.
+ * artalk_op_pcm_push / artalk_op_pcm_take: one launch of pcm_push_kernel / pcm_take_kernel on the caller's own buffers, for tests: the n
+ * descriptors (host memory; the library fills tile_groups / n_tiles) are checked, copied to table_dev (table_bytes >= n x sizeof) and read
+ * there by the launch.  artalk_op_pcm_desc_bytes: sizeof the two descriptors (which = 0: push, 1: take). */
+#define ARTALK_PCM_S16 1
+#define ARTALK_PCM_F32 2
+#define ARTALK_PCM_MAX_TAPS 1024
+#define ARTALK_PCM_MAX_CHANNELS 8
+#define ARTALK_PCM_NO_DEVICE (-1)
+typedef struct artalk_pcm artalk_pcm;
+typedef struct artalk_pcm_desc {
+    const float* taps;        /* [nw][2 width + orig], device                                                                        */
+    const void* data;         /* the packet: frames x nch interleaved samples of `format`                                             */
+    const float* carry_in;    /* [nch][carry_stride]: carry_n frames a channel                                                        */
+    float* carry_out;         /* [nch][carry_stride]: carry_out_n frames a channel, written by the packet's last tile                 */
+    float* ring;              /* ring_cap samples                                                                                     */
+    int32_t orig, nw, width, nch, format, frames;
+    int32_t lead;             /* the span's frame v is the signal's frame v - lead + (first frame of the carry in): v < lead is skipped */
+    int32_t carry_n, carry_from, carry_out_n, carry_stride;
+    int32_t ring_cap, ring_pos, n_out;      /* output o of the launch goes to ring[(ring_pos + o) % ring_cap]                          */
+    int32_t tile_groups, n_tiles;           /* filled by the library                                                                  */
+} artalk_pcm_desc;
+typedef struct artalk_pcm_take_desc {
+    const float* ring;
+    int32_t ring_cap, read_pos, n_valid, reserved;
+} artalk_pcm_take_desc;
+int artalk_pcm_create(int device, int block, int ring_blocks, int max_streams, artalk_pcm** out);
+void artalk_pcm_destroy(artalk_pcm* p);
+const char* artalk_pcm_last_error(artalk_pcm* p);
+int artalk_pcm_set_rate(artalk_pcm* p, int sample_rate, const float* taps_host, int orig, int nw, int width);
+int artalk_pcm_open(artalk_pcm* p, int sample_rate, int channels, int format, int64_t* id_out);
+int artalk_pcm_close(artalk_pcm* p, int64_t id);
+int artalk_pcm_push(artalk_pcm* p, const int64_t* ids, int n, const void* const* data, const int64_t* frames, int on_device, void* stream);
+int artalk_pcm_end(artalk_pcm* p, const int64_t* ids, int n, void* stream);
+int artalk_pcm_available(artalk_pcm* p, int64_t id, int64_t* samples, int* ended);
+int artalk_pcm_take(artalk_pcm* p, const int64_t* ids, int n, float* out_dev, int64_t out_stride, int64_t* n_valid_host, void* stream);
+int artalk_op_pcm_plan(int64_t n_before, int64_t frames, int end, int orig, int nw, int width, int64_t* out6);
+int artalk_op_pcm_desc_bytes(int which);
+int artalk_op_pcm_push(artalk_pcm_desc* descs_host, int n, void* table_dev, int64_t table_bytes, void* stream);
+int artalk_op_pcm_take(const artalk_pcm_take_desc* descs_host, int n, void* table_dev, int64_t table_bytes, float* out_dev, int64_t out_stride,
+                       int block, void* stream);
 
 /* Live streams through the head ("Live streams through the head"): many independent streams rendered by one call,
  * each frame naming its stream and its avatar.  Nothing here changes artalk_gaga_render / _render_u8, the avatar of
