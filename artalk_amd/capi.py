@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("ARTALK_LIB") or os.path.join(_HERE, "libartalk_hip.so
 OK, EINVAL, EKEY, EMISSING, EHIP, ESTATE, ECAPACITY, EBUSY = 0, -1, -2, -3, -4, -5, -6, -7
 DTYPE_F32, DTYPE_I64 = 0, 1
 FRAMES_RGB24, FRAMES_YUV420P = 1, 2      # ARTALK_FRAMES_* of include/artalk_hip.h
+JPEG_420, JPEG_444, JPEG_HEADER_BYTES = 1, 2, 629      # ARTALK_JPEG_* of include/artalk_hip.h; the header every stream starts with
 PCM_S16, PCM_F32, PCM_MAX_TAPS, PCM_MAX_CHANNELS = 1, 2, 1024, 8      # ARTALK_PCM_* of include/artalk_hip.h
 
 # every symbol include/artalk_hip.h declares (checked by tests/test_capi_symbols.py)
@@ -64,6 +65,8 @@ SYMBOLS = [
     "artalk_pcm_create", "artalk_pcm_destroy", "artalk_pcm_last_error", "artalk_pcm_set_rate", "artalk_pcm_open", "artalk_pcm_close",
     "artalk_pcm_push", "artalk_pcm_end", "artalk_pcm_available", "artalk_pcm_take", "artalk_op_pcm_plan", "artalk_op_pcm_desc_bytes",
     "artalk_op_pcm_push", "artalk_op_pcm_take",
+    "artalk_jpeg_default_cap", "artalk_jpeg_bound", "artalk_jpeg_header", "artalk_jpeg_create", "artalk_jpeg_destroy", "artalk_jpeg_last_error",
+    "artalk_jpeg_encode", "artalk_op_jpeg_check", "artalk_jpeg_set_timing", "artalk_jpeg_get_timing",
 ]
 
 # ARTALK_ATTN_* of include/artalk_hip.h: the kernels of attention.hip, as artalk_op_attention_plan names them
@@ -479,6 +482,20 @@ def lib() -> C.CDLL:
                 ("op_pcm_desc_bytes", [i32], i32),
                 ("op_pcm_push", [C.POINTER(PcmDesc), i32, vp, i64, vp], i32),
                 ("op_pcm_take", [C.POINTER(PcmTakeDesc), i32, vp, i64, vp, i64, i32, vp], i32)):
+            f = getattr(L, "artalk_" + name)
+            f.argtypes, f.restype = args, res
+    if hasattr(L, "artalk_jpeg_encode"):      # (an older build loaded through ARTALK_LIB for an A/B run lacks the JPEG encoder)
+        for name, args, res in (
+                ("jpeg_default_cap", [i32, i32], i64),
+                ("jpeg_bound", [i32, i32, i32], i64),
+                ("jpeg_header", [i32, i32, i32, i32, vp, i32], i32),
+                ("jpeg_create", [i32, C.POINTER(vp)], i32),
+                ("jpeg_destroy", [vp], None),
+                ("jpeg_last_error", [vp], C.c_char_p),
+                ("jpeg_encode", [vp, vp, i32, i32, i32, i32, i32, vp, i64, vp, vp], i32),
+                ("jpeg_set_timing", [vp, i32], i32),
+                ("jpeg_get_timing", [vp, C.POINTER(C.c_double), i32], i32),
+                ("op_jpeg_check", [i32, i32, i32, i32, i32, i64, i32, i32, i32, C.c_char_p, i32], i32)):
             f = getattr(L, "artalk_" + name)
             f.argtypes, f.restype = args, res
     L.artalk_savgol.argtypes = [vp, vp, vp, i32, vp]

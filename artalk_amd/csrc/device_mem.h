@@ -95,6 +95,16 @@ private:
     std::unique_ptr<std::remove_pointer_t<hipStream_t>, Destroy> s_;
 };
 
+// A handle's device for the length of a call: made current in the constructor, the caller's put back in the destructor
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) (void)hipSetDevice(dev); else prev = -1;
+    }
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
 // Time per stage of one call, from events on the call's stream: the interval that ENDS at a mark belongs to the mark's stage
 // (stage < 0: to none).  A mark whose event cannot be made is skipped.  Disabled, no method makes a HIP call.
 class StageTimer {

@@ -196,15 +196,6 @@ int pcm_take_desc_check(const artalk_pcm_take_desc* d, int block, std::string* e
     return ARTALK_OK;
 }
 
-struct DeviceGuard {      // the handle's device for the length of a call
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev); else prev = -1;
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 }  // namespace
 
 struct PcmRate {

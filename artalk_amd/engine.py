@@ -222,14 +222,16 @@ class ARTAvatarInferEngine:
             audio_stream.close()
         st.close()
 
-    def stream_render(self, streams, frames, spans, output=None, host=False, order="time"):
+    def stream_render(self, streams, frames, spans, output=None, host=False, order="time", jpeg=None):
         """Photoreal frames of what ``stream_step(smooth=True)`` or ``stream_flush`` returned for ``streams``: ``frames`` (n, R, 106) and
         ``spans[i] = (first, count)`` -> ``(images, index)`` from one ``GAGAvatar.render_streams`` call.  ``images`` holds
         ``sum(count)`` frames - (.., 3, S, S) in [0, 1], or with ``output="rgb24"`` / ``"yuv420p"`` the 8-bit frames of
         ``artalk_amd.frames`` (``host=True``: in pinned memory on the CPU) - in ``order`` ("time": frame k of every stream before frame
         k + 1 of any; "stream": stream by stream); ``index`` (CPU, int64) names every frame: (position in ``streams``, absolute frame
         number ``first + k``).  Every stream keeps its own forehead EMA across steps.  A stream opened without ``shape_id`` raises
-        ``ValueError``."""
+        ``ValueError``.  ``output="jpeg"`` (``jpeg=dict(quality=, subsampling=, cap=)``): ``images`` is ``(data (.., cap), sizes)``, one
+        baseline JPEG stream per frame (``artalk_amd.frames.encode_jpeg``) - with ``host=True`` what a Motion-JPEG sender puts on the
+        wire after ``frames.split_jpeg``."""
         head, flame = getattr(self, "GAGAvatar", None), getattr(self, "GAGAvatar_flame", None)
         if head is None or flame is None:
             raise RuntimeError("stream_render needs the GAGAvatar head and its scale-5 FLAME model (engine.GAGAvatar, engine.GAGAvatar_flame)")
@@ -240,7 +242,7 @@ class ARTAvatarInferEngine:
         if len(spans) != len(streams):
             raise ValueError(f"spans holds {len(spans)} entries, streams {len(streams)}")
         images, index = head.render_streams([books[st.id] for st in streams], frames, flame, counts=[int(c) for _, c in spans], order=order,
-                                            out="float" if output is None else output, host=host)
+                                            out="float" if output is None else output, host=host, jpeg=jpeg)
         if index.shape[0]:
             index[:, 1] += torch.tensor([int(f) for f, _ in spans], dtype=torch.int64)[index[:, 0]]
         return images, index
@@ -351,7 +353,7 @@ class ARTAvatarInferEngine:
 
     smooth_motion_savgol_device = smooth_motion_savgol
 
-    def rendering(self, audio, pred_motions, shape_id="mesh", shape_code=None, save_name="ARTAvatar.mp4", *, output=None):
+    def rendering(self, audio, pred_motions, shape_id="mesh", shape_code=None, save_name="ARTAvatar.mp4", *, output=None, jpeg=None):
         """Downstream of the boundary (inference.py:59-87).  Produces the vertices the reference's mesh branch would
         feed its renderer when a FLAME model has been plugged in.  With a renderer plugged into ``engine.mesh_renderer`` as well
         (``artalk_amd.render.RenderMesh``) it returns what the reference stacks into ``pred_images`` (inference.py:70-72, :83):
@@ -362,8 +364,17 @@ class ARTAvatarInferEngine:
         (``artalk_amd.frames``): uint8 ``(T, S, S, 3)`` or ``(T, S * 3 // 2, S)`` on the device, the reference's
         ``(x * 255).astype(np.uint8)`` hand-over (inference.py:83-86, app/utils_videos.py) without the host round trip;
         ``artalk_amd.frames.write_y4m`` writes the second as a file any encoder reads.  It needs images: with no renderer plugged in it
-        raises ``ValueError``.  Muxing and the audio track (PyAV) are not part of this package."""
-        if output is not None:
+        raises ``ValueError``.  Muxing and the audio track (PyAV) are not part of this package.
+
+        ``output="jpeg"`` (``jpeg=dict(quality=, subsampling=, cap=)``) returns ``(data uint8 (T, cap), sizes int64 (T,))`` on the device
+        instead: one baseline JPEG stream per frame, ``artalk_amd.frames.encode_jpeg`` of the ``"rgb24"`` frames;
+        ``artalk_amd.frames.write_mjpeg`` writes them as a Motion-JPEG file."""
+        if output == "jpeg":
+            from .frames import encode_jpeg, jpeg_options, pack_frames
+            quality, subsampling, cap = jpeg_options(jpeg)      # ValueError for a bad option, before anything runs
+        elif jpeg is not None:
+            raise ValueError('jpeg= goes with output="jpeg"')
+        elif output is not None:
             from .frames import format_code, pack_frames
             format_code(output)      # ValueError for an unknown format, before anything runs
         head = getattr(self, "GAGAvatar", None)      # (engines assembled without __init__ have no such attribute)
@@ -373,6 +384,8 @@ class ARTAvatarInferEngine:
             if flame is None:
                 raise RuntimeError("plug an artalk_amd.flame.FLAMEModel built with scale=5.0 into engine.GAGAvatar_flame")
             head.set_avatar_id(shape_id)
+            if output == "jpeg":
+                return head.render_clip(pred_motions, flame, out="jpeg", jpeg=jpeg)
             return head.render_clip(pred_motions, flame) if output is None else head.render_clip(pred_motions, flame, out=output)
         if shape_id != "mesh" or self.flame_model is None:
             raise NotImplementedError("rendering is outside the audio->motion path; plug a FLAME model into "
@@ -392,4 +405,6 @@ class ARTAvatarInferEngine:
         if renderer is None:
             return verts
         images = renderer(verts)[0] / 255.0
+        if output == "jpeg":
+            return encode_jpeg(pack_frames(images, "rgb24"), quality=quality, subsampling=subsampling, cap=cap)
         return images if output is None else pack_frames(images, output)      # the reference's / 255.0 * 255.0 round trip

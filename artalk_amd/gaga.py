@@ -108,6 +108,44 @@ class GagaStream:
             raise ValueError(f"stream {self.id} is closed")
 
 
+class _JpegPieces:
+    """The ``(data, sizes)`` result of a render call with ``out="jpeg"``, filled piece by piece: each piece of rgb24 frames is encoded on
+    the current stream into its slots (``frames.JpegEncoder``); with ``host`` its slots and sizes are then copied to the pinned result on
+    a copy stream, behind an event, while the caller renders the next piece."""
+
+    def __init__(self, T, S, device, jpeg, host):
+        quality, subsampling, cap = _frames.jpeg_options(jpeg)
+        self.cap = _frames.jpeg_default_cap(S, S) if cap is None else cap
+        self.encoder = _frames.jpeg_encoder(device, quality, subsampling)
+        self.data = torch.empty((T, self.cap), dtype=torch.uint8, device=device)
+        self.sizes = torch.empty((T,), dtype=torch.int64, device=device)
+        self.host = bool(host)
+        if self.host:
+            self.data_host = torch.empty((T, self.cap), dtype=torch.uint8, pin_memory=True)
+            self.sizes_host = torch.empty((T,), dtype=torch.int64, pin_memory=True)
+            self.copy_stream = torch.cuda.Stream(device)
+
+    def put(self, t0, rgb):
+        t1 = t0 + int(rgb.shape[0])
+        self.encoder.encode(rgb, cap=self.cap, out=(self.data[t0:t1], self.sizes[t0:t1]))
+        if self.host:
+            done = torch.cuda.Event()
+            done.record()
+            self.copy_stream.wait_event(done)
+            with torch.cuda.stream(self.copy_stream):
+                self.data_host[t0:t1].copy_(self.data[t0:t1], non_blocking=True)
+                self.sizes_host[t0:t1].copy_(self.sizes[t0:t1], non_blocking=True)
+
+    def finish(self):
+        """(also after a failure: a copy may be in flight)"""
+        if self.host:
+            torch.cuda.current_stream().wait_stream(self.copy_stream)
+            torch.cuda.current_stream().synchronize()
+
+    def result(self):
+        return (self.data_host, self.sizes_host) if self.host else (self.data, self.sizes)
+
+
 class GAGAvatar:
     """``GAGAvatar(avatars, upsampler, water_mark=None, image_size=512, n_dynamic=5023, forehead_indices=None, device="cuda")``.
 
@@ -474,7 +512,7 @@ class GAGAvatar:
         return None if self._h is None else int(capi.lib().artalk_gaga_set_slab(self._h, self._slab))
 
     @torch.no_grad()
-    def render_clip(self, motion_codes, flame_model, randomize_noise=True, noise=None, out="float", host=False):
+    def render_clip(self, motion_codes, flame_model, randomize_noise=True, noise=None, out="float", host=False, jpeg=None):
         """motion_codes (T, 106) on the device -> (T, 3, S, S) in [0, 1] on the device, from one library call.  ``flame_model``: an
         ``artalk_amd.flame.FLAMEModel`` built with ``scale=5.0``.  Unlike the reference, ``motion_codes`` is NOT modified (there
         ``transform_emoca_to_p3d`` flips the sign of columns 100 and 102 in place through a view).  ``randomize_noise=True`` draws the
@@ -484,7 +522,16 @@ class GAGAvatar:
         ``out="rgb24"`` or ``"yuv420p"`` returns the frames as a video encoder takes them instead (``artalk_amd.frames``): uint8
         ``(T, S, S, 3)`` or ``(T, S * 3 // 2, S)``, byte-equal to ``pack_frames(render_clip(...), out)``, from one
         ``artalk_gaga_render_u8`` call that never holds the fp32 clip.  With ``host=True`` the result is a pinned CPU tensor, filled slab
-        by slab while the next slab renders; the method synchronises the current stream before it returns it."""
+        by slab while the next slab renders; the method synchronises the current stream before it returns it.
+
+        ``out="jpeg"`` returns ``(data uint8 (T, cap), sizes int64 (T,))`` instead, one baseline JPEG stream per frame
+        (``artalk_amd.frames.encode_jpeg``; ``jpeg=dict(quality=, subsampling=, cap=)``, defaults 90, "420", ``jpeg_default_cap``),
+        byte-equal to ``encode_jpeg(render_clip(..., out="rgb24"))``: the clip is rendered in pieces of the slab in force, each piece
+        is encoded on the device and, with ``host=True``, copied to the pinned result while the next piece renders."""
+        if out == "jpeg":
+            return self._render_clip_jpeg(motion_codes, flame_model, randomize_noise, noise, host, jpeg)
+        if jpeg is not None:
+            raise ValueError('jpeg= goes with out="jpeg"')
         fmt = self._format(out, host)
         m = self._device_motion(self._check_motion(motion_codes), dense=False)
         T = int(m.shape[0])
@@ -593,7 +640,7 @@ class GAGAvatar:
 
     @torch.no_grad()
     def render_streams(self, streams, motion_codes, flame_model, counts=None, firsts=None, order="time", randomize_noise=True, noise=None,
-                       out="float", host=False, host_buffer=None):
+                       out="float", host=False, host_buffer=None, jpeg=None):
         """Frames of many streams from one library call (``artalk_gaga_render_streams``).  ``streams``: n open ``GagaStream``s, each at
         most once; ``motion_codes`` (n, R, 106) on the device - what ``stream_step(smooth=True)`` returns - with ``counts[i]`` valid rows
         from row ``firsts[i]`` (defaults: R and 0).  Returns ``(frames, index)``: ``frames`` (sum(counts), 3, S, S) in [0, 1], or with
@@ -602,7 +649,16 @@ class GAGAvatar:
         frame equals the frame a head of its own would render for that stream: each stream's forehead EMA walks its own frames only.
         Noise as in ``render_clip`` (a per-frame ``noise`` follows the order of ``frames``).  ``host_buffer``: with ``host=True``, a
         pinned uint8 tensor of the result's shape to fill and return instead of a new one - it is filled slab by slab, so another
-        thread of a live sender can take a slab's frames out of it while the later slabs still render."""
+        thread of a live sender can take a slab's frames out of it while the later slabs still render.
+
+        ``out="jpeg"``: ``((data, sizes), index)`` with one JPEG stream per frame as in ``render_clip`` (``jpeg=`` as there; no
+        ``host_buffer``), the frames in the same order and byte-equal to ``encode_jpeg`` of the ``out="rgb24"`` frames."""
+        if out == "jpeg":
+            if host_buffer is not None:
+                raise ValueError('host_buffer goes with out="rgb24" or out="yuv420p"')
+            return self._render_streams_jpeg(streams, motion_codes, flame_model, counts, firsts, order, randomize_noise, noise, host, jpeg)
+        if jpeg is not None:
+            raise ValueError('jpeg= goes with out="jpeg"')
         fmt = self._format(out, host)
         streams = list(streams)
         for st in streams:
@@ -663,3 +719,76 @@ class GAGAvatar:
                 torch.cuda.current_stream().synchronize()      # (also after a failure: a copy may be in flight)
         self._raise_rc(rc, "artalk_gaga_render_streams")
         return (res_host if host else res), index
+
+    # ---- JPEG out: the render calls in pieces of a slab, each piece encoded on the device ("JPEG out") ----
+    def _noise_rows(self, noise, T, rows):
+        """The given per-layer noise for the frames ``rows`` (a slice or an index tensor) of a call over T frames."""
+        if noise is None:
+            return None
+        for i, n in enumerate(noise):
+            if not isinstance(n, torch.Tensor) or n.dim() != 4 or n.shape[0] not in (1, T):
+                raise ValueError(f"noise[{i}] must be a CUDA tensor of shape (1 or {T}, 1, r, r)")
+        return [n if n.shape[0] == 1 else n[rows] for n in noise]
+
+    def _render_clip_jpeg(self, motion_codes, flame_model, randomize_noise, noise, host, jpeg):
+        m = self._device_motion(self._check_motion(motion_codes), dense=False)
+        T = int(m.shape[0])
+        with torch.cuda.device(m.device):
+            pieces = _JpegPieces(T, self.image_size, m.device, jpeg, host)
+            self._ensure(flame_model)
+            slab = max(1, int(self.slab_in_force()))
+            try:
+                for t0 in range(0, T, slab):
+                    t1 = min(T, t0 + slab)
+                    rgb = self.render_clip(m[t0:t1], flame_model, randomize_noise=randomize_noise, noise=self._noise_rows(noise, T, slice(t0, t1)),
+                                           out="rgb24")
+                    pieces.put(t0, rgb)
+            finally:
+                pieces.finish()
+        return pieces.result()
+
+    def _render_streams_jpeg(self, streams, motion_codes, flame_model, counts, firsts, order, randomize_noise, noise, host, jpeg):
+        streams = list(streams)
+        m = motion_codes
+        if not isinstance(m, torch.Tensor) or m.dim() != 3 or m.shape[2] < MOTION_DIM or m.shape[0] != len(streams):
+            raise ValueError(f"motion_codes must be a ({len(streams)}, R, {MOTION_DIM}) tensor: one block of rows per listed stream")
+        m = self._device_motion(m, dense=True)
+        n, R = int(m.shape[0]), int(m.shape[1])
+        counts = [R] * n if counts is None else [int(c) for c in counts]
+        firsts = [0] * n if firsts is None else [int(f) for f in firsts]
+        if len(counts) != n or len(firsts) != n:
+            raise ValueError(f"counts and firsts must hold {n} entries each")
+        rows, which, ks = self.plan_frames(counts, order, firsts, R)
+        if any(f + c > R for f, c in zip(firsts, counts)):
+            raise ValueError(f"a stream's rows firsts[i] .. firsts[i] + counts[i] must lie within its {R} rows")
+        T = len(rows)
+        index = torch.tensor([which, ks], dtype=torch.int64).t().contiguous().reshape(T, 2)
+        with torch.cuda.device(m.device):
+            pieces = _JpegPieces(T, self.image_size, m.device, jpeg, host)
+            # a call over no frames checks the streams, reserves the pool and uploads the avatars: the slab in force is the pool's after it
+            self.render_streams(streams, m, flame_model, counts=[0] * n, firsts=firsts, order=order, out="rgb24")
+            slab = max(1, int(self.stream_slab_in_force()))
+            try:
+                for t0 in range(0, T, slab):
+                    t1 = min(T, t0 + slab)
+                    # the piece's frames of stream i are consecutive: k_lo[i] .. k_lo[i] + c[i] - 1
+                    c, k_lo = [0] * n, [0] * n
+                    for t in range(t0, t1):
+                        if c[which[t]] == 0:
+                            k_lo[which[t]] = ks[t]
+                        c[which[t]] += 1
+                    place = {(which[t], ks[t]): t - t0 for t in range(t0, t1)}
+                    _, sub_which, sub_ks = self.plan_frames(c, order)
+                    # frame q of the piece's own call is frame to[q] of the piece in this call's order
+                    to = [place[(i, k_lo[i] + k)] for i, k in zip(sub_which, sub_ks)]
+                    straight = to == list(range(t1 - t0))
+                    to_dev = None if straight else torch.tensor(to, dtype=torch.int64, device=m.device)
+                    sub_noise = self._noise_rows(noise, T, slice(t0, t1) if straight else to_dev + t0)
+                    rgb, _ = self.render_streams(streams, m, flame_model, counts=c, firsts=[f + k for f, k in zip(firsts, k_lo)], order=order,
+                                                 randomize_noise=randomize_noise, noise=sub_noise, out="rgb24")
+                    if not straight:
+                        rgb = torch.empty_like(rgb).index_copy_(0, to_dev, rgb)
+                    pieces.put(t0, rgb)
+            finally:
+                pieces.finish()
+        return pieces.result(), index

@@ -463,6 +463,43 @@ int artalk_gaga_render_u8(artalk_gaga* g, const float* motion_dev, int64_t motio
                           const int64_t* noise_batch_strides, int activation, int format, uint8_t* out_dev, uint8_t* out_host_or_null,
                           void* stream);
 
+/* JPEG out ("JPEG out"): rgb24 frames [F][H][W][3] on the device (what artalk_frames_pack writes) -> one baseline
+ * JPEG stream per frame, out_dev [F][cap] and sizes_dev [F], all on the device: what a Motion-JPEG sender puts on the wire.  The stream is
+ * defined exactly, in integers: SOI, JFIF 1.1 APP0, two DQT, SOF0 (Y Cb Cr, 4:2:0 or 4:4:4), the four Annex K DHT, DRI = the
+ * MCUs of one MCU row, SOS, the scan with RSTn after every MCU row but the last, EOI; full-range BT.601, libjpeg's quality scaling of
+ * the Annex K tables.  The header is 629 bytes.  Byte parity with libjpeg is unpinned.
+ * artalk_jpeg_default_cap: H W 3 + 1024, enough for any but noise-like pictures at the highest qualities.  artalk_jpeg_bound: enough for
+ * every picture: 20 + 63 x 26 bits per block, every byte stuffed, two marker bytes per MCU row, the header.  Both: ARTALK_EINVAL for H or W
+ * outside 1..16384 (the bound also for an unknown subsampling).
+ * artalk_jpeg_header: the 629 header bytes of a size, quality and subsampling into host memory (host only); returns 629.
+ * artalk_jpeg_encode: two launches on `stream` for all F frames, no host wait: every count the host needs is arithmetic on H, W and the
+ * subsampling.  sizes[f] = the bytes of frame f's stream at out[f * cap]; a stream that does not fit cap gives sizes[f] = -(the bytes it
+ * needs) and its slot's content is unspecified, as are the bytes of a slot behind sizes[f].  Nothing outside [f cap, (f + 1) cap) is
+ * written for frame f.  rgb needs no alignment.  Byte-identical from run to run.  The encoder owns its scratch (the worst case of the
+ * call's segments, grown by doubling) and one uploaded header per (H, W, quality, subsampling); the first call of a size, and a call that
+ * grows scratch, waits for `stream` and is refused while `stream` is being captured.  F == 0 succeeds and launches nothing.
+ * ARTALK_EINVAL with a message (artalk_jpeg_last_error; of a NULL encoder: the thread's last message) before the device is touched:
+ * quality outside 1..100, an unknown subsampling, H or W outside 1..16384, F < 0 or above 65535, a NULL pointer with F > 0,
+ * cap < 629 + 2.  artalk_op_jpeg_check (host only): the same checks on plain numbers; returns the code and copies the message.
+ * artalk_jpeg_set_timing (default off; ARTALK_EINVAL for a NULL encoder): events around the two launches; a timed call waits for its last
+ * launch.  artalk_jpeg_get_timing: launch_ms[0 .. min(n, 2)) = the rows kernel (colour, DCT, quantisation, entropy coding) and the pack
+ * kernel (stuffing, markers, header) of the last timed call; returns 2. */
+#define ARTALK_JPEG_420 1
+#define ARTALK_JPEG_444 2
+typedef struct artalk_jpeg artalk_jpeg;
+int64_t artalk_jpeg_default_cap(int H, int W);
+int64_t artalk_jpeg_bound(int H, int W, int subsampling);
+int artalk_jpeg_header(int H, int W, int quality, int subsampling, uint8_t* out_host, int out_cap);
+int artalk_jpeg_create(int device, artalk_jpeg** out);
+void artalk_jpeg_destroy(artalk_jpeg* j);
+const char* artalk_jpeg_last_error(artalk_jpeg* j);
+int artalk_jpeg_encode(artalk_jpeg* j, const uint8_t* rgb_dev, int F, int H, int W, int quality, int subsampling, uint8_t* out_dev, int64_t cap,
+                       int64_t* sizes_dev, void* stream);
+int artalk_jpeg_set_timing(artalk_jpeg* j, int enable);
+int artalk_jpeg_get_timing(const artalk_jpeg* j, double* launch_ms, int n);
+int artalk_op_jpeg_check(int F, int H, int W, int quality, int subsampling, int64_t cap, int have_rgb, int have_out, int have_sizes, char* msg,
+                         int msg_cap);
+
 /* Live audio in ("Live audio in"): raw PCM packets of any size -> the model's 16 kHz mono blocks, on the device.  A
  * streaming form of torchaudio's Resample(sr, 16000)(x).mean(dim=0) (inference.py:230-231): the 16 kHz samples are bit for bit those of
  * artalk_op_resample_mean on the whole concatenated signal, whatever the packet sizes.  An object of its own, not tied to a model handle.
