@@ -16,8 +16,8 @@ namespace {
 // device of the model and the stream of this call: the caller's, or the model's own (graph capture needs a real stream)
 int call_stream(artalk_model* m, void* stream, hipStream_t* s) {
     (void)hipSetDevice(m->device);
-    if (!stream && !m->own_stream) HIPCHK(m, hipStreamCreate(&m->own_stream));
-    *s = stream ? (hipStream_t)stream : m->own_stream;
+    if (!stream && !m->own_stream.create(hipStreamDefault)) return fail(m, ARTALK_EHIP, "creating the model's own stream failed");
+    *s = stream ? (hipStream_t)stream : m->own_stream.get();
     return ARTALK_OK;
 }
 // the style flags of a call, checked before anything is enqueued or any state changes; *encode = some clip brings a style clip (flag 1)
@@ -43,15 +43,14 @@ int grow_sessions(artalk_model* m, int64_t n_slots) {
     artalk_model::Sessions& ss = m->sess;
     if (m->cfg.code_dim % 4) return fail(m, ARTALK_EINVAL, "sessions need a code_dim that is a multiple of 4 (16-byte rows)");
     while ((int64_t)ss.owner.size() < n_slots) {
-        void* p = nullptr;
-        HIPCHK(m, hipMalloc(&p, (size_t)artalk_model::kSessBlock * m->sess_slot_floats() * sizeof(float)));
-        ss.blocks.push_back(static_cast<float*>(p));
+        DevBuf<float> block;
+        if (!block.alloc((size_t)artalk_model::kSessBlock * m->sess_slot_floats())) return fail(m, ARTALK_EHIP, "hipMalloc failed for a block of session slots");
+        ss.blocks.emplace_back(std::move(block));      // (the vector may move its owners; the device blocks stay where they are)
         ss.owner.resize(ss.owner.size() + artalk_model::kSessBlock, 0);
     }
-    if (ss.smooth_cap < (int64_t)ss.owner.size()) {      // the table of artalk_session_smooth: one row per slot is always enough (hipFree waits for the device)
-        if (ss.smooth_tab) (void)hipFree(ss.smooth_tab);
-        ss.smooth_tab = nullptr; ss.smooth_cap = 0;
-        HIPCHK(m, hipMalloc(&ss.smooth_tab, ss.owner.size() * (sizeof(float*) + sizeof(int4))));
+    if (ss.smooth_cap < (int64_t)ss.owner.size()) {      // the table of artalk_session_smooth: one row per slot is always enough (freeing the old one waits for the device)
+        ss.smooth_cap = 0;
+        if (!ss.smooth_tab.alloc(ss.owner.size() * (sizeof(float*) + sizeof(int4)))) return fail(m, ARTALK_EHIP, "hipMalloc failed for the table of artalk_session_smooth");
         ss.smooth_cap = (int64_t)ss.owner.size();
     }
     return ARTALK_OK;
@@ -126,8 +125,8 @@ int smooth_check(artalk_model::Sessions& ss, const int64_t* ids, int n, bool hav
 namespace {
 // the device table of this call's slots (row i = slot[i]) through the pinned slot `stg`; the caller records stg->done afterwards
 int stage_session_slots(artalk_model* m, hipStream_t s, artalk_model::Stage* stg, const int* slot, int n) {
-    for (int i = 0; i < n; ++i) stg->slots[i] = m->sess_slot(slot[i]);
-    HIPCHK(m, hipMemcpyAsync(m->ws.sess_slots, stg->slots, (size_t)n * sizeof(float*), hipMemcpyHostToDevice, s));
+    for (int i = 0; i < n; ++i) stg->slots.get()[i] = m->sess_slot(slot[i]);
+    HIPCHK(m, hipMemcpyAsync(m->ws.sess_slots, stg->slots.get(), (size_t)n * sizeof(float*), hipMemcpyHostToDevice, s));
     return ARTALK_OK;
 }
 
@@ -168,7 +167,7 @@ int artalk_infer_samples(artalk_model* m, const float* audio_dev, int64_t audio_
     // chunk list, chunk-index major: chunk (j, b) for all b with n_chunks[b] > j  -> active clips are a prefix
     artalk_model::Stage* stg = nullptr;
     if (int rc = next_stage(m, &stg)) return rc;
-    long* src = stg->src;
+    long* src = stg->src.get();
     std::vector<int> base((size_t)maxch + 1, 0), Bj((size_t)maxch, 0);
     {
         int idx = 0;
@@ -315,9 +314,9 @@ int artalk_stream_chunk(artalk_model* m, const float* audio_dev, int64_t chunk_s
     if (B > w.maxB) return fail(m, ARTALK_ESTATE, "workspace was re-reserved since artalk_stream_begin; begin again");
     artalk_model::Stage* stg = nullptr;
     if (int rc = next_stage(m, &stg)) return rc;
-    for (int b = 0; b < B; ++b) stg->src[b] = (long)b * chunk_stride;
-    HIPCHK(m, hipMemcpyAsync(w.src_off, stg->src, B * sizeof(long), hipMemcpyHostToDevice, s));
-    HIPCHK(m, hipEventRecord(stg->done, s));
+    for (int b = 0; b < B; ++b) stg->src.get()[b] = (long)b * chunk_stride;
+    HIPCHK(m, hipMemcpyAsync(w.src_off, stg->src.get(), B * sizeof(long), hipMemcpyHostToDevice, s));
+    HIPCHK(m, hipEventRecord(stg->done.get(), s));
     stg->used = true;
     ProfilingOff quiet(m);      // restored on every exit path
     for (int c0 = 0; c0 < B; c0 += w.G) run_wav2vec(m, audio_dev, c0, std::min(w.G, B - c0), nullptr, s);
@@ -393,10 +392,10 @@ int artalk_session_step(artalk_model* m, const int64_t* ids, int n, const float*
     Workspace& w = m->ws;
     artalk_model::Stage* stg = nullptr;
     if (int rc = next_stage(m, &stg)) return rc;
-    for (int b = 0; b < n; ++b) stg->src[b] = (long)b * chunk_stride;
-    HIPCHK(m, hipMemcpyAsync(w.src_off, stg->src, n * sizeof(long), hipMemcpyHostToDevice, s));
+    for (int b = 0; b < n; ++b) stg->src.get()[b] = (long)b * chunk_stride;
+    HIPCHK(m, hipMemcpyAsync(w.src_off, stg->src.get(), n * sizeof(long), hipMemcpyHostToDevice, s));
     if (int rc = stage_session_slots(m, s, stg, slot.data(), n)) return rc;
-    HIPCHK(m, hipEventRecord(stg->done, s));
+    HIPCHK(m, hipEventRecord(stg->done.get(), s));
     stg->used = true;
     m->stream_B = 0; m->stream_scales_ended = false;      // (see artalk_session_open)
     HIPCHK(m, hipMemsetAsync(w.status, 0, 4 * sizeof(int), s));      // every step has a status word, and a ticket, of its own
@@ -447,14 +446,14 @@ int artalk_session_smooth(artalk_model* m, const int64_t* ids, int n, const floa
     artalk_model::Stage* stg = nullptr;
     if (int rc = next_stage(m, &stg)) return rc;
     for (int i = 0; i < n; ++i) {
-        stg->slots[i] = m->sess_slot(st[i]->slot);
-        stg->smooth[i] = make_int4((int)st[i]->seen, n_frames ? n_frames[i] : 100, last && last[i] ? 1 : 0, 0);
+        stg->slots.get()[i] = m->sess_slot(st[i]->slot);
+        stg->smooth.get()[i] = make_int4((int)st[i]->seen, n_frames ? n_frames[i] : 100, last && last[i] ? 1 : 0, 0);
     }
-    float** slots_dev = static_cast<float**>(ss.smooth_tab);
+    float** slots_dev = reinterpret_cast<float**>(ss.smooth_tab.get());
     int4* meta_dev = reinterpret_cast<int4*>(slots_dev + ss.smooth_cap);
-    HIPCHK(m, hipMemcpyAsync(slots_dev, stg->slots, (size_t)n * sizeof(float*), hipMemcpyHostToDevice, s));
-    HIPCHK(m, hipMemcpyAsync(meta_dev, stg->smooth, (size_t)n * sizeof(int4), hipMemcpyHostToDevice, s));
-    HIPCHK(m, hipEventRecord(stg->done, s));
+    HIPCHK(m, hipMemcpyAsync(slots_dev, stg->slots.get(), (size_t)n * sizeof(float*), hipMemcpyHostToDevice, s));
+    HIPCHK(m, hipMemcpyAsync(meta_dev, stg->smooth.get(), (size_t)n * sizeof(int4), hipMemcpyHostToDevice, s));
+    HIPCHK(m, hipEventRecord(stg->done.get(), s));
     stg->used = true;
     launch_savgol_stream(slots_dev, meta_dev, (long)m->sess_carry_off(), raw_dev, (long)raw_stride, out_dev, (long)out_stride, n,
                          m->cfg.motion_dim, s);

@@ -1,4 +1,5 @@
-// Owners of what the host side takes from the HIP runtime: device blocks, pinned host blocks, events, streams, the events of a stage or call timer.
+// Owners of what the host side takes from the HIP runtime: device blocks and pools of them, pinned host blocks, events, streams, graph
+// executables, the events of a stage or call timer.
 // Host code only.  Every type is move-only, takes nothing in its constructor and gives back what it holds in its destructor, so an
 // object made of them is destroyed by `delete` and an early return leaks nothing.  A call that fails leaves its object empty
 // (capacity 0), clears the runtime's last error - the caller reports the failure once, and it does not come back from a later
@@ -61,14 +62,35 @@ public:
     }
 };
 
+// Device blocks that live and die together (the engine's weights, its workspace): take() hands out zero-filled blocks, the first
+// failure is remembered in ok() - as WeightStore does for uploads - and clear() frees every block and forgets it.
+class DevPool {
+public:
+    // zero-filled block of max(n, 1) elements (the fill runs on the null stream), or null
+    template <typename T>
+    T* take(int64_t n) {
+        DevBuf<unsigned char> b;
+        if (!b.alloc_zero((size_t)(n > 0 ? n : 1) * sizeof(T))) { ok_ = false; return nullptr; }
+        blocks_.push_back(std::move(b));
+        return reinterpret_cast<T*>(blocks_.back().get());
+    }
+    bool ok() const { return ok_; }
+    void clear() { blocks_.clear(); ok_ = true; }
+
+private:
+    std::vector<DevBuf<unsigned char>> blocks_;
+    bool ok_ = true;
+};
+
 class Event {
 public:
     hipEvent_t get() const { return e_.get(); }
     void reset() { e_.reset(); }
-    bool create() {
+    // flags: hipEventDefault (the event can be timed) or hipEventDisableTiming
+    bool create(unsigned flags = hipEventDefault) {
         if (e_) return true;
         hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); return false; }
+        if (hipEventCreateWithFlags(&e, flags) != hipSuccess) { (void)hipGetLastError(); return false; }
         e_.reset(e);
         return true;
     }
@@ -78,21 +100,42 @@ private:
     std::unique_ptr<std::remove_pointer_t<hipEvent_t>, Destroy> e_;
 };
 
-// A non-blocking stream of the current device (a copy stream beside the caller's)
+// A stream of the current device: non-blocking (a copy stream beside the caller's), blocking (the engine's own stream for callers
+// that pass none), or restricted to the compute units of a mask
 class Stream {
 public:
     hipStream_t get() const { return s_.get(); }
-    bool create() {
-        if (s_) return true;
+    void reset() { s_.reset(); }
+    bool create(unsigned flags = hipStreamNonBlocking) {
         hipStream_t s = nullptr;
-        if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); return false; }
-        s_.reset(s);
-        return true;
+        return s_ || keep(hipStreamCreateWithFlags(&s, flags), s);
+    }
+    bool create_masked(const uint32_t* words, int n) {
+        hipStream_t s = nullptr;
+        return s_ || keep(hipExtStreamCreateWithCUMask(&s, (uint32_t)n, words), s);
     }
 
 private:
+    bool keep(hipError_t e, hipStream_t s) {
+        if (e != hipSuccess) { (void)hipGetLastError(); return false; }
+        s_.reset(s);
+        return true;
+    }
     struct Destroy { void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); } };
     std::unique_ptr<std::remove_pointer_t<hipStream_t>, Destroy> s_;
+};
+
+// One instantiated graph
+class GraphExec {
+public:
+    GraphExec() = default;
+    explicit GraphExec(hipGraphExec_t g) : g_(g) {}
+    hipGraphExec_t get() const { return g_.get(); }
+    void reset() { g_.reset(); }
+
+private:
+    struct Destroy { void operator()(hipGraphExec_t g) const { (void)hipGraphExecDestroy(g); } };
+    std::unique_ptr<std::remove_pointer_t<hipGraphExec_t>, Destroy> g_;
 };
 
 // A handle's device for the length of a call: made current in the constructor, the caller's put back in the destructor
@@ -194,16 +237,5 @@ struct WsLayout {
     int64_t off = 0;
     int64_t take(int64_t n) { const int64_t at = off; off += (n + 3) & ~(int64_t)3; return at; }
 };
-
-// zero-filled device block whose pointer goes into `pool` (a null entry records a failure): the engine's weight and workspace pools
-template <typename T>
-T* dalloc_in(std::vector<void*>& pool, int64_t n) {
-    void* p = nullptr;
-    if (n <= 0) n = 1;
-    if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) { pool.push_back(nullptr); return nullptr; }
-    (void)hipMemset(p, 0, n * sizeof(T));
-    pool.push_back(p);
-    return reinterpret_cast<T*>(p);
-}
 
 }  // namespace artalk

@@ -28,11 +28,11 @@ bool ktimer_events(hipEvent_t* e0, hipEvent_t* e1) {
     KernelTimer* t = g_ktimer;
     if (!t) return false;
     while (t->pool.size() < t->used + 2) {
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) return false;
-        t->pool.push_back(e);
+        Event e;
+        if (!e.create()) return false;
+        t->pool.push_back(std::move(e));
     }
-    *e0 = t->pool[t->used]; *e1 = t->pool[t->used + 1];
+    *e0 = t->pool[t->used].get(); *e1 = t->pool[t->used + 1].get();
     t->recs.emplace_back(t->bucket, t->used);
     t->used += 2;
     return true;
@@ -41,15 +41,16 @@ bool ktimer_events(hipEvent_t* e0, hipEvent_t* e1) {
 
 namespace {
 // ------------------------------------------------------------------------------------------------ profiling
-hipEvent_t next_event(artalk_model* m, hipStream_t s, size_t* idx) {
+// records the next event of the pool on s; false: the event cannot be made, nothing is recorded and the caller skips its mark or pair
+bool next_event(artalk_model* m, hipStream_t s, size_t* idx) {
     if (m->ev_used == m->ev_pool.size()) {
-        hipEvent_t e;
-        (void)hipEventCreate(&e);
-        m->ev_pool.push_back(e);
+        Event e;
+        if (!e.create()) return false;
+        m->ev_pool.push_back(std::move(e));
     }
     *idx = m->ev_used++;
-    (void)hipEventRecord(m->ev_pool[*idx], s);
-    return m->ev_pool[*idx];
+    (void)hipEventRecord(m->ev_pool[*idx].get(), s);
+    return true;
 }
 void kbucket(artalk_model* m, int b) { m->ktimer.bucket = b; }
 }  // namespace
@@ -58,8 +59,7 @@ namespace artalk {      // called from other files: declared in model.h
 void stage_mark(artalk_model* m, hipStream_t s, int bucket) {
     if (!m->profiling || m->in_graph_body) return;
     size_t i;
-    next_event(m, s, &i);
-    m->marks.emplace_back(bucket, i);
+    if (next_event(m, s, &i)) m->marks.emplace_back(bucket, i);
 }
 }  // namespace artalk
 
@@ -123,14 +123,10 @@ bool gemm(artalk_model* m, const GemmArgs& g0, hipStream_t s, const LnArgs* fuse
         }
     }
     if (g.a_packed && plan.path == GEMM_F32) { m->err = "internal: P8 activation handed to an fp32 GEMM"; m->sticky_error = true; return false; }
-    const bool timed = m->profiling && plan.dominant && !m->in_body;
     size_t i0 = 0, i1 = 0;
-    if (timed) next_event(m, s, &i0);
+    const bool timed = m->profiling && plan.dominant && !m->in_body && next_event(m, s, &i0);
     run_gemm(g, plan, fuse_ln, s);
-    if (timed) {
-        next_event(m, s, &i1);
-        m->dom_events.emplace_back(i0, gemm_flops(g));
-    }
+    if (timed && next_event(m, s, &i1)) m->dom_events.emplace_back(i0, gemm_flops(g));      // (i1 == i0 + 1: artalk_get_profile)
     return plan.fused_ln;
 }
 
@@ -418,7 +414,7 @@ int run_init_history(artalk_model* m, int B, hipStream_t s) {
         HIPCHK(m, hipMemcpyAsync(ih.fdec, w.prev_fdec, nf, hipMemcpyDeviceToDevice, s));
         HIPCHK(m, hipMemcpyAsync(ih.msfeat, w.msfeat, nm, hipMemcpyDeviceToDevice, s));
         // The cache is complete before this call returns to its caller's enqueue loop: a later call on ANOTHER stream reads it with no
-        // ordering against this fill otherwise.  Once per model and mode, beside the hipMalloc above.  A fill that raised a
+        // ordering against this fill otherwise.  Once per model and mode, beside the allocation above.  A fill that raised a
         // health flag (the range guard of the P8 format, a non-finite value) is NOT kept: every later call would reuse the damaged
         // history with a clean status word; it is recomputed - and flagged again - by the next call instead.
         int flags[4] = {0, 0, 0, 0};
@@ -584,14 +580,11 @@ Workspace clip_view(const artalk_model* m, int b0, int branch) {
 // HIP multiplexes streams onto a few hardware queues (4 by default): every extra stream a process creates can end up sharing a
 // queue with the caller's stream and serialise the branches, so side streams are created lazily and only as many as are used.
 int ensure_side_streams(artalk_model* m, int n) {
-    if (!m->fork_ev) HIPCHK(m, hipEventCreateWithFlags(&m->fork_ev, hipEventDisableTiming));
-    for (int i = 0; i < n && i < 3; ++i) {
-        if (m->side_stream[i]) continue;
-        if (m->cu_mask.empty()) HIPCHK(m, hipStreamCreateWithFlags(&m->side_stream[i], hipStreamNonBlocking));
-        else HIPCHK(m, hipExtStreamCreateWithCUMask(&m->side_stream[i], (uint32_t)m->cu_mask.size(), m->cu_mask.data()));
-        HIPCHK(m, hipEventCreateWithFlags(&m->join_ev[i], hipEventDisableTiming));
-    }
-    return ARTALK_OK;
+    bool ok = m->fork_ev.create(hipEventDisableTiming);
+    for (int i = 0; ok && i < n && i < 3; ++i)      // (a create on a member that holds something keeps it)
+        ok = (m->cu_mask.empty() ? m->side_stream[i].create() : m->side_stream[i].create_masked(m->cu_mask.data(), (int)m->cu_mask.size())) &&
+             m->join_ev[i].create(hipEventDisableTiming);
+    return ok ? ARTALK_OK : fail(m, ARTALK_EHIP, "creating the side streams of the clip groups and their events failed");
 }
 int body_branches(const artalk_model* m, int B) {
     // measured at batch 32: 1 branch 54.9 ms, 2 branches 49.5 ms, 4 branches 77-120 ms (queue sharing / contention)
@@ -617,7 +610,6 @@ int evict_graphs(artalk_model* m, const long long* keep, int n_keep) {
         }
         if (victim == m->graphs.end()) break;
         HIPCHK(m, hipDeviceSynchronize());      // the victim may still be running on a side stream of an earlier call
-        (void)hipGraphExecDestroy(victim->second.exec);
         m->graphs.erase(victim);
     }
     return ARTALK_OK;
@@ -649,7 +641,7 @@ int run_body(artalk_model* m, int B, hipStream_t s, int n_next) {
     const bool fork = g.n > 1 && m->profiling != 3;
     if (fork) { if (int rc = ensure_side_streams(m, g.n - 1)) return rc; }
     hipStream_t st[4] = {s, s, s, s};
-    for (int h = 1; fork && h < g.n; ++h) st[h] = m->side_stream[h - 1];
+    for (int h = 1; fork && h < g.n; ++h) st[h] = m->side_stream[h - 1].get();
     Workspace views[4];
     for (int h = 0; h < g.n; ++h) views[h] = clip_view(m, g.b0[h], h);
     auto launch_group = [&](int h) { m->view = &views[h]; run_chunk_body(m, g.b0[h + 1] - g.b0[h], st[h], g.nre[h]); m->view = nullptr; };
@@ -666,20 +658,20 @@ int run_body(artalk_model* m, int B, hipStream_t s, int n_next) {
         HIPCHK(m, hipStreamEndCapture(st[h], &graph));
         HIPCHK(m, hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
         (void)hipGraphDestroy(graph);
-        m->graphs.emplace(g.key[h], artalk_model::GraphEntry{exec, ++m->graph_clock});
+        m->graphs.emplace(g.key[h], artalk_model::GraphEntry{GraphExec(exec), ++m->graph_clock});
         ++m->graph_captures;
     }
     if (fork) {
-        HIPCHK(m, hipEventRecord(m->fork_ev, s));
-        for (int h = 1; h < g.n; ++h) HIPCHK(m, hipStreamWaitEvent(st[h], m->fork_ev, 0));
+        HIPCHK(m, hipEventRecord(m->fork_ev.get(), s));
+        for (int h = 1; h < g.n; ++h) HIPCHK(m, hipStreamWaitEvent(st[h], m->fork_ev.get(), 0));
     }
     for (int h = 0; h < g.n; ++h) {
-        if (g.graphs) HIPCHK(m, hipGraphLaunch(m->graphs[g.key[h]].exec, st[h]));
+        if (g.graphs) HIPCHK(m, hipGraphLaunch(m->graphs[g.key[h]].exec.get(), st[h]));
         else launch_group(h);
     }
     for (int h = 1; fork && h < g.n; ++h) {
-        HIPCHK(m, hipEventRecord(m->join_ev[h - 1], st[h]));
-        HIPCHK(m, hipStreamWaitEvent(s, m->join_ev[h - 1], 0));
+        HIPCHK(m, hipEventRecord(m->join_ev[h - 1].get(), st[h]));
+        HIPCHK(m, hipStreamWaitEvent(s, m->join_ev[h - 1].get(), 0));
     }
     return ARTALK_OK;
 }
@@ -694,10 +686,10 @@ int begin_clips(artalk_model* m, hipStream_t s, int B, const float* style_motion
     Workspace& w = m->ws;
     if (!has_style) style_motion_dev = nullptr;
     if (style_motion_dev) {
-        std::memcpy(stg->has, has_style, (size_t)B);
-        HIPCHK(m, hipMemcpyAsync(w.has_style, stg->has, B, hipMemcpyHostToDevice, s));
+        std::memcpy(stg->has.get(), has_style, (size_t)B);
+        HIPCHK(m, hipMemcpyAsync(w.has_style, stg->has.get(), B, hipMemcpyHostToDevice, s));
     }
-    HIPCHK(m, hipEventRecord(stg->done, s));   // pinned slot: no synchronisation, the slot is reused kStageSlots calls later
+    HIPCHK(m, hipEventRecord(stg->done.get(), s));   // pinned slot: no synchronisation, the slot is reused kStageSlots calls later
     stg->used = true;
     HIPCHK(m, hipMemsetAsync(w.status, 0, 4 * sizeof(int), s));
     stage_mark(m, s, PB_OTHER);

@@ -3,6 +3,9 @@
 // so a sequence of them can be captured into a hipGraph.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "device_mem.h"
+
 #include <climits>
 #include <cstdint>
 
@@ -19,7 +22,7 @@ namespace artalk {
 // without the gap to its neighbours.  Durations are summed per bucket (a stage of the path, a scale step of the body).
 struct KernelTimer {
     int bucket = 0;
-    std::vector<hipEvent_t> pool; size_t used = 0;
+    std::vector<Event> pool; size_t used = 0;
     std::vector<std::pair<int, size_t>> recs;      // (bucket, index of the start event; the stop event is the next one)
 };
 extern thread_local KernelTimer* g_ktimer;          // engine.hip; null = plain launches

@@ -128,8 +128,8 @@ struct artalk_model {
     std::string err;
     bool finalized = false;
     std::map<std::string, Slot> slots;
-    std::vector<void*> allocs;      // weights (model lifetime)
-    std::vector<void*> ws_allocs;   // workspace (re-allocated when a larger batch arrives)
+    DevPool weights;                // weights and what lives as long: packed and bf16 copies, audit block, initial-history cache
+    DevPool ws_pool;                // workspace (re-allocated when a larger batch arrives)
     int64_t weight_bytes = 0;
     struct PackRange { const float* base; int64_t n; unsigned int* packed; uint16_t* bf16; };
     std::vector<PackRange> wranges;   // every weight allocation, its packed f16x3 copy (built at finalize) and its bf16 copy (built on
@@ -139,7 +139,7 @@ struct artalk_model {
     int splitk_tiles = 192, splitk_target = 384;   // split-K when the grid has fewer tiles than splitk_tiles; aim at splitk_target workgroups
     // headroom audit (artalk_set_audit): max |x| * 16 at every producer of a P8 operand, by site name
     bool audit = false;
-    unsigned int* audit_vals = nullptr;            // device, kAuditSlots floats (as bits)
+    unsigned int* audit_vals = nullptr;            // device (of `weights`), kAuditSlots floats (as bits)
     std::vector<std::string> audit_names;
     std::map<std::string, int> audit_index;
     std::vector<int*> audit_exp;                   // the site's exponent (SiteExps member) per audit slot: what artalk_calibrate adjusts
@@ -170,7 +170,7 @@ struct artalk_model {
     // needs - it is scratch, and the batch call, lockstep streaming, artalk_style_encode and workspace growth may use it freely.
     static constexpr int kSessBlock = 32;
     struct Sessions {
-        std::vector<float*> blocks;                // device blocks of kSessBlock slots
+        std::vector<DevBuf<float>> blocks;         // device blocks of kSessBlock slots
         std::vector<int64_t> owner;                // per slot: the id of the session that holds it, 0 = free
         // an open session: its slot, and where its streaming smoother stands (artalk_session_smooth): raw frames consumed, and whether
         // a `last` call has emitted the tail.  Born zero with the id, dropped with it: a slot reused under a new id starts clean.
@@ -178,13 +178,13 @@ struct artalk_model {
         std::map<int64_t, Open> open;              // id -> state
         std::set<int64_t> ended_by_scales;         // ids a change of site scales closed (a step on one says so; artalk_session_close forgets it)
         int64_t next_id = 1;                       // ids are never reused during the model's life
-        void* smooth_tab = nullptr; int64_t smooth_cap = 0;      // device table of one artalk_session_smooth call: [cap slot pointers | cap int4]
+        DevBuf<unsigned char> smooth_tab; int64_t smooth_cap = 0;      // device table of one artalk_session_smooth call: [cap slot pointers | cap int4]
     } sess;
     // slot: [style | prev_in | prev_fdec | smoother carry]; the carry (the last 9 raw frames, padded to 16 bytes) is read and written in
     // place by savgol_stream_kernel and never visits the workspace: SessionRows and the gather / scatter cover the first three fields only
     int64_t sess_carry_off() const { return slot_carry_off(cfg.code_dim); }
     int64_t sess_slot_floats() const { return sess_carry_off() + (kSavgolCarry * (int64_t)cfg.motion_dim + 3) / 4 * 4; }
-    float* sess_slot(int i) const { return sess.blocks[i / kSessBlock] + (int64_t)(i % kSessBlock) * sess_slot_floats(); }
+    float* sess_slot(int i) const { return sess.blocks[i / kSessBlock].get() + (int64_t)(i % kSessBlock) * sess_slot_floats(); }
     Workspace* view = nullptr;        // workspace view (clip sub-range) the body launchers currently work on; null = m->ws
     bool sticky_error = false;        // set by internal consistency checks inside the launch sequence; reported by artalk_infer
     // derived sizes
@@ -219,29 +219,29 @@ struct artalk_model {
     bool use_graphs = true;
     bool in_graph_body = false;   // capturing: no events
     bool in_body = false;         // inside run_chunk_body (captured or eager)
-    std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;
+    std::vector<Event> ev_pool; size_t ev_used = 0;
     std::vector<std::pair<size_t, double>> dom_events;   // (event index of start, flops)
     std::vector<std::pair<int, size_t>> marks;          // (bucket of the interval ending here, event index), caller's stream
     hipStream_t prof_stream = nullptr;
-    hipStream_t side_stream[3] = {nullptr, nullptr, nullptr};   // extra branches of the AR body (run_body)
-    hipEvent_t fork_ev = nullptr, join_ev[3] = {nullptr, nullptr, nullptr};
+    Stream side_stream[3];            // extra branches of the AR body (run_body)
+    Event fork_ev, join_ev[3];
     int branches = 0;                 // 0 = automatic (2 for B >= 8), else forced 1/2/4
-    hipStream_t own_stream = nullptr;   // used when the caller passes stream == NULL (graph capture needs a real stream)
+    Stream own_stream;                // used when the caller passes stream == NULL (graph capture needs a real stream)
     // graphs: one per (active batch size, clip group, precision, re-encoded clips), LRU-bounded (run_body)
-    struct GraphEntry { hipGraphExec_t exec = nullptr; long long last_use = 0; };
+    struct GraphEntry { GraphExec exec; long long last_use = 0; };
     std::map<long long, GraphEntry> graphs;
     long long graph_clock = 0, graph_captures = 0;
     // Pinned host staging for the small per-call tables (chunk offsets, style flags): a ring of slots, each guarded by an event
     // recorded after its H2D copies, so artalk_infer never has to wait for its own copies (it blocks only if kStageSlots calls
     // are still in flight).  h_status receives the device status word at the end of every call (async), status_ev marks it.
     static constexpr int kStageSlots = 4;
-    struct Stage { long* src = nullptr; uint8_t* has = nullptr; float** slots = nullptr; int4* smooth = nullptr; hipEvent_t done = nullptr; bool used = false; };
+    struct Stage { PinnedBuf<long> src; PinnedBuf<uint8_t> has; PinnedBuf<float*> slots; PinnedBuf<int4> smooth; Event done; bool used = false; };
     Stage stage[kStageSlots];
     int stage_cap_c = 0, stage_cap_b = 0, stage_next = 0;
     // one slot per call in flight (ring of kStatusSlots, indexed by the call's ticket): a caller that keeps several calls queued reads
     // each call's own word (artalk_get_status_of)
     static constexpr int kStatusSlots = 4;
-    int* h_status = nullptr; hipEvent_t status_ev[kStatusSlots] = {nullptr, nullptr, nullptr, nullptr}; bool status_pending = false;
+    PinnedBuf<int> h_status; Event status_ev[kStatusSlots]; bool status_pending = false;
     long long ticket = 0;          // number of calls that have published a status word; the last one's ticket is `ticket`, slot (ticket - 1) % kStatusSlots
 };
 
@@ -267,7 +267,7 @@ struct ProfilingOff {
 };
 
 template <typename T>
-T* dalloc(artalk_model* m, int64_t n) { return dalloc_in<T>(m->allocs, n); }
+T* dalloc(artalk_model* m, int64_t n) { return m->weights.take<T>(n); }
 
 // ---- the functions that cross a file boundary, by the file that defines them
 // engine.hip: the stages of the path and the chunk step (calls.hip runs them)

@@ -215,7 +215,7 @@ int build_registry(artalk_model* m) {
         add_linear(m, p + ".feed_forward.intermediate_dense", Fi, Hs, L.ff1_w, L.ff1_b);
         add_linear(m, p + ".feed_forward.output_dense", Hs, Fi, L.ff2_w, L.ff2_b);
     }
-    for (void* p : m->allocs) if (!p) return fail(m, ARTALK_EHIP, "hipMalloc failed while allocating weights");
+    if (!m->weights.ok()) return fail(m, ARTALK_EHIP, "hipMalloc failed while allocating weights");
     return ARTALK_OK;
 }
 
@@ -225,40 +225,29 @@ int upload(artalk_model* m, float* dst, const float* src, int64_t n) {
 }
 
 // the captured body graphs (engine.hip: run_body) hold workspace pointers, site exponents and grid sizes: dropped when one changes
-void drop_graphs(artalk_model* m) {
-    for (auto& g : m->graphs) (void)hipGraphExecDestroy(g.second.exec);
-    m->graphs.clear();
-}
-
-void free_stage(artalk_model* m) {
-    for (auto& st : m->stage) {
-        if (st.src) (void)hipHostFree(st.src);
-        if (st.has) (void)hipHostFree(st.has);
-        if (st.slots) (void)hipHostFree(st.slots);
-        if (st.smooth) (void)hipHostFree(st.smooth);
-        st.src = nullptr; st.has = nullptr; st.slots = nullptr; st.smooth = nullptr; st.used = false;
-    }
-    m->stage_cap_c = m->stage_cap_b = 0;
-}
+void drop_graphs(artalk_model* m) { m->graphs.clear(); }
 }  // namespace
 
 namespace artalk {      // called from other files: declared in model.h
+// The status slots once, and a ring of pinned slots for maxB clips and maxC chunks: a whole ring, or a failure with the caps at 0 (the
+// next call builds it again).  The slots' `done` events live through a regrow.
 int ensure_stage(artalk_model* m, int maxB, int maxC) {
-    if (!m->h_status) {
-        HIPCHK(m, hipHostMalloc(reinterpret_cast<void**>(&m->h_status), artalk_model::kStatusSlots * sizeof(int), hipHostMallocDefault));
-        std::memset(m->h_status, 0, artalk_model::kStatusSlots * sizeof(int));
-        for (auto& e : m->status_ev) HIPCHK(m, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (!m->h_status.get()) {
+        bool ok = true;
+        for (auto& e : m->status_ev) ok = ok && e.create(hipEventDisableTiming);
+        if (!ok || !m->h_status.alloc(artalk_model::kStatusSlots)) return fail(m, ARTALK_EHIP, "the pinned status slots or their events could not be taken from the runtime");
+        std::memset(m->h_status.get(), 0, artalk_model::kStatusSlots * sizeof(int));
     }
     if (maxB <= m->stage_cap_b && maxC <= m->stage_cap_c) return ARTALK_OK;
-    for (auto& st : m->stage) if (st.used) HIPCHK(m, hipEventSynchronize(st.done));
-    free_stage(m);
-    for (auto& st : m->stage) {
-        HIPCHK(m, hipHostMalloc(reinterpret_cast<void**>(&st.src), (size_t)3 * maxC * sizeof(long), hipHostMallocDefault));
-        HIPCHK(m, hipHostMalloc(reinterpret_cast<void**>(&st.has), (size_t)maxB, hipHostMallocDefault));
-        HIPCHK(m, hipHostMalloc(reinterpret_cast<void**>(&st.slots), (size_t)maxB * sizeof(float*), hipHostMallocDefault));
-        HIPCHK(m, hipHostMalloc(reinterpret_cast<void**>(&st.smooth), (size_t)maxB * sizeof(int4), hipHostMallocDefault));
-        if (!st.done) HIPCHK(m, hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
+    for (auto& st : m->stage) if (st.used) HIPCHK(m, hipEventSynchronize(st.done.get()));
+    m->stage_cap_c = m->stage_cap_b = 0;
+    bool ok = true;
+    for (auto& st : m->stage) {      // (alloc gives the old block back first)
+        st.used = false;
+        ok = ok && st.src.alloc((size_t)3 * maxC) && st.has.alloc((size_t)maxB) && st.slots.alloc((size_t)maxB) && st.smooth.alloc((size_t)maxB) &&
+             st.done.create(hipEventDisableTiming);
     }
+    if (!ok) return fail(m, ARTALK_EHIP, "the pinned staging ring or its events could not be taken from the runtime");
     m->stage_cap_b = maxB; m->stage_cap_c = maxC;
     return ARTALK_OK;
 }
@@ -266,7 +255,7 @@ int ensure_stage(artalk_model* m, int maxB, int maxC) {
 int next_stage(artalk_model* m, artalk_model::Stage** out) {
     artalk_model::Stage& st = m->stage[m->stage_next];
     m->stage_next = (m->stage_next + 1) % artalk_model::kStageSlots;
-    if (st.used) HIPCHK(m, hipEventSynchronize(st.done));
+    if (st.used) HIPCHK(m, hipEventSynchronize(st.done.get()));
     *out = &st;
     return ARTALK_OK;
 }
@@ -274,9 +263,9 @@ int next_stage(artalk_model* m, artalk_model::Stage** out) {
 int publish_status(artalk_model* m, hipStream_t s) {
     const int slot = (int)(m->ticket % artalk_model::kStatusSlots);
     // the slot's previous user is kStatusSlots calls back: its copy has long landed unless the caller queued more calls than slots
-    if (m->ticket >= artalk_model::kStatusSlots) HIPCHK(m, hipEventSynchronize(m->status_ev[slot]));
-    HIPCHK(m, hipMemcpyAsync(m->h_status + slot, m->ws.status, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(m, hipEventRecord(m->status_ev[slot], s));
+    if (m->ticket >= artalk_model::kStatusSlots) HIPCHK(m, hipEventSynchronize(m->status_ev[slot].get()));
+    HIPCHK(m, hipMemcpyAsync(m->h_status.get() + slot, m->ws.status, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(m, hipEventRecord(m->status_ev[slot].get(), s));
     ++m->ticket;
     m->status_pending = true;
     HIPCHK(m, hipGetLastError());
@@ -308,17 +297,16 @@ int reserve(artalk_model* m, int maxB, int maxC) {
     maxB = std::max(maxB, m->ws.maxB); maxC = std::max(maxC, m->ws.maxC);
     (void)hipDeviceSynchronize();
     drop_graphs(m);
-    for (void* p : m->ws_allocs) if (p) (void)hipFree(p);
-    m->ws_allocs.clear();
+    m->ws_pool.clear();
     m->ws = Workspace();
     m->stream_B = 0; m->stream_scales_ended = false;          // the streaming history lived in the workspace that was just dropped: a session must begin again
     m->status_pending = false;
     Workspace& w = m->ws;
     const int CD = c.w2v_conv_dim, Hs = c.w2v_hidden;
     w.maxB = maxB; w.maxC = maxC; w.G = std::min(maxC, 96);
-    auto F = [&](int64_t n) { w.bytes += n * 4; return dalloc_in<float>(m->ws_allocs, n); };
+    auto F = [&](int64_t n) { w.bytes += n * 4; return m->ws_pool.take<float>(n); };
     const int G = w.G;
-    w.src_off = dalloc_in<long>(m->ws_allocs, (int64_t)3 * maxC);      // chunk table of a call [C] | in pass order [C] | gather table [C] (ConvPasses)
+    w.src_off = m->ws_pool.take<long>((int64_t)3 * maxC);      // chunk table of a call [C] | in pass order [C] | gather table [C] (ConvPasses)
     w.xnorm = F((int64_t)G * kSamplesPerChunk);
     w.convA = F(((int64_t)G * m->conv_S[0] + 16) * CD);
     w.convB = F(((int64_t)G * m->conv_S[1] + 16) * CD);
@@ -327,22 +315,21 @@ int reserve(artalk_model* m, int maxB, int maxC) {
     w.silu_cond = F((int64_t)maxC * kNTok * kCond);
     for (const ClipBuf& cb : clip_buffers(m)) {      // maxB clips of each; the buffers that are not per clip keep their place between them
         const int64_t n = (cb.f == &Workspace::cache ? c.ar_depth : 1) * maxB * cb.n;      // the cache: [depth][maxB][...]
-        if (cb.f) w.*cb.f = F(n); else w.*cb.u8 = dalloc_in<uint8_t>(m->ws_allocs, n);
+        if (cb.f) w.*cb.f = F(n); else w.*cb.u8 = m->ws_pool.take<uint8_t>(n);
         if (cb.f == &Workspace::logits) {
             w.splitk_floats = (int64_t)8 << 20; w.splitk = F(w.splitk_floats); w.splitk_b[0] = w.splitk;
             for (int i = 1; i < 4; ++i) w.splitk_b[i] = F(w.splitk_floats);
         }
         if (cb.u8 == &Workspace::hist_bits) {
-            w.has_style = dalloc_in<uint8_t>(m->ws_allocs, maxB);
-            w.status = dalloc_in<int>(m->ws_allocs, 4);
-            w.sess_slots = dalloc_in<float*>(m->ws_allocs, maxB);
+            w.has_style = m->ws_pool.take<uint8_t>(maxB);
+            w.status = m->ws_pool.take<int>(4);
+            w.sess_slots = m->ws_pool.take<float*>(maxB);
         }
     }
     const int S = c.style_dim, SL = c.style_len;
     w.s_in = F((int64_t)maxB * SL * 128); w.s_h = F((int64_t)maxB * SL * S); w.s_qkv = F((int64_t)maxB * SL * 3 * S);
     w.s_att = F((int64_t)maxB * SL * S); w.s_ffn = F((int64_t)maxB * SL * c.style_ffn); w.s_tmp = F((int64_t)maxB * SL * S);
-    for (void* p : m->ws_allocs)
-        if (!p) return fail(m, ARTALK_EHIP, "hipMalloc failed while reserving workspace");
+    if (!m->ws_pool.ok()) return fail(m, ARTALK_EHIP, "hipMalloc failed while reserving workspace");
     // the zero fills above run on the null stream; callers use non-blocking streams, which do not order against it
     HIPCHK(m, hipDeviceSynchronize());
     return ensure_stage(m, maxB, maxC);
@@ -513,24 +500,7 @@ void artalk_destroy(artalk_model* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
     (void)hipDeviceSynchronize();
-    drop_graphs(m);
-    for (auto e : m->ev_pool) (void)hipEventDestroy(e);
-    for (auto e : m->ktimer.pool) (void)hipEventDestroy(e);
-    if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
-    for (int i = 0; i < 3; ++i) {
-        if (m->side_stream[i]) (void)hipStreamDestroy(m->side_stream[i]);
-        if (m->join_ev[i]) (void)hipEventDestroy(m->join_ev[i]);
-    }
-    if (m->fork_ev) (void)hipEventDestroy(m->fork_ev);
-    free_stage(m);
-    for (auto& st : m->stage) if (st.done) (void)hipEventDestroy(st.done);
-    if (m->h_status) (void)hipHostFree(m->h_status);
-    for (auto& e : m->status_ev) if (e) (void)hipEventDestroy(e);
-    for (void* p : m->allocs) if (p) (void)hipFree(p);
-    for (void* p : m->ws_allocs) if (p) (void)hipFree(p);
-    for (float* p : m->sess.blocks) if (p) (void)hipFree(p);
-    if (m->sess.smooth_tab) (void)hipFree(m->sess.smooth_tab);
-    delete m;
+    delete m;      // (every member that holds something of the runtime's gives it back: device_mem.h)
 }
 
 int artalk_set_tensor(artalk_model* m, const char* key, const void* host_ptr, int dtype, int ndim, const int64_t* shape) {
@@ -707,8 +677,8 @@ int artalk_set_audit(artalk_model* m, int enable) {
     if (!m) return ARTALK_EINVAL;
     (void)hipSetDevice(m->device);
     if (enable && !m->audit_vals) {
-        HIPCHK(m, hipMalloc(reinterpret_cast<void**>(&m->audit_vals), kAuditSlots * sizeof(unsigned int)));
-        m->allocs.push_back(m->audit_vals);
+        m->audit_vals = dalloc<unsigned int>(m, kAuditSlots);
+        if (!m->audit_vals) return fail(m, ARTALK_EHIP, "hipMalloc failed for the audit block");
     }
     if (enable) {
         HIPCHK(m, hipDeviceSynchronize());
@@ -849,8 +819,8 @@ int artalk_set_cu_mask(artalk_model* m, const uint32_t* mask, int n_words) {
     if (hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, m->device) == hipSuccess && dev_cus > 0) n = std::min(n, dev_cus);
     m->n_cus = n;
     for (int i = 0; i < 3; ++i) {      // side streams are re-created (masked) on demand
-        if (m->side_stream[i]) { (void)hipStreamDestroy(m->side_stream[i]); m->side_stream[i] = nullptr; }
-        if (m->join_ev[i]) { (void)hipEventDestroy(m->join_ev[i]); m->join_ev[i] = nullptr; }
+        m->side_stream[i].reset();
+        m->join_ev[i].reset();
     }
     drop_graphs(m);      // the GEMM grids were captured for the old CU count
     m->invalidate_init_hist();
@@ -870,8 +840,8 @@ int artalk_get_status(artalk_model* m, int* flags, void* stream) {
     if (!m->status_pending) { *flags = 0; return ARTALK_OK; }
     (void)hipSetDevice(m->device);
     const int slot = (int)((m->ticket - 1) % artalk_model::kStatusSlots);
-    HIPCHK(m, hipEventSynchronize(m->status_ev[slot]));
-    *flags = m->h_status[slot];
+    HIPCHK(m, hipEventSynchronize(m->status_ev[slot].get()));
+    *flags = m->h_status.get()[slot];
     return ARTALK_OK;
 }
 long long artalk_last_ticket(artalk_model* m) { return m ? m->ticket : -1; }
@@ -881,8 +851,8 @@ int artalk_get_status_of(artalk_model* m, long long ticket, int* flags) {
     if (!m->status_pending) { *flags = 0; return ARTALK_OK; }      // the workspace was re-created since: nothing of that call is left
     (void)hipSetDevice(m->device);
     const int slot = (int)((ticket - 1) % artalk_model::kStatusSlots);
-    HIPCHK(m, hipEventSynchronize(m->status_ev[slot]));
-    *flags = m->h_status[slot];
+    HIPCHK(m, hipEventSynchronize(m->status_ev[slot].get()));
+    *flags = m->h_status.get()[slot];
     return ARTALK_OK;
 }
 int artalk_poll_status(artalk_model* m, int* flags) {
@@ -890,10 +860,10 @@ int artalk_poll_status(artalk_model* m, int* flags) {
     if (!m->status_pending) { *flags = 0; return ARTALK_OK; }
     (void)hipSetDevice(m->device);
     const int slot = (int)((m->ticket - 1) % artalk_model::kStatusSlots);
-    const hipError_t e = hipEventQuery(m->status_ev[slot]);
+    const hipError_t e = hipEventQuery(m->status_ev[slot].get());
     if (e == hipErrorNotReady) return ARTALK_EBUSY;
     if (e != hipSuccess) { m->err = std::string("hipEventQuery: ") + hipGetErrorString(e); return ARTALK_EHIP; }
-    *flags = m->h_status[slot];
+    *flags = m->h_status.get()[slot];
     return ARTALK_OK;
 }
 
@@ -902,7 +872,7 @@ int artalk_get_profile(artalk_model* m, double* out, int n) {
     if (!m->profiling || m->marks.size() < 2) return fail(m, ARTALK_ESTATE, "profiling was not enabled for the last artalk_infer");
     (void)hipSetDevice(m->device);
     HIPCHK(m, hipStreamSynchronize(m->prof_stream));
-    auto ms = [&](size_t a, size_t b) { float t = 0.f; (void)hipEventElapsedTime(&t, m->ev_pool[a], m->ev_pool[b]); return (double)t; };
+    auto ms = [&](size_t a, size_t b) { float t = 0.f; (void)hipEventElapsedTime(&t, m->ev_pool[a].get(), m->ev_pool[b].get()); return (double)t; };
     double r[10] = {0};
     for (size_t i = 1; i < m->marks.size(); ++i) {
         const int b = m->marks[i].first;
@@ -926,7 +896,7 @@ int artalk_get_kernel_sums(artalk_model* m, double* out, int n) {
     for (int i = 0; i <= KB_N; ++i) out[i] = 0.0;
     for (const auto& r : m->ktimer.recs) {
         float t = 0.f;
-        if (hipEventElapsedTime(&t, m->ktimer.pool[r.second], m->ktimer.pool[r.second + 1]) != hipSuccess) continue;
+        if (hipEventElapsedTime(&t, m->ktimer.pool[r.second].get(), m->ktimer.pool[r.second + 1].get()) != hipSuccess) continue;
         const int b = r.first >= 0 && r.first < KB_N ? r.first : KB_OTHER;
         out[b] += t;
         out[KB_N] += 1.0;

@@ -65,23 +65,20 @@ int artalk_op_gemm_f16s_ex(const float* A, int64_t lda, const float* W, const fl
                            int force_cfg, int a_exp, int* status_dev, void* stream) {
     if (!A || !W || !C || K % 32 != 0 || M <= 32 || N <= 0 || !op_exp_ok(a_exp)) return ARTALK_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    unsigned int* wp = nullptr;
-    if (hipMalloc(&wp, (size_t)N * K * 4) != hipSuccess) return ARTALK_EHIP;
-    launch_pack_split(W, wp, (long)N * K, true, s);
+    DevBuf<unsigned int> wp, ap;
+    if (!wp.alloc((size_t)N * K)) return ARTALK_EHIP;
+    launch_pack_split(W, wp.get(), (long)N * K, true, s);
     GemmArgs g;
-    g.A = A; g.lda = lda; g.W = W; g.Wp = wp; g.ldw = K; g.bias = bias; g.C = C; g.ldc = N; g.M = M; g.N = N; g.K = K; g.act = act;
+    g.A = A; g.lda = lda; g.W = W; g.Wp = wp.get(); g.ldw = K; g.bias = bias; g.C = C; g.ldc = N; g.M = M; g.N = N; g.K = K; g.act = act;
     g.force_cfg = force_cfg & 0xff;
     g.a_exp = a_exp; g.status = status_dev;
-    unsigned int* ap = nullptr;
     if (force_cfg >= 0 && (force_cfg & 0x100)) {   // tuning: pre-packed A (what a fused producer would hand over)
-        if (hipMalloc(&ap, (size_t)M * lda * 4) != hipSuccess) { (void)hipFree(wp); return ARTALK_EHIP; }
-        launch_pack_split(A, ap, (long)M * lda, false, s, status_dev, a_exp);
-        g.A = reinterpret_cast<const float*>(ap); g.a_packed = 1;
+        if (!ap.alloc((size_t)M * lda)) return ARTALK_EHIP;
+        launch_pack_split(A, ap.get(), (long)M * lda, false, s, status_dev, a_exp);
+        g.A = reinterpret_cast<const float*>(ap.get()); g.a_packed = 1;
     }
     run_gemm(g, plan_gemm(g, GemmPolicy{1, true}, nullptr), nullptr, s);
-    (void)hipStreamSynchronize(s);
-    (void)hipFree(wp);
-    if (ap) (void)hipFree(ap);
+    (void)hipStreamSynchronize(s);      // (the temporaries go when the function returns)
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
 }
 
@@ -101,39 +98,35 @@ int artalk_op_gemm_bf16(const float* A, int64_t lda, const float* W, const float
     const int T = force_cfg < 0 ? 0 : (force_cfg >> 25) & 63;
     if ((cfg > 2 && cfg != 0xff) || S > 16 || (am && (T <= 0 || M % T != 0 || K % 64 != 0 || nb * 64 > lda))) return ARTALK_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    void* wb = nullptr;
-    float* part = nullptr;
-    if (hipMalloc(&wb, (size_t)nb * N * K * 2) != hipSuccess) return ARTALK_EHIP;
-    if (S > 1 && hipMalloc(&part, (size_t)S * nb * M * N * 4) != hipSuccess) { (void)hipFree(wb); return ARTALK_EHIP; }
-    launch_pack_bf16(W, wb, (long)nb * N * K, s);
+    DevBuf<uint16_t> wb;
+    DevBuf<float> part;
+    if (!wb.alloc((size_t)nb * N * K)) return ARTALK_EHIP;
+    if (S > 1 && !part.alloc((size_t)S * nb * M * N)) return ARTALK_EHIP;
+    launch_pack_bf16(W, wb.get(), (long)nb * N * K, s);
     GemmArgs g;
-    g.A = A; g.lda = lda; g.W = W; g.Wb = wb; g.ldw = K; g.bias = bias; g.C = C; g.ldc = N; g.gate = gate; g.ldg = N; g.R = R; g.ldr = N;
+    g.A = A; g.lda = lda; g.W = W; g.Wb = wb.get(); g.ldw = K; g.bias = bias; g.C = C; g.ldc = N; g.gate = gate; g.ldg = N; g.R = R; g.ldr = N;
     g.M = M; g.N = N; g.K = K; g.act = act; g.force_cfg = cfg == 0xff ? -1 : cfg;
     g.batch = nb; g.sA = am ? 64 : (long)M * lda; g.sW = (long)N * K; g.sBias = bias ? N : 0; g.sC = (long)M * N; g.sR = R ? (long)M * N : 0;
     if (am) { g.amode = 1; g.pc_T = T; g.pc_tstride = T; g.pc_pad = K / 64 / 2; g.pc_cin = 64; }
     if (S > 1) {
-        if (nb > 1 || am) { (void)hipFree(wb); (void)hipFree(part); return ARTALK_EINVAL; }     // (split-K is a batch-1 plain-window form)
-        g.splitk = S; g.partial = part;
+        if (nb > 1 || am) return ARTALK_EINVAL;     // (split-K is a batch-1 plain-window form)
+        g.splitk = S; g.partial = part.get();
     }
     run_gemm(g, plan_gemm(g, GemmPolicy{2}, nullptr), nullptr, s);
     (void)hipStreamSynchronize(s);
-    (void)hipFree(wb);
-    if (part) (void)hipFree(part);
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
 }
 
 // split-K scratch of the tuning entry point below (never used by the model path): the current buffer and the ones it outgrew
-static float* g_op_scratch = nullptr;
-static size_t g_op_scratch_cap = 0;
-static std::vector<float*> g_op_retired;
+// (never destroyed: at process exit the runtime may be gone before a static destructor runs; artalk_op_release_scratch frees them)
+static DevBuf<float>& g_op_scratch = *new DevBuf<float>;
+static std::vector<DevBuf<float>>& g_op_retired = *new std::vector<DevBuf<float>>;
 // Frees every scratch buffer of artalk_op_gemm_f16s_packed (current and retired).  The caller guarantees that no captured graph
 // that replays such a launch is used afterwards (tools/* destroy their graphs first; pytest calls it at session end).
 int artalk_op_release_scratch(void) {
     if (hipDeviceSynchronize() != hipSuccess) return ARTALK_EHIP;
-    for (float* p : g_op_retired) (void)hipFree(p);
     g_op_retired.clear();
-    if (g_op_scratch) (void)hipFree(g_op_scratch);
-    g_op_scratch = nullptr; g_op_scratch_cap = 0;
+    g_op_scratch.reset();
     return ARTALK_OK;
 }
 // building blocks for tuning the split GEMM without allocation noise: pack once, then launch on packed operands
@@ -176,18 +169,17 @@ int artalk_op_gemm_f16s_packed_ex(const void* A, int a_packed, int64_t lda, cons
         if (cls == P8_SMALL) {     // bits 8-15: split-K factor (slabs in a temporary)
             g.w_nt = (force_cfg >> 16) & 1;      // tuning: bit 16 = non-temporal weight pieces
             if (S > 1) {
-                const size_t need = (size_t)S * M * N * 4;
-                if (need > g_op_scratch_cap) {
+                const size_t need = (size_t)S * M * N;      // floats
+                if (need > g_op_scratch.capacity()) {
                     // a smaller scratch is NOT freed here: graphs captured from earlier calls (tools/gemm_f16s_bench.py replays one per
                     // variant) still write to it - freeing it turned their replay into a memory fault.  It is RETIRED instead and freed by
                     // artalk_op_release_scratch(), which the owner of those graphs calls once they are gone.  At least 64 MB, so that it rarely grows.
-                    const size_t cap = std::max(need, (size_t)64 << 20);
-                    float* fresh = nullptr;
-                    if (hipMalloc(&fresh, cap) != hipSuccess) return ARTALK_EHIP;
-                    if (g_op_scratch) g_op_retired.push_back(g_op_scratch);
-                    g_op_scratch = fresh; g_op_scratch_cap = cap;
+                    DevBuf<float> fresh;
+                    if (!fresh.alloc(std::max(need, (size_t)16 << 20))) return ARTALK_EHIP;
+                    if (g_op_scratch.get()) g_op_retired.push_back(std::move(g_op_scratch));
+                    g_op_scratch = std::move(fresh);
                 }
-                g.splitk = S; g.partial = g_op_scratch;
+                g.splitk = S; g.partial = g_op_scratch.get();
             }
         }
     }
@@ -386,18 +378,16 @@ int artalk_op_gemm_rows(const artalk_op_gemm_rows_args* a, void* stream) {
     if (g_rows_dry_run) return ARTALK_OK;
     // ---- the device from here on
     hipStream_t s = (hipStream_t)stream;
-    void* wcopy = nullptr;
-    float* part = nullptr;
-    if (a->mode != 0 && hipMalloc(&wcopy, (size_t)w_last * (p8 ? 4 : 2)) != hipSuccess) return ARTALK_EHIP;
-    if (g.splitk > 1 && hipMalloc(&part, (size_t)g.splitk * M * N * 4) != hipSuccess) { if (wcopy) (void)hipFree(wcopy); return ARTALK_EHIP; }
-    g.partial = part;
-    if (p8) { launch_pack_split(a->W, (unsigned int*)wcopy, w_last, true, s); g.Wp = (const unsigned int*)wcopy; }
-    if (a->mode == 2) { launch_pack_bf16(a->W, wcopy, w_last, s); g.Wb = wcopy; }
+    DevBuf<unsigned char> wcopy;      // the weights packed (4 bytes each) or in bf16 (2 bytes each)
+    DevBuf<float> part;
+    if (a->mode != 0 && !wcopy.alloc((size_t)w_last * (p8 ? 4 : 2))) return ARTALK_EHIP;
+    if (g.splitk > 1 && !part.alloc((size_t)g.splitk * M * N)) return ARTALK_EHIP;
+    g.partial = part.get();
+    if (p8) { launch_pack_split(a->W, (unsigned int*)wcopy.get(), w_last, true, s); g.Wp = (const unsigned int*)wcopy.get(); }
+    if (a->mode == 2) { launch_pack_bf16(a->W, wcopy.get(), w_last, s); g.Wb = wcopy.get(); }
     run_gemm(g, plan, &ln, s);
     if (a->ln_Y && !plan.fused_ln) launch_layernorm(ln, s);
     const hipError_t e1 = hipStreamSynchronize(s);
-    if (wcopy) (void)hipFree(wcopy);
-    if (part) (void)hipFree(part);
     return (e1 == hipSuccess && hipGetLastError() == hipSuccess) ? ARTALK_OK : ARTALK_EHIP;
 }
 
@@ -511,14 +501,13 @@ int artalk_op_w2v_front_ex(const float* audio, int C, int n, const float* w, con
     hipStream_t s = (hipStream_t)stream;
     std::vector<long> off(C);
     for (int i = 0; i < C; ++i) off[i] = (long)i * n;
-    long* doff = nullptr;
-    if (hipMalloc(&doff, C * sizeof(long)) != hipSuccess) return ARTALK_EHIP;
-    (void)hipMemcpy(doff, off.data(), C * sizeof(long), hipMemcpyHostToDevice);
+    DevBuf<long> doff;
+    if (!doff.alloc(C)) return ARTALK_EHIP;
+    (void)hipMemcpy(doff.get(), off.data(), C * sizeof(long), hipMemcpyHostToDevice);
     const int T = (n - 10) / 5 + 1;
-    launch_audio_normalize(audio, doff, xnorm_out, C, n, s);
+    launch_audio_normalize(audio, doff.get(), xnorm_out, C, n, s);
     launch_conv0(xnorm_out, n, w, bias, lnw, lnb, Y, C, T, T, s, out_p8 ? 1 : 0, out_p8 ? status_dev : nullptr, p8_exp);
     (void)hipStreamSynchronize(s);
-    (void)hipFree(doff);
     return hipGetLastError() == hipSuccess ? ARTALK_OK : ARTALK_EHIP;
 }
 
@@ -570,13 +559,11 @@ int artalk_op_w2v_front_rows(const float* audio, int64_t audio_elems, const int6
     if (g_rows_dry_run) return ARTALK_OK;
     hipStream_t s = (hipStream_t)stream;
     std::vector<long> off(chunk_off, chunk_off + C);
-    long* doff = nullptr;
-    if (hipMalloc(&doff, C * sizeof(long)) != hipSuccess) return ARTALK_EHIP;
-    if (hipMemcpy(doff, off.data(), C * sizeof(long), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(doff); return ARTALK_EHIP; }
-    launch_audio_normalize(audio, doff, xnorm_out, C, n, s);
+    DevBuf<long> doff;
+    if (!doff.upload(off.data(), C)) return ARTALK_EHIP;
+    launch_audio_normalize(audio, doff.get(), xnorm_out, C, n, s);
     launch_conv0(xnorm_out, n, w, bias, lnw, lnb, Y, C, T, (int)row_stride, s, out_p8 ? 1 : 0, out_p8 ? status_dev : nullptr, p8_exp);
     const hipError_t e1 = hipStreamSynchronize(s);
-    (void)hipFree(doff);
     return (e1 == hipSuccess && hipGetLastError() == hipSuccess) ? ARTALK_OK : ARTALK_EHIP;
 }
 
@@ -613,25 +600,24 @@ int artalk_op_posconv_rows(int mode, const float* X, int64_t x_elems, const floa
     if (op_overlap(X, (int64_t)(n_chunks - 1) * Ts * H + (int64_t)T * H, C, M * H)) return ARTALK_EINVAL;      // a row of X is read by many rows of C
     if (g_rows_dry_run) return ARTALK_OK;
     hipStream_t s = (hipStream_t)stream;
-    void* wcopy = nullptr;
-    if (mode != 0 && hipMalloc(&wcopy, (size_t)(H * K) * (mode == 1 ? 4 : 2)) != hipSuccess) return ARTALK_EHIP;
+    DevBuf<unsigned char> wcopy;      // the weights packed (4 bytes each) or in bf16 (2 bytes each)
+    if (mode != 0 && !wcopy.alloc((size_t)(H * K) * (mode == 1 ? 4 : 2))) return ARTALK_EHIP;
     GemmArgs g;
     g.A = X; g.lda = H; g.W = W; g.ldw = K; g.bias = bias; g.C = C; g.ldc = H; g.R = R; g.ldr = H;
     g.M = (int)M; g.act = act; g.a_exp = a_exp; g.K = (int)K;
     if (mode == 1) {
-        launch_pack_split(W, (unsigned int*)wcopy, H * K, true, s);
-        g.N = (int)H; g.Wp = (const unsigned int*)wcopy; g.status = status_dev;
+        launch_pack_split(W, (unsigned int*)wcopy.get(), H * K, true, s);
+        g.N = (int)H; g.Wp = (const unsigned int*)wcopy.get(); g.status = status_dev;
         launch_posconv_p8(g, n_chunks, T, Ts, s);
     } else {
         // the grouped GEMM over grid.z of run_wav2vec (amode 1)
         g.amode = 1; g.pc_T = T; g.pc_tstride = Ts; g.pc_pad = taps / 2; g.pc_cin = cg;
         g.N = cg; g.force_cfg = force_cfg;
         g.batch = groups; g.sA = cg; g.sW = (long)cg * K; g.sBias = bias ? cg : 0; g.sC = cg; g.sR = R ? cg : 0;
-        if (mode == 2) { launch_pack_bf16(W, wcopy, H * K, s); g.Wb = wcopy; }
+        if (mode == 2) { launch_pack_bf16(W, wcopy.get(), H * K, s); g.Wb = wcopy.get(); }
         run_gemm(g, plan_gemm(g, GemmPolicy{mode}, nullptr), nullptr, s);
     }
     const hipError_t e1 = hipStreamSynchronize(s);
-    if (wcopy) (void)hipFree(wcopy);
     return (e1 == hipSuccess && hipGetLastError() == hipSuccess) ? ARTALK_OK : ARTALK_EHIP;
 }
 
@@ -738,12 +724,10 @@ int artalk_op_savgol_stream(float* const* slots_dev, const float* raw, int64_t r
     hipStream_t s = (hipStream_t)stream;
     std::vector<int4> meta((size_t)n);
     for (int i = 0; i < n; ++i) meta[i] = make_int4(seen[i], n_frames[i], last[i] ? 1 : 0, 0);
-    int4* dmeta = nullptr;
-    if (hipMalloc(&dmeta, (size_t)n * sizeof(int4)) != hipSuccess) return ARTALK_EHIP;
-    if (hipMemcpy(dmeta, meta.data(), (size_t)n * sizeof(int4), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(dmeta); return ARTALK_EHIP; }
-    launch_savgol_stream(slots_dev, dmeta, (long)slot_carry_off(kOpCodeDim), raw, (long)raw_stride, out, (long)out_stride, n, kOpMotionDim, s);
+    DevBuf<int4> dmeta;
+    if (!dmeta.upload(meta.data(), (size_t)n)) return ARTALK_EHIP;
+    launch_savgol_stream(slots_dev, dmeta.get(), (long)slot_carry_off(kOpCodeDim), raw, (long)raw_stride, out, (long)out_stride, n, kOpMotionDim, s);
     const hipError_t e1 = hipStreamSynchronize(s);
-    (void)hipFree(dmeta);
     return (e1 == hipSuccess && hipGetLastError() == hipSuccess) ? ARTALK_OK : ARTALK_EHIP;
 }
 int artalk_op_session_smooth_check(const int64_t* open_ids, const int64_t* open_seen, const uint8_t* open_done, int n_open,

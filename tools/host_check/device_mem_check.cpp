@@ -1,5 +1,5 @@
-// Walks the owner types of artalk_amd/csrc/device_mem.h on the host, built with -fsanitize=address,undefined (Makefile beside this
-// file; tests/test_device_mem_cpu.py builds and runs it).  Without a usable device every HIP call fails, which is exactly the failure
+// Walks the owner types of artalk_amd/csrc/device_mem.h (blocks, pools, events, streams, graph executables, timers) on the host, built
+// with -fsanitize=address,undefined (Makefile beside this file; tests/test_device_mem_cpu.py builds and runs it).  Without a usable device every HIP call fails, which is exactly the failure
 // path of every method: the object must then be empty, its capacity 0, and the runtime's last error cleared.  With a device the same
 // walk checks the success path.  Exit status 0 and no sanitizer output: all held.
 // "Cleared" where the runtime cannot initialise for want of a device: there hipGetLastError() itself answers hipErrorNoDevice on
@@ -82,10 +82,50 @@ static void walk_devbuf() {
     check_state(d, d.upload(nullptr, 0), 0);             // nothing to copy: a block of 1 all the same
 }
 
-static void walk_event() {
+static void walk_pool() {
+    DevPool p;
+    CHECK(p.ok());
+    float* a = p.take<float>(100);
+    CHECK(p.ok() == (a != nullptr));
+    if (a) ++g_taken;
+    else CHECK(hipGetLastError() == g_quiet);
+    unsigned char* z = p.take<unsigned char>(0);         // 0 elements take 1
+    CHECK(p.ok() == (a != nullptr && z != nullptr) && (!a || !z || (void*)z != (void*)a));
+    if (a) {
+        float back[100];
+        CHECK(hipDeviceSynchronize() == hipSuccess);      // (the zero fill runs on the null stream)
+        CHECK(hipMemcpy(back, a, sizeof(back), hipMemcpyDeviceToHost) == hipSuccess);
+        for (float v : back) CHECK(v == 0.f);
+    }
+    const bool was_ok = p.ok();
+    DevPool q(std::move(p));                             // the blocks and the remembered failure move together
+    CHECK(q.ok() == was_ok);
+    q.clear();
+    CHECK(q.ok());                                       // clear() forgets the failure
+    q.clear();                                           // double clear
+    long* l = q.take<long>(-5);                          // a negative count takes 1 as well
+    CHECK(q.ok() == (l != nullptr));
+    if (!l) CHECK(hipGetLastError() == g_quiet);
+}
+
+static void walk_graph_exec() {
+    GraphExec g;                                         // (instantiating a graph needs a device: the empty owner's moves and resets)
+    CHECK(g.get() == nullptr);
+    GraphExec h(std::move(g));
+    CHECK(g.get() == nullptr && h.get() == nullptr);
+    GraphExec k{nullptr};
+    k = std::move(h);
+    CHECK(k.get() == nullptr);
+    k.reset();
+    k.reset();
+    CHECK(k.get() == nullptr);
+    CHECK(hipGetLastError() == g_quiet);
+}
+
+static void walk_event(unsigned flags) {
     Event e;
     CHECK(e.get() == nullptr);
-    const bool ok = e.create();
+    const bool ok = flags == hipEventDefault ? e.create() : e.create(flags);
     CHECK(ok == (e.get() != nullptr));
     if (ok) ++g_taken;
     else CHECK(hipGetLastError() == g_quiet);
@@ -116,6 +156,20 @@ static void walk_stream() {
     Stream u;
     u = std::move(t);
     CHECK(t.get() == nullptr && u.get() == h);
+    u.reset();
+    u.reset();                                           // double reset
+    CHECK(u.get() == nullptr);
+    const uint32_t words[8] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0, 0, 0};
+    const bool masked = u.create_masked(words, 8);       // a stream on half of the compute units
+    CHECK(masked == (u.get() != nullptr));
+    if (masked) ++g_taken;
+    else CHECK(hipGetLastError() == g_quiet);
+    h = u.get();
+    CHECK(u.create_masked(words, 8) == masked && u.create() == masked && u.get() == h);      // a second create of either kind keeps the stream
+    Stream b;
+    const bool blocking = b.create(hipStreamDefault);    // the flags of the plain create
+    CHECK(blocking == (b.get() != nullptr));
+    if (!blocking) CHECK(hipGetLastError() == g_quiet);
 }
 
 static void walk_timer() {
@@ -155,8 +209,11 @@ int main() {
     walk_block<PinnedBuf<char>>();
     walk_block<PinnedBuf<float>>();
     walk_devbuf();
-    walk_event();
+    walk_pool();
+    walk_event(hipEventDefault);
+    walk_event(hipEventDisableTiming);
     walk_stream();
+    walk_graph_exec();
     walk_timer();
     std::printf("device_mem_check: %d checks held (%s)\n", g_checks, g_taken ? "with a device" : "no device: failure paths");
     return 0;
